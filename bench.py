@@ -15,7 +15,10 @@ behaviour and outputs -- are timed too and reported as `sam2pairs_only`; `--dedu
 100 M-pair shard (weak scaling; shard r = groups [r*P, (r+1)*P) of one seeded data set); the only
 exchange is the group-count all_gather + 8-counter all_reduce at the end (quirks Q1/Q2).
 
-`value` = pairs processed by all ranks / wall time of K steps (max over ranks), inputs resident.
+`value` = pairs processed by all ranks / wall time of K steps (max over ranks), inputs resident; `ms_per_step` = that wall time / K.
+A plain run does only what `value` needs (set-up, W warm-up steps, the K timed steps).  `--full` adds `sam2pairs_only`, `counters`,
+`roofline`, `cpu_baseline`, `end_to_end` and the legs below.  `--dump-outputs DIR` writes what the last timed step computed to
+DIR/*.npy (see dump_outputs).
 `roofline`: the fused tile kernel (k_fast), algorithmic bytes (SAM bytes in + .pairs bytes out)
 per launch over its HIP-event launch duration, against 8 TB/s HBM.
 `cpu_baseline`: the reference itself (oracle/_ref/sam2pairs.ref, built from /root/reference by
@@ -45,6 +48,71 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_SEED = 20260104
+DUMP_LINES = 16384              # lines sampled from each text output of the last block
+DUMP_ARRAY_BYTES = 16 << 20     # cap per sampled array; with the flag sample every dump stays under 40 MB
+DUMP_FLAGS = 1 << 20            # duplicate flags sampled
+
+
+def _sample_idx(n, k, salt):
+    """A fixed, seeded, sorted sample of k distinct indices out of n (all of them when n <= k)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n)
+    return np.unique(np.random.default_rng([DUMP_SEED, salt]).integers(0, n, size=k))
+
+
+def _text_sample(buf, salt):
+    """Text the any-order path left (its line order depends on the schedule) -> its canonical form, the sorted lines.  Returns
+    a seeded sample of those lines as byte values (rows zero-padded to the longest sampled line, float32) and [lines, bytes,
+    SHA-256 of the sorted text as sixteen 16-bit words] (float64, exact): the sample shows where outputs differ, the digest whether."""
+    import hashlib
+    import numpy as np
+    lines = buf.tobytes().split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    lines.sort()
+    digest = np.frombuffer(hashlib.sha256(b"\n".join(lines)).digest(), dtype=">u2")
+    idx = _sample_idx(len(lines), DUMP_LINES, salt)
+    width = max([len(lines[i]) for i in idx], default=0)
+    idx = idx[:max(1, DUMP_ARRAY_BYTES // (4 * max(width, 1)))]
+    rows = np.zeros((len(idx), width), dtype=np.float32)
+    for r, i in enumerate(idx):
+        row = np.frombuffer(lines[i], dtype=np.uint8)
+        rows[r, :row.size] = row
+    return rows, np.concatenate(([len(lines), buf.size], digest)).astype(np.float64)
+
+
+def dump_outputs(out_dir, ctx, sam, chrstat, flags, counts, prefix=""):
+    """What a caller of the timed path holds after its last step, as .npy files (float32 / float64, < 40 MB in all):
+      pairs_lines / sam_lines + *_summary   the last block's .pairs (and .sam) text, sampled in canonical order (_text_sample);
+      chrstat_counts                        the per-chromosome-pair counts, rows in name order (extensions on);
+      dup_flags_sample                      duplicate flags of the reported pairs in input order, seeded sample (extensions on);
+      step_counts                           [reported pairs, duplicates, flags] of the step (extensions on).
+    Inputs are seeded, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+
+    pairs, sam_text = ctx.fetch_last_block_np()
+    rows, summary = _text_sample(pairs, 1)
+    save("pairs_lines", rows)
+    save("pairs_summary", summary)
+    if sam:
+        rows, summary = _text_sample(sam_text, 2)
+        save("sam_lines", rows)
+        save("sam_summary", summary)
+    if chrstat is not None:
+        recs = sorted(line.rsplit(b"\t", 1) for line in chrstat.splitlines() if line)
+        save("chrstat_counts", np.array([float(c) for _k, c in recs], dtype=np.float64))
+    if flags is not None:
+        f = np.frombuffer(flags, dtype=np.uint8)
+        save("dup_flags_sample", f[_sample_idx(f.size, DUMP_FLAGS, 3)].astype(np.float32))
+        save("step_counts", np.array([counts.get("reported_pairs", 0), counts.get("duplicates", 0), f.size], dtype=np.float64))
 
 
 def cpu_baseline(ctx, ds, sample_groups, threads, mode="unc"):
@@ -204,8 +272,12 @@ def main():
     ap.add_argument("--mode", default="unc", choices=["unc", "flash"])
     ap.add_argument("--dedup", default="yes", choices=["yes", "no"],
                     help="yes (BASELINE.json's metric, sam2pairs+dedup): every step also marks duplicate pairs and counts chromosome pairs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the sam=yes and flash resident legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the steps without the extensions (sam2pairs_only), the counters and "
+                         "k_fast roofline of one more pass, the CPU reference and the end-to-end executables, the sam=yes / flash / C4 / C5 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU reference and the end-to-end executables")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the sam=yes, flash, C4 and C5 resident legs")
     ap.add_argument("--leg-pairs", type=int, default=32_000_000, help="read pairs of the sam=yes / flash legs")
     ap.add_argument("--cpu-sample-pairs", type=int, default=12_000_000, help="pairs of the file the CPU reference and the end-to-end executables are timed on (~16 s of reference time per run)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI)")
@@ -266,6 +338,7 @@ def main():
     drop_last = rank == world - 1          # every rank holds pairs; the input's end is on the last one (quirk Q1)
     global_dedup = dedup and dist is not None and args.backend == "nccl"
     ext_out = {}
+    last_chrstat = [None]               # the per-chromosome-pair table of the last step (--dump-outputs)
 
     def run_steps(c, steps, with_dedup):
         """`steps` passes of the hot path over the resident data set.  With dedup every step is a whole input: sam2pairs over all
@@ -285,6 +358,7 @@ def main():
                 else:
                     tot, dups, _ = c.ext_dedup(drop_last, want_flags=False)
                 rows = c.ext_chrstat(drop_last)
+                last_chrstat[0] = rows
                 ext_out.update(reported_pairs=tot, duplicates=dups, chrstat_rows=len(rows.splitlines()))
         c.sync()
 
@@ -313,61 +387,20 @@ def main():
     tm_ms, tm_launch, tm_bytes = tmg.tile_kernel_ms, tmg.tile_launches, tmg.tile_bytes
     tiles_seen, tiles_deferred = tmg.tiles, tmg.deferred_tiles
 
-    # the same passes without the extensions (exactly the reference's behaviour and outputs), on a second context
-    plain = None
-    if dedup:
-        ctx2 = m.Context(args.mode, 0.5, 10, args.sam == "yes", 8, device=local, tiles=tiles)      # (no extensions)
-        el2, tmg2 = timed(ctx2, False)
-        plain = (el2, tmg2.tile_kernel_ms, tmg2.tile_launches)
-        ctx2.close()
-
-    # ---- one more (untimed) pass for the end-of-input bookkeeping and the counters of ONE pass
-    ctx.reset()
-    for (p, n, _g) in ds.blocks:
-        ctx.submit_device(p, n)
-    my_groups = ctx.group_count()
-    if dist is not None:
-        gl = [None] * world
-        dist.all_gather_object(gl, my_groups)
-        offset = sum(gl[:rank])
-        total = sum(gl)
-        last_nonempty = max(i for i, g in enumerate(gl) if g > 0)
-        st = ctx.finish(drop_last=(rank == last_nonempty), group_offset=offset, total_groups=total)
-        cnt = torch.tensor([st.lowMap, st.manyHits, st.unpaired, st.selfCircle, st.trans, st.cis10K, st.cis1K, st.cis0, st.pairs, st.pair_bytes,
-                            ext_out.get("duplicates", 0)], dtype=torch.int64, device=tdev)
-        dist.all_reduce(cnt)
-        counters = [int(x) for x in cnt.tolist()]
-    else:
-        st = ctx.finish(True)
-        counters = [st.lowMap, st.manyHits, st.unpaired, st.selfCircle, st.trans, st.cis10K, st.cis1K, st.cis0, st.pairs, st.pair_bytes,
-                    ext_out.get("duplicates", 0)]
+    if args.dump_outputs:
+        flags = None
+        if dedup:       # the step asked the marking for its counts only: the same call again, flags fetched
+            if global_dedup:
+                flags, _d, _a = shard.dedup_exchange(ctx, rank, world, drop_last, dist, torch, torch.device("cuda", local), want_flags=True)
+            else:
+                _t, _d, flags = ctx.ext_dedup(drop_last, want_flags=True)
+        dump_outputs(args.dump_outputs, ctx, args.sam == "yes", last_chrstat[0], flags, ext_out, prefix=f"rank{rank}_" if world > 1 else "")
 
     pairs_per_step = ds.total_groups
-    out_bytes_step = st.pair_bytes + (st.sam_bytes if args.sam == "yes" else 0)
-    algo_bytes_step = ds.total_bytes + out_bytes_step
     total_pairs = pairs_per_step * args.steps * world
     value = total_pairs / elapsed
     result = None
     if rank == 0:
-        achieved = (algo_bytes_step * args.steps) / (tm_ms / 1e3) / 1e9 if tm_ms > 0 else 0.0
-        # HBM traffic of k_fast per launch: rocprofv3 cannot run inside this process, so the figure comes from the committed
-        # PMC passes of this same command (tools/round_profiles.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs, FETCH_SIZE
-        # doubled as MI355X_MICROARCH.md prescribes for 16-byte-per-lane streams), as measured traffic / algorithmic bytes,
-        # applied to this run's algorithmic bytes per launch.  Only for the profiled workload shape; otherwise null.
-        traffic, traffic_src = None, None
-        try:
-            import glob
-            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))
-            if cands and tm_launch and args.config == "C2" and args.read_len == 150 and args.sam == "no" and args.mode == "unc":
-                tj = json.loads(open(cands[-1]).read())
-                if tj.get("block_groups") == args.block_groups and ("duplicate marking" in tj.get("workload", "")) == dedup:
-                    traffic = tj["traffic_over_algorithmic"] * algo_bytes_step * args.steps / tm_launch
-                    traffic_src = f"profiles/{os.path.basename(cands[-1])}: traffic/algorithmic = {tj['traffic_over_algorithmic']:.3f} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)"
-        except Exception:
-            traffic, traffic_src = None, None
-        cpu, e2e = None, None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu, e2e = cpu_baseline(ctx, ds, args.cpu_sample_pairs, 8, args.mode)
         result = {
             "metric": ("read-pairs/sec through sam2pairs+dedup" if dedup else "read-pairs/sec through sam2pairs")
                       + f" ({args.read_len} bp PE, {'mm10' if genome else 'hg38'} names, SAM text resident in HBM)",
@@ -390,12 +423,70 @@ def main():
                 "pairs_per_gpu": ds.total_groups,
                 "sam_bytes_per_gpu": ds.total_bytes,
                 "bytes_per_pair_in": ds.total_bytes / ds.total_groups,
-                "bytes_per_pair_out": out_bytes_step / ds.total_groups,
                 "block_groups": args.block_groups,
                 "blocks": ds.n_blocks,
                 "parallelism": f"shard{world}: independent read-group shards, no data-path collective",
             },
-            "roofline": {
+        }
+        if dedup:
+            result["dedup"] = dict(ext_out, scope=("global: hash-partitioned all_to_all of the key space over RCCL inside every step (microcket_amd.shard.dedup_exchange)"
+                                                   if global_dedup else "one GPU holds the whole input" if world == 1 else "per GPU shard (gloo rehearsal)"),
+                                   note="extension, not in the reference's sam2pairs: default off in the library, never changes stdout/.sam/.log")
+
+    if args.full:
+        # the same passes without the extensions (exactly the reference's behaviour and outputs), on a second context
+        plain = None
+        if dedup:
+            ctx2 = m.Context(args.mode, 0.5, 10, args.sam == "yes", 8, device=local, tiles=tiles)      # (no extensions)
+            el2, tmg2 = timed(ctx2, False)
+            plain = (el2, tmg2.tile_kernel_ms, tmg2.tile_launches)
+            ctx2.close()
+
+        # ---- one more (untimed) pass for the end-of-input bookkeeping and the counters of ONE pass
+        ctx.reset()
+        for (p, n, _g) in ds.blocks:
+            ctx.submit_device(p, n)
+        my_groups = ctx.group_count()
+        if dist is not None:
+            gl = [None] * world
+            dist.all_gather_object(gl, my_groups)
+            offset = sum(gl[:rank])
+            total = sum(gl)
+            last_nonempty = max(i for i, g in enumerate(gl) if g > 0)
+            st = ctx.finish(drop_last=(rank == last_nonempty), group_offset=offset, total_groups=total)
+            cnt = torch.tensor([st.lowMap, st.manyHits, st.unpaired, st.selfCircle, st.trans, st.cis10K, st.cis1K, st.cis0, st.pairs, st.pair_bytes,
+                                ext_out.get("duplicates", 0)], dtype=torch.int64, device=tdev)
+            dist.all_reduce(cnt)
+            counters = [int(x) for x in cnt.tolist()]
+        else:
+            st = ctx.finish(True)
+            counters = [st.lowMap, st.manyHits, st.unpaired, st.selfCircle, st.trans, st.cis10K, st.cis1K, st.cis0, st.pairs, st.pair_bytes,
+                        ext_out.get("duplicates", 0)]
+
+        out_bytes_step = st.pair_bytes + (st.sam_bytes if args.sam == "yes" else 0)
+        algo_bytes_step = ds.total_bytes + out_bytes_step
+        if rank == 0:
+            achieved = (algo_bytes_step * args.steps) / (tm_ms / 1e3) / 1e9 if tm_ms > 0 else 0.0
+            # HBM traffic of k_fast per launch: rocprofv3 cannot run inside this process, so the figure comes from the committed
+            # PMC passes of this same command (tools/round_profiles.sh: separate --pmc FETCH_SIZE / WRITE_SIZE runs, FETCH_SIZE
+            # doubled as MI355X_MICROARCH.md prescribes for 16-byte-per-lane streams), as measured traffic / algorithmic bytes,
+            # applied to this run's algorithmic bytes per launch.  Only for the profiled workload shape; otherwise null.
+            traffic, traffic_src = None, None
+            try:
+                import glob
+                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))
+                if cands and tm_launch and args.config == "C2" and args.read_len == 150 and args.sam == "no" and args.mode == "unc":
+                    tj = json.loads(open(cands[-1]).read())
+                    if tj.get("block_groups") == args.block_groups and ("duplicate marking" in tj.get("workload", "")) == dedup:
+                        traffic = tj["traffic_over_algorithmic"] * algo_bytes_step * args.steps / tm_launch
+                        traffic_src = f"profiles/{os.path.basename(cands[-1])}: traffic/algorithmic = {tj['traffic_over_algorithmic']:.3f} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE)"
+            except Exception:
+                traffic, traffic_src = None, None
+            cpu, e2e = None, None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu, e2e = cpu_baseline(ctx, ds, args.cpu_sample_pairs, 8, args.mode)
+            result["config"]["bytes_per_pair_out"] = out_bytes_step / ds.total_groups
+            result["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_fast (fused newline scan / parse / classify / format)",
                 "achieved": achieved,
@@ -411,30 +502,26 @@ def main():
                 "algorithmic_bytes_per_launch": algo_bytes_step * args.steps / tm_launch if tm_launch else None,
                 "tiles": tiles_seen,
                 "tiles_left_to_generic_kernel": tiles_deferred,
-            },
-            "cpu_baseline": cpu,
-            "counters": dict(zip(["lowMap", "manyHits", "unpaired", "selfCircle", "trans", "cis10K", "cis1K", "cis0", "pairs", "pair_bytes", "duplicates"], counters)),
-        }
-        if dedup:
-            result["dedup"] = dict(ext_out, scope=("global: hash-partitioned all_to_all of the key space over RCCL inside every step (microcket_amd.shard.dedup_exchange)"
-                                                   if global_dedup else "one GPU holds the whole input" if world == 1 else "per GPU shard (gloo rehearsal)"),
-                                   note="extension, not in the reference's sam2pairs: default off in the library, never changes stdout/.sam/.log")
-            el2, ms2, ln2 = plain
-            ach2 = (algo_bytes_step * args.steps) / (ms2 / 1e3) / 1e9 if ms2 > 0 else 0.0
-            result["sam2pairs_only"] = {"value": total_pairs / el2, "unit": "read-pairs/s", "ms_per_step": el2 / args.steps * 1e3,
-                                        "note": "the same steps without the extensions: exactly the reference's behaviour and outputs",
-                                        "roofline": {"achieved": ach2, "unit": "GB/s", "frac": ach2 / HBM_PEAK_GBS, "avg_launch_ms": ms2 / ln2 if ln2 else None}}
-        if e2e:
-            result["end_to_end"] = e2e
-            if e2e.get("sam_no", {}).get("speedup"):
-                result["speedup_vs_cpu_baseline"] = e2e["sam_no"]["speedup"]
-                result["speedup_note"] = "like for like: both executables on the same file, process start to exit (end_to_end.sam_no)"
-        if cpu:
-            result["kernel_only_ratio_vs_cpu_baseline"] = value / cpu["value"]
-            result["kernel_only_ratio_note"] = "`value` has its input resident in HBM and leaves its output there; the CPU run reads a file: NOT like for like"
+            }
+            result["cpu_baseline"] = cpu
+            result["counters"] = dict(zip(["lowMap", "manyHits", "unpaired", "selfCircle", "trans", "cis10K", "cis1K", "cis0", "pairs", "pair_bytes", "duplicates"], counters))
+            if dedup:
+                el2, ms2, ln2 = plain
+                ach2 = (algo_bytes_step * args.steps) / (ms2 / 1e3) / 1e9 if ms2 > 0 else 0.0
+                result["sam2pairs_only"] = {"value": total_pairs / el2, "unit": "read-pairs/s", "ms_per_step": el2 / args.steps * 1e3,
+                                            "note": "the same steps without the extensions: exactly the reference's behaviour and outputs",
+                                            "roofline": {"achieved": ach2, "unit": "GB/s", "frac": ach2 / HBM_PEAK_GBS, "avg_launch_ms": ms2 / ln2 if ln2 else None}}
+            if e2e:
+                result["end_to_end"] = e2e
+                if e2e.get("sam_no", {}).get("speedup"):
+                    result["speedup_vs_cpu_baseline"] = e2e["sam_no"]["speedup"]
+                    result["speedup_note"] = "like for like: both executables on the same file, process start to exit (end_to_end.sam_no)"
+            if cpu:
+                result["kernel_only_ratio_vs_cpu_baseline"] = value / cpu["value"]
+                result["kernel_only_ratio_note"] = "`value` has its input resident in HBM and leaves its output there; the CPU run reads a file: NOT like for like"
     ds.close()
     ctx.close()
-    if world == 1 and not args.no_extra_legs and result is not None:
+    if args.full and world == 1 and not args.no_extra_legs and result is not None:
         # the other shapes of the same path, each with its own k_fast roofline (the 94 GB data set above is released first)
         legs_steps = max(1, min(args.steps, 5))
         try:

@@ -35,11 +35,21 @@ def test_krmdup_oracle_matches_golden():
         assert util.sha(b"\n".join(util.fastq_records(inter))) == c["pipe_records_sha256"], c["name"]
 
 
-@pytest.mark.skipif(not os.path.exists(util.KRMDUP_REF), reason="oracle/_ref/krmdup.ref not built (needs /root/reference)")
+REF_BUILD_CASES = ((41, 5000, 80, ()), (42, 66000, 40, ("-k", "0", "-s", "8", "-S", "8")), (43, 100, 30, ()))
+
+
 def test_krmdup_oracle_matches_reference_build():
-    for seed, pairs, rl, args in ((41, 5000, 80, ()), (42, 66000, 40, ("-k", "0", "-s", "8", "-S", "8")), (43, 100, 30, ())):
+    """Against what oracle/_ref/krmdup.ref printed for these inputs (tests/golden/ref_build_golden.json), and against that build
+    directly whenever it is present."""
+    with open(os.path.join(util.GOLDEN, "ref_build_golden.json")) as f:
+        rec = json.load(f)["krmdup"]
+    for seed, pairs, rl, args in REF_BUILD_CASES:
         text = util.synth_fastq(seed, pairs, rl)
-        rc, r1, r2, log, err = util.krmdup_run_cli(util.KRMDUP_REF, text, False, args)
-        assert rc == 0, err
         o1, o2, ol = util.krmdup_oracle(text, **_kw(args))
-        assert (o1, o2, ol) == (r1, r2, log), (seed, args)
+        want = rec[str(seed)]
+        assert util.sha(text) == want["input_sha256"], seed
+        assert (util.sha(o1), util.sha(o2), ol.decode()) == (want["read1_sha256"], want["read2_sha256"], want["log"]), (seed, args)
+        if os.path.exists(util.KRMDUP_REF):
+            rc, r1, r2, log, err = util.krmdup_run_cli(util.KRMDUP_REF, text, False, args)
+            assert rc == 0, err
+            assert (o1, o2, ol) == (r1, r2, log), (seed, args)

@@ -1,8 +1,8 @@
 """The oracle (oracle/sam2pairs_oracle.c, a CPU restatement) is pinned:
   * against the committed golden vectors, which hold outputs of the REFERENCE ITSELF
     (tests/golden/golden.json, made by tests/golden/make_golden.py from oracle/_ref);
-  * against oracle/_ref directly whenever that build is present (this container; it also travels
-    to the GPU box with the snapshot)."""
+  * against what oracle/_ref printed for further seeded inputs (tests/golden/ref_build_golden.json), and against
+    oracle/_ref directly whenever that build is present."""
 import os
 
 import pytest
@@ -40,35 +40,63 @@ def test_oracle_matches_golden(golden):
     assert n >= 50
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("profile,seed,groups,modes", [
-    ("unc", 101, 4000, ("unc",)), ("flash", 102, 4000, ("flash",)), ("stress", 103, 9000, ("unc", "flash")),
-])
+REF_BUILD_INPUTS = [("unc", 101, 4000, ("unc",)), ("flash", 102, 4000, ("flash",)), ("stress", 103, 9000, ("unc", "flash"))]
+REF_BUILD_GRID = ((2, 0.5, 10, True), (4, 0.5, 10, True), (8, 0.5, 10, True), (4, 0.8, 30, False), (5, 0.5, 0, True))
+Q2_THREADS = (2, 4, 8)
+
+
+def ref_key(profile, seed, groups, mode, T, ratio, mapq, sam):
+    return f"{profile}/{seed}/{groups}/{mode}/T{T}/r{ratio}/q{mapq}/sam{int(sam)}"
+
+
+def _ref_build_golden():
+    """What oracle/_ref printed for the inputs below (tests/golden/make_ref_build_golden.py): the checks hold without that build."""
+    import json
+    with open(os.path.join(util.GOLDEN, "ref_build_golden.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("profile,seed,groups,modes", REF_BUILD_INPUTS)
 def test_oracle_matches_reference_build(profile, seed, groups, modes):
     text = util.synth(profile, seed, groups)
+    rec = _ref_build_golden()["sam2pairs"]
     for mode in modes:
-        for (T, ratio, mapq, sam) in ((2, 0.5, 10, True), (4, 0.5, 10, True), (8, 0.5, 10, True), (4, 0.8, 30, False), (5, 0.5, 0, True)):
-            rc, rp, rs, rl, err = util.ref_run(text, mode, T, ratio, mapq, sam)
-            assert rc == 0
+        for (T, ratio, mapq, sam) in REF_BUILD_GRID:
             op, osam, ol, st = util.oracle_run(text, mode, T, ratio, mapq, sam)
-            assert util.canon(rp) == util.canon(op), (profile, mode, T, ratio, mapq)
-            assert util.canon(rs) == util.canon(osam), (profile, mode, T, ratio, mapq)
-            assert rl == ol, (profile, mode, T, ratio, mapq, rl, ol)
+            want = rec[ref_key(profile, seed, groups, mode, T, ratio, mapq, sam)]
+            assert util.sha(text) == want["input_sha256"], (profile, seed, groups)
+            assert util.sha(util.canon(op)) == want["pairs_sha256"], (profile, mode, T, ratio, mapq)
+            assert util.sha(util.canon(osam)) == want["sam_sha256"], (profile, mode, T, ratio, mapq)
+            assert ol.decode() == want["log"], (profile, mode, T, ratio, mapq, want["log"], ol)
+            if util.have_ref():
+                rc, rp, rs, rl, err = util.ref_run(text, mode, T, ratio, mapq, sam)
+                assert rc == 0
+                assert util.canon(rp) == util.canon(op), (profile, mode, T, ratio, mapq)
+                assert util.canon(rs) == util.canon(osam), (profile, mode, T, ratio, mapq)
+                assert rl == ol, (profile, mode, T, ratio, mapq, rl, ol)
 
 
-@pytest.mark.skipif(not util.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+def q2_input():
+    return util.synth("unc", 77, (1 << 18) + (1 << 17), read_len=50)
+
+
 def test_quirk_q2_across_batches():
     """K just above 2^18 surviving groups with a LARGE remainder (keeps the reference clear of its
     own `loaded` race): the logged selfCircle depends on the thread count exactly as the closed form says."""
-    n = (1 << 18) + (1 << 17)
-    text = util.synth("unc", 77, n, read_len=50)
-    for T in (2, 4, 8):
-        rc, rp, rs, rl, err = util.ref_run(text, "unc", T, 0.5, 0, False)
-        assert rc == 0
+    text = q2_input()
+    rec = _ref_build_golden()["quirk_q2"]
+    for T in Q2_THREADS:
         op, osam, ol, st = util.oracle_run(text, "unc", T, 0.5, 0, False)
         assert st.groups % (1 << 18) >= (1 << 16)
-        assert rl == ol, (T, rl, ol)
-        assert util.sha(util.canon(rp)) == util.sha(util.canon(op))
+        want = rec[str(T)]
+        assert util.sha(text) == want["input_sha256"]
+        assert ol.decode() == want["log"], (T, want["log"], ol)
+        assert util.sha(util.canon(op)) == want["pairs_sha256"]
+        if util.have_ref():
+            rc, rp, rs, rl, err = util.ref_run(text, "unc", T, 0.5, 0, False)
+            assert rc == 0
+            assert rl == ol, (T, rl, ol)
+            assert util.sha(util.canon(rp)) == util.sha(util.canon(op))
 
 
 def test_oracle_cli_exit_codes(tmp_path):

@@ -7,12 +7,12 @@ set -e
 TAG=${1:-round}
 R=$PWD; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-timeout -k 10 600 python3 $R/bench.py > $O/bench_100M.json 2> $O/bench_100M.err
+timeout -k 10 600 python3 $R/bench.py --full > $O/bench_100M.json 2> $O/bench_100M.err
 echo "bench done"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-extra-legs > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-legs > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 echo "stats done"
-timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-legs > $O/pmc_fetch.json 2> $O/pmc_fetch.err
-timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-legs > $O/pmc_write.json 2> $O/pmc_write.err
+timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra-legs > $O/pmc_fetch.json 2> $O/pmc_fetch.err
+timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra-legs > $O/pmc_write.json 2> $O/pmc_write.err
 echo "pmc done"
 cd $R
 python3 tools/summarize_pmc.py $(ls $O/pmc_fetch/*/*counter_collection.csv | head -1) $(ls $O/pmc_write/*/*counter_collection.csv | head -1) $O/pmc_fetch.json > $O/pmc_summary.txt
