@@ -40,7 +40,8 @@ enum {
     MKT_E_NOMEM = -4,
     MKT_E_CAPACITY = -5,     /* a QNAME group does not fit the block buffer */
     MKT_E_KERNEL = -6,       /* the kernel reported an internal error bit */
-    MKT_E_STATE = -7         /* call order violated (e.g. submit after finish) */
+    MKT_E_STATE = -7,        /* call order violated (e.g. submit after finish) */
+    MKT_E_IO = -8            /* a temporary file could not be created, written or read (the error text names it) */
 };
 
 /* tile geometry selection (tests force the small-tile build to exercise every slow path) */
@@ -278,6 +279,18 @@ int mkt_bam_commit(mkt_bam* b, size_t n);                                  /* ..
 int mkt_bam_run(mkt_bam* b, int sorted, int level, uint64_t* records, uint64_t* bam_bytes, uint64_t* bai_bytes);
 int mkt_bam_read(mkt_bam* b, int which, uint64_t off, size_t n, const char** ptr);  /* result bytes through the pinned buffers; *ptr valid until the next call but one */
 int mkt_bam_fetch(mkt_bam* b, int which /* 0: the BAM, 1: the BAI */, uint64_t off, char* out, size_t n);
+/* Out-of-core mode, for inputs larger than HBM (samtools sort's sorted runs + merge).  Called before the first byte.  run_bytes:
+ * alignment text per run (0: off -- the single pass above; MKT_BAM_RUNS_AUTO: the single pass while it fits the GPU, runs from where the
+ * text or the rest of the pass would not).  Sorted: every run is sorted on the GPU and written to <tmp_prefix>.runs / <tmp_prefix>.keys, which are removed
+ * again (only when this object created them) on success, on every error return and in mkt_bam_destroy; mkt_bam_pull then merges the runs on the GPU window by window.
+ * Input order (sorted = 0): no temporary files; pieces of the BAM are ready while the input arrives (pull them between adds).
+ * sorted / level must equal those given to mkt_bam_run.  The result equals the single-pass result byte for byte, BAI included.
+ * Until a run is cut (input within the budget) the single pass runs.  With runs, mkt_bam_run reports bam_bytes = 0 (sorted) and
+ * bai_bytes = 0: mkt_bam_stats has both after the last piece. */
+#define MKT_BAM_RUNS_AUTO (~(uint64_t)0)
+int mkt_bam_spill(mkt_bam* b, uint64_t run_bytes, const char* tmp_prefix, int sorted, int level);
+int mkt_bam_pull(mkt_bam* b, const char** ptr, size_t* n);                /* the next piece of the BAM (<= 64 MiB, pinned; *n = 0: none now / the end after run) */
+int mkt_bam_stats(const mkt_bam* b, uint64_t stats[5] /* runs, temporary bytes written, peak device bytes held, BAM bytes so far, BAI bytes */);
 
 /* surviving QNAME groups seen so far (synchronises the context's stream); sharded runs exchange
  * these counts before mkt_finish */

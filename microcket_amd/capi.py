@@ -20,7 +20,7 @@ EXPORTS = [
     "mkt_rmdup_create", "mkt_rmdup_destroy", "mkt_rmdup_error", "mkt_rmdup_reserve", "mkt_rmdup_add", "mkt_rmdup_run", "mkt_rmdup_fetch",
     "mkt_rmdup_begin", "mkt_rmdup_push", "mkt_rmdup_stats",
     "mkt_bam_create", "mkt_bam_destroy", "mkt_bam_error", "mkt_bam_note", "mkt_bam_add", "mkt_bam_add_device", "mkt_bam_run", "mkt_bam_fetch",
-    "mkt_bam_reserve", "mkt_bam_window", "mkt_bam_commit", "mkt_bam_read",
+    "mkt_bam_reserve", "mkt_bam_window", "mkt_bam_commit", "mkt_bam_read", "mkt_bam_spill", "mkt_bam_pull", "mkt_bam_stats",
 ]
 
 
@@ -173,6 +173,9 @@ def load_library():
     L.mkt_bam_window.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.mkt_bam_commit.argtypes = [C.c_void_p, C.c_size_t]
     L.mkt_bam_read.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.mkt_bam_spill.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_int, C.c_int]
+    L.mkt_bam_pull.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    L.mkt_bam_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -566,33 +569,74 @@ def run_sam2pairs(in_sam, mode, prefix, threads=4, ratio=0.5, mapq=10, sam="yes"
     return p.returncode, p.stdout, p.stderr
 
 
-def sam_to_bam(sam: bytes, sorted=True, level=2, device=0, piece=1 << 24, notes=None):
+BAM_RUNS_AUTO = (1 << 64) - 1      # MKT_BAM_RUNS_AUTO: one pass while the text fits the GPU, sorted runs from where it would not
+_tmp_seq = [0]
+
+
+def sam_to_bam(sam: bytes, sorted=True, level=2, device=0, piece=1 << 24, notes=None, run_bytes=None, tmp=None, stats=None):
     """SAM text (header lines + alignment lines) -> (BAM bytes, BAI bytes or b"", records) on the GPU: mkt_bam_* in include/mkt.h.
-    notes: a list that receives mkt_bam_note() (why no index was made), if given."""
+    notes: a list that receives mkt_bam_note() (why no index was made), if given.
+    run_bytes: out-of-core mode (mkt_bam_spill): alignment text per sorted run ("auto" or BAM_RUNS_AUTO: runs only where the text
+    would not fit); tmp: prefix of the temporary files (default: a fresh name in the system's temporary directory).  stats: a dict
+    that receives runs, tmp_bytes and peak_device_bytes, if given."""
     L = load_library()
     h = C.c_void_p()
     rc = L.mkt_bam_create(device, C.byref(h))
     if rc != 0:
         raise MktError(f"mkt_bam_create: {L.mkt_strerror(rc).decode()}")
-    try:
-        for k in range(0, len(sam), piece):
-            part = sam[k:k + piece]
-            rc = L.mkt_bam_add(h, part, len(part))
-            if rc != 0:
-                raise MktError(f"mkt_bam_add: {L.mkt_strerror(rc).decode()}: {L.mkt_bam_error(h).decode()}")
-        nrec, nbam, nbai = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        rc = L.mkt_bam_run(h, 1 if sorted else 0, level, C.byref(nrec), C.byref(nbam), C.byref(nbai))
+
+    def check(rc, what):
         if rc != 0:
-            raise MktError(f"mkt_bam_run: {L.mkt_strerror(rc).decode()}: {L.mkt_bam_error(h).decode()}")
-        outs = []
-        for which, n in ((0, nbam.value), (1, nbai.value)):
-            buf = C.create_string_buffer(max(n, 1))
-            rc = L.mkt_bam_fetch(h, which, 0, buf, n)
-            if rc != 0:
-                raise MktError(f"mkt_bam_fetch: {L.mkt_strerror(rc).decode()}: {L.mkt_bam_error(h).decode()}")
-            outs.append(buf.raw[:n])
+            raise MktError(f"{what}: {L.mkt_strerror(rc).decode()}: {L.mkt_bam_error(h).decode()}")
+
+    try:
+        if run_bytes is None:
+            for k in range(0, len(sam), piece):
+                part = sam[k:k + piece]
+                check(L.mkt_bam_add(h, part, len(part)), "mkt_bam_add")
+            nrec, nbam, nbai = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            check(L.mkt_bam_run(h, 1 if sorted else 0, level, C.byref(nrec), C.byref(nbam), C.byref(nbai)), "mkt_bam_run")
+            outs = []
+            for which, n in ((0, nbam.value), (1, nbai.value)):
+                buf = C.create_string_buffer(max(n, 1))
+                check(L.mkt_bam_fetch(h, which, 0, buf, n), "mkt_bam_fetch")
+                outs.append(buf.raw[:n])
+            bam, bai = outs
+        else:
+            if tmp is None:
+                import tempfile
+                _tmp_seq[0] += 1
+                tmp = os.path.join(tempfile.gettempdir(), f"mkt_bam.{os.getpid()}.{_tmp_seq[0]}")
+            budget = BAM_RUNS_AUTO if run_bytes == "auto" else int(run_bytes)
+            check(L.mkt_bam_spill(h, budget, str(tmp).encode(), 1 if sorted else 0, level), "mkt_bam_spill")
+            parts = []
+
+            def drain():
+                ptr, n = C.c_void_p(), C.c_size_t()
+                while True:
+                    check(L.mkt_bam_pull(h, C.byref(ptr), C.byref(n)), "mkt_bam_pull")
+                    if not n.value:
+                        return
+                    parts.append(C.string_at(ptr.value, n.value))
+
+            for k in range(0, len(sam), piece):
+                part = sam[k:k + piece]
+                check(L.mkt_bam_add(h, part, len(part)), "mkt_bam_add")
+                drain()                    # (input order: pieces are ready while the input arrives)
+            nrec, nbam, nbai = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            check(L.mkt_bam_run(h, 1 if sorted else 0, level, C.byref(nrec), C.byref(nbam), C.byref(nbai)), "mkt_bam_run")
+            drain()
+            st = (C.c_uint64 * 5)()
+            check(L.mkt_bam_stats(h, st), "mkt_bam_stats")
+            buf = C.create_string_buffer(max(st[4], 1))
+            check(L.mkt_bam_fetch(h, 1, 0, buf, st[4]), "mkt_bam_fetch")
+            bam, bai = b"".join(parts), buf.raw[:st[4]]
+        if stats is not None:
+            st = (C.c_uint64 * 5)()
+            check(L.mkt_bam_stats(h, st), "mkt_bam_stats")
+            stats.update(runs=st[0], tmp_bytes=st[1], peak_device_bytes=st[2])
         if notes is not None:
             notes.append(L.mkt_bam_note(h).decode())
-        return outs[0], outs[1], nrec.value
+        return bam, bai, nrec.value
     finally:
         L.mkt_bam_destroy(h)

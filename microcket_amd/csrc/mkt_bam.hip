@@ -24,6 +24,9 @@
 #include <string.h>
 #include <algorithm>
 #include <chrono>
+#include <errno.h>
+#include <fcntl.h>
+#include <unistd.h>
 #include <map>
 #include <string>
 #include <vector>
@@ -876,12 +879,19 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
 // ---- BAI reductions -------------------------------------------------------------------------------------------------------
 struct BaiHead { uint32_t r; int32_t tid; uint32_t bin; uint32_t pad; uint64_t voff; };
 struct BaiRef { unsigned long long n_mapped, n_unmapped, beg, end; };          // beg: min start voffset, end: max end voffset
-__device__ inline uint64_t voffset(uint64_t uoff, const uint64_t* coff) {
+// Where the records of one launch sit in the file: record r starts at the uncompressed offset ubase + off[r]; coff[k] is the
+// compressed offset of block blk0 + k relative to cbase (the compressed bytes before block blk0).  One launch over the whole
+// file: {hdr_len, 0, 0}; a window of a stream: the blocks compressed so far lie before blk0.
+struct VoffMap { uint64_t ubase, blk0, cbase; };
+__device__ inline uint64_t voffset(uint64_t uoff, const uint64_t* coff, const VoffMap& vm) {
     const uint64_t b = uoff / BGZF_RAW;
-    return (coff[b] << 16) | (uoff - b * BGZF_RAW);
+    return ((vm.cbase + coff[b - vm.blk0]) << 16) | (uoff - b * BGZF_RAW);
 }
-__global__ void k_bai(const BamIdx* idx, const uint64_t* off /* [n + 1] */, uint64_t n, uint64_t hdr_len, const uint64_t* coff, const uint64_t* lin_off, uint32_t nref,
-                      unsigned long long* lin, BaiRef* refs, uint64_t* head_flag /* [n]: 1 where a run of records in one bin starts */, unsigned long long* no_coor) {
+// prev: the record before idx[0] (the last of the previous window), or null.  no_coor: [0] records without coordinates, [1] "no
+// index possible", [2] atomicMin of the virtual offsets of records without coordinates (the first of them: they sort last).
+__global__ void k_bai(const BamIdx* idx, const uint64_t* off /* [n + 1] */, uint64_t n, VoffMap vm, const uint64_t* coff, const uint64_t* lin_off, uint32_t nref,
+                      unsigned long long* lin, BaiRef* refs, uint64_t* head_flag /* [n]: 1 where a run of records in one bin starts */, unsigned long long* no_coor,
+                      const BamIdx* prev) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n) head_flag[r] = 0;
     const int lane = threadIdx.x & 63;
@@ -890,11 +900,14 @@ __global__ void k_bai(const BamIdx* idx, const uint64_t* off /* [n + 1] */, uint
     if (r < n) x = idx[r];
     const bool placed = r < n && x.tid >= 0;
     const uint64_t nc = __ballot(r < n && x.tid < 0);
-    if (nc && lane == (int)__builtin_ctzll(nc)) atomicAdd(no_coor, (unsigned long long)__popcll(nc));
+    if (nc && lane == (int)__builtin_ctzll(nc)) {
+        atomicAdd(no_coor, (unsigned long long)__popcll(nc));
+        atomicMin(no_coor + 2, (unsigned long long)voffset(vm.ubase + off[r], coff, vm));
+    }
     const uint64_t pm = __ballot(placed);
     if (!pm) return;
     uint64_t v0 = 0, v1 = 0;
-    if (placed) { v0 = voffset(hdr_len + off[r], coff); v1 = voffset(hdr_len + off[r + 1], coff); }
+    if (placed) { v0 = voffset(vm.ubase + off[r], coff, vm); v1 = voffset(vm.ubase + off[r + 1], coff, vm); }
     const uint32_t bin = x.bin & 0xFFFFu;
     const bool unm = (x.bin >> 18) & 1u;                           // FLAG 0x4
     // per-reference counts and file range: the records are sorted, so a wave nearly always holds ONE reference -> one set of atomics
@@ -929,42 +942,170 @@ __global__ void k_bai(const BamIdx* idx, const uint64_t* off /* [n + 1] */, uint
     // a record that reaches past its reference's LN (the linear index is sized by LN) or past the 2^29 bases a BAI can address:
     // no index can describe it (no_coor[1] != 0 -> the host writes none and says why)
     if ((uint64_t)w1 >= nwin || x.end > (1 << 29) || bin > 37449u) atomicOr(no_coor + 1, 1ull);
-    bool head = r == 0;
-    if (!head) { const BamIdx y = idx[r - 1]; head = y.tid != x.tid || (y.bin & 0xFFFFu) != bin; }
+    bool head = r == 0 && !prev;
+    if (!head) { const BamIdx y = r ? idx[r - 1] : *prev; head = y.tid != x.tid || (y.bin & 0xFFFFu) != bin; }
     if (head) head_flag[r] = 1;
 }
 // the run starts, in file order (head_pos = exclusive scan of head_flag)
-__global__ void k_bai_heads(const BamIdx* idx, const uint64_t* off, uint64_t n, uint64_t hdr_len, const uint64_t* coff, const uint64_t* head_pos, BaiHead* heads) {
+__global__ void k_bai_heads(const BamIdx* idx, const uint64_t* off, uint64_t n, VoffMap vm, const uint64_t* coff, const uint64_t* head_pos, BaiHead* heads, const BamIdx* prev) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const BamIdx x = idx[r];
     if (x.tid < 0) return;
-    bool head = r == 0;
-    if (!head) { const BamIdx y = idx[r - 1]; head = y.tid != x.tid || ((y.bin ^ x.bin) & 0xFFFFu) != 0u; }
+    bool head = r == 0 && !prev;
+    if (!head) { const BamIdx y = r ? idx[r - 1] : *prev; head = y.tid != x.tid || ((y.bin ^ x.bin) & 0xFFFFu) != 0u; }
     if (!head) return;
     BaiHead h;
-    h.r = (uint32_t)r; h.tid = x.tid; h.bin = x.bin & 0xFFFFu; h.pad = 0; h.voff = voffset(hdr_len + off[r], coff);
+    h.r = (uint32_t)r; h.tid = x.tid; h.bin = x.bin & 0xFFFFu; h.pad = 0; h.voff = voffset(vm.ubase + off[r], coff, vm);
     heads[head_pos[r]] = h;
+}
+
+// ---- out-of-core mode: run formation and the merge of the runs -----------------------------------------------------------------
+// What a run file keeps per record besides its bytes, in the run's sorted order: the sort key, the record's size, what the index
+// needs.
+struct SpillRec { uint64_t hi; uint32_t size, pad; BamIdx ix; };
+static_assert(sizeof(SpillRec) == 32, "run key file layout");
+
+// position + 1 of the last (mode 0: atomicMax) or first (mode 1: atomicMin, ~0 = none) newline in text[a, b)
+__global__ void k_find_nl(const uint8_t* text, uint64_t a, uint64_t b, int first, unsigned long long* out) {
+    unsigned long long best = first ? ~0ull : 0ull;
+    for (uint64_t p = a + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < b; p += (uint64_t)gridDim.x * blockDim.x)
+        if (text[p] == '\n') { const unsigned long long v = p + 1; best = first ? (v < best ? v : best) : (v > best ? v : best); }
+    if (first) { if (best != ~0ull) atomicMin(out, best); }
+    else if (best) atomicMax(out, best);
+}
+// a run's records in sorted order -> what its key file holds
+__global__ void k_spill_recs(const SortRec* rec, const uint32_t* size, const BamIdx* idx, uint64_t n, SpillRec* out) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    SpillRec x;
+    x.hi = rec[r].hi; x.size = size[rec[r].idx]; x.pad = 0; x.ix = idx[r];
+    out[r] = x;
+}
+// merge: the safe records of a round, concatenated in run order -> sort records (idx = place in the concatenation)
+__global__ void k_merge_keys(const SpillRec* in, uint64_t n, SortRec* rec) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    SortRec r;
+    r.hi = in[i].hi; r.lo = 0; r.idx = (uint32_t)i;
+    rec[i] = r;
+}
+__global__ void k_merge_sizes(const SortRec* rec, const SpillRec* in, uint64_t n, uint64_t* off, BamIdx* idx) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const SpillRec& x = in[rec[r].idx];
+    off[r] = x.size;
+    idx[r] = x.ix;
+}
+// the records in merged order: one wave per record, 64 consecutive bytes per step (a record is a few hundred bytes; source
+// and destination offsets are arbitrary, so the lanes move single bytes -- coalesced across the wave)
+constexpr int MG_WAVES = 4;
+__global__ __launch_bounds__(64 * MG_WAVES) void k_merge_gather(const uint8_t* src, const uint64_t* src_off, const SortRec* rec, const SpillRec* in, uint64_t n,
+                                                                const uint64_t* off, uint8_t* dst) {
+    const uint64_t r = (uint64_t)blockIdx.x * MG_WAVES + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t j = rec[r].idx;
+    const uint32_t size = in[j].size;
+    const uint8_t* s = src + src_off[j];
+    uint8_t* d = dst + off[r];
+    for (uint32_t i = lane; i < size; i += 64u) d[i] = s[i];
 }
 
 }  // namespace mkt
 
 // ---------------------------------------------------------------------------------------------------------------------------
+struct BamHeader {                                     // the parsed header: BAM header bytes, reference dictionary, the lookup table's host side
+    std::string hdr;
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+    uint32_t tcap = 64;
+    std::vector<unsigned long long> th;
+    std::vector<int32_t> tidv;
+    std::vector<uint32_t> noff;
+    std::string blob;
+};
+struct SpillRun { uint64_t data_off = 0, key_off = 0, nrec = 0; };      // a sorted run: its records and keys in the two temporary files
+struct SpillCur {                                      // a run's window during the merge
+    uint64_t next = 0, data_next = 0;                  // first record / byte not yet loaded
+    std::vector<SpillRec> keys;                        // loaded, not yet emitted
+    std::string bytes;
+};
+struct BgzfStream {                                    // BGZF output of a stream: d_win = the partial last block (carry bytes), then the current window
+    uint8_t* d_win = nullptr; size_t cap = 0;
+    uint64_t carry = 0, blk0 = 0, cbase = 0;           // blk0: file block at d_win[0]; cbase: compressed bytes before it
+    uint8_t* d_comp = nullptr; size_t comp_cap = 0;
+    uint64_t* d_csize = nullptr; size_t csize_cap = 0;
+    uint32_t* d_scratch = nullptr; size_t scratch_cap = 0;
+    uint8_t* d_pack = nullptr; size_t pack_cap = 0;
+    uint64_t* d_hflag = nullptr; size_t hflag_cap = 0;
+    BaiHead* d_heads = nullptr; size_t heads_cap = 0;
+};
+struct BaiAcc {                                        // the index across the windows of a stream: small arrays that stay resident
+    bool on = false, has_prev = false;
+    std::vector<uint64_t> lin_off;
+    uint64_t* d_lin_off = nullptr;
+    unsigned long long *d_lin = nullptr, *d_nocoor = nullptr;
+    BaiRef* d_refs = nullptr;
+    BamIdx* d_prev = nullptr;
+    std::vector<BaiHead> heads;
+    uint64_t end_voff = 0;
+};
+struct MergeBufs {                                     // one merge round on the device (grow-only)
+    SpillRec* rec = nullptr; size_t rec_cap = 0;
+    uint64_t* src = nullptr; size_t src_cap = 0;
+    uint8_t* bytes = nullptr; size_t bytes_cap = 0;
+    SortRec *rA = nullptr, *rB = nullptr; size_t rA_cap = 0, rB_cap = 0;
+    uint32_t* hist = nullptr; size_t hist_cap = 0;
+    uint64_t* off = nullptr; size_t off_cap = 0;
+    BamIdx* idx = nullptr; size_t idx_cap = 0;
+};
+
 struct mkt_bam {
     int device = 0;
     hipStream_t stream = nullptr;
     uint8_t* d_text = nullptr; size_t cap = 0, len = 0;
+    uint64_t tstart = 0;                                // text before this offset has gone into runs (out-of-core mode)
     bool header_done = false, ran = false;
     std::string header, pending;
     uint8_t* d_bam = nullptr; uint64_t bam_len = 0;
     std::string bai;
     uint64_t records = 0;
-    // pinned staging for callers that move files (mkt_bam_window / _commit / _read): two slots, used alternately
+    // pinned staging for callers that move files (mkt_bam_window / _commit / _read / _pull): two slots, used alternately
     char* h_io[2] = {nullptr, nullptr};
     hipEvent_t ev_io[2] = {nullptr, nullptr};
     bool io_busy[2] = {false, false};
     int io_slot = 0;
     std::string err, note;
+    // device bytes held by this object (every allocation goes through dalloc / dfree)
+    std::map<void*, size_t> dmem;
+    size_t dev_now = 0, dev_peak = 0;
+    size_t dev_limit = 0;                               // $MKT_BAM_DEVICE_LIMIT: device bytes this object may hold (as if HBM ended there)
+    // out-of-core mode (mkt_bam_spill)
+    bool spill_set = false, autob = false, spilled = false;
+    uint64_t budget = 0;                                // text bytes per run; 0 = single pass
+    int sp_sorted = 1, sp_level = 2;
+    std::string tmp_path[2];                            // records, keys
+    int tmp_fd[2] = {-1, -1};
+    bool tmp_made[2] = {false, false};                  // created by this object (only those are removed)
+    char* h_stage = nullptr;                            // pinned staging of run data on its way to the temporary files
+    uint64_t tmp_bytes = 0, nruns = 0, rounds = 0;
+    std::vector<SpillRun> runs;
+    std::vector<SpillCur> cur;
+    bool hdr_ready = false;
+    BamHeader H;
+    RefTab rt{};
+    void* d_rt[4] = {nullptr, nullptr, nullptr, nullptr};
+    CrcTabs* d_ct = nullptr;
+    uint32_t* d_err = nullptr;
+    unsigned long long* d_nl = nullptr;
+    BgzfStream bs;
+    BaiAcc bx;
+    MergeBufs mb;
+    std::string outq; size_t outq_pos = 0;              // compressed bytes not yet pulled
+    uint64_t out_total = 0, pull_off = 0;
+    bool merging = false, done = false;
+    double t_form = 0, t_merge = 0;
 };
 constexpr size_t kBamIoCap = (size_t)64 << 20;
 static int bfail(mkt_bam* s, int code, const char* fmt, ...) {
@@ -978,27 +1119,66 @@ static int bfail(mkt_bam* s, int code, const char* fmt, ...) {
 }
 #define BCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bfail((s), MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 
+static void dtrack(mkt_bam* s, void* p, size_t n) {
+    s->dmem[p] = n;
+    s->dev_now += n;
+    if (s->dev_now > s->dev_peak) s->dev_peak = s->dev_now;
+}
+static hipError_t dalloc(mkt_bam* s, void** p, size_t n) {
+    *p = nullptr;
+    if (s->dev_limit && s->dev_now + n > s->dev_limit) return hipErrorOutOfMemory;
+    const hipError_t e = hipMalloc(p, n);
+    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return e; }
+    dtrack(s, *p, n);
+    return hipSuccess;
+}
+static uint64_t device_free(mkt_bam* s) {                           // what this object may still allocate
+    size_t fr = 0, tot = 0;
+    (void)hipMemGetInfo(&fr, &tot);
+    if (s->dev_limit) { const uint64_t l = s->dev_limit > s->dev_now ? s->dev_limit - s->dev_now : 0; if (l < fr) fr = (size_t)l; }
+    return fr;
+}
+static void dfree(mkt_bam* s, void* p) {
+    if (!p) return;
+    auto it = s->dmem.find(p);
+    if (it != s->dmem.end()) { s->dev_now -= it->second; s->dmem.erase(it); }
+    (void)hipFree(p);
+}
+// a device buffer that only grows (its contents are not kept)
+template <typename T>
+static int dgrow(mkt_bam* s, T*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap && p) return MKT_OK;
+    dfree(s, p); p = nullptr; cap = 0;
+    const hipError_t e = dalloc(s, (void**)&p, bytes);
+    if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    cap = bytes;
+    return MKT_OK;
+}
+
+// room for `need` bytes of text counted from tstart (the text before tstart is dropped)
 static int bam_reserve(mkt_bam* s, size_t need) {
-    if (need <= s->cap) return MKT_OK;
+    if (s->tstart + need <= s->cap) return MKT_OK;
     size_t ncap = s->cap ? s->cap : ((size_t)64 << 20);
+    if (!s->cap && s->budget && ncap > 2 * s->budget + ((size_t)1 << 20)) ncap = 2 * s->budget + ((size_t)1 << 20);     // runs: sized by the budget
     while (ncap < need) ncap *= 2;
     uint8_t* nb = nullptr;
     // (doubling keeps old and new side by side during the copy; when that does not fit: just enough; when that does not either, the
     //  input is larger than one GPU takes -- text + records + compressed blocks are resident together, ~2.2 x the .sam: INTEGRATION.md)
-    hipError_t e = hipMalloc((void**)&nb, ncap + 64);
-    if (e != hipSuccess) { (void)hipGetLastError(); ncap = need + ((size_t)64 << 20); e = hipMalloc((void**)&nb, ncap + 64); }
+    hipError_t e = dalloc(s, (void**)&nb, ncap + 64);
+    if (e != hipSuccess) { ncap = need + ((size_t)64 << 20); e = dalloc(s, (void**)&nb, ncap + 64); }
+    if (e != hipSuccess) { ncap = need; e = dalloc(s, (void**)&nb, ncap + 64); }
     if (e != hipSuccess) {
-        (void)hipGetLastError();
         size_t fr = 0, tot = 0;
         (void)hipMemGetInfo(&fr, &tot);
         return bfail(s, MKT_E_NOMEM, "the SAM input (%.1f GB so far) does not fit this GPU (%.1f of %.1f GB free): sam2bam keeps the whole input in HBM "
-                     "(samtools sort spills to disk instead); convert the modes' .sam files one by one", (double)need / 1e9, (double)fr / 1e9, (double)tot / 1e9);
+                     "unless it is given a run budget (sam2bam -m, mkt_bam_spill); convert the modes' .sam files one by one", (double)need / 1e9, (double)fr / 1e9, (double)tot / 1e9);
     }
     if (s->d_text) {
         BCHK(s, hipStreamSynchronize(s->stream));
-        if (s->len) BCHK(s, hipMemcpy(nb, s->d_text, s->len, hipMemcpyDeviceToDevice));
-        BCHK(s, hipFree(s->d_text));
+        if (s->len > s->tstart) BCHK(s, hipMemcpy(nb, s->d_text + s->tstart, s->len - s->tstart, hipMemcpyDeviceToDevice));
+        dfree(s, s->d_text);
     }
+    s->len -= s->tstart; s->tstart = 0;
     s->d_text = nb; s->cap = ncap;
     return MKT_OK;
 }
@@ -1024,153 +1204,11 @@ static void crc_tables(CrcTabs* ct) {
 static void put_le32(std::string& s, uint32_t v) { char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)}; s.append(b, 4); }
 static void put_le64(std::string& s, uint64_t v) { put_le32(s, (uint32_t)v); put_le32(s, (uint32_t)(v >> 32)); }
 
-extern "C" {
-
-int mkt_bam_create(int device, mkt_bam** out) {
-    if (!out) return MKT_E_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MKT_E_NO_DEVICE;
-    if (device < 0 || device >= ndev) return MKT_E_ARG;
-    mkt_bam* s = new mkt_bam();
-    s->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return MKT_E_HIP; }
-    *out = s;
-    return MKT_OK;
-}
-void mkt_bam_destroy(mkt_bam* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    if (s->d_text) (void)hipFree(s->d_text);
-    if (s->d_bam) (void)hipFree(s->d_bam);
-    for (int k = 0; k < 2; ++k) { if (s->h_io[k]) (void)hipHostFree(s->h_io[k]); if (s->ev_io[k]) (void)hipEventDestroy(s->ev_io[k]); }
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-const char* mkt_bam_error(const mkt_bam* s) { return s ? s->err.c_str() : ""; }
-const char* mkt_bam_note(const mkt_bam* s) { return s ? s->note.c_str() : ""; }
-
-// The next bytes of the SAM stream (any chunking).  Leading '@' lines are the header; everything from the first other line on
-// is alignment text and goes to the device.
-static int bam_add_bytes(mkt_bam* s, const char* bytes, size_t n, bool pinned_async) {
-    if (s->ran) return bfail(s, MKT_E_STATE, "add after run");
-    BCHK(s, hipSetDevice(s->device));
-    if (!s->header_done) {
-        s->pending.append(bytes, n);
-        size_t p = 0;
-        for (;;) {
-            if (p >= s->pending.size()) break;
-            if (s->pending[p] != '@') { s->header_done = true; break; }
-            const size_t e = s->pending.find('\n', p);
-            if (e == std::string::npos) break;              // an unfinished header line: wait for more
-            s->header.append(s->pending, p, e + 1 - p);
-            p = e + 1;
-        }
-        s->pending.erase(0, p);
-        if (!s->header_done) return MKT_OK;
-        std::string rest;
-        rest.swap(s->pending);
-        if (rest.empty()) return MKT_OK;
-        int rc = bam_reserve(s, s->len + rest.size() + 1);
-        if (rc) return rc;
-        BCHK(s, hipMemcpy(s->d_text + s->len, rest.data(), rest.size(), hipMemcpyHostToDevice));
-        s->len += rest.size();
-        return MKT_OK;
-    }
-    int rc = bam_reserve(s, s->len + n + 1);
-    if (rc) return rc;
-    if (n) BCHK(s, hipMemcpyAsync(s->d_text + s->len, bytes, n, hipMemcpyHostToDevice, s->stream));
-    if (!pinned_async) BCHK(s, hipStreamSynchronize(s->stream));       // the caller may reuse `bytes`
-    s->len += n;
-    return MKT_OK;
-}
-int mkt_bam_add(mkt_bam* s, const char* bytes, size_t n) {
-    if (!s || (n && !bytes)) return MKT_E_ARG;
-    return bam_add_bytes(s, bytes, n, false);
-}
-// room for `bytes` of alignment text, so that the buffer does not grow (and get copied) while the stream comes in
-int mkt_bam_reserve(mkt_bam* s, size_t bytes) {
-    if (!s) return MKT_E_ARG;
-    if (s->ran) return bfail(s, MKT_E_STATE, "reserve after run");
-    BCHK(s, hipSetDevice(s->device));
-    return bam_reserve(s, bytes + 1);
-}
-static int bam_io_slot(mkt_bam* s, int k) {
-    if (!s->h_io[k]) {
-        BCHK(s, hipHostMalloc((void**)&s->h_io[k], kBamIoCap, hipHostMallocDefault));
-        BCHK(s, hipEventCreateWithFlags(&s->ev_io[k], hipEventDisableTiming));
-    }
-    if (s->io_busy[k]) { BCHK(s, hipEventSynchronize(s->ev_io[k])); s->io_busy[k] = false; }
-    return MKT_OK;
-}
-// A pinned host buffer for the next bytes of the SAM stream (read a file straight into it), then mkt_bam_commit: the copy to the
-// GPU runs while the caller fills the other buffer.
-int mkt_bam_window(mkt_bam* s, char** buf, size_t* cap) {
-    if (!s || !buf || !cap) return MKT_E_ARG;
-    if (s->ran) return bfail(s, MKT_E_STATE, "window after run");
-    BCHK(s, hipSetDevice(s->device));
-    int rc = bam_io_slot(s, s->io_slot);
-    if (rc) return rc;
-    *buf = s->h_io[s->io_slot]; *cap = kBamIoCap;
-    return MKT_OK;
-}
-int mkt_bam_commit(mkt_bam* s, size_t n) {
-    if (!s || n > kBamIoCap) return MKT_E_ARG;
-    const int k = s->io_slot;
-    if (!s->h_io[k]) return bfail(s, MKT_E_STATE, "commit without window");
-    int rc = bam_add_bytes(s, s->h_io[k], n, true);
-    if (rc) return rc;
-    BCHK(s, hipEventRecord(s->ev_io[k], s->stream));
-    s->io_busy[k] = true;
-    s->io_slot = k ^ 1;
-    return MKT_OK;
-}
-// alignment lines that are already on the device (no header lines)
-int mkt_bam_add_device(mkt_bam* s, const void* d_bytes, size_t n) {
-    if (!s || (n && !d_bytes)) return MKT_E_ARG;
-    if (s->ran) return bfail(s, MKT_E_STATE, "add after run");
-    if (!s->pending.empty()) return bfail(s, MKT_E_STATE, "device text after an unfinished header line");
-    s->header_done = true;
-    BCHK(s, hipSetDevice(s->device));
-    int rc = bam_reserve(s, s->len + n + 1);
-    if (rc) return rc;
-    if (n) BCHK(s, hipMemcpyAsync(s->d_text + s->len, d_bytes, n, hipMemcpyDeviceToDevice, s->stream));
-    BCHK(s, hipStreamSynchronize(s->stream));
-    s->len += n;
-    return MKT_OK;
-}
-
-int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* bam_bytes, uint64_t* bai_bytes) {
-    if (!s) return MKT_E_ARG;
-    if (s->ran) return bfail(s, MKT_E_STATE, "run twice");
-    BCHK(s, hipSetDevice(s->device));
-    if (records) *records = 0;
-    if (bam_bytes) *bam_bytes = 0;
-    if (bai_bytes) *bai_bytes = 0;
-    s->ran = true;
-    if (!s->pending.empty()) {                                     // a last header line without newline, or a file of header lines only
-        if (s->pending[0] == '@') { s->header += s->pending; s->header += '\n'; s->pending.clear(); }
-    }
-    hipStream_t st = s->stream;
-    const bool verbose = getenv("MKT_VERBOSE") != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {                            // (call sites follow a stream synchronisation)
-        if (!verbose) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
-    BCHK(s, hipStreamSynchronize(st));                            // (copies of mkt_bam_commit may still be on their way)
-    if (s->len) {
-        char last = 0;
-        BCHK(s, hipMemcpy(&last, s->d_text + s->len - 1, 1, hipMemcpyDeviceToHost));
-        if (last != '\n') { const char nl = '\n'; int rc = bam_reserve(s, s->len + 2); if (rc) return rc; BCHK(s, hipMemcpy(s->d_text + s->len, &nl, 1, hipMemcpyHostToDevice)); ++s->len; }
-    }
-    // ---- header: text (with @HD SO:coordinate when sorting) and the reference dictionary from @SQ
+// header: text (with @HD SO:coordinate when sorting), the reference dictionary from @SQ, the BAM header bytes, the name table
+static int bam_parse_header(mkt_bam* s, bool sorted, BamHeader& H) {
     std::string text = s->header;
-    std::vector<std::string> names;
-    std::vector<uint32_t> lens;
+    std::vector<std::string>& names = H.names;
+    std::vector<uint32_t>& lens = H.lens;
     {
         size_t p = 0;
         while (p < text.size()) {
@@ -1213,22 +1251,24 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
         }
     }
     const uint32_t nref = (uint32_t)names.size();
-    std::string hdr;                                               // SAMv1 4.2: magic, l_text, text, n_ref, (l_name, name, l_ref)*
+    std::string& hdr = H.hdr;                                      // SAMv1 4.2: magic, l_text, text, n_ref, (l_name, name, l_ref)*
     hdr.append("BAM\1", 4);
     put_le32(hdr, (uint32_t)text.size());
     hdr += text;
     put_le32(hdr, nref);
     for (uint32_t i = 0; i < nref; ++i) { put_le32(hdr, (uint32_t)names[i].size() + 1); hdr += names[i]; hdr += '\0'; put_le32(hdr, lens[i]); }
-    const uint64_t hdr_len = hdr.size();
     // reference table for the device
-    uint32_t tcap = 64;
+    uint32_t& tcap = H.tcap;
+    tcap = 64;
     while (tcap < 4 * nref + 4) tcap <<= 1;
-    std::vector<unsigned long long> th(tcap, 0ull);
-    std::vector<int32_t> tidv(tcap, -1);
-    std::vector<uint32_t> noff(nref + 1, 0);
-    std::string blob;
+    H.th.assign(tcap, 0ull);
+    H.tidv.assign(tcap, -1);
+    H.noff.assign(nref + 1, 0);
+    std::vector<unsigned long long>& th = H.th;
+    std::vector<int32_t>& tidv = H.tidv;
+    std::string& blob = H.blob;
     for (uint32_t i = 0; i < nref; ++i) {
-        noff[i] = (uint32_t)blob.size(); blob += names[i];
+        H.noff[i] = (uint32_t)blob.size(); blob += names[i];
         unsigned long long h = 0xcbf29ce484222325ull;
         for (unsigned char c : names[i]) { h ^= c; h *= 0x100000001b3ull; }
         if (!h) h = 1;
@@ -1238,13 +1278,850 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
         if (dup) return bfail(s, MKT_E_ARG, "reference name %s twice in the header", names[i].c_str());
         th[k] = h; tidv[k] = (int32_t)i;
     }
-    noff[nref] = (uint32_t)blob.size();
+    H.noff[nref] = (uint32_t)blob.size();
+    return MKT_OK;
+}
+
+static bool bai_possible(const BamHeader& H) {                     // the BAI format ends at 2^29 bases per reference
+    for (uint32_t l : H.lens) if (l > (1u << 29)) return false;
+    return true;
+}
+static void bai_lin_off(const BamHeader& H, std::vector<uint64_t>& lin_off) {
+    const uint32_t nref = (uint32_t)H.names.size();
+    lin_off.assign(nref + 1, 0);
+    for (uint32_t i = 0; i < nref; ++i) lin_off[i + 1] = lin_off[i] + ((uint64_t)H.lens[i] >> 14) + 2;
+}
+// The .bai from what the reductions gathered: the bin-run heads in file order, per-reference counts and ranges, the linear index,
+// the virtual offset where the records without coordinates start (or the data ends).
+static void bai_assemble(mkt_bam* s, uint32_t nref, const std::vector<uint64_t>& lin_off, const std::vector<BaiRef>& refs, std::vector<unsigned long long>& lin,
+                         const std::vector<BaiHead>& heads, unsigned long long no_coor, unsigned long long beyond, uint64_t off_end) {
+    const uint64_t nheads = heads.size(), nlin = lin_off[nref];
+    // per reference (the run starts come in file order = by reference): a stable counting sort by bin
+    std::vector<uint32_t> bin_cnt(65536, 0), bin_at(65536, 0);      // (every 16-bit value: a record past 2^29 bases carries a bin beyond 37449; no index is kept then, see below)
+    std::vector<uint32_t> order(nheads);
+    std::vector<std::pair<size_t, size_t>> ref_range(nref, {0, 0});
+    {
+        size_t i = 0;
+        for (uint32_t t = 0; t < nref && i < nheads; ++t) {
+            size_t j = i;
+            while (j < nheads && (uint32_t)heads[j].tid == t) ++j;
+            ref_range[t] = {i, j};
+            i = j;
+        }
+    }
+    std::string& o = s->bai;                                        // SAMv1 5.2
+    o.reserve(64 + (size_t)nheads * 28 + nlin * 8 + (size_t)nref * 64);
+    o.append("BAI\1", 4);
+    put_le32(o, nref);
+    for (uint32_t t = 0; t < nref; ++t) {
+        const bool any = refs[t].n_mapped + refs[t].n_unmapped > 0;
+        const size_t i0 = ref_range[t].first, i1 = ref_range[t].second;
+        std::vector<uint32_t> used;                                 // the bins of this reference, ascending
+        for (size_t i = i0; i < i1; ++i) if (bin_cnt[heads[i].bin]++ == 0) used.push_back(heads[i].bin);
+        std::sort(used.begin(), used.end());
+        uint32_t at = 0;
+        for (uint32_t b : used) { bin_at[b] = at; at += bin_cnt[b]; }
+        for (size_t i = i0; i < i1; ++i) order[i0 + bin_at[heads[i].bin]++] = (uint32_t)i;
+        put_le32(o, (uint32_t)used.size() + (any ? 1u : 0u));
+        size_t k = i0;
+        for (uint32_t b : used) {
+            put_le32(o, b);
+            put_le32(o, bin_cnt[b]);
+            for (uint32_t c = 0; c < bin_cnt[b]; ++c, ++k) {
+                const size_t i = order[k];
+                put_le64(o, heads[i].voff);
+                put_le64(o, i + 1 < nheads ? heads[i + 1].voff : off_end);
+            }
+            bin_cnt[b] = 0;
+        }
+        if (any) {                                                  // the pseudo-bin: file range of the reference, mapped / unmapped counts
+            put_le32(o, 37450u); put_le32(o, 2u);
+            put_le64(o, refs[t].beg); put_le64(o, refs[t].end);
+            put_le64(o, refs[t].n_mapped); put_le64(o, refs[t].n_unmapped);
+        }
+        // linear index: up to the last window that a record touched; empty windows take the next one's offset
+        const uint64_t a = lin_off[t], b = lin_off[t + 1];
+        uint64_t last = a;
+        for (uint64_t k = a; k < b; ++k) if (lin[k] != ~0ull) last = k + 1;
+        unsigned long long nextv = 0;
+        for (uint64_t k = last; k > a;) { --k; if (lin[k] == ~0ull) lin[k] = nextv; else nextv = lin[k]; }
+        put_le32(o, (uint32_t)(last - a));
+        for (uint64_t k = a; k < last; ++k) put_le64(o, lin[k]);
+    }
+    put_le64(o, no_coor);
+    if (beyond) {
+        s->bai.clear();
+        s->note = "no index written: a record lies past its reference's LN or past the 2^29 bases a BAI index can address (samtools index would need -c)";
+    }
+}
+static const char kNoIndexLongRef[] = "no index written: a reference is longer than the 2^29 bases a BAI index can address (samtools index would need -c)";
+static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static constexpr uint64_t kDzPerBlock = (uint64_t)DZ_WAVES * DZ_WAVE_SCRATCH * sizeof(uint32_t);     // deflate scratch per block of a launch
+// nblocks BGZF blocks of raw[0, nraw) -> comp (BGZF_STRIDE apart), their sizes -> csize; `batch` blocks per deflate launch
+static void bgzf_launch(const uint8_t* raw, uint64_t nraw, uint64_t nblocks, int level, const CrcTabs* ct, uint8_t* comp, uint64_t* csize, uint32_t* scratch,
+                        uint64_t batch, hipStream_t st) {
+    if (level > 0) {
+        for (uint64_t fb = 0; fb < nblocks; fb += batch) {
+            const unsigned g = (unsigned)(nblocks - fb < batch ? nblocks - fb : batch);
+            if (level >= 2) hipLaunchKernelGGL(k_bgzf_deflate<true>, dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch);
+            else hipLaunchKernelGGL(k_bgzf_deflate<false>, dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch);
+        }
+    } else {
+        hipLaunchKernelGGL(k_bgzf_stored, dim3((unsigned)nblocks), dim3(BWG), 0, st, raw, nraw, ct, comp, csize);
+    }
+}
+
+// ---- out-of-core mode ------------------------------------------------------------------------------------------------------
+// Run formation: the text is cut into runs of at most `budget` bytes of whole lines (a longer line is a run of its own); every run
+// goes through the single-pass kernels (line index, keys, stable radix sort, size scan, records) and its sorted records are
+// appended to <prefix>.runs, their keys, sizes and index fields (SpillRec) to <prefix>.keys.  The merge reads every run in
+// windows; per round the records up to the smallest last-loaded record of the runs that still have records on disk, in the
+// order T = (key, run, place in the run), are safe: their keys, concatenated in run order, go through the same stable radix
+// sort, a scan of their sizes gives each its output offset, and k_merge_gather puts the bytes in place.  T is the order the
+// stable sort of the whole input gives, so the merged file is the single-pass file byte for byte.  BGZF blocks are cut at the
+// same raw offsets (the partial last block of a window is carried into the next) and the index reductions run per window.
+static void spill_remove(mkt_bam* s) {
+    for (int k = 0; k < 2; ++k) {
+        if (s->tmp_fd[k] >= 0) { close(s->tmp_fd[k]); s->tmp_fd[k] = -1; }
+        if (s->tmp_made[k]) { (void)unlink(s->tmp_path[k].c_str()); s->tmp_made[k] = false; }
+    }
+}
+static int spill_guard(mkt_bam* s, int rc) {                       // on any error: no temporary file stays behind
+    if (rc != MKT_OK && s) spill_remove(s);
+    return rc;
+}
+static void spill_free_device(mkt_bam* s) {
+    BgzfStream& b = s->bs;
+    for (void* p : {(void*)b.d_win, (void*)b.d_comp, (void*)b.d_csize, (void*)b.d_scratch, (void*)b.d_pack, (void*)b.d_hflag, (void*)b.d_heads}) dfree(s, p);
+    b = BgzfStream();
+    MergeBufs& m = s->mb;
+    for (void* p : {(void*)m.rec, (void*)m.src, (void*)m.bytes, (void*)m.rA, (void*)m.rB, (void*)m.hist, (void*)m.off, (void*)m.idx}) dfree(s, p);
+    m = MergeBufs();
+    BaiAcc& x = s->bx;
+    for (void* p : {(void*)x.d_lin_off, (void*)x.d_lin, (void*)x.d_nocoor, (void*)x.d_refs, (void*)x.d_prev}) dfree(s, p);
+    x.d_lin_off = nullptr; x.d_lin = nullptr; x.d_nocoor = nullptr; x.d_refs = nullptr; x.d_prev = nullptr;
+    for (int k = 0; k < 4; ++k) { dfree(s, s->d_rt[k]); s->d_rt[k] = nullptr; }
+    dfree(s, s->d_ct); s->d_ct = nullptr;
+    dfree(s, s->d_err); s->d_err = nullptr;
+    dfree(s, s->d_nl); s->d_nl = nullptr;
+}
+static int write_all(mkt_bam* s, int k, const void* p, size_t n) {
+    const char* c = (const char*)p;
+    while (n) {
+        const ssize_t w = write(s->tmp_fd[k], c, n);
+        if (w < 0) { if (errno == EINTR) continue; return bfail(s, MKT_E_IO, "write error on the temporary file %s: %s", s->tmp_path[k].c_str(), strerror(errno)); }
+        c += w; n -= (size_t)w; s->tmp_bytes += (uint64_t)w;
+    }
+    return MKT_OK;
+}
+// device bytes -> temporary file k, 64 MiB at a time through pinned memory
+static int write_dev(mkt_bam* s, int k, const void* d, uint64_t n) {
+    if (!s->h_stage) BCHK(s, hipHostMalloc((void**)&s->h_stage, kBamIoCap, hipHostMallocDefault));
+    for (uint64_t o = 0; o < n; o += kBamIoCap) {
+        const size_t m = (size_t)(n - o < kBamIoCap ? n - o : kBamIoCap);
+        BCHK(s, hipMemcpyAsync(s->h_stage, (const char*)d + o, m, hipMemcpyDeviceToHost, s->stream));
+        BCHK(s, hipStreamSynchronize(s->stream));
+        const int rc = write_all(s, k, s->h_stage, m);
+        if (rc) return rc;
+    }
+    return MKT_OK;
+}
+static int read_at(mkt_bam* s, int k, void* p, size_t n, uint64_t off) {
+    char* c = (char*)p;
+    while (n) {
+        const ssize_t r = pread(s->tmp_fd[k], c, n, (off_t)off);
+        if (r <= 0) { if (r < 0 && errno == EINTR) continue; return bfail(s, MKT_E_IO, "read error on the temporary file %s: %s", s->tmp_path[k].c_str(), r < 0 ? strerror(errno) : "short file"); }
+        c += r; n -= (size_t)r; off += (uint64_t)r;
+    }
+    return MKT_OK;
+}
+
+// the header is known (the first alignment line has arrived): parse it once, put the name table on the device, open the run files
+static int spill_begin(mkt_bam* s) {
+    if (s->hdr_ready) return MKT_OK;
+    int rc = bam_parse_header(s, s->sp_sorted != 0, s->H);
+    if (rc) return rc;
+    const BamHeader& H = s->H;
+    const uint32_t nref = (uint32_t)H.names.size();
+    hipStream_t st = s->stream;
+    const size_t sz[4] = {H.tcap * sizeof(unsigned long long), H.tcap * sizeof(int32_t), (nref + 1) * sizeof(uint32_t), H.blob.size() + 16};
+    const void* src[4] = {H.th.data(), H.tidv.data(), H.noff.data(), H.blob.data()};
+    for (int k = 0; k < 4; ++k) {
+        BCHK(s, dalloc(s, &s->d_rt[k], sz[k]));
+        if (k < 3 || !H.blob.empty()) BCHK(s, hipMemcpyAsync(s->d_rt[k], src[k], k < 3 ? sz[k] : H.blob.size(), hipMemcpyHostToDevice, st));
+    }
+    CrcTabs ct;
+    crc_tables(&ct);
+    BCHK(s, dalloc(s, (void**)&s->d_ct, sizeof(CrcTabs)));
+    BCHK(s, dalloc(s, (void**)&s->d_err, 256));
+    BCHK(s, hipMemcpyAsync(s->d_ct, &ct, sizeof ct, hipMemcpyHostToDevice, st));
+    BCHK(s, hipMemsetAsync(s->d_err, 0, 256, st));
+    BCHK(s, hipStreamSynchronize(st));
+    s->rt.hash = (const unsigned long long*)s->d_rt[0]; s->rt.id = (const int32_t*)s->d_rt[1]; s->rt.name_off = (const uint32_t*)s->d_rt[2];
+    s->rt.names = (const uint8_t*)s->d_rt[3]; s->rt.mask = H.tcap - 1; s->rt.nref = nref;
+    if (s->sp_sorted) {
+        for (int k = 0; k < 2; ++k) {
+            s->tmp_fd[k] = open(s->tmp_path[k].c_str(), O_RDWR | O_CREAT | O_TRUNC, 0600);
+            if (s->tmp_fd[k] < 0) return bfail(s, MKT_E_IO, "cannot create the temporary file %s: %s", s->tmp_path[k].c_str(), strerror(errno));
+            s->tmp_made[k] = true;
+        }
+    }
+    s->hdr_ready = true;
+    return MKT_OK;
+}
+
+// ---- the BGZF stream
+static int bs_reserve(mkt_bam* s, uint64_t n) {                  // room for n more bytes after the carry
+    BgzfStream& b = s->bs;
+    const size_t need = b.carry + n + 64;                          // (the deflate kernel reads up to 15 bytes past a block's end)
+    if (need <= b.cap) return MKT_OK;
+    size_t ncap = b.cap ? b.cap : ((size_t)1 << 20);
+    while (ncap < need) ncap *= 2;
+    uint8_t* nb = nullptr;
+    const hipError_t e = dalloc(s, (void**)&nb, ncap);
+    if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", ncap, hipGetErrorString(e));
+    if (b.carry) BCHK(s, hipMemcpyAsync(nb, b.d_win, b.carry, hipMemcpyDeviceToDevice, s->stream));
+    BCHK(s, hipStreamSynchronize(s->stream));
+    dfree(s, b.d_win);
+    b.d_win = nb; b.cap = ncap;
+    return MKT_OK;
+}
+struct BaiWin { const BamIdx* idx; const uint64_t* off; uint64_t n; uint64_t ubase; };
+// n_new bytes have been put after the carry: compress the complete blocks (all of them when final), reduce the window's records
+// into the index, queue the compressed bytes for mkt_bam_pull, keep the partial last block
+static int bs_commit(mkt_bam* s, uint64_t n_new, bool final, const BaiWin* w) {
+    BgzfStream& b = s->bs;
+    hipStream_t st = s->stream;
+    const uint64_t len = b.carry + n_new;
+    const uint64_t nfull = final ? (len + BGZF_RAW - 1) / BGZF_RAW : len / BGZF_RAW;
+    const uint64_t nraw = final ? len : nfull * BGZF_RAW;
+    int rc = dgrow(s, b.d_csize, b.csize_cap, (nfull + 2) * sizeof(uint64_t));
+    if (rc) return rc;
+    uint64_t ctot = 0;
+    if (nfull) {
+        rc = dgrow(s, b.d_comp, b.comp_cap, nfull * (uint64_t)BGZF_STRIDE + 64);
+        if (rc) return rc;
+        uint64_t cap_b = s->budget / (4 * (uint64_t)BGZF_RAW);       // blocks per deflate launch: the scratch follows the budget
+        cap_b = cap_b < 16 ? 16 : (cap_b > 2048 ? 2048 : cap_b);
+        const uint64_t batch = nfull < cap_b ? nfull : cap_b;
+        if (s->sp_level > 0 && (rc = dgrow(s, b.d_scratch, b.scratch_cap, batch * kDzPerBlock + 64))) return rc;
+        bgzf_launch(b.d_win, nraw, nfull, s->sp_level, s->d_ct, b.d_comp, b.d_csize, b.d_scratch, batch, st);
+        BCHK(s, hipGetLastError());
+        BCHK(s, launch_exscan(b.d_csize, nfull, b.d_csize + nfull, st));
+        BCHK(s, hipMemcpyAsync(&ctot, b.d_csize + nfull, sizeof ctot, hipMemcpyDeviceToHost, st));
+    } else BCHK(s, hipMemsetAsync(b.d_csize, 0, 2 * sizeof(uint64_t), st));
+    BaiAcc& x = s->bx;
+    if (x.on && w && w->n) {
+        const uint64_t n = w->n;
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        if ((rc = dgrow(s, b.d_hflag, b.hflag_cap, (n + 2) * sizeof(uint64_t)))) return rc;
+        const VoffMap vm{w->ubase, b.blk0, b.cbase};
+        hipLaunchKernelGGL(k_bai, dim3(grid), dim3(256), 0, st, w->idx, w->off, n, vm, (const uint64_t*)b.d_csize, (const uint64_t*)x.d_lin_off, s->rt.nref,
+                           x.d_lin, x.d_refs, b.d_hflag, x.d_nocoor, (const BamIdx*)(x.has_prev ? x.d_prev : nullptr));
+        BCHK(s, hipGetLastError());
+        BCHK(s, launch_exscan(b.d_hflag, n, b.d_hflag + n, st));
+        uint64_t nheads = 0;
+        BCHK(s, hipMemcpyAsync(&nheads, b.d_hflag + n, sizeof nheads, hipMemcpyDeviceToHost, st));
+        BCHK(s, hipStreamSynchronize(st));
+        if (nheads) {
+            if ((rc = dgrow(s, b.d_heads, b.heads_cap, (nheads + 1) * sizeof(BaiHead)))) return rc;
+            hipLaunchKernelGGL(k_bai_heads, dim3(grid), dim3(256), 0, st, w->idx, w->off, n, vm, (const uint64_t*)b.d_csize, (const uint64_t*)b.d_hflag, b.d_heads,
+                               (const BamIdx*)(x.has_prev ? x.d_prev : nullptr));
+            BCHK(s, hipGetLastError());
+            const size_t h0 = x.heads.size();
+            x.heads.resize(h0 + nheads);
+            BCHK(s, hipMemcpyAsync(x.heads.data() + h0, b.d_heads, nheads * sizeof(BaiHead), hipMemcpyDeviceToHost, st));
+        }
+        BCHK(s, hipMemcpyAsync(x.d_prev, w->idx + (n - 1), sizeof(BamIdx), hipMemcpyDeviceToDevice, st));
+        x.has_prev = true;
+    }
+    if (final && x.on) {                                           // virtual offset of the end of the data
+        const uint64_t uo = b.blk0 * BGZF_RAW + len, bb = uo / BGZF_RAW;
+        uint64_t c = 0;
+        BCHK(s, hipMemcpyAsync(&c, b.d_csize + (bb - b.blk0), sizeof c, hipMemcpyDeviceToHost, st));
+        BCHK(s, hipStreamSynchronize(st));
+        x.end_voff = ((b.cbase + c) << 16) | (uo - bb * BGZF_RAW);
+    }
+    BCHK(s, hipStreamSynchronize(st));
+    if (ctot) {
+        if ((rc = dgrow(s, b.d_pack, b.pack_cap, ctot + 64))) return rc;
+        hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)nfull), dim3(BWG), 0, st, (const uint8_t*)b.d_comp, (const uint64_t*)b.d_csize, nfull, b.d_pack);
+        BCHK(s, hipGetLastError());
+        if (s->outq_pos == s->outq.size()) { s->outq.clear(); s->outq_pos = 0; }
+        const size_t q0 = s->outq.size();
+        s->outq.resize(q0 + ctot);
+        BCHK(s, hipMemcpyAsync(&s->outq[q0], b.d_pack, ctot, hipMemcpyDeviceToHost, st));
+    }
+    if (!final) {
+        const uint64_t rem = len - nfull * BGZF_RAW;                 // (< one block, from >= one block in: the ranges do not overlap)
+        if (nfull && rem) BCHK(s, hipMemcpyAsync(b.d_win, b.d_win + nfull * BGZF_RAW, rem, hipMemcpyDeviceToDevice, st));
+        b.carry = rem;
+    } else {
+        s->outq.append((const char*)kBgzfEof, 28);
+        b.carry = 0;
+    }
+    BCHK(s, hipStreamSynchronize(st));
+    b.blk0 += nfull; b.cbase += ctot;
+    s->out_total += ctot + (final ? 28 : 0);
+    return MKT_OK;
+}
+
+// ---- run formation
+static int find_nl(mkt_bam* s, uint64_t a, uint64_t b, bool first, uint64_t* pos /* position + 1; 0 = none */) {
+    *pos = 0;
+    if (a >= b) return MKT_OK;
+    if (!s->d_nl) BCHK(s, dalloc(s, (void**)&s->d_nl, 64));
+    hipStream_t st = s->stream;
+    BCHK(s, hipMemsetAsync(s->d_nl, first ? 0xFF : 0, sizeof(unsigned long long), st));
+    const uint64_t want = (b - a + 255) / 256;
+    const unsigned grid = (unsigned)(want < 1024 ? want : 1024);
+    hipLaunchKernelGGL(k_find_nl, dim3(grid), dim3(256), 0, st, (const uint8_t*)s->d_text, a, b, first ? 1 : 0, s->d_nl);
+    BCHK(s, hipGetLastError());
+    unsigned long long v = 0;
+    BCHK(s, hipMemcpyAsync(&v, s->d_nl, sizeof v, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipStreamSynchronize(st));
+    *pos = (first && v == ~0ull) ? 0 : v;
+    return MKT_OK;
+}
+// text[a, b) (whole lines) -> one run (sorted) or the next piece of the stream (input order)
+static int spill_form(mkt_bam* s, uint64_t a, uint64_t b) {
+    int rc = spill_begin(s);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = s->stream;
+    const bool sorted = s->sp_sorted != 0;
+    const uint8_t* text = s->d_text + a;
+    std::vector<void*> own;
+    auto cleanup = [&]() { for (void* p : own) dfree(s, p); own.clear(); };
+#define SALLOC(ptr, bytes_) do { hipError_t e_ = dalloc(s, (void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } own.push_back((void*)(ptr)); } while (0)
+#define SRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+    uint64_t nl = 0;
+    uint64_t* d_starts = nullptr;
+    SRUN(sort_line_index(text, b - a, st, &d_starts, &nl));
+    dtrack(s, d_starts, (nl + 2) * sizeof(uint64_t));
+    own.push_back(d_starts);
+    if (nl >= (1ull << 32) - 1) { cleanup(); return bfail(s, MKT_E_ARG, "%llu lines: records are indexed with 32 bits", (unsigned long long)nl); }
+    SortRec *rA = nullptr, *rB = nullptr;
+    uint32_t *d_size = nullptr, *d_hist = nullptr;
+    uint64_t* d_off = nullptr;
+    BamIdx* d_idx = nullptr;
+    const unsigned lgrid = (unsigned)((nl + 255) / 256);
+    SALLOC(rA, (nl + 1) * sizeof(SortRec));
+    SALLOC(d_size, (nl + 1) * sizeof(uint32_t));
+    SALLOC(d_off, (nl + 2) * sizeof(uint64_t));
+    hipLaunchKernelGGL(k_bam_keys, dim3(lgrid), dim3(256), 0, st, text, (const uint64_t*)d_starts, nl, s->rt, rA, d_size, s->d_err);
+    if (sorted) {
+        SALLOC(rB, (nl + 1) * sizeof(SortRec));
+        SALLOC(d_hist, kSortHistBytes);
+        int tbits = 1;
+        while ((1ull << tbits) <= (uint64_t)s->rt.nref) ++tbits;
+        sort_radix_passes(rA, rB, nl, d_hist, 1, 0, 33 + tbits, st);
+    }
+    uint32_t herr = 0;
+    SRUN(hipMemcpyAsync(&herr, s->d_err, sizeof herr, hipMemcpyDeviceToHost, st));
+    SRUN(hipStreamSynchronize(st));
+    if (herr) {
+        cleanup();
+        return bfail(s, MKT_E_ARG, "not SAM alignment text (error bits 0x%x: 1 fewer than 11 fields, 2 reference name not in the header, 4 number, 8 CIGAR, 16 optional field, 32 SEQ / QUAL lengths, 64 QNAME length)", herr);
+    }
+    hipLaunchKernelGGL(k_bam_sizes, dim3(lgrid), dim3(256), 0, st, (const SortRec*)rA, (const uint32_t*)d_size, nl, d_off);
+    SRUN(launch_exscan(d_off, nl, d_off + nl, st));
+    uint64_t total = 0;
+    SRUN(hipMemcpyAsync(&total, d_off + nl, sizeof total, hipMemcpyDeviceToHost, st));
+    SRUN(hipStreamSynchronize(st));
+    SALLOC(d_idx, (nl + 1) * sizeof(BamIdx));
+    if (sorted) {
+        uint8_t* d_raw = nullptr;
+        SpillRec* d_rec = nullptr;
+        SALLOC(d_raw, total + 64);
+        SALLOC(d_rec, (nl + 1) * sizeof(SpillRec));
+        hipLaunchKernelGGL(k_bam_write, dim3(lgrid), dim3(256), 0, st, text, (const uint64_t*)d_starts, nl, s->rt, (const SortRec*)rA, (const uint64_t*)d_off, d_raw, d_idx, s->d_err);
+        hipLaunchKernelGGL(k_spill_recs, dim3(lgrid), dim3(256), 0, st, (const SortRec*)rA, (const uint32_t*)d_size, (const BamIdx*)d_idx, nl, d_rec);
+        SRUN(hipGetLastError());
+        SpillRun r;
+        r.data_off = (uint64_t)lseek(s->tmp_fd[0], 0, SEEK_CUR);
+        r.key_off = (uint64_t)lseek(s->tmp_fd[1], 0, SEEK_CUR);
+        r.nrec = nl;
+        rc = write_dev(s, 0, d_raw, total);
+        if (!rc) rc = write_dev(s, 1, d_rec, nl * sizeof(SpillRec));
+        cleanup();
+        if (rc) return rc;
+        s->runs.push_back(r);
+    } else {
+        if (!s->spilled) {                                         // the first piece: the header goes first
+            if ((rc = bs_reserve(s, s->H.hdr.size()))) { cleanup(); return rc; }
+            SRUN(hipMemcpyAsync(s->bs.d_win, s->H.hdr.data(), s->H.hdr.size(), hipMemcpyHostToDevice, st));
+            s->bs.carry = s->H.hdr.size();
+        }
+        if ((rc = bs_reserve(s, total))) { cleanup(); return rc; }
+        hipLaunchKernelGGL(k_bam_write, dim3(lgrid), dim3(256), 0, st, text, (const uint64_t*)d_starts, nl, s->rt, (const SortRec*)rA, (const uint64_t*)d_off,
+                           s->bs.d_win + s->bs.carry, d_idx, s->d_err);
+        SRUN(hipGetLastError());
+        rc = bs_commit(s, total, false, nullptr);
+        cleanup();
+        if (rc) return rc;
+    }
+#undef SALLOC
+#undef SRUN
+    s->spilled = true;
+    s->records += nl;
+    ++s->nruns;
+    s->t_form += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return MKT_OK;
+}
+// cut runs off the front of the resident text: the longest prefix of whole lines within the budget, or one line when the first
+// line alone is longer.  final: the text is complete (and ends with a newline).
+static int spill_cut(mkt_bam* s, bool final) {
+    if (!s->budget || !s->header_done) return MKT_OK;
+    for (;;) {
+        const uint64_t a = s->tstart, avail = s->len - a;
+        if (!avail) break;
+        uint64_t end = 0;
+        if (final && avail <= s->budget) end = s->len;
+        else if (avail < s->budget) break;
+        else {
+            int rc = find_nl(s, a, a + s->budget, false, &end);
+            if (rc) return rc;
+            if (!end && (rc = find_nl(s, a + s->budget, s->len, true, &end))) return rc;
+            if (!end) break;                                       // (final text ends with a newline: not reached then)
+        }
+        int rc = spill_form(s, a, end);
+        if (rc) return rc;
+        s->tstart = end;
+    }
+    return MKT_OK;
+}
+static uint64_t auto_budget(mkt_bam* s) {                          // runs for the rest of the input once the text no longer fits
+    // (of what is free besides the resident text: a run needs about 1.2 x its text again while it is formed, and the text buffer
+    //  of later runs up to 2 x the budget)
+    const uint64_t b = device_free(s) / 4;
+    return b < ((uint64_t)64 << 10) ? ((uint64_t)64 << 10) : b;
+}
+// room for n more bytes of text: the unconsumed tail moves to the front of the buffer when that is free; "auto": when the text no
+// longer fits, what is resident becomes runs
+static int text_room(mkt_bam* s, size_t n) {
+    if (s->len + n + 1 <= s->cap) return MKT_OK;
+    const uint64_t tail = s->len - s->tstart;
+    if (s->tstart && tail <= s->tstart && tail + n + 1 <= s->cap) {
+        if (tail) BCHK(s, hipMemcpyAsync(s->d_text, s->d_text + s->tstart, tail, hipMemcpyDeviceToDevice, s->stream));
+        BCHK(s, hipStreamSynchronize(s->stream));
+        s->len = tail; s->tstart = 0;
+        return MKT_OK;
+    }
+    int rc = bam_reserve(s, tail + n + 1);
+    if (rc == MKT_E_NOMEM && s->autob && !s->budget && s->header_done) {
+        s->budget = auto_budget(s);
+        s->err.clear();
+        if ((rc = spill_cut(s, false))) return rc;
+        return text_room(s, n);
+    }
+    return rc;
+}
+
+// ---- the merge
+static uint64_t merge_window_bytes(const mkt_bam* s) {             // record bytes loaded across all runs at a time
+    // (half the budget: a round also holds the gathered window, its compressed blocks and the deflate scratch, all about as large)
+    const uint64_t lo = (uint64_t)64 << 10, hi = (uint64_t)1 << 30, w = s->budget / 2;
+    return w < lo ? lo : (w > hi ? hi : w);
+}
+// the merge is set up: the last run is on disk, the text is gone
+static int merge_begin(mkt_bam* s) {
+    const BamHeader& H = s->H;
+    const uint32_t nref = (uint32_t)H.names.size();
+    hipStream_t st = s->stream;
+    s->cur.assign(s->runs.size(), SpillCur());
+    BaiAcc& x = s->bx;
+    x.on = bai_possible(H);
+    if (!x.on) s->note = kNoIndexLongRef;
+    if (x.on) {
+        bai_lin_off(H, x.lin_off);
+        const uint64_t nlin = x.lin_off[nref];
+        std::vector<BaiRef> init(nref);
+        for (auto& r : init) { r.n_mapped = 0; r.n_unmapped = 0; r.beg = ~0ull; r.end = 0; }
+        BCHK(s, dalloc(s, (void**)&x.d_lin_off, (nref + 1) * sizeof(uint64_t)));
+        BCHK(s, dalloc(s, (void**)&x.d_lin, (nlin + 1) * sizeof(unsigned long long)));
+        BCHK(s, dalloc(s, (void**)&x.d_refs, (nref + 1) * sizeof(BaiRef)));
+        BCHK(s, dalloc(s, (void**)&x.d_nocoor, 256));
+        BCHK(s, dalloc(s, (void**)&x.d_prev, sizeof(BamIdx) + 64));
+        BCHK(s, hipMemcpyAsync(x.d_lin_off, x.lin_off.data(), (nref + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        BCHK(s, hipMemsetAsync(x.d_lin, 0xFF, (nlin + 1) * sizeof(unsigned long long), st));
+        if (nref) BCHK(s, hipMemcpyAsync(x.d_refs, init.data(), nref * sizeof(BaiRef), hipMemcpyHostToDevice, st));
+        BCHK(s, hipMemsetAsync(x.d_nocoor, 0, 256, st));
+        BCHK(s, hipMemsetAsync(x.d_nocoor + 2, 0xFF, sizeof(unsigned long long), st));
+    }
+    int rc = bs_reserve(s, H.hdr.size());
+    if (rc) return rc;
+    BCHK(s, hipMemcpyAsync(s->bs.d_win, H.hdr.data(), H.hdr.size(), hipMemcpyHostToDevice, st));
+    BCHK(s, hipStreamSynchronize(st));
+    s->bs.carry = H.hdr.size();
+    s->merging = true;
+    return MKT_OK;
+}
+static int merge_finish(mkt_bam* s) {
+    BaiAcc& x = s->bx;
+    if (x.on) {
+        const BamHeader& H = s->H;
+        const uint32_t nref = (uint32_t)H.names.size();
+        std::vector<BaiRef> refs(nref);
+        std::vector<unsigned long long> lin(x.lin_off[nref]);
+        unsigned long long nc[3] = {0, 0, 0};
+        hipStream_t st = s->stream;
+        if (nref) BCHK(s, hipMemcpyAsync(refs.data(), x.d_refs, nref * sizeof(BaiRef), hipMemcpyDeviceToHost, st));
+        if (!lin.empty()) BCHK(s, hipMemcpyAsync(lin.data(), x.d_lin, lin.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        BCHK(s, hipMemcpyAsync(nc, x.d_nocoor, sizeof nc, hipMemcpyDeviceToHost, st));
+        BCHK(s, hipStreamSynchronize(st));
+        const uint64_t off_end = nc[0] ? nc[2] : x.end_voff;        // the first record without coordinates, or the end of the data
+        s->bai.clear();
+        bai_assemble(s, nref, x.lin_off, refs, lin, x.heads, nc[0], nc[1], off_end);
+        std::vector<BaiHead>().swap(x.heads);
+    }
+    spill_remove(s);
+    spill_free_device(s);
+    s->merging = false;
+    s->done = true;
+    if (getenv("MKT_VERBOSE"))
+        fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", ("merge, " + std::to_string(s->rounds) + " rounds").c_str(), s->t_merge);
+    return MKT_OK;
+}
+// one round: top every run's window up, emit the records that are safe
+static int merge_round(mkt_bam* s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t R = s->runs.size();
+    const uint64_t wb = merge_window_bytes(s) / R + 1;
+    int rc;
+    for (size_t r = 0; r < R; ++r) {
+        const SpillRun& run = s->runs[r];
+        SpillCur& c = s->cur[r];
+        while (c.next < run.nrec && c.bytes.size() < wb) {
+            const uint64_t want = (wb - c.bytes.size()) / 128 + 1;
+            const uint64_t k = run.nrec - c.next < want ? run.nrec - c.next : want;
+            std::vector<SpillRec> kk(k);
+            if ((rc = read_at(s, 1, kk.data(), k * sizeof(SpillRec), run.key_off + c.next * sizeof(SpillRec)))) return rc;
+            uint64_t take = 0, bytes = 0;
+            while (take < k && (c.keys.empty() && take == 0 ? true : c.bytes.size() + bytes + kk[take].size <= wb)) bytes += kk[take++].size;
+            if (!take) break;
+            const size_t b0 = c.bytes.size();
+            c.bytes.resize(b0 + bytes);
+            if ((rc = read_at(s, 0, &c.bytes[b0], bytes, run.data_off + c.data_next))) return rc;
+            c.keys.insert(c.keys.end(), kk.begin(), kk.begin() + take);
+            c.next += take; c.data_next += bytes;
+            if (take < k) break;
+        }
+    }
+    // the bound: the smallest last-loaded record, in T order, of the runs with records still on disk
+    bool bounded = false;
+    uint64_t bhi = 0;
+    size_t brun = 0;
+    for (size_t r = 0; r < R; ++r) {
+        const SpillCur& c = s->cur[r];
+        if (c.next >= s->runs[r].nrec || c.keys.empty()) continue;
+        const uint64_t h = c.keys.back().hi;
+        if (!bounded || h < bhi) { bounded = true; bhi = h; brun = r; }
+    }
+    // safe prefixes, concatenated in run order
+    std::vector<SpillRec> hrec;
+    std::vector<uint64_t> hsrc;
+    std::vector<std::pair<size_t, uint64_t>> take;                 // per run: safe records, their bytes (uploaded straight from the run's window)
+    uint64_t nb = 0;
+    for (size_t r = 0; r < R; ++r) {
+        SpillCur& c = s->cur[r];
+        size_t cnt = c.keys.size();
+        if (bounded) {
+            auto le = [&](const SpillRec& k) { return k.hi < bhi || (k.hi == bhi && r <= brun); };
+            cnt = (size_t)(std::partition_point(c.keys.begin(), c.keys.end(), le) - c.keys.begin());
+        }
+        uint64_t rb = 0;
+        for (size_t i = 0; i < cnt; ++i) { hsrc.push_back(nb + rb); rb += c.keys[i].size; }
+        hrec.insert(hrec.end(), c.keys.begin(), c.keys.begin() + cnt);
+        take.emplace_back(cnt, rb);
+        nb += rb;
+    }
+    bool final = true;
+    for (size_t r = 0; r < R; ++r) if (s->cur[r].next < s->runs[r].nrec || s->cur[r].keys.size() > take[r].first) final = false;
+    const uint64_t n = hrec.size();
+    hipStream_t st = s->stream;
+    MergeBufs& m = s->mb;
+    uint64_t ubase = s->bs.blk0 * BGZF_RAW + s->bs.carry;
+    if (n) {
+        if ((rc = dgrow(s, m.rec, m.rec_cap, (n + 1) * sizeof(SpillRec))) || (rc = dgrow(s, m.src, m.src_cap, (n + 1) * sizeof(uint64_t))) ||
+            (rc = dgrow(s, m.bytes, m.bytes_cap, nb + 64)) || (rc = dgrow(s, m.rA, m.rA_cap, (n + 1) * sizeof(SortRec))) ||
+            (rc = dgrow(s, m.rB, m.rB_cap, (n + 1) * sizeof(SortRec))) || (rc = dgrow(s, m.hist, m.hist_cap, kSortHistBytes)) ||
+            (rc = dgrow(s, m.off, m.off_cap, (n + 2) * sizeof(uint64_t))) || (rc = dgrow(s, m.idx, m.idx_cap, (n + 1) * sizeof(BamIdx))) ||
+            (rc = bs_reserve(s, nb)))
+            return rc;
+        BCHK(s, hipMemcpyAsync(m.rec, hrec.data(), n * sizeof(SpillRec), hipMemcpyHostToDevice, st));
+        BCHK(s, hipMemcpyAsync(m.src, hsrc.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        uint64_t at = 0;
+        for (size_t r = 0; r < R; ++r) {
+            if (take[r].second) BCHK(s, hipMemcpyAsync(m.bytes + at, s->cur[r].bytes.data(), take[r].second, hipMemcpyHostToDevice, st));
+            at += take[r].second;
+        }
+        BCHK(s, hipStreamSynchronize(st));
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        hipLaunchKernelGGL(k_merge_keys, dim3(grid), dim3(256), 0, st, (const SpillRec*)m.rec, n, m.rA);
+        int tbits = 1;
+        while ((1ull << tbits) <= (uint64_t)s->rt.nref) ++tbits;
+        SortRec *rA = m.rA, *rB = m.rB;
+        sort_radix_passes(rA, rB, n, m.hist, 1, 0, 33 + tbits, st);
+        hipLaunchKernelGGL(k_merge_sizes, dim3(grid), dim3(256), 0, st, (const SortRec*)rA, (const SpillRec*)m.rec, n, m.off, m.idx);
+        BCHK(s, launch_exscan(m.off, n, m.off + n, st));
+        hipLaunchKernelGGL(k_merge_gather, dim3((unsigned)((n + MG_WAVES - 1) / MG_WAVES)), dim3(64 * MG_WAVES), 0, st, (const uint8_t*)m.bytes, (const uint64_t*)m.src,
+                           (const SortRec*)rA, (const SpillRec*)m.rec, n, (const uint64_t*)m.off, s->bs.d_win + s->bs.carry);
+        BCHK(s, hipGetLastError());
+    }
+    for (size_t r = 0; r < R; ++r) {
+        SpillCur& c = s->cur[r];
+        c.keys.erase(c.keys.begin(), c.keys.begin() + take[r].first);
+        c.bytes.erase(0, take[r].second);
+    }
+    const BaiWin w{m.idx, m.off, n, ubase};
+    if ((rc = bs_commit(s, nb, final, &w))) return rc;
+    ++s->rounds;
+    s->t_merge += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (final) return merge_finish(s);
+    return MKT_OK;
+}
+
+extern "C" {
+
+int mkt_bam_create(int device, mkt_bam** out) {
+    if (!out) return MKT_E_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MKT_E_NO_DEVICE;
+    if (device < 0 || device >= ndev) return MKT_E_ARG;
+    mkt_bam* s = new mkt_bam();
+    s->device = device;
+    if (const char* e = getenv("MKT_BAM_DEVICE_LIMIT")) s->dev_limit = (size_t)strtoull(e, nullptr, 10);
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return MKT_E_HIP; }
+    *out = s;
+    return MKT_OK;
+}
+void mkt_bam_destroy(mkt_bam* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);
+    spill_remove(s);
+    spill_free_device(s);
+    if (s->d_text) dfree(s, s->d_text);
+    if (s->d_bam) dfree(s, s->d_bam);
+    for (int k = 0; k < 2; ++k) { if (s->h_io[k]) (void)hipHostFree(s->h_io[k]); if (s->ev_io[k]) (void)hipEventDestroy(s->ev_io[k]); }
+    if (s->h_stage) (void)hipHostFree(s->h_stage);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+const char* mkt_bam_error(const mkt_bam* s) { return s ? s->err.c_str() : ""; }
+const char* mkt_bam_note(const mkt_bam* s) { return s ? s->note.c_str() : ""; }
+
+int mkt_bam_spill(mkt_bam* s, uint64_t run_bytes, const char* tmp_prefix, int sorted, int level) {
+    if (!s) return MKT_E_ARG;
+    if (s->ran || s->header_done || !s->header.empty() || !s->pending.empty() || s->spill_set) return bfail(s, MKT_E_STATE, "mkt_bam_spill after the first byte");
+    if (run_bytes && (!tmp_prefix || !tmp_prefix[0]) && sorted) return bfail(s, MKT_E_ARG, "a run budget needs a temporary-file prefix");
+    s->spill_set = true;
+    s->autob = run_bytes == MKT_BAM_RUNS_AUTO;
+    s->budget = s->autob ? 0 : run_bytes;
+    s->sp_sorted = sorted ? 1 : 0;
+    s->sp_level = level;
+    if (tmp_prefix && tmp_prefix[0]) { s->tmp_path[0] = std::string(tmp_prefix) + ".runs"; s->tmp_path[1] = std::string(tmp_prefix) + ".keys"; }
+    return MKT_OK;
+}
+
+// The next bytes of the SAM stream (any chunking).  Leading '@' lines are the header; everything from the first other line on
+// is alignment text and goes to the device.
+static int bam_add_bytes(mkt_bam* s, const char* bytes, size_t n, bool pinned_async) {
+    if (s->ran) return bfail(s, MKT_E_STATE, "add after run");
+    BCHK(s, hipSetDevice(s->device));
+    if (!s->header_done) {
+        s->pending.append(bytes, n);
+        size_t p = 0;
+        for (;;) {
+            if (p >= s->pending.size()) break;
+            if (s->pending[p] != '@') { s->header_done = true; break; }
+            const size_t e = s->pending.find('\n', p);
+            if (e == std::string::npos) break;              // an unfinished header line: wait for more
+            s->header.append(s->pending, p, e + 1 - p);
+            p = e + 1;
+        }
+        s->pending.erase(0, p);
+        if (!s->header_done) return MKT_OK;
+        std::string rest;
+        rest.swap(s->pending);
+        if (rest.empty()) return MKT_OK;
+        int rc = text_room(s, rest.size());
+        if (rc) return rc;
+        BCHK(s, hipMemcpy(s->d_text + s->len, rest.data(), rest.size(), hipMemcpyHostToDevice));
+        s->len += rest.size();
+        return spill_cut(s, false);
+    }
+    int rc = text_room(s, n);
+    if (rc) return rc;
+    if (n) BCHK(s, hipMemcpyAsync(s->d_text + s->len, bytes, n, hipMemcpyHostToDevice, s->stream));
+    if (!pinned_async) BCHK(s, hipStreamSynchronize(s->stream));       // the caller may reuse `bytes`
+    s->len += n;
+    return spill_cut(s, false);
+}
+int mkt_bam_add(mkt_bam* s, const char* bytes, size_t n) {
+    if (!s || (n && !bytes)) return MKT_E_ARG;
+    return spill_guard(s, bam_add_bytes(s, bytes, n, false));
+}
+// room for `bytes` of alignment text, so that the buffer does not grow (and get copied) while the stream comes in
+int mkt_bam_reserve(mkt_bam* s, size_t bytes) {
+    if (!s) return MKT_E_ARG;
+    if (s->ran) return bfail(s, MKT_E_STATE, "reserve after run");
+    BCHK(s, hipSetDevice(s->device));
+    if (s->budget) {                                               // runs: room for two runs and a window of input at most
+        const size_t most = (size_t)s->budget * 2 + kBamIoCap;
+        if (bytes > most) bytes = most;
+    }
+    const int rc = bam_reserve(s, bytes + 1);
+    if (rc == MKT_E_NOMEM && s->autob && !s->budget) {            // "auto": the input will not fit -> runs from the start
+        s->budget = auto_budget(s);
+        s->err.clear();
+        return MKT_OK;
+    }
+    return rc;
+}
+static int bam_io_slot(mkt_bam* s, int k) {
+    if (!s->h_io[k]) {
+        BCHK(s, hipHostMalloc((void**)&s->h_io[k], kBamIoCap, hipHostMallocDefault));
+        BCHK(s, hipEventCreateWithFlags(&s->ev_io[k], hipEventDisableTiming));
+    }
+    if (s->io_busy[k]) { BCHK(s, hipEventSynchronize(s->ev_io[k])); s->io_busy[k] = false; }
+    return MKT_OK;
+}
+// A pinned host buffer for the next bytes of the SAM stream (read a file straight into it), then mkt_bam_commit: the copy to the
+// GPU runs while the caller fills the other buffer.
+int mkt_bam_window(mkt_bam* s, char** buf, size_t* cap) {
+    if (!s || !buf || !cap) return MKT_E_ARG;
+    if (s->ran) return bfail(s, MKT_E_STATE, "window after run");
+    BCHK(s, hipSetDevice(s->device));
+    int rc = bam_io_slot(s, s->io_slot);
+    if (rc) return rc;
+    *buf = s->h_io[s->io_slot]; *cap = kBamIoCap;
+    return MKT_OK;
+}
+int mkt_bam_commit(mkt_bam* s, size_t n) {
+    if (!s || n > kBamIoCap) return MKT_E_ARG;
+    const int k = s->io_slot;
+    if (!s->h_io[k]) return bfail(s, MKT_E_STATE, "commit without window");
+    int rc = bam_add_bytes(s, s->h_io[k], n, true);
+    if (rc) return spill_guard(s, rc);
+    BCHK(s, hipEventRecord(s->ev_io[k], s->stream));
+    s->io_busy[k] = true;
+    s->io_slot = k ^ 1;
+    return MKT_OK;
+}
+// alignment lines that are already on the device (no header lines)
+int mkt_bam_add_device(mkt_bam* s, const void* d_bytes, size_t n) {
+    if (!s || (n && !d_bytes)) return MKT_E_ARG;
+    if (s->ran) return bfail(s, MKT_E_STATE, "add after run");
+    if (!s->pending.empty()) return bfail(s, MKT_E_STATE, "device text after an unfinished header line");
+    s->header_done = true;
+    BCHK(s, hipSetDevice(s->device));
+    int rc = text_room(s, n);
+    if (rc) return spill_guard(s, rc);
+    if (n) BCHK(s, hipMemcpyAsync(s->d_text + s->len, d_bytes, n, hipMemcpyDeviceToDevice, s->stream));
+    BCHK(s, hipStreamSynchronize(s->stream));
+    s->len += n;
+    return spill_guard(s, spill_cut(s, false));
+}
+
+// the end of the input in out-of-core mode: the last runs; sorted: the merge is set up (mkt_bam_pull drives it), input order:
+// the last blocks are queued
+static int spill_run_end(mkt_bam* s) {
+    int rc = spill_cut(s, true);
+    if (rc) return rc;
+    dfree(s, s->d_text); s->d_text = nullptr; s->cap = s->len = 0; s->tstart = 0;
+    if (getenv("MKT_VERBOSE"))
+        fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", (std::to_string(s->nruns) + (s->sp_sorted ? " runs formed" : " pieces converted")).c_str(), s->t_form);
+    if (s->sp_sorted) return merge_begin(s);
+    if ((rc = bs_commit(s, 0, true, nullptr))) return rc;
+    spill_free_device(s);
+    s->done = true;
+    return MKT_OK;
+}
+static int bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* bam_bytes, uint64_t* bai_bytes);
+static int bam_single(mkt_bam* s, int sorted, int level, bool verbose);
+int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* bam_bytes, uint64_t* bai_bytes) {
+    if (!s) return MKT_E_ARG;
+    return spill_guard(s, bam_run(s, sorted, level, records, bam_bytes, bai_bytes));
+}
+static int bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* bam_bytes, uint64_t* bai_bytes) {
+    if (s->ran) return bfail(s, MKT_E_STATE, "run twice");
+    if (s->spill_set && ((sorted != 0) != (s->sp_sorted != 0) || level != s->sp_level)) return bfail(s, MKT_E_ARG, "sorted / level differ from those given to mkt_bam_spill");
+    BCHK(s, hipSetDevice(s->device));
+    if (records) *records = 0;
+    if (bam_bytes) *bam_bytes = 0;
+    if (bai_bytes) *bai_bytes = 0;
+    s->ran = true;
+    if (!s->pending.empty()) {                                     // a last header line without newline, or a file of header lines only
+        if (s->pending[0] == '@') { s->header += s->pending; s->header += '\n'; s->pending.clear(); }
+    }
+    hipStream_t st = s->stream;
+    const bool verbose = getenv("MKT_VERBOSE") != nullptr;
+    BCHK(s, hipStreamSynchronize(st));                            // (copies of mkt_bam_commit may still be on their way)
+    if (s->len > s->tstart) {
+        char last = 0;
+        BCHK(s, hipMemcpy(&last, s->d_text + s->len - 1, 1, hipMemcpyDeviceToHost));
+        if (last != '\n') { const char nl = '\n'; int rc = text_room(s, 1); if (rc) return rc; BCHK(s, hipMemcpy(s->d_text + s->len, &nl, 1, hipMemcpyHostToDevice)); ++s->len; }
+    }
+    if (s->budget && !s->spilled && s->len > s->budget) {         // ("auto" switched before the header was complete)
+        int rc = spill_cut(s, false);
+        if (rc) return rc;
+    }
+    int rc = s->spilled ? MKT_OK : bam_single(s, sorted, level, verbose);
+    if (rc == MKT_E_NOMEM && s->autob && s->d_text && s->header_done) {
+        // "auto": the single pass does not fit beside the resident text -> that text becomes runs (nothing of the pass is left)
+        if (verbose) fprintf(stderr, "[mkt_bam] %s: runs instead\n", s->err.c_str());
+        s->err.clear();
+        if (!s->budget) s->budget = auto_budget(s);
+        rc = spill_cut(s, true);
+        if (!rc && !s->spilled) rc = bfail(s, MKT_E_NOMEM, "no run could be formed");
+    }
+    if (rc) return rc;
+    if (s->spilled) {
+        if ((rc = spill_run_end(s))) return rc;
+        if (records) *records = s->records;
+        if (bam_bytes) *bam_bytes = s->done ? s->out_total : 0;    // (sorted: known once mkt_bam_pull has handed out the last piece)
+        return MKT_OK;
+    }
+    if (records) *records = s->records;
+    if (bam_bytes) *bam_bytes = s->bam_len;
+    if (bai_bytes) *bai_bytes = s->bai.size();
+    return MKT_OK;
+}
+// the single pass: everything resident
+static int bam_single(mkt_bam* s, int sorted, int level, bool verbose) {
+    hipStream_t st = s->stream;
+    auto t_prev = std::chrono::steady_clock::now();
+    auto mark = [&](const char* what) {                            // (call sites follow a stream synchronisation)
+        if (!verbose) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    };
+    // ---- header: text (with @HD SO:coordinate when sorting), the reference dictionary from @SQ, the name table
+    BamHeader H;
+    {
+        int rc = bam_parse_header(s, sorted != 0, H);
+        if (rc) return rc;
+    }
+    const std::vector<std::string>& names = H.names;
+    const std::string& hdr = H.hdr;
+    const uint32_t nref = (uint32_t)names.size();
+    const uint64_t hdr_len = hdr.size();
+    const uint32_t tcap = H.tcap;
+    const std::vector<unsigned long long>& th = H.th;
+    const std::vector<int32_t>& tidv = H.tidv;
+    const std::vector<uint32_t>& noff = H.noff;
+    const std::string& blob = H.blob;
+    (void)names;
 
     std::vector<void*> owned;
-    auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
-#define BALLOC(ptr, bytes_) do { hipError_t e_ = hipMalloc((void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } owned.push_back((void*)(ptr)); } while (0)
+    auto cleanup = [&]() { for (void* p : owned) dfree(s, p); owned.clear(); };
+#define BALLOC(ptr, bytes_) do { hipError_t e_ = dalloc(s, (void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } owned.push_back((void*)(ptr)); } while (0)
 #define BRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    auto drop = [&](void* p) { (void)hipFree(p); owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end()); };
+    auto drop = [&](void* p) { dfree(s, p); owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end()); };
     unsigned long long* d_th = nullptr; int32_t* d_tid = nullptr; uint32_t* d_noff = nullptr; uint8_t* d_blob = nullptr;
     CrcTabs* d_ct = nullptr;
     uint32_t* d_err = nullptr;
@@ -1270,7 +2147,10 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
     uint64_t nl = 0;
     uint64_t* d_starts = nullptr;
     if (s->len) {
-        BRUN(sort_line_index(s->d_text, s->len, st, &d_starts, &nl));
+        const hipError_t eli = sort_line_index(s->d_text, s->len, st, &d_starts, &nl);
+        if (eli == hipErrorOutOfMemory) { (void)hipGetLastError(); cleanup(); return bfail(s, MKT_E_NOMEM, "the line index does not fit beside the text"); }
+        BRUN(eli);
+        dtrack(s, d_starts, (nl + 2) * sizeof(uint64_t));
         owned.push_back(d_starts);
     }
     mark("header + line index");
@@ -1308,6 +2188,21 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
         BRUN(hipStreamSynchronize(st));
     }
     const uint64_t nraw = hdr_len + total;
+    if (s->autob) {
+        // "auto": does the rest of the pass fit?  Next the records and their index fields beside the text and the sort records; then,
+        // with those gone, the compressed blocks, the deflate scratch, the packed BAM and the index's head flags.
+        const uint64_t nblk = (nraw + BGZF_RAW - 1) / BGZF_RAW;
+        uint64_t batch = ((uint64_t)8 << 30) / kDzPerBlock;
+        if (batch > nblk) batch = nblk;
+        const uint64_t next = nraw + 64 + (nl + 1) * sizeof(BamIdx);
+        const uint64_t freed = s->cap + 64 + (nl + 2) * sizeof(uint64_t) + (nl + 1) * (2 * sizeof(SortRec) + sizeof(uint32_t)) + kSortHistBytes;
+        const uint64_t later = 2 * nblk * (uint64_t)BGZF_STRIDE + (nblk + 2) * sizeof(uint64_t) + (level > 0 ? batch * kDzPerBlock : 0) + (nl + 2) * sizeof(uint64_t);
+        const uint64_t fr = device_free(s), slack = ((uint64_t)1 << 20) + (next + later) / 20;
+        if (next + slack > fr || next + later + slack > fr + freed) {
+            cleanup();
+            return bfail(s, MKT_E_NOMEM, "the single pass does not fit this GPU (%.2f GB free beside the text)", (double)fr / 1e9);
+        }
+    }
     BALLOC(d_raw, nraw + 64);
     BRUN(hipMemcpyAsync(d_raw, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
     if (nl) {
@@ -1320,7 +2215,7 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
         drop(rA); if (rB) drop(rB); drop(d_size); drop(d_starts);
         rA = rB = nullptr;
     }
-    (void)hipFree(s->d_text); s->d_text = nullptr; s->cap = s->len = 0;
+    dfree(s, s->d_text); s->d_text = nullptr; s->cap = s->len = 0;
 
     // ---- BGZF
     const uint64_t nblocks = (nraw + BGZF_RAW - 1) / BGZF_RAW;
@@ -1329,21 +2224,12 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
     uint32_t* d_scratch = nullptr;
     BALLOC(d_comp, nblocks * (uint64_t)BGZF_STRIDE + 64);
     BALLOC(d_csize, (nblocks + 2) * sizeof(uint64_t));
-    if (level > 0) {
-        // the token lists and bit streams of the blocks of one launch: at most 8 GB of scratch
-        const uint64_t per_block = (uint64_t)DZ_WAVES * DZ_WAVE_SCRATCH * sizeof(uint32_t);
-        uint64_t batch = ((uint64_t)8 << 30) / per_block;
-        if (batch > nblocks) batch = nblocks;
-        if (batch < 1) batch = 1;
-        BALLOC(d_scratch, batch * per_block + 64);
-        for (uint64_t fb = 0; fb < nblocks; fb += batch) {
-            const unsigned g = (unsigned)(nblocks - fb < batch ? nblocks - fb : batch);
-            if (level >= 2) hipLaunchKernelGGL(k_bgzf_deflate<true>, dim3(g), dim3(DZ_THREADS), 0, st, (const uint8_t*)d_raw, nraw, fb, (const CrcTabs*)d_ct, d_comp, d_csize, d_scratch);
-            else hipLaunchKernelGGL(k_bgzf_deflate<false>, dim3(g), dim3(DZ_THREADS), 0, st, (const uint8_t*)d_raw, nraw, fb, (const CrcTabs*)d_ct, d_comp, d_csize, d_scratch);
-        }
-    } else {
-        hipLaunchKernelGGL(k_bgzf_stored, dim3((unsigned)nblocks), dim3(BWG), 0, st, (const uint8_t*)d_raw, nraw, (const CrcTabs*)d_ct, d_comp, d_csize);
-    }
+    // the token lists and bit streams of the blocks of one launch (levels 1, 2): at most 8 GB of scratch
+    uint64_t batch = ((uint64_t)8 << 30) / kDzPerBlock;
+    if (batch > nblocks) batch = nblocks;
+    if (batch < 1) batch = 1;
+    if (level > 0) BALLOC(d_scratch, batch * kDzPerBlock + 64);
+    bgzf_launch(d_raw, nraw, nblocks, level, d_ct, d_comp, d_csize, d_scratch, batch, st);
     BRUN(hipGetLastError());
     BRUN(launch_exscan(d_csize, nblocks, d_csize + nblocks, st));
     uint64_t clen = 0;
@@ -1352,25 +2238,24 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
     mark(level > 0 ? "BGZF deflate" : "BGZF stored");
     drop(d_raw);
     if (d_scratch) drop(d_scratch);
-    static const unsigned char eof_block[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    { hipError_t e_ = hipMalloc((void**)&s->d_bam, clen + 28 + 64); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of the BAM failed: %s", hipGetErrorString(e_)); } }
+    { hipError_t e_ = dalloc(s, (void**)&s->d_bam, clen + 28 + 64); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of the BAM failed: %s", hipGetErrorString(e_)); } }
     hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)nblocks), dim3(BWG), 0, st, (const uint8_t*)d_comp, (const uint64_t*)d_csize, nblocks, s->d_bam);
-    BRUN(hipMemcpyAsync(s->d_bam + clen, eof_block, 28, hipMemcpyHostToDevice, st));
+    BRUN(hipMemcpyAsync(s->d_bam + clen, kBgzfEof, 28, hipMemcpyHostToDevice, st));
     BRUN(hipGetLastError());
     BRUN(hipStreamSynchronize(st));
     s->bam_len = clen + 28;
     s->records = nl;
+    s->nruns = nl ? 1 : 0;
     drop(d_comp);
     mark("pack");
 
     // ---- BAI (coordinate order only; the format ends at 2^29 bases per reference -- longer ones would need a CSI index: none is made then)
     s->bai.clear();
     s->note.clear();
-    bool bai_ok = true;
-    for (uint32_t i = 0; i < nref; ++i) if (lens[i] > (1u << 29)) bai_ok = false;
+    const bool bai_ok = bai_possible(H);
     if (sorted && bai_ok) {
-        std::vector<uint64_t> lin_off(nref + 1, 0);
-        for (uint32_t i = 0; i < nref; ++i) lin_off[i + 1] = lin_off[i] + ((uint64_t)lens[i] >> 14) + 2;
+        std::vector<uint64_t> lin_off;
+        bai_lin_off(H, lin_off);
         const uint64_t nlin = lin_off[nref];
         uint64_t* d_lin_off = nullptr;
         unsigned long long *d_lin = nullptr, *d_nocoor = nullptr;
@@ -1394,8 +2279,8 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
         BRUN(hipMemsetAsync(d_nocoor, 0, 256, st));
         uint64_t nheads = 0;
         if (nl) {
-            hipLaunchKernelGGL(k_bai, dim3(lgrid), dim3(256), 0, st, (const BamIdx*)d_idx, (const uint64_t*)d_off, nl, hdr_len, (const uint64_t*)d_csize, (const uint64_t*)d_lin_off, nref,
-                               d_lin, d_refs, d_hflag, d_nocoor);
+            hipLaunchKernelGGL(k_bai, dim3(lgrid), dim3(256), 0, st, (const BamIdx*)d_idx, (const uint64_t*)d_off, nl, VoffMap{hdr_len, 0, 0}, (const uint64_t*)d_csize, (const uint64_t*)d_lin_off, nref,
+                               d_lin, d_refs, d_hflag, d_nocoor, (const BamIdx*)nullptr);
             BRUN(hipGetLastError());
             BRUN(launch_exscan(d_hflag, nl, d_hflag + nl, st));
             BRUN(hipMemcpyAsync(&nheads, d_hflag + nl, sizeof nheads, hipMemcpyDeviceToHost, st));
@@ -1408,7 +2293,8 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
         heads.resize(nheads);
         if (nheads) {
             BALLOC(d_heads, ((size_t)nheads + 1) * sizeof(BaiHead));
-            hipLaunchKernelGGL(k_bai_heads, dim3(lgrid), dim3(256), 0, st, (const BamIdx*)d_idx, (const uint64_t*)d_off, nl, hdr_len, (const uint64_t*)d_csize, (const uint64_t*)d_hflag, d_heads);
+            hipLaunchKernelGGL(k_bai_heads, dim3(lgrid), dim3(256), 0, st, (const BamIdx*)d_idx, (const uint64_t*)d_off, nl, VoffMap{hdr_len, 0, 0}, (const uint64_t*)d_csize, (const uint64_t*)d_hflag, d_heads,
+                               (const BamIdx*)nullptr);
             BRUN(hipGetLastError());
             BRUN(hipMemcpyAsync(heads.data(), d_heads, (size_t)nheads * sizeof(BaiHead), hipMemcpyDeviceToHost, st));
             BRUN(hipStreamSynchronize(st));
@@ -1426,73 +2312,14 @@ int mkt_bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_t* 
             BRUN(hipMemcpy(&cb, d_csize + b, sizeof cb, hipMemcpyDeviceToHost));
             off_end = (cb << 16) | (uo - b * BGZF_RAW);
         }
-        // per reference (the run starts come in file order = by reference): a stable counting sort by bin
-        std::vector<uint32_t> bin_cnt(65536, 0), bin_at(65536, 0);      // (every 16-bit value: a record past 2^29 bases carries a bin beyond 37449; no index is kept then, see below)
-        std::vector<uint32_t> order(nheads);
-        std::vector<std::pair<size_t, size_t>> ref_range(nref, {0, 0});
-        {
-            size_t i = 0;
-            for (uint32_t t = 0; t < nref && i < nheads; ++t) {
-                size_t j = i;
-                while (j < nheads && (uint32_t)heads[j].tid == t) ++j;
-                ref_range[t] = {i, j};
-                i = j;
-            }
-        }
-        std::string& o = s->bai;                                    // SAMv1 5.2
-        o.reserve(64 + (size_t)nheads * 28 + nlin * 8 + (size_t)nref * 64);
-        o.append("BAI\1", 4);
-        put_le32(o, nref);
-        for (uint32_t t = 0; t < nref; ++t) {
-            const bool any = refs[t].n_mapped + refs[t].n_unmapped > 0;
-            const size_t i0 = ref_range[t].first, i1 = ref_range[t].second;
-            std::vector<uint32_t> used;                             // the bins of this reference, ascending
-            for (size_t i = i0; i < i1; ++i) if (bin_cnt[heads[i].bin]++ == 0) used.push_back(heads[i].bin);
-            std::sort(used.begin(), used.end());
-            uint32_t at = 0;
-            for (uint32_t b : used) { bin_at[b] = at; at += bin_cnt[b]; }
-            for (size_t i = i0; i < i1; ++i) order[i0 + bin_at[heads[i].bin]++] = (uint32_t)i;
-            put_le32(o, (uint32_t)used.size() + (any ? 1u : 0u));
-            size_t k = i0;
-            for (uint32_t b : used) {
-                put_le32(o, b);
-                put_le32(o, bin_cnt[b]);
-                for (uint32_t c = 0; c < bin_cnt[b]; ++c, ++k) {
-                    const size_t i = order[k];
-                    put_le64(o, heads[i].voff);
-                    put_le64(o, i + 1 < nheads ? heads[i + 1].voff : off_end);
-                }
-                bin_cnt[b] = 0;
-            }
-            if (any) {                                              // the pseudo-bin: file range of the reference, mapped / unmapped counts
-                put_le32(o, 37450u); put_le32(o, 2u);
-                put_le64(o, refs[t].beg); put_le64(o, refs[t].end);
-                put_le64(o, refs[t].n_mapped); put_le64(o, refs[t].n_unmapped);
-            }
-            // linear index: up to the last window that a record touched; empty windows take the next one's offset
-            const uint64_t a = lin_off[t], b = lin_off[t + 1];
-            uint64_t last = a;
-            for (uint64_t k = a; k < b; ++k) if (lin[k] != ~0ull) last = k + 1;
-            unsigned long long nextv = 0;
-            for (uint64_t k = last; k > a;) { --k; if (lin[k] == ~0ull) lin[k] = nextv; else nextv = lin[k]; }
-            put_le32(o, (uint32_t)(last - a));
-            for (uint64_t k = a; k < last; ++k) put_le64(o, lin[k]);
-        }
-        put_le64(o, no_coor);
-        if (beyond) {
-            s->bai.clear();
-            s->note = "no index written: a record lies past its reference's LN or past the 2^29 bases a BAI index can address (samtools index would need -c)";
-        }
+        bai_assemble(s, nref, lin_off, refs, lin, heads, no_coor, beyond, off_end);
         mark("BAI");
     } else if (sorted) {
-        s->note = "no index written: a reference is longer than the 2^29 bases a BAI index can address (samtools index would need -c)";
+        s->note = kNoIndexLongRef;
     }
     cleanup();
 #undef BALLOC
 #undef BRUN
-    if (records) *records = s->records;
-    if (bam_bytes) *bam_bytes = s->bam_len;
-    if (bai_bytes) *bai_bytes = s->bai.size();
     return MKT_OK;
 }
 
@@ -1528,6 +2355,51 @@ int mkt_bam_read(mkt_bam* s, int which, uint64_t off, size_t n, const char** ptr
     BCHK(s, hipStreamSynchronize(s->stream));
     *ptr = s->h_io[k];
     s->io_slot = k ^ 1;
+    return MKT_OK;
+}
+
+
+// The BAM in order, at most 64 MiB per call, through the pinned buffers (*ptr valid until the next call but one).  *n = 0: nothing
+// more now -- after mkt_bam_run that is the end of the file, and the BAI (mkt_bam_stats, mkt_bam_read / _fetch) is complete.
+// Out-of-core mode, sorted: each call drives the merge until a piece is ready; input order: pieces are ready as the input arrives.
+int mkt_bam_pull(mkt_bam* s, const char** ptr, size_t* n) {
+    if (!s || !ptr || !n) return MKT_E_ARG;
+    *ptr = nullptr; *n = 0;
+    BCHK(s, hipSetDevice(s->device));
+    if (!s->spilled) {
+        if (!s->ran) return MKT_OK;
+        const uint64_t m = s->bam_len - s->pull_off < kBamIoCap ? s->bam_len - s->pull_off : kBamIoCap;
+        if (!m) return MKT_OK;
+        const int rc = mkt_bam_read(s, 0, s->pull_off, (size_t)m, ptr);
+        if (rc) return rc;
+        s->pull_off += m; *n = (size_t)m;
+        return MKT_OK;
+    }
+    while (s->outq_pos == s->outq.size() && s->merging) {
+        const int rc = merge_round(s);
+        if (rc) return spill_guard(s, rc);
+    }
+    const size_t avail = s->outq.size() - s->outq_pos;
+    if (!avail) return MKT_OK;
+    const size_t m = avail < kBamIoCap ? avail : kBamIoCap;
+    const int k = s->io_slot;
+    const int rc = bam_io_slot(s, k);
+    if (rc) return rc;
+    memcpy(s->h_io[k], s->outq.data() + s->outq_pos, m);
+    s->outq_pos += m;
+    if (s->outq_pos == s->outq.size()) { s->outq.clear(); s->outq_pos = 0; }
+    s->io_slot = k ^ 1;
+    *ptr = s->h_io[k]; *n = m;
+    s->pull_off += m;
+    return MKT_OK;
+}
+int mkt_bam_stats(const mkt_bam* s, uint64_t stats[5]) {
+    if (!s || !stats) return MKT_E_ARG;
+    stats[0] = s->nruns;
+    stats[1] = s->tmp_bytes;
+    stats[2] = s->dev_peak;
+    stats[3] = s->spilled ? s->out_total : s->bam_len;
+    stats[4] = s->bai.size();
     return MKT_OK;
 }
 

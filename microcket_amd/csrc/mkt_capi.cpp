@@ -139,6 +139,7 @@ const char* mkt_strerror(int code) {
     case MKT_E_CAPACITY: return "a QNAME group does not fit the block buffer";
     case MKT_E_KERNEL: return "kernel reported an internal error";
     case MKT_E_STATE: return "call order violated";
+    case MKT_E_IO: return "temporary file error";
     default: return "unknown error";
     }
 }
