@@ -1162,30 +1162,149 @@ uint32_t finish_chunk_tiles() { return NTF; }
 
 // ---------------------------------------------------------------------------------------------
 // Extension A9: duplicate marking over the run's key list (input order).  A pair is a duplicate when
-// an EARLIER pair has the same (chr1, pos1, chr2, pos2, strand1, strand2).  Hand-written LSD radix
-// sort of one u64 per pair, (32-bit key hash << 32 | input index) -- 4-bit digits, ballot ranking,
-// stable -- over only as many hash bits as the pair count needs (log2 n + 2: equal-digit runs then hold
-// 1/4 element on average); every element then looks back inside its run for an equal FULL key (exact;
-// hash ties only cost time, and within a run earlier in memory = earlier in the input).
+// an EARLIER pair has the same (chr1, pos1, chr2, pos2, strand1, strand2).  One u64 per pair,
+// rec = (top 64 - ib bits of the key's mix64 hash) << ib | input index, ib = ceil(log2 n); a stable LSD radix
+// sort over only as many hash bits as the pair count needs (log2 n + 2, rounded up to whole 7-bit digits: equal-digit
+// runs then hold 1/4 element on average); every element then looks back inside its run for an equal hash field
+// (64 - ib bits) and only then for an equal FULL key (exact; hash ties only cost time, and within a run earlier in
+// memory = earlier in the input).
+//
+// One pass = per-tile digit counts (digit-major: counts[d * G + g]) -> one workgroup per digit scans its row -> the
+// scatter: a workgroup ranks its tile of DS_T records stably by digit (peers by ballots, per-wave running counts in LDS,
+// prefix over the waves), reorders the tile in LDS and writes each digit's run to its global offset as contiguous
+// stores (~DS_T / DS_R records per run).  The first pass's counts come from k_dd_prep, which also builds the records.
 constexpr int DD_WG = 256;
+constexpr int DS_WG = 512;                                     // scatter / count workgroup: 8 waves
+constexpr int DS_NW = DS_WG / 64;
+constexpr int DS_T = 8192;                                     // records per tile: 64 KiB of LDS, 2 workgroups per CU
+constexpr int DS_K = DS_T / DS_WG;                             // records per lane
+constexpr int DS_D = 7, DS_R = 1 << DS_D;                      // digit bits, digit values
+constexpr int DS_SCAN_WG = 1024, DS_SCAN_V = 8;                // k_dd_dscan: 8 counters per thread
 constexpr uint64_t kKeyMask1 = 0xFFFFFFFFC000FFFFull;          // posB, the two strand bits and the lane (0 unless MKT_EXT_LANES) of KeyRec::k1
+static_assert(DS_R == 2 * 64, "the scatter's prologue gives each lane of wave 0 two digits");
 
 __device__ inline bool key_eq(const KeyRec& x, const KeyRec& y) { return x.k0 == y.k0 && (x.k1 & kKeyMask1) == (y.k1 & kKeyMask1); }
 
-__global__ void k_dd_init(const KeyRec* keys, uint64_t n, uint64_t* rec) {
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x)
-        rec[j] = (mix64(keys[j].k0 ^ mix64(keys[j].k1 & kKeyMask1)) & 0xFFFFFFFF00000000ull) | j;
-}
-__global__ __launch_bounds__(DD_WG) void k_dd_hist(const uint64_t* rec, uint64_t n, uint64_t per, int shift, uint32_t* hist, uint32_t G) {
-    __shared__ uint32_t cnt[16];
-    if (threadIdx.x < 16) cnt[threadIdx.x] = 0;
+// records in input order + the first digit's per-tile counts
+__global__ __launch_bounds__(DS_WG) void k_dd_prep(const KeyRec* keys, uint64_t n, int ib, uint64_t* rec, uint32_t* cnt, uint32_t G) {
+    __shared__ uint32_t c[DS_R];
+    if (threadIdx.x < DS_R) c[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t b = (uint64_t)blockIdx.x * per, e = b + per < n ? b + per : n;
-    for (uint64_t j = b + threadIdx.x; j < e; j += DD_WG) atomicAdd(&cnt[(rec[j] >> shift) & 15u], 1u);
+    const uint64_t b = (uint64_t)blockIdx.x * DS_T, e = b + DS_T < n ? b + DS_T : n, hi = ~((1ull << ib) - 1ull);
+    for (uint64_t j = b + threadIdx.x; j < e; j += DS_WG) {
+        const uint64_t r = (mix64(keys[j].k0 ^ mix64(keys[j].k1 & kKeyMask1)) & hi) | j;
+        rec[j] = r;
+        atomicAdd(&c[(r >> ib) & (DS_R - 1)], 1u);
+    }
     __syncthreads();
-    if (threadIdx.x < 16) hist[threadIdx.x * G + blockIdx.x] = cnt[threadIdx.x];
+    if (threadIdx.x < DS_R) cnt[threadIdx.x * G + blockIdx.x] = c[threadIdx.x];
 }
-__global__ __launch_bounds__(NT) void k_dd_scan(uint32_t* hist, uint32_t m) {       // exclusive scan of m counters, one workgroup
+__global__ __launch_bounds__(DS_WG) void k_dd_count(const uint64_t* rec, uint64_t n, int shift, uint32_t* cnt, uint32_t G) {
+    __shared__ uint32_t c[DS_R];
+    if (threadIdx.x < DS_R) c[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t b = (uint64_t)blockIdx.x * DS_T, m = (b + DS_T < n ? b + DS_T : n) - b;
+    const ulonglong2* v = reinterpret_cast<const ulonglong2*>(rec + b);     // a tile starts 64 KiB into a 256-byte aligned array
+    for (uint64_t i = threadIdx.x; i < m / 2; i += DS_WG) {
+        const ulonglong2 x = v[i];
+        atomicAdd(&c[(x.x >> shift) & (DS_R - 1)], 1u);
+        atomicAdd(&c[(x.y >> shift) & (DS_R - 1)], 1u);
+    }
+    if ((m & 1) && threadIdx.x == 0) atomicAdd(&c[(rec[b + m - 1] >> shift) & (DS_R - 1)], 1u);
+    __syncthreads();
+    if (threadIdx.x < DS_R) cnt[threadIdx.x * G + blockIdx.x] = c[threadIdx.x];
+}
+// one workgroup per digit d: exclusive scan of counts[d * G .. d * G + G) in place, the row's total to tot[d]
+__global__ __launch_bounds__(DS_SCAN_WG) void k_dd_dscan(uint32_t* cnt, uint32_t G, uint32_t* tot) {
+    __shared__ uint32_t wsum[DS_SCAN_WG / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t* row = cnt + (uint64_t)blockIdx.x * G;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < G; base += DS_SCAN_WG * DS_SCAN_V) {
+        const uint32_t i0 = base + threadIdx.x * DS_SCAN_V;
+        uint32_t v[DS_SCAN_V], s = 0;
+#pragma unroll
+        for (int k = 0; k < DS_SCAN_V; ++k) { v[k] = i0 + k < G ? row[i0 + k] : 0u; s += v[k]; }
+        const uint32_t inc = wave_iscan32(s);
+        if (lane == 63) wsum[wv] = inc;
+        __syncthreads();
+        uint32_t pre = carry, all = 0;
+#pragma unroll
+        for (int w = 0; w < DS_SCAN_WG / 64; ++w) { const uint32_t x = wsum[w]; if (w < wv) pre += x; all += x; }
+        pre += inc - s;
+#pragma unroll
+        for (int k = 0; k < DS_SCAN_V; ++k) { if (i0 + k < G) row[i0 + k] = pre; pre += v[k]; }
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
+}
+__global__ __launch_bounds__(DS_WG, 4) void k_dd_scatter(const uint64_t* rec, uint64_t n, int shift, const uint32_t* cnt, const uint32_t* tot, uint32_t G, uint64_t* rec2) {
+    __shared__ uint64_t tile[DS_T];
+    __shared__ uint32_t wrun[DS_NW][DS_R];      // per wave: running count of each digit, then the wave's first slot in the tile
+    __shared__ uint32_t gdelta[DS_R];           // global offset of the digit's run minus its offset in the tile
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const uint64_t b = (uint64_t)blockIdx.x * DS_T, m = (b + DS_T < n ? b + DS_T : n) - b;
+    uint32_t gc0 = 0, gc1 = 0, t0 = 0, t1 = 0;
+    if (wv == 0) {                              // lane l of wave 0 owns digits 2l, 2l + 1
+        gc0 = cnt[(uint64_t)(2 * lane) * G + blockIdx.x]; gc1 = cnt[(uint64_t)(2 * lane + 1) * G + blockIdx.x];
+        t0 = tot[2 * lane]; t1 = tot[2 * lane + 1];
+    }
+    for (int i = tid; i < DS_NW * DS_R; i += DS_WG) (&wrun[0][0])[i] = 0u;
+    __syncthreads();
+    // wave wv ranks records [wv * DS_T / DS_NW, (wv + 1) * DS_T / DS_NW) of the tile, 64 at a time, in input order
+    uint64_t r[DS_K];
+    uint32_t loc[DS_K / 2];                     // rank of record k among the wave's records of its digit (< 2^16), two per register
+    const uint64_t lt = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int k = 0; k < DS_K; ++k) {
+        const uint64_t i = (uint64_t)wv * (DS_T / DS_NW) + k * 64 + lane;
+        r[k] = i < m ? rec[b + i] : 0ull;
+    }
+#pragma unroll
+    for (int k = 0; k < DS_K; ++k) {
+        const uint64_t i = (uint64_t)wv * (DS_T / DS_NW) + k * 64 + lane;
+        const bool live = i < m;
+        const uint32_t d = (uint32_t)(r[k] >> shift) & (DS_R - 1);
+        uint64_t peers = __ballot(live);
+#pragma unroll
+        for (int q = 0; q < DS_D; ++q) {
+            const uint64_t s = __ballot((d >> q) & 1u);
+            peers &= ((d >> q) & 1u) ? s : ~s;
+        }
+        const uint32_t before = wrun[wv][d];
+        const uint32_t rk = before + (uint32_t)__popcll(peers & lt);
+        loc[k / 2] = k & 1 ? loc[k / 2] | rk << 16 : rk;
+        if (live && (peers & lt) == 0) wrun[wv][d] = before + (uint32_t)__popcll(peers);   // the lowest peer lane
+    }
+    __syncthreads();
+    if (wv == 0) {
+        uint32_t c0 = 0, c1 = 0;
+        for (int w = 0; w < DS_NW; ++w) {
+            const uint32_t x0 = wrun[w][2 * lane], x1 = wrun[w][2 * lane + 1];
+            wrun[w][2 * lane] = c0; wrun[w][2 * lane + 1] = c1;
+            c0 += x0; c1 += x1;
+        }
+        const uint32_t s = c0 + c1, ts = t0 + t1;
+        const uint32_t e0 = wave_iscan32(s) - s, g0 = wave_iscan32(ts) - ts + gc0;        // tile offsets, global offsets
+        const uint32_t e1 = e0 + c0, g1 = g0 + t0 - gc0 + gc1;
+        for (int w = 0; w < DS_NW; ++w) { wrun[w][2 * lane] += e0; wrun[w][2 * lane + 1] += e1; }
+        gdelta[2 * lane] = g0 - e0; gdelta[2 * lane + 1] = g1 - e1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < DS_K; ++k) {
+        const uint64_t i = (uint64_t)wv * (DS_T / DS_NW) + k * 64 + lane;
+        if (i < m) tile[wrun[wv][(uint32_t)(r[k] >> shift) & (DS_R - 1)] + ((loc[k / 2] >> (16 * (k & 1))) & 0xFFFFu)] = r[k];
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < m; i += DS_WG) {           // runs of equal digits leave as contiguous stores
+        const uint64_t x = tile[i];
+        rec2[gdelta[(uint32_t)(x >> shift) & (DS_R - 1)] + i] = x;
+    }
+}
+// exclusive scan of m counters, one workgroup (launch_partition)
+__global__ __launch_bounds__(NT) void k_dd_scan(uint32_t* hist, uint32_t m) {
     __shared__ ScanScratch sc;
     __shared__ uint64_t carry;
     if (threadIdx.x == 0) carry = 0;
@@ -1200,87 +1319,64 @@ __global__ __launch_bounds__(NT) void k_dd_scan(uint32_t* hist, uint32_t m) {   
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(DD_WG) void k_dd_scatter(const uint64_t* rec, uint64_t n, uint64_t per, int shift, const uint32_t* hist, uint32_t G, uint64_t* rec2) {
-    __shared__ uint32_t base[16];
-    __shared__ uint32_t wcnt[DD_WG / 64][16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid < 16) base[tid] = hist[tid * G + blockIdx.x];
-    __syncthreads();
-    const uint64_t b = (uint64_t)blockIdx.x * per, e = b + per < n ? b + per : n;
-    for (uint64_t j0 = b; j0 < e; j0 += DD_WG) {            // sub-tiles in input order keep the pass stable
-        const uint64_t j = j0 + tid;
-        const bool live = j < e;
-        const uint64_t rv = live ? rec[j] : 0;
-        const uint32_t d = live ? (uint32_t)((rv >> shift) & 15u) : 16u;
-        uint32_t rank = 0;
-#pragma unroll
-        for (uint32_t dd = 0; dd < 16; ++dd) {
-            const uint64_t m = __ballot(d == dd);
-            if (d == dd) rank = __popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) wcnt[wv][dd] = __popcll(m);
-        }
-        __syncthreads();
-        if (live) {
-            uint32_t o = base[d] + rank;
-            for (int w = 0; w < wv; ++w) o += wcnt[w][d];
-            rec2[o] = rv;
-        }
-        __syncthreads();
-        if (tid < 16) { uint32_t s = 0; for (int w = 0; w < DD_WG / 64; ++w) s += wcnt[w][tid]; base[tid] += s; }
-        __syncthreads();
-    }
-}
-// run = neighbours that agree on the sorted hash bits.  Keys are fetched (random 24-byte gathers) only on a full 32-bit
-// hash match with an earlier element of the run, i.e. almost never unless it IS a duplicate; flags start out zeroed.
-__global__ void k_dd_mark(const KeyRec* keys, const uint64_t* rec, uint64_t n, uint64_t run_mask, uint8_t* flags, DedupResult* res) {
-    uint32_t mine = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) {
+// run = neighbours that agree on the sorted hash bits.  Keys are fetched (random 24-byte gathers) only when the whole hash
+// field (64 - ib bits) matches an earlier element of the run, i.e. almost never unless it IS a duplicate; flags start out zeroed.
+// One element per thread, its predecessor loaded beside it: a run holds 1/4 element on average, so nearly every thread is done
+// after those two loads (a grid-stride loop here was bound by one dependent round trip per element and iteration).
+__global__ __launch_bounds__(256) void k_dd_mark(const KeyRec* keys, const uint64_t* rec, uint64_t n, int ib, uint64_t run_mask, uint8_t* flags, DedupResult* res) {
+    const uint64_t imask = (1ull << ib) - 1ull, j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool dup = false;
+    if (j < n) {
         const uint64_t r = rec[j];
-        bool dup = false, have = false;
+        uint64_t o = j ? rec[j - 1] : ~r;
+        bool have = false;
         KeyRec me;
-        for (uint64_t b = j; b-- > 0;) {
-            const uint64_t o = rec[b];
-            if ((o ^ r) & run_mask) break;                                  // left the run
-            if ((o >> 32) != (r >> 32)) continue;
-            if (!have) { me = keys[(uint32_t)r]; have = true; }
-            if (key_eq(keys[(uint32_t)o], me)) { dup = true; break; }       // earlier in the run = earlier in the input
+        for (uint64_t b = j - 1; !((o ^ r) & run_mask);) {                 // while inside the run
+            if (!((o ^ r) >> ib)) {
+                if (!have) { me = keys[r & imask]; have = true; }
+                if (key_eq(keys[o & imask], me)) { dup = true; break; }     // earlier in the run = earlier in the input
+            }
+            if (b-- == 0) break;
+            o = rec[b];
         }
-        if (dup) { flags[(uint32_t)r] = 1; ++mine; }
+        if (dup) flags[r & imask] = 1;
     }
-    if (mine) atomicAdd((unsigned long long*)&res->dups, (unsigned long long)mine);
+    const uint64_t m = __ballot(dup);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd((unsigned long long*)&res->dups, (unsigned long long)__popcll(m));
     if (blockIdx.x == 0 && threadIdx.x == 0) res->total = n;
 }
 size_t dedup_work_bytes(uint64_t n) {
-    const uint64_t G = 1024;
-    return (size_t)(n * (8 + 8) + 16 * G * 4 + 4096);
+    const uint64_t G = (n + DS_T - 1) / DS_T;
+    return (size_t)(n * (8 + 8) + DS_R * (G + 1) * 4 + 4096);
 }
 hipError_t launch_dedup(const KeyRec* keys, uint64_t n, uint8_t* flags, void* work, size_t work_bytes, DedupResult* d_res, hipStream_t s) {
     hipError_t e = hipMemsetAsync(d_res, 0, sizeof(DedupResult), s);
     if (e != hipSuccess || n == 0) return e;
     if (work_bytes < dedup_work_bytes(n) || n >= (1ull << 32)) return hipErrorInvalidValue;
-    uint8_t* w = (uint8_t*)work;
-    uint64_t* rA = (uint64_t*)w; w += n * 8;
-    uint64_t* rB = (uint64_t*)w; w += n * 8;
-    uint32_t* hist = (uint32_t*)(((uintptr_t)w + 255) & ~(uintptr_t)255);
-    uint32_t G = (uint32_t)((n + 8191) / 8192);
-    if (G > 1024) G = 1024;
-    if (G == 0) G = 1;
-    const uint64_t per = (n + G - 1) / G;
+    const uint32_t G = (uint32_t)((n + DS_T - 1) / DS_T);
+    uint8_t* w = (uint8_t*)(((uintptr_t)work + 255) & ~(uintptr_t)255);
+    uint64_t* rA = (uint64_t*)w; w += ((n * 8 + 255) & ~255ull);
+    uint64_t* rB = (uint64_t*)w; w += ((n * 8 + 255) & ~255ull);
+    uint32_t* cnt = (uint32_t*)w;
+    uint32_t* tot = cnt + (uint64_t)DS_R * G;
+    int ib = 1;                                               // index bits: ceil(log2 n), 1 .. 32
+    while ((1ull << ib) < n) ++ib;
     int bits = 2;                                             // log2(n) + 2, in whole digits, 12 .. 32
     while (bits < 34 && (1ull << (bits - 2)) < n) ++bits;
     bits = bits < 12 ? 12 : (bits > 32 ? 32 : bits);
-    const int passes = (bits + 3) / 4;
-    hipLaunchKernelGGL(k_dd_init, dim3(1024), dim3(256), 0, s, keys, n, rA);
+    const int passes = (bits + DS_D - 1) / DS_D;
+    const int sorted = passes * DS_D < 64 - ib ? passes * DS_D : 64 - ib;
+    hipLaunchKernelGGL(k_dd_prep, dim3(G), dim3(DS_WG), 0, s, keys, n, ib, rA, cnt, G);
     for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(k_dd_hist, dim3(G), dim3(DD_WG), 0, s, (const uint64_t*)rA, n, per, 32 + 4 * p, hist, G);
-        hipLaunchKernelGGL(k_dd_scan, dim3(1), dim3(NT), 0, s, hist, 16u * G);
-        hipLaunchKernelGGL(k_dd_scatter, dim3(G), dim3(DD_WG), 0, s, (const uint64_t*)rA, n, per, 32 + 4 * p, (const uint32_t*)hist, G, rB);
+        if (p) hipLaunchKernelGGL(k_dd_count, dim3(G), dim3(DS_WG), 0, s, (const uint64_t*)rA, n, ib + DS_D * p, cnt, G);
+        hipLaunchKernelGGL(k_dd_dscan, dim3(DS_R), dim3(DS_SCAN_WG), 0, s, cnt, G, tot);
+        hipLaunchKernelGGL(k_dd_scatter, dim3(G), dim3(DS_WG), 0, s, (const uint64_t*)rA, n, ib + DS_D * p, (const uint32_t*)cnt, (const uint32_t*)tot, G, rB);
         uint64_t* t = rA; rA = rB; rB = t;
     }
-    const uint64_t run_mask = ((passes * 4 >= 32 ? 0xFFFFFFFFull : ((1ull << (passes * 4)) - 1ull))) << 32;
+    const uint64_t run_mask = ((1ull << sorted) - 1ull) << ib;
     e = hipMemsetAsync(flags, 0, n, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_dd_mark, dim3(1024), dim3(256), 0, s, keys, (const uint64_t*)rA, n, run_mask, flags, d_res);
+    hipLaunchKernelGGL(k_dd_mark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, (const uint64_t*)rA, n, ib, run_mask, flags, d_res);
     return hipGetLastError();
 }
 
