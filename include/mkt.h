@@ -296,6 +296,49 @@ int mkt_bam_stats(const mkt_bam* b, uint64_t stats[5] /* runs, temporary bytes w
  * these counts before mkt_finish */
 int mkt_group_count(mkt_ctx* ctx, uint64_t* groups);
 
+/* ---- pairs -> binned contact matrix at several resolutions (the driver's last stage, microcket:520-554) -------------------
+ * What `juicer_tools pre -r ...` and `cooler cload pairix` spend their time on: the sparse binned matrix.  The containers they
+ * write (.hic, .cool), balancing and zoomify are out of scope; parity with those tools is unpinned.  Bin drop-in: bin/pairs2matrix.
+ *
+ * Definition.  chromsizes: lines name<TAB>length (anno/<genome>.info; empty and '#' lines ignored); FILE ORDER IS BIN ORDER.
+ * For a resolution r >= 1: chromosome i of length L_i owns n_i = ceil(L_i / r) bins, off_i = n_0 + .. + n_(i-1), nbins = sum n_i;
+ * bin(chr_i, pos) = off_i + (pos - 1) / r for the 1-based positions of a .pairs line (columns 2-5: chrA posA chrB posB).
+ * A pair is SKIPPED (counted, never binned, never an error) when a chromosome is not in the table or a position is 0 or > L_i.
+ * Every other pair adds 1 to cell (min(b1, b2), max(b1, b2)) -- decided on bin ids, not on the order of the text's two sides.
+ * Result: the non-empty cells (bin1, bin2, count) strictly ascending in (bin1, bin2); it depends on the multiset of pairs only
+ * (input order, chunking and the route the pairs came by never change a byte); sum(count) + skipped == pairs.
+ *
+ * Limits (MKT_E_ARG / MKT_E_CAPACITY with a message): 1 .. 16 resolutions per object; nbins < 2^32 at every resolution; fewer than
+ * 2^32 pairs per object (counts are uint32_t); names of 1 .. 63 bytes, at most 8192 of them, none twice; lengths < 2^32.
+ *
+ * The table and the resolutions are fixed at create time (mkt_matrix_error(NULL): why the last create failed).  Pairs arrive by
+ * any mix of the add forms; only 16 bytes per pair stay on the device, the text of one add call is resident during that call only.
+ *   mkt_matrix_add         .pairs text from the host in ANY chunking (a partial last line is carried to the next call; '#' lines
+ *                          are ignored).  Lines with fewer than five columns or a non-decimal position make mkt_matrix_run fail.
+ *   mkt_matrix_add_device  whole lines already on the device
+ *   mkt_matrix_add_keys    the reported pairs of a context created with MKT_EXT_KEYS on the same device (drop_last as in
+ *                          mkt_finish); skip_flags (may be NULL): one byte per reported pair in input order, e.g. what
+ *                          mkt_ext_dedup returns -- flagged pairs are left out (not counted as pairs): the matrix without duplicates
+ *   mkt_matrix_run         bins everything added so far at every resolution; pairs / skipped: the totals.  More pairs may be added
+ *                          and run called again.
+ *   mkt_matrix_info        nbins (valid before run), cells and bytes of COO text of resolution res_index
+ *   mkt_matrix_fetch       cells [first, first + n) as arrays (any of the three may be NULL)
+ *   mkt_matrix_fetch_text  bytes [off, off + n) of the lines "bin1<TAB>bin2<TAB>count\n", made on the device: what
+ *                          `cooler load -f coo <chromsizes>:<r>` reads
+ *   mkt_matrix_timing      device time (ms, HIP events) the last run spent on resolution res_index */
+typedef struct mkt_matrix mkt_matrix;
+int mkt_matrix_create(int device, const char* chromsizes, size_t len, const uint32_t* resolutions, uint32_t n_res, mkt_matrix** out);
+void mkt_matrix_destroy(mkt_matrix* m);
+const char* mkt_matrix_error(const mkt_matrix* m);
+int mkt_matrix_add(mkt_matrix* m, const char* bytes, size_t n);
+int mkt_matrix_add_device(mkt_matrix* m, const void* d_bytes, size_t n);
+int mkt_matrix_add_keys(mkt_matrix* m, mkt_ctx* ctx, int drop_last, const uint8_t* skip_flags, size_t n_flags);
+int mkt_matrix_run(mkt_matrix* m, uint64_t* pairs, uint64_t* skipped);
+int mkt_matrix_info(const mkt_matrix* m, uint32_t res_index, uint64_t* nbins, uint64_t* nnz, uint64_t* text_bytes);
+int mkt_matrix_fetch(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint32_t* bin1, uint32_t* bin2, uint32_t* count);
+int mkt_matrix_fetch_text(mkt_matrix* m, uint32_t res_index, uint64_t off, char* out, size_t n);
+int mkt_matrix_timing(const mkt_matrix* m, uint32_t res_index, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

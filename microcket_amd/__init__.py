@@ -9,6 +9,7 @@ from .capi import (  # noqa: F401
     Context,
     EXT_KEYS,
     EXT_LANES,
+    Matrix,
     MktError,
     MODE_FLASH,
     MODE_UNC,
@@ -27,6 +28,6 @@ from .capi import (  # noqa: F401
 )
 
 __all__ = [
-    "Context", "EXT_KEYS", "EXT_LANES", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
+    "Context", "EXT_KEYS", "EXT_LANES", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
     "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam",
 ]

@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_matrix.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -148,6 +148,20 @@ def build_sam2bam(force=False):
     return SAM2BAM
 
 
+PAIRS2MATRIX = os.path.join(HERE, "bin", "pairs2matrix")
+
+
+def build_pairs2matrix(force=False):
+    """bin/pairs2matrix: .pairs -> binned contact matrices (COO text, bins, counts) at several resolutions on the GPU: the
+    computation behind the driver's `juicer_tools pre` / `cooler cload` stage (microcket:520-554)."""
+    src = os.path.join(CSRC, "pairs2matrix_main.cpp")
+    if force or _newer(PAIRS2MATRIX, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(PAIRS2MATRIX), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", PAIRS2MATRIX, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return PAIRS2MATRIX
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -186,6 +200,7 @@ def build_all(force=False, extras=True):
     build_pairsort(force)
     build_krmdup(force)
     build_sam2bam(force)
+    build_pairs2matrix(force)
     build_makestat(force)
     if extras:
         build_oracle()

@@ -21,6 +21,8 @@ EXPORTS = [
     "mkt_rmdup_begin", "mkt_rmdup_push", "mkt_rmdup_stats",
     "mkt_bam_create", "mkt_bam_destroy", "mkt_bam_error", "mkt_bam_note", "mkt_bam_add", "mkt_bam_add_device", "mkt_bam_run", "mkt_bam_fetch",
     "mkt_bam_reserve", "mkt_bam_window", "mkt_bam_commit", "mkt_bam_read", "mkt_bam_spill", "mkt_bam_pull", "mkt_bam_stats",
+    "mkt_matrix_create", "mkt_matrix_destroy", "mkt_matrix_error", "mkt_matrix_add", "mkt_matrix_add_device", "mkt_matrix_add_keys", "mkt_matrix_run",
+    "mkt_matrix_info", "mkt_matrix_fetch", "mkt_matrix_fetch_text", "mkt_matrix_timing",
 ]
 
 
@@ -176,6 +178,19 @@ def load_library():
     L.mkt_bam_spill.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_int, C.c_int]
     L.mkt_bam_pull.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.mkt_bam_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mkt_matrix_create.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.mkt_matrix_destroy.argtypes = [C.c_void_p]
+    L.mkt_matrix_destroy.restype = None
+    L.mkt_matrix_error.argtypes = [C.c_void_p]
+    L.mkt_matrix_error.restype = C.c_char_p
+    L.mkt_matrix_add.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.mkt_matrix_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.mkt_matrix_add_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.mkt_matrix_run.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mkt_matrix_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mkt_matrix_fetch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mkt_matrix_fetch_text.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_matrix_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -498,6 +513,79 @@ class PairsSorter:
     def close(self):
         if self.h:
             self.L.mkt_sorter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Matrix:
+    """Reported pairs -> binned contact matrices at several resolutions on the GPU: see mkt_matrix_* in include/mkt.h (where the
+    binning is defined).  chromsizes: bytes of name<TAB>length lines, file order = bin order; resolutions: 1 .. 16 bin sizes in bp."""
+
+    def __init__(self, chromsizes: bytes, resolutions, device=0):
+        self.L = load_library()
+        self.resolutions = [int(r) for r in resolutions]
+        arr = (C.c_uint32 * max(len(self.resolutions), 1))(*self.resolutions)
+        self.h = C.c_void_p()
+        rc = self.L.mkt_matrix_create(device, chromsizes, len(chromsizes), arr, len(self.resolutions), C.byref(self.h))
+        if rc != 0:
+            raise MktError(f"mkt_matrix_create: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_matrix_error(None).decode()}")
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise MktError(f"{what}: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_matrix_error(self.h).decode()}")
+
+    def add(self, data: bytes):
+        """.pairs text in any chunking (a partial last line is carried)"""
+        self._chk(self.L.mkt_matrix_add(self.h, data, len(data)), "mkt_matrix_add")
+
+    def add_device(self, d_ptr, n):
+        self._chk(self.L.mkt_matrix_add_device(self.h, C.c_void_p(d_ptr), n), "mkt_matrix_add_device")
+
+    def add_keys(self, ctx, drop_last=True, flags=None):
+        """The reported pairs of a Context created with EXT_KEYS; flags (bytes, one per reported pair, e.g. from ext_dedup): leave those out."""
+        self._chk(self.L.mkt_matrix_add_keys(self.h, ctx.h, 1 if drop_last else 0, flags, len(flags) if flags is not None else 0), "mkt_matrix_add_keys")
+
+    def run(self):
+        """(pairs seen, pairs skipped)"""
+        p, s = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.mkt_matrix_run(self.h, C.byref(p), C.byref(s)), "mkt_matrix_run")
+        return p.value, s.value
+
+    def info(self, res):
+        """(nbins, non-empty cells, bytes of COO text) of resolution index res"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.L.mkt_matrix_info(self.h, res, C.byref(a), C.byref(b), C.byref(c)), "mkt_matrix_info")
+        return a.value, b.value, c.value
+
+    def cells(self, res):
+        """(bin1, bin2, count): three numpy uint32 arrays, ascending in (bin1, bin2)"""
+        import numpy as np
+        nnz = self.info(res)[1]
+        out = [np.zeros(nnz, dtype=np.uint32) for _ in range(3)]
+        if nnz:
+            self._chk(self.L.mkt_matrix_fetch(self.h, res, 0, nnz, *[a.ctypes.data_as(C.c_void_p) for a in out]), "mkt_matrix_fetch")
+        return tuple(out)
+
+    def text(self, res):
+        """the lines bin1<TAB>bin2<TAB>count of resolution index res, as made on the device"""
+        n = self.info(res)[2]
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_matrix_fetch_text(self.h, res, 0, buf, n), "mkt_matrix_fetch_text")
+        return buf.raw[:n]
+
+    def timing_ms(self, res):
+        ms = C.c_double()
+        self._chk(self.L.mkt_matrix_timing(self.h, res, C.byref(ms)), "mkt_matrix_timing")
+        return ms.value
+
+    def close(self):
+        if self.h:
+            self.L.mkt_matrix_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):

@@ -1379,6 +1379,23 @@ hipError_t launch_dedup(const KeyRec* keys, uint64_t n, uint8_t* flags, void* wo
     hipLaunchKernelGGL(k_dd_mark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keys, (const uint64_t*)rA, n, ib, run_mask, flags, d_res);
     return hipGetLastError();
 }
+// The same passes for other users (mkt_matrix.hip): a stable LSD sort of n < 2^32 u64 records over bits [lo_bit, lo_bit + nbits),
+// rounded up to whole 7-bit digits (bits past 63 read as zero).  rA / rB: 16-byte aligned, n records each; the sorted records end
+// up in rA (the pointers are swapped as needed).  cnt: radix64_count_bytes(n).
+size_t radix64_count_bytes(uint64_t n) { return (size_t)(DS_R * ((n + DS_T - 1) / DS_T + 1) * 4 + 4096); }
+hipError_t launch_radix64(uint64_t*& rA, uint64_t*& rB, uint64_t n, int lo_bit, int nbits, uint32_t* cnt, hipStream_t s) {
+    if (n == 0 || nbits <= 0) return hipSuccess;
+    if (n >= (1ull << 32) || lo_bit < 0 || lo_bit + nbits > 64) return hipErrorInvalidValue;
+    const uint32_t G = (uint32_t)((n + DS_T - 1) / DS_T);
+    uint32_t* tot = cnt + (uint64_t)DS_R * G;
+    for (int sh = lo_bit; sh < lo_bit + nbits; sh += DS_D) {
+        hipLaunchKernelGGL(k_dd_count, dim3(G), dim3(DS_WG), 0, s, (const uint64_t*)rA, n, sh, cnt, G);
+        hipLaunchKernelGGL(k_dd_dscan, dim3(DS_R), dim3(DS_SCAN_WG), 0, s, cnt, G, tot);
+        hipLaunchKernelGGL(k_dd_scatter, dim3(G), dim3(DS_WG), 0, s, (const uint64_t*)rA, n, sh, (const uint32_t*)cnt, (const uint32_t*)tot, G, rB);
+        uint64_t* t = rA; rA = rB; rB = t;
+    }
+    return hipGetLastError();
+}
 
 // ---- sharded duplicate marking (one context per GPU): hash-partitioned exchange of the key space ----------------
 // Every rank sends each key record to rank mix64(key) % world (RCCL all_to_all over xGMI, microcket_amd/shard.py), so equal

@@ -1,0 +1,659 @@
+// mkt_matrix.hip -- the last stage of the driver (microcket:520-554): reported pairs -> a binned contact matrix at several
+// resolutions, on the GPU.  The containers the driver's tools write (.hic, .cool) are out of scope; what is computed here is what
+// they spend their time on, the sparse upper-triangle matrix, handed back as arrays and as the COO text `cooler load -f coo` reads.
+//
+// Definition (include/mkt.h has it in full): chromosome i of length L_i owns ceil(L_i / r) bins in table order; a pair
+// (chrA, posA, chrB, posB) adds 1 to cell (min, max) of its two bin ids; a pair with a chromosome that is not in the table or a
+// position of 0 or past the chromosome's end is counted as skipped.  The result depends on the multiset of pairs only.
+//
+// Data: one 16-byte MxRec per pair stays resident (chromosome index and position of both sides); the .pairs text that produced it
+// does not.  Per resolution: records -> u64 key = bin1 << B | bin2 (B = bits of nbins), the stable 7-bit LSD radix passes of the
+// duplicate marker over the 2B significant bits (launch_radix64), then run-length reduction: head flags on key[j] != key[j - 1], a
+// scan for the output slots, and a cell's count is the DIFFERENCE of two neighbouring head positions -- exact for runs of any length
+// across tiles and workgroups, no atomics on the counts, no dependence on the order anything ran in.  Then the COO text: byte length
+// per cell, a scan, a write through LDS.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/mkt.h"
+#include "mkt_launch.h"
+#include "mkt_sortlib.h"
+
+using namespace mkt;
+
+namespace mkt {
+
+constexpr int MXWG = 256;
+constexpr uint32_t MX_SKIP = 0xFFFFFFFFu;          // MxRec::ia of a skipped pair
+constexpr uint32_t MX_NONE = 0xFFFFFFFEu;          // ... of something that is not a pair (a '#' line, a pair left out by its flag)
+struct MxRec { uint32_t ia, pa, ib, pb; };         // table index and 1-based position of the two sides
+static_assert(sizeof(MxRec) == 16, "one 16-byte vector per pair");
+
+// the given table, read-only on the device: open addressing over FNV-1a of the name (nothing is ever inserted by a kernel)
+constexpr uint32_t kMxSlots = 2 * kChrSlots;
+struct MxTab {
+    unsigned long long hash[kMxSlots];             // 0 = empty
+    uint16_t idx[kMxSlots];                        // table index of the slot's name
+    uint8_t name[kChrSlots][64];                   // by table index; [63] = length (<= 63)
+    uint32_t len[kChrSlots];                       // L_i
+};
+enum { ME_FIELDS = 1 };
+struct MxCounters { unsigned long long skipped, none; uint32_t err, pad; };
+
+__host__ __device__ inline uint64_t mx_fnv(const uint8_t* p, uint64_t n) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (uint64_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
+    return h ? h : 1ull;
+}
+__device__ inline uint32_t mx_exscan(uint32_t v, uint32_t* total, uint32_t* sh /* [MXWG / 64] */) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, d, 64); if (lane >= d) inc += y; }
+    if (lane == 63) sh[wv] = inc;
+    __syncthreads();
+    uint32_t pre = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < MXWG / 64; ++w) { if (w < wv) pre += sh[w]; tot += sh[w]; }
+    __syncthreads();
+    *total = tot;
+    return pre + inc - v;
+}
+// one add per wave for the two counters
+__device__ inline void mx_count(bool skipped, bool none, MxCounters* c) {
+    const uint64_t bs = __ballot(skipped), bn = __ballot(none);
+    if ((threadIdx.x & 63) == 0) {
+        if (bs) atomicAdd(&c->skipped, (unsigned long long)__popcll(bs));
+        if (bn) atomicAdd(&c->none, (unsigned long long)__popcll(bn));
+    }
+}
+__device__ inline MxRec mx_make(uint32_t ia, uint64_t pa, uint32_t ib, uint64_t pb, const MxTab* tab, bool* skipped) {
+    MxRec r;
+    const bool ok = ia < kChrSlots && ib < kChrSlots && pa >= 1 && pb >= 1 && pa <= tab->len[ia < kChrSlots ? ia : 0] && pb <= tab->len[ib < kChrSlots ? ib : 0];
+    *skipped = !ok;
+    r.ia = ok ? ia : MX_SKIP; r.pa = (uint32_t)pa; r.ib = ib; r.pb = (uint32_t)pb;
+    return r;
+}
+
+// ---- .pairs text -> records: rid \t chr1 \t pos1 \t chr2 \t pos2 [\t ...] \n, one lane per line (the newline index is the sorter's)
+__global__ __launch_bounds__(MXWG) void k_mx_parse(const uint8_t* text, const uint64_t* starts, uint64_t nlines, const MxTab* tab, MxRec* rec, MxCounters* cnt) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool skipped = false, none = false;
+    if (j < nlines) {
+        const uint64_t ls = starts[j], le = starts[j + 1] - 1;                    // le: the newline
+        MxRec r;
+        r.ia = MX_NONE; r.pa = 0; r.ib = 0; r.pb = 0;
+        if (ls < le && text[ls] == '#') none = true;                              // a 4DN header line
+        else {
+            uint64_t tabs[5];
+            int nt = 0;
+            for (uint64_t p = ls; p < le && nt < 5; ++p) if (text[p] == '\t') tabs[nt++] = p;
+            if (nt < 4) { atomicOr(&cnt->err, (uint32_t)ME_FIELDS); none = true; }
+            else {
+                const uint64_t p5 = nt >= 5 ? tabs[4] : le;
+                auto num = [&](uint64_t a, uint64_t b) -> uint64_t {              // a plain decimal field; anything past 2^32 only has to stay past it
+                    uint64_t v = 0;
+                    if (a == b) atomicOr(&cnt->err, (uint32_t)ME_FIELDS);
+                    for (uint64_t p = a; p < b; ++p) {
+                        const uint32_t d = (uint32_t)text[p] - (uint32_t)'0';
+                        if (d > 9u) { atomicOr(&cnt->err, (uint32_t)ME_FIELDS); break; }
+                        if (v < (1ull << 40)) v = v * 10 + d;
+                    }
+                    return v;
+                };
+                auto find = [&](uint64_t a, uint64_t b) -> uint32_t {
+                    const uint64_t L = b - a;
+                    if (L == 0 || L > 63) return MX_SKIP;
+                    const uint64_t h = mx_fnv(text + a, L);
+                    uint32_t s = (uint32_t)(h >> 17) & (kMxSlots - 1u);
+                    for (uint32_t probe = 0; probe < kMxSlots; ++probe) {
+                        const unsigned long long cur = tab->hash[s];
+                        if (cur == 0ull) return MX_SKIP;
+                        if (cur == h) {
+                            const uint32_t i = tab->idx[s];
+                            const uint8_t* nm = tab->name[i];
+                            bool same = nm[63] == (uint8_t)L;
+                            for (uint64_t k = 0; same && k < L; ++k) same = nm[k] == text[a + k];
+                            if (same) return i;
+                        }
+                        s = (s + 1u) & (kMxSlots - 1u);
+                    }
+                    return MX_SKIP;
+                };
+                const uint32_t ia = find(tabs[0] + 1, tabs[1]), ib = find(tabs[2] + 1, tabs[3]);
+                r = mx_make(ia, num(tabs[1] + 1, tabs[2]), ib, num(tabs[3] + 1, p5), tab, &skipped);
+            }
+        }
+        rec[j] = r;
+    }
+    mx_count(skipped, none, cnt);
+}
+
+// ---- a context's key records (mkt_core.h KeyRec) -> records; lut: the context's chromosome slot -> table index (0xFFFF: not in the table)
+__global__ __launch_bounds__(MXWG) void k_mx_from_keys(const KeyRec* keys, uint64_t n, const uint16_t* lut, const uint8_t* flags, const MxTab* tab, MxRec* rec, MxCounters* cnt) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool skipped = false, none = false;
+    if (j < n) {
+        const KeyRec k = keys[j];
+        MxRec r;
+        if (flags && flags[j]) { none = true; r.ia = MX_NONE; r.pa = 0; r.ib = 0; r.pb = 0; }
+        else {
+            const uint32_t a = lut[(k.k0 >> 45) & (kChrSlots - 1u)], b = lut[(k.k0 >> 32) & (kChrSlots - 1u)];
+            r = mx_make(a == 0xFFFFu ? MX_SKIP : a, k.k0 & 0xFFFFFFFFull, b == 0xFFFFu ? MX_SKIP : b, k.k1 >> 32, tab, &skipped);
+        }
+        rec[j] = r;
+    }
+    mx_count(skipped, none, cnt);
+}
+
+// ---- one resolution: key = bin1 << B | bin2, bin1 <= bin2; what is not binned gets nbins << B | nbins and sorts behind every cell
+__global__ __launch_bounds__(MXWG) void k_mx_keys(const MxRec* rec, uint64_t n, const uint32_t* off, uint32_t r, int B, uint64_t nbins, uint64_t* key) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint4 x = reinterpret_cast<const uint4*>(rec)[j];
+    uint64_t k = (nbins << B) | nbins;
+    if (x.x < MX_NONE) {
+        const uint32_t b1 = off[x.x] + (x.y - 1u) / r, b2 = off[x.z] + (x.w - 1u) / r;
+        k = ((uint64_t)(b1 < b2 ? b1 : b2) << B) | (uint64_t)(b1 < b2 ? b2 : b1);
+    }
+    key[j] = k;
+}
+constexpr uint32_t MX_TILE = 8 * MXWG;                        // sorted keys per workgroup in the two head passes
+__device__ inline bool mx_head(const uint64_t* key, uint64_t j) { return j == 0 || key[j] != key[j - 1]; }
+__global__ __launch_bounds__(MXWG) void k_mx_head_count(const uint64_t* key, uint64_t nv, uint64_t* sums) {
+    __shared__ uint32_t sh[MXWG / 64];
+    const uint64_t b = (uint64_t)blockIdx.x * MX_TILE;
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < MX_TILE / MXWG; ++k) { const uint64_t j = b + k * MXWG + threadIdx.x; if (j < nv && mx_head(key, j)) ++c; }
+    uint32_t tot;
+    (void)mx_exscan(c, &tot, sh);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+// sums: exclusive prefixes now.  Cell s = the s-th run: its two bin ids and the position of its head among the sorted keys.
+__global__ __launch_bounds__(MXWG) void k_mx_cells(const uint64_t* key, uint64_t nv, const uint64_t* sums, int B, uint32_t* bin1, uint32_t* bin2, uint32_t* pos) {
+    __shared__ uint32_t sh[MXWG / 64];
+    const uint64_t b = (uint64_t)blockIdx.x * MX_TILE;
+    uint64_t at = sums[blockIdx.x];
+    const uint64_t lo = (1ull << B) - 1ull;                    // B <= 32
+    for (uint32_t k = 0; k < MX_TILE / MXWG; ++k) {            // sub-tiles in order
+        const uint64_t j = b + k * MXWG + threadIdx.x;
+        const bool h = j < nv && mx_head(key, j);
+        uint32_t tot;
+        const uint32_t ex = mx_exscan(h ? 1u : 0u, &tot, sh);
+        if (h) { const uint64_t x = key[j], s = at + ex; bin1[s] = (uint32_t)(x >> B); bin2[s] = (uint32_t)(x & lo); pos[s] = (uint32_t)j; }
+        at += tot;
+    }
+}
+// count = distance to the next head (the last run ends at nv); and the bytes of "bin1 \t bin2 \t count \n" per workgroup of cells
+constexpr uint32_t MX_CPW = 4 * MXWG;                         // cells per workgroup in the text passes
+constexpr uint32_t MX_LINE_MAX = 33;                          // 3 x 10 digits, 2 tabs, newline
+__device__ inline uint32_t mx_line_len(uint32_t a, uint32_t b, uint32_t c) { return dec_digits(a) + dec_digits(b) + dec_digits(c) + 3u; }
+__global__ __launch_bounds__(MXWG) void k_mx_counts(const uint32_t* bin1, const uint32_t* bin2, const uint32_t* pos, uint64_t nnz, uint64_t nv, uint32_t* count, uint64_t* tsums) {
+    __shared__ uint32_t sh[MXWG / 64];
+    const uint64_t b = (uint64_t)blockIdx.x * MX_CPW;
+    uint32_t bytes = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < MX_CPW / MXWG; ++k) {
+        const uint64_t s = b + k * MXWG + threadIdx.x;
+        if (s < nnz) {
+            const uint32_t c = (uint32_t)((s + 1 < nnz ? (uint64_t)pos[s + 1] : nv) - pos[s]);
+            count[s] = c;
+            bytes += mx_line_len(bin1[s], bin2[s], c);
+        }
+    }
+    uint32_t tot;
+    (void)mx_exscan(bytes, &tot, sh);
+    if (threadIdx.x == 0) tsums[blockIdx.x] = tot;
+}
+__device__ inline uint32_t mx_put(uint8_t* p, uint32_t v, uint8_t tail) {        // v in decimal and one byte behind it; returns the bytes written
+    uint64_t hi8; uint32_t lo2;
+    dec10(v, hi8, lo2);
+    const uint32_t nd = dec_digits(v), drop = 10u - nd;
+    for (uint32_t k = 0; k < nd; ++k) { const uint32_t q = drop + k; p[k] = (uint8_t)(q < 8u ? (hi8 >> (8u * q)) : ((uint64_t)lo2 >> (8u * (q - 8u)))); }
+    p[nd] = tail;
+    return nd + 1u;
+}
+// tsums: exclusive prefixes now.  The workgroup's lines are laid out in LDS and leave as aligned 4-byte stores.
+__global__ __launch_bounds__(MXWG) void k_mx_text(const uint32_t* bin1, const uint32_t* bin2, const uint32_t* count, uint64_t nnz, const uint64_t* tsums, uint8_t* out) {
+    __shared__ uint32_t sh[MXWG / 64];
+    __shared__ uint32_t buf32[(MX_CPW * MX_LINE_MAX + 3) / 4 + 1];
+    uint8_t* buf = reinterpret_cast<uint8_t*>(buf32);
+    const uint64_t b = (uint64_t)blockIdx.x * MX_CPW;
+    uint32_t carry = 0;
+    for (uint32_t k = 0; k < MX_CPW / MXWG; ++k) {
+        const uint64_t s = b + k * MXWG + threadIdx.x;
+        uint32_t a = 0, c = 0, d = 0, len = 0;
+        if (s < nnz) { a = bin1[s]; c = bin2[s]; d = count[s]; len = mx_line_len(a, c, d); }
+        uint32_t tot;
+        const uint32_t ex = mx_exscan(len, &tot, sh);
+        if (s < nnz) {
+            uint8_t* p = buf + carry + ex;
+            p += mx_put(p, a, '\t');
+            p += mx_put(p, c, '\t');
+            (void)mx_put(p, d, '\n');
+        }
+        carry += tot;
+    }
+    __syncthreads();
+    const uint32_t T = carry;                                                    // the workgroup's bytes
+    uint8_t* dst = out + tsums[blockIdx.x];
+    uint32_t head = (uint32_t)((4u - ((uintptr_t)dst & 3u)) & 3u);
+    if (head > T) head = T;
+    if (threadIdx.x < head) dst[threadIdx.x] = buf[threadIdx.x];
+    const uint32_t words = (T - head) / 4u;
+    uint32_t* dw = reinterpret_cast<uint32_t*>(dst + head);
+    for (uint32_t w = threadIdx.x; w < words; w += MXWG) {
+        const uint8_t* q = buf + head + 4u * w;
+        dw[w] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    }
+    const uint32_t done = head + 4u * words;
+    if (threadIdx.x < T - done) dst[done + threadIdx.x] = buf[done + threadIdx.x];
+}
+
+}  // namespace mkt
+
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct MxRes {
+    uint32_t r = 0;
+    uint64_t nbins = 0;
+    int B = 0;
+    std::vector<uint32_t> off;
+    uint32_t* d_off = nullptr;
+    uint64_t nnz = 0, text_bytes = 0;
+    uint32_t *d_b1 = nullptr, *d_b2 = nullptr, *d_cnt = nullptr;
+    uint8_t* d_text = nullptr;
+    double ms = 0;
+};
+thread_local std::string g_mx_create_err;
+}  // namespace
+
+struct mkt_matrix {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+    std::unordered_map<std::string, uint32_t> index;
+    MxTab* d_tab = nullptr;
+    MxCounters* d_counters = nullptr;
+    MxRec* d_rec = nullptr; uint64_t rec_cap = 0, n = 0;
+    uint8_t* d_text = nullptr; size_t text_cap = 0;
+    std::string carry;                              // an incomplete last line of the text seen so far
+    bool ran = false;
+    uint64_t pairs = 0, skipped = 0;
+    std::vector<MxRes> res;
+    std::string err;
+};
+
+static int mfail(mkt_matrix* m, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (m) m->err = buf; else g_mx_create_err = buf;
+    return code;
+}
+#define MCHK(m, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mfail((m), MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+
+// lines name \t length [\t ...]; empty lines and '#' lines are ignored.  Returns an empty string or what is wrong.
+static std::string mx_parse_table(const char* txt, size_t len, std::vector<std::string>& names, std::vector<uint32_t>& lens) {
+    size_t p = 0, line = 0;
+    char msg[160];
+    while (p < len) {
+        const char* nlp = (const char*)memchr(txt + p, '\n', len - p);
+        size_t q = nlp ? (size_t)(nlp - txt) : len, e = q;
+        ++line;
+        if (e > p && txt[e - 1] == '\r') --e;
+        if (e > p && txt[p] != '#') {
+            size_t t = p;
+            while (t < e && txt[t] != '\t') ++t;
+            if (t == p || t - p > 63) { snprintf(msg, sizeof msg, "chromosome table line %zu: a name of 1 .. 63 bytes is needed", line); return msg; }
+            size_t d = t + 1;
+            uint64_t v = 0;
+            size_t nd = 0;
+            while (d < e && txt[d] >= '0' && txt[d] <= '9' && nd < 11) { v = v * 10 + (uint64_t)(txt[d] - '0'); ++d; ++nd; }
+            if (t >= e || nd == 0 || (d < e && txt[d] != '\t') || v > 0xFFFFFFFFull) { snprintf(msg, sizeof msg, "chromosome table line %zu: no length (name<TAB>length, length < 2^32)", line); return msg; }
+            names.emplace_back(txt + p, t - p);
+            lens.push_back((uint32_t)v);
+        }
+        p = q + 1;
+    }
+    if (names.empty()) return "chromosome table: no chromosome";
+    if (names.size() > kChrSlots) return "chromosome table: more than 8192 chromosomes";
+    return "";
+}
+
+static void mx_free_results(mkt_matrix* m) {
+    for (MxRes& r : m->res) {
+        if (r.d_b1) (void)hipFree(r.d_b1);
+        if (r.d_b2) (void)hipFree(r.d_b2);
+        if (r.d_cnt) (void)hipFree(r.d_cnt);
+        if (r.d_text) (void)hipFree(r.d_text);
+        r.d_b1 = r.d_b2 = r.d_cnt = nullptr; r.d_text = nullptr; r.nnz = 0; r.text_bytes = 0; r.ms = 0;
+    }
+    m->ran = false;
+}
+static int mx_reserve_rec(mkt_matrix* m, uint64_t need) {
+    if (need >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "%llu pairs: a matrix object holds fewer than 2^32 (counts are 32-bit)", (unsigned long long)need);
+    if (need <= m->rec_cap) return MKT_OK;
+    uint64_t ncap = m->rec_cap ? m->rec_cap : (1ull << 20);
+    while (ncap < need) ncap *= 2;
+    MxRec* nb = nullptr;
+    { hipError_t e_ = hipMalloc((void**)&nb, ncap * sizeof(MxRec)); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of %llu pair records failed: %s", (unsigned long long)ncap, hipGetErrorString(e_)); }
+    if (m->d_rec) {
+        MCHK(m, hipStreamSynchronize(m->stream));
+        if (m->n) MCHK(m, hipMemcpy(nb, m->d_rec, m->n * sizeof(MxRec), hipMemcpyDeviceToDevice));
+        MCHK(m, hipFree(m->d_rec));
+    }
+    m->d_rec = nb; m->rec_cap = ncap;
+    return MKT_OK;
+}
+static int mx_reserve_text(mkt_matrix* m, size_t need) {
+    if (need <= m->text_cap) return MKT_OK;
+    size_t ncap = m->text_cap ? m->text_cap : ((size_t)64 << 20);
+    while (ncap < need) ncap *= 2;
+    if (m->d_text) { MCHK(m, hipStreamSynchronize(m->stream)); MCHK(m, hipFree(m->d_text)); m->d_text = nullptr; m->text_cap = 0; }
+    { hipError_t e_ = hipMalloc((void**)&m->d_text, ncap + 64); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of %zu text bytes failed: %s", ncap, hipGetErrorString(e_)); }
+    m->text_cap = ncap;
+    return MKT_OK;
+}
+// d_text[0, n) holds whole lines: index them, one record per line behind the ones that are there
+static int mx_process_text(mkt_matrix* m, size_t n) {
+    if (n == 0) return MKT_OK;
+    uint64_t* d_starts = nullptr;
+    uint64_t nl = 0;
+    MCHK(m, sort_line_index(m->d_text, n, m->stream, &d_starts, &nl));
+    int rc = nl ? mx_reserve_rec(m, m->n + nl) : MKT_OK;
+    if (rc == MKT_OK && nl) {
+        hipLaunchKernelGGL(k_mx_parse, dim3((unsigned)((nl + MXWG - 1) / MXWG)), dim3(MXWG), 0, m->stream, (const uint8_t*)m->d_text, (const uint64_t*)d_starts, nl,
+                           (const MxTab*)m->d_tab, m->d_rec + m->n, m->d_counters);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+        if (e != hipSuccess) rc = mfail(m, MKT_E_HIP, "parsing %llu .pairs lines failed: %s", (unsigned long long)nl, hipGetErrorString(e));
+        else m->n += nl;
+    }
+    (void)hipFree(d_starts);
+    return rc;
+}
+
+extern "C" {
+
+int mkt_matrix_create(int device, const char* chromsizes, size_t len, const uint32_t* resolutions, uint32_t n_res, mkt_matrix** out) {
+    if (!out) return MKT_E_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return mfail(nullptr, MKT_E_NO_DEVICE, "no usable HIP device (there is no CPU path)");
+    if (device < 0 || device >= ndev) return mfail(nullptr, MKT_E_ARG, "device %d of %d", device, ndev);
+    if ((len && !chromsizes) || !resolutions) return mfail(nullptr, MKT_E_ARG, "null argument");
+    if (n_res == 0 || n_res > 16) return mfail(nullptr, MKT_E_ARG, "%u resolutions: 1 .. 16 per matrix object", n_res);
+    mkt_matrix* m = new mkt_matrix();
+    m->device = device;
+    const std::string bad = mx_parse_table(chromsizes, len, m->names, m->lens);
+    if (!bad.empty()) { delete m; return mfail(nullptr, MKT_E_ARG, "%s", bad.c_str()); }
+    const uint32_t nc = (uint32_t)m->names.size();
+    for (uint32_t i = 0; i < nc; ++i)
+        if (!m->index.emplace(m->names[i], i).second) { const std::string nm = m->names[i]; delete m; return mfail(nullptr, MKT_E_ARG, "chromosome table: %s is there twice", nm.c_str()); }
+    m->res.resize(n_res);
+    for (uint32_t k = 0; k < n_res; ++k) {
+        MxRes& r = m->res[k];
+        r.r = resolutions[k];
+        if (r.r == 0) { delete m; return mfail(nullptr, MKT_E_ARG, "resolution %u of the list is 0", k); }
+        r.off.resize(nc);
+        uint64_t nb = 0;
+        for (uint32_t i = 0; i < nc; ++i) { r.off[i] = (uint32_t)nb; nb += ((uint64_t)m->lens[i] + r.r - 1) / r.r; if (nb >= (1ull << 32)) break; }
+        if (nb >= (1ull << 32)) { const uint32_t rr = r.r; delete m; return mfail(nullptr, MKT_E_CAPACITY, "resolution %u: 2^32 bins or more (bin ids are 32-bit)", rr); }
+        r.nbins = nb;
+        r.B = 0;
+        while (r.B < 32 && (1ull << r.B) <= nb) ++r.B;              // nbins itself (the key of what is not binned) fits B bits
+    }
+    // the device side
+    auto dfail = [&](const char* what, hipError_t e) { mkt_matrix_destroy(m); return mfail(nullptr, MKT_E_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return dfail("hipSetDevice", e);
+    if ((e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)) != hipSuccess) return dfail("hipStreamCreate", e);
+    if ((e = hipEventCreate(&m->ev0)) != hipSuccess || (e = hipEventCreate(&m->ev1)) != hipSuccess) return dfail("hipEventCreate", e);
+    std::vector<uint8_t> hostTab(sizeof(MxTab), 0);
+    MxTab* ht = reinterpret_cast<MxTab*>(hostTab.data());
+    for (uint32_t i = 0; i < nc; ++i) {
+        const std::string& nm = m->names[i];
+        memcpy(ht->name[i], nm.data(), nm.size());
+        ht->name[i][63] = (uint8_t)nm.size();
+        ht->len[i] = m->lens[i];
+        const uint64_t h = mx_fnv((const uint8_t*)nm.data(), nm.size());
+        uint32_t s = (uint32_t)(h >> 17) & (kMxSlots - 1u);
+        while (ht->hash[s]) s = (s + 1u) & (kMxSlots - 1u);            // at most 8192 names in 16384 slots
+        ht->hash[s] = h; ht->idx[s] = (uint16_t)i;
+    }
+    if ((e = hipMalloc((void**)&m->d_tab, sizeof(MxTab))) != hipSuccess) return dfail("hipMalloc", e);
+    if ((e = hipMemcpy(m->d_tab, ht, sizeof(MxTab), hipMemcpyHostToDevice)) != hipSuccess) return dfail("hipMemcpy", e);
+    if ((e = hipMalloc((void**)&m->d_counters, sizeof(MxCounters))) != hipSuccess) return dfail("hipMalloc", e);
+    if ((e = hipMemset(m->d_counters, 0, sizeof(MxCounters))) != hipSuccess) return dfail("hipMemset", e);
+    for (MxRes& r : m->res) {
+        if ((e = hipMalloc((void**)&r.d_off, (size_t)nc * 4)) != hipSuccess) return dfail("hipMalloc", e);
+        if ((e = hipMemcpy(r.d_off, r.off.data(), (size_t)nc * 4, hipMemcpyHostToDevice)) != hipSuccess) return dfail("hipMemcpy", e);
+    }
+    *out = m;
+    return MKT_OK;
+}
+
+void mkt_matrix_destroy(mkt_matrix* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->stream) (void)hipStreamSynchronize(m->stream);
+    mx_free_results(m);
+    for (MxRes& r : m->res) if (r.d_off) (void)hipFree(r.d_off);
+    if (m->d_tab) (void)hipFree(m->d_tab);
+    if (m->d_counters) (void)hipFree(m->d_counters);
+    if (m->d_rec) (void)hipFree(m->d_rec);
+    if (m->d_text) (void)hipFree(m->d_text);
+    if (m->ev0) (void)hipEventDestroy(m->ev0);
+    if (m->ev1) (void)hipEventDestroy(m->ev1);
+    if (m->stream) (void)hipStreamDestroy(m->stream);
+    delete m;
+}
+const char* mkt_matrix_error(const mkt_matrix* m) { return m ? m->err.c_str() : g_mx_create_err.c_str(); }
+
+int mkt_matrix_add(mkt_matrix* m, const char* bytes, size_t n) {
+    if (!m || (n && !bytes)) return MKT_E_ARG;
+    MCHK(m, hipSetDevice(m->device));
+    size_t end = n;                                                    // bytes[0, end): up to the last newline
+    while (end > 0 && bytes[end - 1] != '\n') --end;
+    if (end == 0) { m->carry.append(bytes, n); return MKT_OK; }
+    if (m->ran) mx_free_results(m);
+    const size_t c = m->carry.size();
+    int rc = mx_reserve_text(m, c + end);
+    if (rc) return rc;
+    if (c) MCHK(m, hipMemcpyAsync(m->d_text, m->carry.data(), c, hipMemcpyHostToDevice, m->stream));
+    MCHK(m, hipMemcpyAsync(m->d_text + c, bytes, end, hipMemcpyHostToDevice, m->stream));
+    MCHK(m, hipStreamSynchronize(m->stream));                          // the caller may reuse `bytes`
+    m->carry.assign(bytes + end, n - end);
+    return mx_process_text(m, c + end);
+}
+int mkt_matrix_add_device(mkt_matrix* m, const void* d_bytes, size_t n) {
+    if (!m || (n && !d_bytes)) return MKT_E_ARG;
+    MCHK(m, hipSetDevice(m->device));
+    if (n == 0) return MKT_OK;
+    if (!m->carry.empty()) return mfail(m, MKT_E_STATE, "device text behind an incomplete host line");
+    if (m->ran) mx_free_results(m);
+    int rc = mx_reserve_text(m, n + 1);
+    if (rc) return rc;
+    MCHK(m, hipMemcpyAsync(m->d_text, d_bytes, n, hipMemcpyDeviceToDevice, m->stream));
+    char last = 0;
+    MCHK(m, hipMemcpyAsync(&last, m->d_text + n - 1, 1, hipMemcpyDeviceToHost, m->stream));
+    MCHK(m, hipStreamSynchronize(m->stream));
+    if (last != '\n') { const char nl = '\n'; MCHK(m, hipMemcpy(m->d_text + n, &nl, 1, hipMemcpyHostToDevice)); ++n; }
+    return mx_process_text(m, n);
+}
+int mkt_matrix_add_keys(mkt_matrix* m, mkt_ctx* ctx, int drop_last, const uint8_t* skip_flags, size_t n_flags) {
+    if (!m || !ctx) return MKT_E_ARG;
+    const void* d_keys = nullptr;
+    uint64_t n = 0;
+    int rc = mkt_ext_keys_device(ctx, drop_last, &d_keys, &n);
+    if (rc) return mfail(m, rc, "the context's key list: %s", mkt_last_error(ctx));
+    if (n == 0) return MKT_OK;
+    if (skip_flags && n_flags < n) return mfail(m, MKT_E_ARG, "%zu flags for %llu reported pairs", n_flags, (unsigned long long)n);
+    hipPointerAttribute_t at;
+    MCHK(m, hipPointerGetAttributes(&at, d_keys));
+    if (at.device != m->device) return mfail(m, MKT_E_ARG, "the context lives on device %d, the matrix on device %d", at.device, m->device);
+    // the context's chromosome slots -> table indices
+    size_t tl = 0;
+    if ((rc = mkt_ext_chr_names(ctx, nullptr, 0, &tl))) return mfail(m, rc, "the context's chromosome names: %s", mkt_last_error(ctx));
+    std::string txt(tl, '\0');
+    if (tl && (rc = mkt_ext_chr_names(ctx, &txt[0], tl, &tl))) return mfail(m, rc, "the context's chromosome names: %s", mkt_last_error(ctx));
+    std::vector<uint16_t> lut(kChrSlots, (uint16_t)0xFFFFu);
+    for (size_t p = 0; p < tl;) {
+        size_t q = txt.find('\n', p);
+        if (q == std::string::npos) q = tl;
+        const size_t t = txt.find('\t', p);
+        if (t != std::string::npos && t < q) {
+            const unsigned long slot = strtoul(txt.c_str() + p, nullptr, 10);
+            const auto it = m->index.find(txt.substr(t + 1, q - t - 1));
+            if (slot < kChrSlots && it != m->index.end()) lut[slot] = (uint16_t)it->second;
+        }
+        p = q + 1;
+    }
+    MCHK(m, hipSetDevice(m->device));
+    if (m->ran) mx_free_results(m);
+    if ((rc = mx_reserve_rec(m, m->n + n))) return rc;
+    uint16_t* d_lut = nullptr;
+    uint8_t* d_flags = nullptr;
+    MCHK(m, hipMalloc((void**)&d_lut, kChrSlots * sizeof(uint16_t)));
+    hipError_t e = hipMemcpyAsync(d_lut, lut.data(), kChrSlots * sizeof(uint16_t), hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess && skip_flags) {
+        e = hipMalloc((void**)&d_flags, n);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_flags, skip_flags, n, hipMemcpyHostToDevice, m->stream);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_mx_from_keys, dim3((unsigned)((n + MXWG - 1) / MXWG)), dim3(MXWG), 0, m->stream, (const KeyRec*)d_keys, n, (const uint16_t*)d_lut,
+                           (const uint8_t*)d_flags, (const MxTab*)m->d_tab, m->d_rec + m->n, m->d_counters);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(m->stream);             // the context may go on (and the host buffers be reused) when this returns
+    (void)hipFree(d_lut);
+    if (d_flags) (void)hipFree(d_flags);
+    if (e != hipSuccess || e2 != hipSuccess) return mfail(m, MKT_E_HIP, "records from %llu keys failed: %s", (unsigned long long)n, hipGetErrorString(e != hipSuccess ? e : e2));
+    m->n += n;
+    return MKT_OK;
+}
+
+int mkt_matrix_run(mkt_matrix* m, uint64_t* pairs, uint64_t* skipped) {
+    if (!m) return MKT_E_ARG;
+    if (pairs) *pairs = 0;
+    if (skipped) *skipped = 0;
+    MCHK(m, hipSetDevice(m->device));
+    if (!m->carry.empty()) {                                            // a last line without its newline
+        std::string last;
+        last.swap(m->carry);
+        last += '\n';
+        const int rc = mkt_matrix_add(m, last.data(), last.size());
+        if (rc) return rc;
+    }
+    mx_free_results(m);
+    hipStream_t st = m->stream;
+    MxCounters hc;
+    MCHK(m, hipMemcpyAsync(&hc, m->d_counters, sizeof hc, hipMemcpyDeviceToHost, st));
+    MCHK(m, hipStreamSynchronize(st));
+    if (hc.err) return mfail(m, MKT_E_ARG, "not .pairs text (error bits 0x%x: 1 = fewer than five fields / non-decimal position)", hc.err);
+    const uint64_t n = m->n, nv = n - hc.skipped - hc.none;
+    m->pairs = n - hc.none; m->skipped = hc.skipped;
+    std::vector<void*> owned;
+    auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
+#define MALLOC(ptr, bytes_) do { hipError_t e_ = hipMalloc((void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); mx_free_results(m); return mfail(m, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } } while (0)
+#define MRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); mx_free_results(m); return mfail(m, MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+    uint64_t *kA = nullptr, *kB = nullptr, *d_sums = nullptr;
+    uint32_t *d_radix = nullptr, *d_pos = nullptr;
+    const uint64_t hblocks = (nv + MX_TILE - 1) / MX_TILE;
+    if (nv) {
+        MALLOC(kA, n * 8 + 64); owned.push_back(kA);
+        MALLOC(kB, n * 8 + 64); owned.push_back(kB);
+        MALLOC(d_radix, radix64_count_bytes(n)); owned.push_back(d_radix);
+        MALLOC(d_sums, ((nv + MX_CPW - 1) / MX_CPW + 2) * 8); owned.push_back(d_sums);   // (at most nv cells: room for the text passes' sums, which are more than the head passes')
+    }
+    for (MxRes& r : m->res) {
+        if (nv == 0) continue;
+        MRUN(hipEventRecord(m->ev0, st));
+        hipLaunchKernelGGL(k_mx_keys, dim3((unsigned)((n + MXWG - 1) / MXWG)), dim3(MXWG), 0, st, (const MxRec*)m->d_rec, n, (const uint32_t*)r.d_off, r.r, r.B, r.nbins, kA);
+        MRUN(launch_radix64(kA, kB, n, 0, 2 * r.B, d_radix, st));
+        hipLaunchKernelGGL(k_mx_head_count, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, d_sums);
+        MRUN(launch_exscan(d_sums, hblocks, d_sums + hblocks, st));
+        uint64_t nnz = 0;
+        MRUN(hipMemcpyAsync(&nnz, d_sums + hblocks, 8, hipMemcpyDeviceToHost, st));
+        MRUN(hipStreamSynchronize(st));
+        if (nnz == 0 || nnz > nv) { cleanup(); mx_free_results(m); return mfail(m, MKT_E_KERNEL, "%llu cells from %llu binned pairs", (unsigned long long)nnz, (unsigned long long)nv); }
+        MALLOC(r.d_b1, nnz * 4); MALLOC(r.d_b2, nnz * 4); MALLOC(r.d_cnt, nnz * 4);
+        MALLOC(d_pos, nnz * 4);
+        owned.push_back(d_pos);
+        hipLaunchKernelGGL(k_mx_cells, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, (const uint64_t*)d_sums, r.B, r.d_b1, r.d_b2, d_pos);
+        const uint64_t tblocks = (nnz + MX_CPW - 1) / MX_CPW;
+        hipLaunchKernelGGL(k_mx_counts, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)d_pos, nnz, nv, r.d_cnt, d_sums);
+        MRUN(launch_exscan(d_sums, tblocks, d_sums + tblocks, st));
+        uint64_t tb = 0;
+        MRUN(hipMemcpyAsync(&tb, d_sums + tblocks, 8, hipMemcpyDeviceToHost, st));
+        MRUN(hipStreamSynchronize(st));
+        MALLOC(r.d_text, tb + 64);
+        hipLaunchKernelGGL(k_mx_text, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)r.d_cnt, nnz, (const uint64_t*)d_sums, r.d_text);
+        MRUN(hipGetLastError());
+        MRUN(hipEventRecord(m->ev1, st));
+        MRUN(hipStreamSynchronize(st));
+        float ms = 0;
+        MRUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+        r.ms = ms; r.nnz = nnz; r.text_bytes = tb;
+        owned.pop_back();
+        (void)hipFree(d_pos); d_pos = nullptr;
+    }
+    cleanup();
+#undef MALLOC
+#undef MRUN
+    m->ran = true;
+    if (pairs) *pairs = m->pairs;
+    if (skipped) *skipped = m->skipped;
+    return MKT_OK;
+}
+
+int mkt_matrix_info(const mkt_matrix* m, uint32_t res_index, uint64_t* nbins, uint64_t* nnz, uint64_t* text_bytes) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const MxRes& r = m->res[res_index];
+    if (nbins) *nbins = r.nbins;
+    if (nnz) *nnz = m->ran ? r.nnz : 0;
+    if (text_bytes) *text_bytes = m->ran ? r.text_bytes : 0;
+    return MKT_OK;
+}
+int mkt_matrix_timing(const mkt_matrix* m, uint32_t res_index, double* ms) {
+    if (!m || !ms || res_index >= m->res.size()) return MKT_E_ARG;
+    *ms = m->ran ? m->res[res_index].ms : 0.0;
+    return MKT_OK;
+}
+int mkt_matrix_fetch(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint32_t* bin1, uint32_t* bin2, uint32_t* count) {
+    if (!m) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    if (!m->ran) return mfail(m, MKT_E_STATE, "fetch before run");
+    const MxRes& r = m->res[res_index];
+    if (first > r.nnz || n > r.nnz - first) return mfail(m, MKT_E_ARG, "cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nnz);
+    MCHK(m, hipSetDevice(m->device));
+    if (n == 0) return MKT_OK;
+    if (bin1) MCHK(m, hipMemcpy(bin1, r.d_b1 + first, n * 4, hipMemcpyDeviceToHost));
+    if (bin2) MCHK(m, hipMemcpy(bin2, r.d_b2 + first, n * 4, hipMemcpyDeviceToHost));
+    if (count) MCHK(m, hipMemcpy(count, r.d_cnt + first, n * 4, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+int mkt_matrix_fetch_text(mkt_matrix* m, uint32_t res_index, uint64_t off, char* out, size_t n) {
+    if (!m || (n && !out)) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    if (!m->ran) return mfail(m, MKT_E_STATE, "fetch before run");
+    const MxRes& r = m->res[res_index];
+    if (off > r.text_bytes || n > r.text_bytes - off) return mfail(m, MKT_E_ARG, "range past the end of the COO text");
+    MCHK(m, hipSetDevice(m->device));
+    if (n) MCHK(m, hipMemcpy(out, r.d_text + off, n, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,167 @@
+// pairs2matrix -- the computation behind the driver's last stage (microcket:520-554: `juicer_tools pre -r 2500000,...,5000` and
+// `cooler cload pairix GINFO:minBIN`) on the GPU: final.pairs -> the sparse binned contact matrix at every resolution asked for.
+// The .hic / .cool containers themselves are not written; the output is what `cooler load -f coo <chrom.sizes>:<r>` ingests.
+// The work is mkt_matrix_* of libmkt_hip.so (include/mkt.h, where the binning is defined); this file only moves bytes.
+//
+//   pairs2matrix -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]        (no input file: stdin; $MKT_DEVICE: GPU ordinal)
+//
+// Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
+// <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
+// (Pairs, Binned, Skipped, then nnz.<r> per resolution).
+// Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "../../include/mkt.h"
+
+static int usage(const char* me) {
+    fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n", me);
+    return 2;
+}
+static bool read_file(const char* fn, std::string& out) {
+    FILE* f = fopen(fn, "rb");
+    if (!f) return false;
+    char buf[65536];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, k);
+    const bool ok = !ferror(f);
+    fclose(f);
+    return ok;
+}
+struct Chrom { std::string name; uint64_t len; };
+// name \t length [\t ...] per line; empty and '#' lines ignored (the library checks the same things: this copy gives exit code 12
+// before a GPU is asked for, and the bins for the .bed files)
+static bool parse_table(const std::string& txt, std::vector<Chrom>& out, std::string& why) {
+    size_t p = 0, line = 0;
+    while (p < txt.size()) {
+        size_t q = txt.find('\n', p);
+        if (q == std::string::npos) q = txt.size();
+        size_t e = q;
+        ++line;
+        if (e > p && txt[e - 1] == '\r') --e;
+        if (e > p && txt[p] != '#') {
+            const size_t t = txt.find('\t', p);
+            if (t == std::string::npos || t >= e || t == p || t - p > 63) { why = "line " + std::to_string(line) + ": name<TAB>length needed (name of 1 .. 63 bytes)"; return false; }
+            size_t d = t + 1;
+            uint64_t v = 0;
+            size_t nd = 0;
+            while (d < e && txt[d] >= '0' && txt[d] <= '9' && nd < 11) { v = v * 10 + (uint64_t)(txt[d] - '0'); ++d; ++nd; }
+            if (nd == 0 || (d < e && txt[d] != '\t') || v > 0xFFFFFFFFull) { why = "line " + std::to_string(line) + ": no length (a decimal number below 2^32)"; return false; }
+            for (const Chrom& c : out) if (c.name == txt.substr(p, t - p)) { why = "line " + std::to_string(line) + ": " + c.name + " is there twice"; return false; }
+            out.push_back({txt.substr(p, t - p), v});
+        }
+        p = q + 1;
+    }
+    if (out.empty()) { why = "no chromosome"; return false; }
+    if (out.size() > 8192) { why = "more than 8192 chromosomes"; return false; }
+    return true;
+}
+static bool parse_res(const char* s, std::vector<uint32_t>& out) {
+    const char* p = s;
+    for (;;) {
+        uint64_t v = 0;
+        int nd = 0;
+        while (*p >= '0' && *p <= '9' && nd < 11) { v = v * 10 + (uint64_t)(*p - '0'); ++p; ++nd; }
+        if (nd == 0 || v == 0 || v > 0xFFFFFFFFull) return false;
+        for (uint32_t x : out) if (x == v) return false;
+        out.push_back((uint32_t)v);
+        if (*p == '\0') break;
+        if (*p != ',') return false;
+        ++p;
+    }
+    return out.size() <= 16;
+}
+static bool write_file(const std::string& fn, const char* p, size_t n, const char* mode = "wb") {
+    FILE* f = fopen(fn.c_str(), mode);
+    if (!f) return false;
+    const bool ok = (n == 0 || fwrite(p, 1, n, f) == n);
+    return (fclose(f) == 0) && ok;
+}
+
+int main(int argc, char* argv[]) {
+    const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
+    std::vector<const char*> files;
+    for (int i = 1; i < argc; ++i) {
+        if (!strcmp(argv[i], "-g") && i + 1 < argc) table = argv[++i];
+        else if (!strcmp(argv[i], "-r") && i + 1 < argc) rlist = argv[++i];
+        else if (!strcmp(argv[i], "-o") && i + 1 < argc) prefix = argv[++i];
+        else if (argv[i][0] == '-' && argv[i][1] != '\0') return usage(argv[0]);
+        else files.push_back(argv[i]);
+    }
+    if (!table || !rlist || !prefix) return usage(argv[0]);
+    std::string ttxt, why;
+    if (!read_file(table, ttxt)) { fprintf(stderr, "Error: read chromosome table failed!\n"); return 10; }
+    std::vector<Chrom> chroms;
+    if (!parse_table(ttxt, chroms, why)) { fprintf(stderr, "Error: bad chromosome table: %s\n", why.c_str()); return 12; }
+    std::vector<uint32_t> res;
+    if (!parse_res(rlist, res)) { fprintf(stderr, "Error: bad resolution list '%s' (1 .. 16 different positive numbers, comma separated)\n", rlist); return 12; }
+    for (uint32_t r : res) {
+        uint64_t nb = 0;
+        for (const Chrom& c : chroms) nb += (c.len + r - 1) / r;
+        if (nb >= (1ull << 32)) { fprintf(stderr, "Error: resolution %u gives 2^32 bins or more\n", r); return 12; }
+    }
+    std::vector<FILE*> in;
+    for (const char* fn : files) {
+        FILE* f = strcmp(fn, "-") ? fopen(fn, "rb") : stdin;
+        if (!f) { fprintf(stderr, "Error: read input file failed!\n"); return 10; }
+        in.push_back(f);
+    }
+    if (in.empty()) in.push_back(stdin);
+
+    const char* e = getenv("MKT_DEVICE");
+    mkt_matrix* m = nullptr;
+    int rc = mkt_matrix_create(e ? atoi(e) : 0, ttxt.data(), ttxt.size(), res.data(), (uint32_t)res.size(), &m);
+    if (rc == MKT_E_NO_DEVICE) { fprintf(stderr, "Error: GPU matrix: %s\n", mkt_strerror(rc)); return 20; }
+    if (rc != MKT_OK) { fprintf(stderr, "Error: GPU matrix: %s: %s\n", mkt_strerror(rc), mkt_matrix_error(nullptr)); return rc == MKT_E_ARG || rc == MKT_E_CAPACITY ? 12 : 21; }
+    auto lib_fail = [&](const char* what) { fprintf(stderr, "Error: %s: %s: %s\n", what, mkt_strerror(rc), mkt_matrix_error(m)); mkt_matrix_destroy(m); return 21; };
+    std::vector<char> buf((size_t)64 << 20);
+    for (FILE* f : in) {
+        char last = '\n';
+        for (;;) {
+            const size_t k = fread(buf.data(), 1, buf.size(), f);
+            if (k == 0) break;
+            last = buf[k - 1];
+            if ((rc = mkt_matrix_add(m, buf.data(), k)) != MKT_OK) return lib_fail("GPU matrix");
+        }
+        if (ferror(f)) { fprintf(stderr, "Error: read input file failed!\n"); mkt_matrix_destroy(m); return 10; }
+        if (f != stdin) fclose(f);
+        if (last != '\n' && (rc = mkt_matrix_add(m, "\n", 1)) != MKT_OK) return lib_fail("GPU matrix");      // a file without a final newline does not run into the next one
+    }
+    uint64_t pairs = 0, skipped = 0;
+    if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
+
+    const std::string pre = prefix;
+    std::string stat = "Pairs\t" + std::to_string(pairs) + "\nBinned\t" + std::to_string(pairs - skipped) + "\nSkipped\t" + std::to_string(skipped) + "\n";
+    for (uint32_t k = 0; k < res.size(); ++k) {
+        uint64_t nbins = 0, nnz = 0, tb = 0;
+        if ((rc = mkt_matrix_info(m, k, &nbins, &nnz, &tb)) != MKT_OK) return lib_fail("GPU matrix");
+        stat += "nnz." + std::to_string(res[k]) + "\t" + std::to_string(nnz) + "\n";
+        const std::string coo = pre + "." + std::to_string(res[k]) + ".coo";
+        FILE* f = fopen(coo.c_str(), "wb");
+        if (!f) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        for (uint64_t off = 0; off < tb; off += buf.size()) {
+            const size_t n = tb - off < buf.size() ? (size_t)(tb - off) : buf.size();
+            if ((rc = mkt_matrix_fetch_text(m, k, off, buf.data(), n)) != MKT_OK) { fclose(f); return lib_fail("GPU matrix"); }
+            if (fwrite(buf.data(), 1, n, f) != n) { fclose(f); fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        }
+        if (fclose(f) != 0) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        std::string bed;
+        const uint64_t r = res[k];
+        const char* mode = "wb";                                                  // the first piece truncates, the others append
+        for (const Chrom& c : chroms)
+            for (uint64_t s = 0; s < c.len; s += r) {
+                bed += c.name; bed += '\t'; bed += std::to_string(s); bed += '\t'; bed += std::to_string(s + r < c.len ? s + r : c.len); bed += '\n';
+                if (bed.size() > ((size_t)32 << 20)) {
+                    if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+                    bed.clear(); mode = "ab";
+                }
+            }
+        if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+    }
+    if (!write_file(pre + ".matrix.stat", stat.data(), stat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+    mkt_matrix_destroy(m);
+    return 0;
+}
