@@ -4,8 +4,8 @@
 //     cat $samheader $sid.flash.sam $sid.unc.sam | samtools view -b | samtools sort -o $sid.valid.bam ;  samtools index $sid.valid.bam
 // i.e. the filtered alignments that sam2pairs wrote, as a coordinate-sorted, BGZF-compressed BAM with its .bai.  Here: newline
 // index, one key per line (reference id, position, strand), the stable LSD radix sort of mkt_sort.hip, an exclusive scan of the
-// record sizes, one pass that writes the binary records in sorted order, BGZF blocks (stored, or LZ77 + fixed-Huffman deflate,
-// CRC-32 per block) and the reductions the BAI needs (linear index, chunk starts, per-reference counts).  Byte / integer work
+// record sizes, one pass that writes the binary records in sorted order, BGZF blocks (level 2, the default: LZ77 + a Huffman
+// code built per block; level 1: the fixed code; level 0: stored; CRC-32 per block) and the reductions the BAI needs (linear index, chunk starts, per-reference counts).  Byte / integer work
 // bound by HBM; no MFMA.
 //
 // Formats: SAM / BAM / BGZF / BAI as published in "Sequence Alignment/Map Format Specification" (samtools/hts-specs, SAMv1
@@ -1038,16 +1038,16 @@ struct BgzfStream {                                    // BGZF output of a strea
     uint64_t* d_csize = nullptr; size_t csize_cap = 0;
     uint32_t* d_scratch = nullptr; size_t scratch_cap = 0;
     uint8_t* d_pack = nullptr; size_t pack_cap = 0;
-    uint64_t* d_hflag = nullptr; size_t hflag_cap = 0;
-    BaiHead* d_heads = nullptr; size_t heads_cap = 0;
 };
-struct BaiAcc {                                        // the index across the windows of a stream: small arrays that stay resident
+struct BaiAcc {                                        // the index across the windows of a file (the single pass: one window): small arrays that stay resident
     bool on = false, has_prev = false;
     std::vector<uint64_t> lin_off;
     uint64_t* d_lin_off = nullptr;
     unsigned long long *d_lin = nullptr, *d_nocoor = nullptr;
     BaiRef* d_refs = nullptr;
     BamIdx* d_prev = nullptr;
+    uint64_t* d_hflag = nullptr; size_t hflag_cap = 0; // per window (grow-only)
+    BaiHead* d_heads = nullptr; size_t heads_cap = 0;
     std::vector<BaiHead> heads;
     uint64_t end_voff = 0;
 };
@@ -1154,6 +1154,34 @@ static int dgrow(mkt_bam* s, T*& p, size_t& cap, size_t bytes) {
     cap = bytes;
     return MKT_OK;
 }
+// the device buffers of one function: freed when it returns, on every path, unless dropped before
+struct DevScope {
+    mkt_bam* s;
+    std::vector<void*> own;
+    explicit DevScope(mkt_bam* s_) : s(s_) {}
+    DevScope(const DevScope&) = delete;
+    DevScope& operator=(const DevScope&) = delete;
+    ~DevScope() { for (void* p : own) dfree(s, p); }
+    template <typename T>
+    int alloc(T*& p, size_t bytes) {
+        const hipError_t e = dalloc(s, (void**)&p, bytes);
+        if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+        own.push_back(p);
+        return MKT_OK;
+    }
+    void adopt(void* p, size_t bytes) { dtrack(s, p, bytes); own.push_back(p); }      // (a buffer that sort_line_index allocated)
+    void drop(void* p) { dfree(s, p); own.erase(std::remove(own.begin(), own.end(), p), own.end()); }
+};
+struct PhaseMarks {                                    // MKT_VERBOSE: the time since the previous mark (call sites follow a stream synchronisation)
+    bool on;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
+        t_prev = now;
+    }
+};
 
 // room for `need` bytes of text counted from tstart (the text before tstart is dropped)
 static int bam_reserve(mkt_bam* s, size_t need) {
@@ -1371,9 +1399,204 @@ static void bgzf_launch(const uint8_t* raw, uint64_t nraw, uint64_t nblocks, int
     }
 }
 
+// ---- the steps of a conversion: the single pass and the out-of-core mode both go through these -------------------------------
+// compress nblocks blocks of raw; csize becomes the blocks' compressed offsets, csize[nblocks] and (after a synchronisation)
+// *ctot their total.  The buffers and the launch batch are the caller's.
+static int bgzf_compress(mkt_bam* s, const uint8_t* raw, uint64_t nraw, uint64_t nblocks, int level, uint8_t* comp, uint64_t* csize, uint32_t* scratch,
+                         uint64_t batch, uint64_t* ctot) {
+    hipStream_t st = s->stream;
+    bgzf_launch(raw, nraw, nblocks, level, s->d_ct, comp, csize, scratch, batch, st);
+    BCHK(s, hipGetLastError());
+    BCHK(s, launch_exscan(csize, nblocks, csize + nblocks, st));
+    BCHK(s, hipMemcpyAsync(ctot, csize + nblocks, sizeof *ctot, hipMemcpyDeviceToHost, st));
+    return MKT_OK;
+}
+// the end of a conversion: what the object holds on the device besides the text and the BAM
+static void bam_free_device(mkt_bam* s) {
+    BgzfStream& b = s->bs;
+    for (void* p : {(void*)b.d_win, (void*)b.d_comp, (void*)b.d_csize, (void*)b.d_scratch, (void*)b.d_pack}) dfree(s, p);
+    b = BgzfStream();
+    MergeBufs& m = s->mb;
+    for (void* p : {(void*)m.rec, (void*)m.src, (void*)m.bytes, (void*)m.rA, (void*)m.rB, (void*)m.hist, (void*)m.off, (void*)m.idx}) dfree(s, p);
+    m = MergeBufs();
+    BaiAcc& x = s->bx;
+    for (void* p : {(void*)x.d_lin_off, (void*)x.d_lin, (void*)x.d_nocoor, (void*)x.d_refs, (void*)x.d_prev, (void*)x.d_hflag, (void*)x.d_heads}) dfree(s, p);
+    x = BaiAcc();
+    for (int k = 0; k < 4; ++k) { dfree(s, s->d_rt[k]); s->d_rt[k] = nullptr; }
+    dfree(s, s->d_ct); s->d_ct = nullptr;
+    dfree(s, s->d_err); s->d_err = nullptr;
+    dfree(s, s->d_nl); s->d_nl = nullptr;
+}
+// the header is known (the first alignment line has arrived, or the input has ended): parse it once, put the name table, the
+// CRC tables and the error word on the device
+static int bam_setup(mkt_bam* s, bool sorted) {
+    if (s->hdr_ready) return MKT_OK;
+    int rc = bam_parse_header(s, sorted, s->H);
+    if (rc) return rc;
+    const BamHeader& H = s->H;
+    const uint32_t nref = (uint32_t)H.names.size();
+    hipStream_t st = s->stream;
+    const size_t sz[4] = {H.tcap * sizeof(unsigned long long), H.tcap * sizeof(int32_t), (nref + 1) * sizeof(uint32_t), H.blob.size() + 16};
+    const void* src[4] = {H.th.data(), H.tidv.data(), H.noff.data(), H.blob.data()};
+    for (int k = 0; k < 4; ++k) {
+        BCHK(s, dalloc(s, &s->d_rt[k], sz[k]));
+        if (k < 3 || !H.blob.empty()) BCHK(s, hipMemcpyAsync(s->d_rt[k], src[k], k < 3 ? sz[k] : H.blob.size(), hipMemcpyHostToDevice, st));
+    }
+    CrcTabs ct;
+    crc_tables(&ct);
+    BCHK(s, dalloc(s, (void**)&s->d_ct, sizeof(CrcTabs)));
+    BCHK(s, dalloc(s, (void**)&s->d_err, 256));
+    BCHK(s, hipMemcpyAsync(s->d_ct, &ct, sizeof ct, hipMemcpyHostToDevice, st));
+    BCHK(s, hipMemsetAsync(s->d_err, 0, 256, st));
+    BCHK(s, hipStreamSynchronize(st));
+    s->rt.hash = (const unsigned long long*)s->d_rt[0]; s->rt.id = (const int32_t*)s->d_rt[1]; s->rt.name_off = (const uint32_t*)s->d_rt[2];
+    s->rt.names = (const uint8_t*)s->d_rt[3]; s->rt.mask = H.tcap - 1; s->rt.nref = nref;
+    s->hdr_ready = true;
+    return MKT_OK;
+}
+
+// the bits of the sort key: strand and position, then the reference id (one more value than references: "none" sorts last)
+static int bam_key_bits(const mkt_bam* s) {
+    int tbits = 1;
+    while ((1ull << tbits) <= (uint64_t)s->rt.nref) ++tbits;
+    return 33 + tbits;
+}
+// resident text (whole lines) as records: the line starts, the keys in output order, the records' sizes and their offsets in
+// the output (off[nl] = total).  The buffers belong to the caller's scope.
+struct BamRecs {
+    uint64_t* d_starts = nullptr;
+    SortRec *rA = nullptr, *rB = nullptr;             // (rB: the sort's other buffer)
+    uint32_t* d_size = nullptr;
+    uint64_t* d_off = nullptr;
+    uint64_t nl = 0, total = 0;
+    unsigned grid() const { return (unsigned)((nl + 255) / 256); }
+};
+static int bam_records(mkt_bam* s, DevScope& own, const uint8_t* text, uint64_t len, bool sorted, PhaseMarks& mark, BamRecs* out) {
+    hipStream_t st = s->stream;
+    BamRecs& R = *out;
+    int rc;
+    if (len) {
+        const hipError_t e = sort_line_index(text, len, st, &R.d_starts, &R.nl);
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return bfail(s, MKT_E_NOMEM, "the line index does not fit beside the text"); }
+        if (e != hipSuccess) return bfail(s, MKT_E_HIP, "sort_line_index failed: %s", hipGetErrorString(e));
+        own.adopt(R.d_starts, (R.nl + 2) * sizeof(uint64_t));
+    }
+    mark("header + line index");
+    const uint64_t nl = R.nl;
+    if (nl >= (1ull << 32) - 1) return bfail(s, MKT_E_ARG, "%llu lines: records are indexed with 32 bits", (unsigned long long)nl);
+    if (!nl) return MKT_OK;
+    if ((rc = own.alloc(R.rA, (nl + 1) * sizeof(SortRec))) || (rc = own.alloc(R.d_size, (nl + 1) * sizeof(uint32_t))) || (rc = own.alloc(R.d_off, (nl + 2) * sizeof(uint64_t)))) return rc;
+    hipLaunchKernelGGL(k_bam_keys, dim3(R.grid()), dim3(256), 0, st, text, (const uint64_t*)R.d_starts, nl, s->rt, R.rA, R.d_size, s->d_err);
+    if (sorted) {
+        uint32_t* d_hist = nullptr;
+        if ((rc = own.alloc(R.rB, (nl + 1) * sizeof(SortRec))) || (rc = own.alloc(d_hist, kSortHistBytes))) return rc;
+        sort_radix_passes(R.rA, R.rB, nl, d_hist, 1, 0, bam_key_bits(s), st);
+    }
+    uint32_t herr = 0;
+    BCHK(s, hipMemcpyAsync(&herr, s->d_err, sizeof herr, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipStreamSynchronize(st));
+    if (herr) return bfail(s, MKT_E_ARG, "not SAM alignment text (error bits 0x%x: 1 fewer than 11 fields, 2 reference name not in the header, 4 number, 8 CIGAR, 16 optional field, 32 SEQ / QUAL lengths, 64 QNAME length)", herr);
+    mark(sorted ? "keys + radix sort" : "keys");
+    hipLaunchKernelGGL(k_bam_sizes, dim3(R.grid()), dim3(256), 0, st, (const SortRec*)R.rA, (const uint32_t*)R.d_size, nl, R.d_off);
+    BCHK(s, launch_exscan(R.d_off, nl, R.d_off + nl, st));
+    BCHK(s, hipMemcpyAsync(&R.total, R.d_off + nl, sizeof R.total, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipStreamSynchronize(st));
+    return MKT_OK;
+}
+// the records' bytes -> dst (at their offsets), their index fields -> d_idx
+static void bam_write(mkt_bam* s, const uint8_t* text, const BamRecs& R, uint8_t* dst, BamIdx* d_idx) {
+    hipLaunchKernelGGL(k_bam_write, dim3(R.grid()), dim3(256), 0, s->stream, text, (const uint64_t*)R.d_starts, R.nl, s->rt, (const SortRec*)R.rA, (const uint64_t*)R.d_off, dst, d_idx, s->d_err);
+}
+
+// ---- the index (coordinate order only; the format ends at 2^29 bases per reference -- longer ones would need a CSI index: none
+// is made then): begin, one call per window of records with the compressed offsets of the blocks they lie in, the end of the
+// data, end
+struct BaiWin { const BamIdx* idx; const uint64_t* off; uint64_t n; };
+static int bai_begin(mkt_bam* s) {
+    const BamHeader& H = s->H;
+    const uint32_t nref = (uint32_t)H.names.size();
+    hipStream_t st = s->stream;
+    BaiAcc& x = s->bx;
+    x.on = bai_possible(H);
+    if (!x.on) { s->note = kNoIndexLongRef; return MKT_OK; }
+    bai_lin_off(H, x.lin_off);
+    const uint64_t nlin = x.lin_off[nref];
+    std::vector<BaiRef> init(nref);
+    for (auto& r : init) { r.n_mapped = 0; r.n_unmapped = 0; r.beg = ~0ull; r.end = 0; }
+    BCHK(s, dalloc(s, (void**)&x.d_lin_off, (nref + 1) * sizeof(uint64_t)));
+    BCHK(s, dalloc(s, (void**)&x.d_lin, (nlin + 1) * sizeof(unsigned long long)));
+    BCHK(s, dalloc(s, (void**)&x.d_refs, (nref + 1) * sizeof(BaiRef)));
+    BCHK(s, dalloc(s, (void**)&x.d_nocoor, 256));
+    BCHK(s, dalloc(s, (void**)&x.d_prev, sizeof(BamIdx) + 64));
+    BCHK(s, hipMemcpyAsync(x.d_lin_off, x.lin_off.data(), (nref + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    BCHK(s, hipMemsetAsync(x.d_lin, 0xFF, (nlin + 1) * sizeof(unsigned long long), st));
+    if (nref) BCHK(s, hipMemcpyAsync(x.d_refs, init.data(), nref * sizeof(BaiRef), hipMemcpyHostToDevice, st));
+    BCHK(s, hipMemsetAsync(x.d_nocoor, 0, 256, st));
+    BCHK(s, hipMemsetAsync(x.d_nocoor + 2, 0xFF, sizeof(unsigned long long), st));
+    BCHK(s, hipStreamSynchronize(st));                             // (init is a local)
+    return MKT_OK;
+}
+static int bai_window(mkt_bam* s, const BaiWin& w, const VoffMap& vm, const uint64_t* coff) {
+    BaiAcc& x = s->bx;
+    if (!x.on || !w.n) return MKT_OK;
+    hipStream_t st = s->stream;
+    const uint64_t n = w.n;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    const BamIdx* prev = x.has_prev ? x.d_prev : nullptr;
+    int rc = dgrow(s, x.d_hflag, x.hflag_cap, (n + 2) * sizeof(uint64_t));
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bai, dim3(grid), dim3(256), 0, st, w.idx, w.off, n, vm, coff, (const uint64_t*)x.d_lin_off, s->rt.nref, x.d_lin, x.d_refs, x.d_hflag, x.d_nocoor, prev);
+    BCHK(s, hipGetLastError());
+    BCHK(s, launch_exscan(x.d_hflag, n, x.d_hflag + n, st));
+    uint64_t nheads = 0;
+    BCHK(s, hipMemcpyAsync(&nheads, x.d_hflag + n, sizeof nheads, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipStreamSynchronize(st));
+    if (nheads) {
+        if ((rc = dgrow(s, x.d_heads, x.heads_cap, (nheads + 1) * sizeof(BaiHead)))) return rc;
+        hipLaunchKernelGGL(k_bai_heads, dim3(grid), dim3(256), 0, st, w.idx, w.off, n, vm, coff, (const uint64_t*)x.d_hflag, x.d_heads, prev);
+        BCHK(s, hipGetLastError());
+        const size_t h0 = x.heads.size();
+        x.heads.resize(h0 + nheads);
+        BCHK(s, hipMemcpyAsync(x.heads.data() + h0, x.d_heads, nheads * sizeof(BaiHead), hipMemcpyDeviceToHost, st));
+    }
+    BCHK(s, hipMemcpyAsync(x.d_prev, w.idx + (n - 1), sizeof(BamIdx), hipMemcpyDeviceToDevice, st));
+    x.has_prev = true;
+    return MKT_OK;
+}
+// the data end at the uncompressed offset uo: its virtual offset (uo on a block boundary: coff[nblocks] is the scan's total)
+static int bai_data_end(mkt_bam* s, uint64_t uo, const VoffMap& vm, const uint64_t* coff) {
+    if (!s->bx.on) return MKT_OK;
+    const uint64_t b = uo / BGZF_RAW;
+    uint64_t c = 0;
+    BCHK(s, hipMemcpyAsync(&c, coff + (b - vm.blk0), sizeof c, hipMemcpyDeviceToHost, s->stream));
+    BCHK(s, hipStreamSynchronize(s->stream));
+    s->bx.end_voff = ((vm.cbase + c) << 16) | (uo - b * BGZF_RAW);
+    return MKT_OK;
+}
+static int bai_end(mkt_bam* s) {
+    BaiAcc& x = s->bx;
+    if (!x.on) return MKT_OK;
+    const uint32_t nref = (uint32_t)s->H.names.size();
+    std::vector<BaiRef> refs(nref);
+    std::vector<unsigned long long> lin(x.lin_off[nref]);
+    unsigned long long nc[3] = {0, 0, 0};
+    hipStream_t st = s->stream;
+    if (nref) BCHK(s, hipMemcpyAsync(refs.data(), x.d_refs, nref * sizeof(BaiRef), hipMemcpyDeviceToHost, st));
+    if (!lin.empty()) BCHK(s, hipMemcpyAsync(lin.data(), x.d_lin, lin.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    BCHK(s, hipMemcpyAsync(nc, x.d_nocoor, sizeof nc, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipStreamSynchronize(st));
+    const uint64_t off_end = nc[0] ? nc[2] : x.end_voff;            // the first record without coordinates, or the end of the data
+    s->bai.clear();
+    bai_assemble(s, nref, x.lin_off, refs, lin, x.heads, nc[0], nc[1], off_end);
+    std::vector<BaiHead>().swap(x.heads);
+    return MKT_OK;
+}
+
 // ---- out-of-core mode ------------------------------------------------------------------------------------------------------
+// Built from the steps above, which the single pass uses too: bam_records and bam_write per run, bgzf_compress and bai_window per
+// window of the merge.
 // Run formation: the text is cut into runs of at most `budget` bytes of whole lines (a longer line is a run of its own); every run
-// goes through the single-pass kernels (line index, keys, stable radix sort, size scan, records) and its sorted records are
+// goes through bam_records (line index, keys, stable radix sort, size scan) and bam_write, and its sorted records are
 // appended to <prefix>.runs, their keys, sizes and index fields (SpillRec) to <prefix>.keys.  The merge reads every run in
 // windows; per round the records up to the smallest last-loaded record of the runs that still have records on disk, in the
 // order T = (key, run, place in the run), are safe: their keys, concatenated in run order, go through the same stable radix
@@ -1389,21 +1612,6 @@ static void spill_remove(mkt_bam* s) {
 static int spill_guard(mkt_bam* s, int rc) {                       // on any error: no temporary file stays behind
     if (rc != MKT_OK && s) spill_remove(s);
     return rc;
-}
-static void spill_free_device(mkt_bam* s) {
-    BgzfStream& b = s->bs;
-    for (void* p : {(void*)b.d_win, (void*)b.d_comp, (void*)b.d_csize, (void*)b.d_scratch, (void*)b.d_pack, (void*)b.d_hflag, (void*)b.d_heads}) dfree(s, p);
-    b = BgzfStream();
-    MergeBufs& m = s->mb;
-    for (void* p : {(void*)m.rec, (void*)m.src, (void*)m.bytes, (void*)m.rA, (void*)m.rB, (void*)m.hist, (void*)m.off, (void*)m.idx}) dfree(s, p);
-    m = MergeBufs();
-    BaiAcc& x = s->bx;
-    for (void* p : {(void*)x.d_lin_off, (void*)x.d_lin, (void*)x.d_nocoor, (void*)x.d_refs, (void*)x.d_prev}) dfree(s, p);
-    x.d_lin_off = nullptr; x.d_lin = nullptr; x.d_nocoor = nullptr; x.d_refs = nullptr; x.d_prev = nullptr;
-    for (int k = 0; k < 4; ++k) { dfree(s, s->d_rt[k]); s->d_rt[k] = nullptr; }
-    dfree(s, s->d_ct); s->d_ct = nullptr;
-    dfree(s, s->d_err); s->d_err = nullptr;
-    dfree(s, s->d_nl); s->d_nl = nullptr;
 }
 static int write_all(mkt_bam* s, int k, const void* p, size_t n) {
     const char* c = (const char*)p;
@@ -1436,37 +1644,16 @@ static int read_at(mkt_bam* s, int k, void* p, size_t n, uint64_t off) {
     return MKT_OK;
 }
 
-// the header is known (the first alignment line has arrived): parse it once, put the name table on the device, open the run files
+// before the first run: the set-up, and the run files (sorted output only)
 static int spill_begin(mkt_bam* s) {
-    if (s->hdr_ready) return MKT_OK;
-    int rc = bam_parse_header(s, s->sp_sorted != 0, s->H);
+    if (s->spilled) return MKT_OK;
+    const int rc = bam_setup(s, s->sp_sorted != 0);
     if (rc) return rc;
-    const BamHeader& H = s->H;
-    const uint32_t nref = (uint32_t)H.names.size();
-    hipStream_t st = s->stream;
-    const size_t sz[4] = {H.tcap * sizeof(unsigned long long), H.tcap * sizeof(int32_t), (nref + 1) * sizeof(uint32_t), H.blob.size() + 16};
-    const void* src[4] = {H.th.data(), H.tidv.data(), H.noff.data(), H.blob.data()};
-    for (int k = 0; k < 4; ++k) {
-        BCHK(s, dalloc(s, &s->d_rt[k], sz[k]));
-        if (k < 3 || !H.blob.empty()) BCHK(s, hipMemcpyAsync(s->d_rt[k], src[k], k < 3 ? sz[k] : H.blob.size(), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < 2 && s->sp_sorted; ++k) {
+        s->tmp_fd[k] = open(s->tmp_path[k].c_str(), O_RDWR | O_CREAT | O_TRUNC, 0600);
+        if (s->tmp_fd[k] < 0) return bfail(s, MKT_E_IO, "cannot create the temporary file %s: %s", s->tmp_path[k].c_str(), strerror(errno));
+        s->tmp_made[k] = true;
     }
-    CrcTabs ct;
-    crc_tables(&ct);
-    BCHK(s, dalloc(s, (void**)&s->d_ct, sizeof(CrcTabs)));
-    BCHK(s, dalloc(s, (void**)&s->d_err, 256));
-    BCHK(s, hipMemcpyAsync(s->d_ct, &ct, sizeof ct, hipMemcpyHostToDevice, st));
-    BCHK(s, hipMemsetAsync(s->d_err, 0, 256, st));
-    BCHK(s, hipStreamSynchronize(st));
-    s->rt.hash = (const unsigned long long*)s->d_rt[0]; s->rt.id = (const int32_t*)s->d_rt[1]; s->rt.name_off = (const uint32_t*)s->d_rt[2];
-    s->rt.names = (const uint8_t*)s->d_rt[3]; s->rt.mask = H.tcap - 1; s->rt.nref = nref;
-    if (s->sp_sorted) {
-        for (int k = 0; k < 2; ++k) {
-            s->tmp_fd[k] = open(s->tmp_path[k].c_str(), O_RDWR | O_CREAT | O_TRUNC, 0600);
-            if (s->tmp_fd[k] < 0) return bfail(s, MKT_E_IO, "cannot create the temporary file %s: %s", s->tmp_path[k].c_str(), strerror(errno));
-            s->tmp_made[k] = true;
-        }
-    }
-    s->hdr_ready = true;
     return MKT_OK;
 }
 
@@ -1486,15 +1673,15 @@ static int bs_reserve(mkt_bam* s, uint64_t n) {                  // room for n m
     b.d_win = nb; b.cap = ncap;
     return MKT_OK;
 }
-struct BaiWin { const BamIdx* idx; const uint64_t* off; uint64_t n; uint64_t ubase; };
 // n_new bytes have been put after the carry: compress the complete blocks (all of them when final), reduce the window's records
-// into the index, queue the compressed bytes for mkt_bam_pull, keep the partial last block
+// (w; they start at the carry's end) into the index, queue the compressed bytes for mkt_bam_pull, keep the partial last block
 static int bs_commit(mkt_bam* s, uint64_t n_new, bool final, const BaiWin* w) {
     BgzfStream& b = s->bs;
     hipStream_t st = s->stream;
     const uint64_t len = b.carry + n_new;
     const uint64_t nfull = final ? (len + BGZF_RAW - 1) / BGZF_RAW : len / BGZF_RAW;
     const uint64_t nraw = final ? len : nfull * BGZF_RAW;
+    const VoffMap vm{b.blk0 * BGZF_RAW + b.carry, b.blk0, b.cbase};
     int rc = dgrow(s, b.d_csize, b.csize_cap, (nfull + 2) * sizeof(uint64_t));
     if (rc) return rc;
     uint64_t ctot = 0;
@@ -1505,43 +1692,10 @@ static int bs_commit(mkt_bam* s, uint64_t n_new, bool final, const BaiWin* w) {
         cap_b = cap_b < 16 ? 16 : (cap_b > 2048 ? 2048 : cap_b);
         const uint64_t batch = nfull < cap_b ? nfull : cap_b;
         if (s->sp_level > 0 && (rc = dgrow(s, b.d_scratch, b.scratch_cap, batch * kDzPerBlock + 64))) return rc;
-        bgzf_launch(b.d_win, nraw, nfull, s->sp_level, s->d_ct, b.d_comp, b.d_csize, b.d_scratch, batch, st);
-        BCHK(s, hipGetLastError());
-        BCHK(s, launch_exscan(b.d_csize, nfull, b.d_csize + nfull, st));
-        BCHK(s, hipMemcpyAsync(&ctot, b.d_csize + nfull, sizeof ctot, hipMemcpyDeviceToHost, st));
+        if ((rc = bgzf_compress(s, b.d_win, nraw, nfull, s->sp_level, b.d_comp, b.d_csize, b.d_scratch, batch, &ctot))) return rc;
     } else BCHK(s, hipMemsetAsync(b.d_csize, 0, 2 * sizeof(uint64_t), st));
-    BaiAcc& x = s->bx;
-    if (x.on && w && w->n) {
-        const uint64_t n = w->n;
-        const unsigned grid = (unsigned)((n + 255) / 256);
-        if ((rc = dgrow(s, b.d_hflag, b.hflag_cap, (n + 2) * sizeof(uint64_t)))) return rc;
-        const VoffMap vm{w->ubase, b.blk0, b.cbase};
-        hipLaunchKernelGGL(k_bai, dim3(grid), dim3(256), 0, st, w->idx, w->off, n, vm, (const uint64_t*)b.d_csize, (const uint64_t*)x.d_lin_off, s->rt.nref,
-                           x.d_lin, x.d_refs, b.d_hflag, x.d_nocoor, (const BamIdx*)(x.has_prev ? x.d_prev : nullptr));
-        BCHK(s, hipGetLastError());
-        BCHK(s, launch_exscan(b.d_hflag, n, b.d_hflag + n, st));
-        uint64_t nheads = 0;
-        BCHK(s, hipMemcpyAsync(&nheads, b.d_hflag + n, sizeof nheads, hipMemcpyDeviceToHost, st));
-        BCHK(s, hipStreamSynchronize(st));
-        if (nheads) {
-            if ((rc = dgrow(s, b.d_heads, b.heads_cap, (nheads + 1) * sizeof(BaiHead)))) return rc;
-            hipLaunchKernelGGL(k_bai_heads, dim3(grid), dim3(256), 0, st, w->idx, w->off, n, vm, (const uint64_t*)b.d_csize, (const uint64_t*)b.d_hflag, b.d_heads,
-                               (const BamIdx*)(x.has_prev ? x.d_prev : nullptr));
-            BCHK(s, hipGetLastError());
-            const size_t h0 = x.heads.size();
-            x.heads.resize(h0 + nheads);
-            BCHK(s, hipMemcpyAsync(x.heads.data() + h0, b.d_heads, nheads * sizeof(BaiHead), hipMemcpyDeviceToHost, st));
-        }
-        BCHK(s, hipMemcpyAsync(x.d_prev, w->idx + (n - 1), sizeof(BamIdx), hipMemcpyDeviceToDevice, st));
-        x.has_prev = true;
-    }
-    if (final && x.on) {                                           // virtual offset of the end of the data
-        const uint64_t uo = b.blk0 * BGZF_RAW + len, bb = uo / BGZF_RAW;
-        uint64_t c = 0;
-        BCHK(s, hipMemcpyAsync(&c, b.d_csize + (bb - b.blk0), sizeof c, hipMemcpyDeviceToHost, st));
-        BCHK(s, hipStreamSynchronize(st));
-        x.end_voff = ((b.cbase + c) << 16) | (uo - bb * BGZF_RAW);
-    }
+    if (w && (rc = bai_window(s, *w, vm, b.d_csize))) return rc;
+    if (final && (rc = bai_data_end(s, b.blk0 * BGZF_RAW + len, vm, b.d_csize))) return rc;
     BCHK(s, hipStreamSynchronize(st));
     if (ctot) {
         if ((rc = dgrow(s, b.d_pack, b.pack_cap, ctot + 64))) return rc;
@@ -1591,78 +1745,37 @@ static int spill_form(mkt_bam* s, uint64_t a, uint64_t b) {
     hipStream_t st = s->stream;
     const bool sorted = s->sp_sorted != 0;
     const uint8_t* text = s->d_text + a;
-    std::vector<void*> own;
-    auto cleanup = [&]() { for (void* p : own) dfree(s, p); own.clear(); };
-#define SALLOC(ptr, bytes_) do { hipError_t e_ = dalloc(s, (void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } own.push_back((void*)(ptr)); } while (0)
-#define SRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    uint64_t nl = 0;
-    uint64_t* d_starts = nullptr;
-    SRUN(sort_line_index(text, b - a, st, &d_starts, &nl));
-    dtrack(s, d_starts, (nl + 2) * sizeof(uint64_t));
-    own.push_back(d_starts);
-    if (nl >= (1ull << 32) - 1) { cleanup(); return bfail(s, MKT_E_ARG, "%llu lines: records are indexed with 32 bits", (unsigned long long)nl); }
-    SortRec *rA = nullptr, *rB = nullptr;
-    uint32_t *d_size = nullptr, *d_hist = nullptr;
-    uint64_t* d_off = nullptr;
+    DevScope own(s);
+    PhaseMarks quiet{false};
+    BamRecs R;
+    if ((rc = bam_records(s, own, text, b - a, sorted, quiet, &R))) return rc;
+    const uint64_t nl = R.nl, total = R.total;
     BamIdx* d_idx = nullptr;
-    const unsigned lgrid = (unsigned)((nl + 255) / 256);
-    SALLOC(rA, (nl + 1) * sizeof(SortRec));
-    SALLOC(d_size, (nl + 1) * sizeof(uint32_t));
-    SALLOC(d_off, (nl + 2) * sizeof(uint64_t));
-    hipLaunchKernelGGL(k_bam_keys, dim3(lgrid), dim3(256), 0, st, text, (const uint64_t*)d_starts, nl, s->rt, rA, d_size, s->d_err);
-    if (sorted) {
-        SALLOC(rB, (nl + 1) * sizeof(SortRec));
-        SALLOC(d_hist, kSortHistBytes);
-        int tbits = 1;
-        while ((1ull << tbits) <= (uint64_t)s->rt.nref) ++tbits;
-        sort_radix_passes(rA, rB, nl, d_hist, 1, 0, 33 + tbits, st);
-    }
-    uint32_t herr = 0;
-    SRUN(hipMemcpyAsync(&herr, s->d_err, sizeof herr, hipMemcpyDeviceToHost, st));
-    SRUN(hipStreamSynchronize(st));
-    if (herr) {
-        cleanup();
-        return bfail(s, MKT_E_ARG, "not SAM alignment text (error bits 0x%x: 1 fewer than 11 fields, 2 reference name not in the header, 4 number, 8 CIGAR, 16 optional field, 32 SEQ / QUAL lengths, 64 QNAME length)", herr);
-    }
-    hipLaunchKernelGGL(k_bam_sizes, dim3(lgrid), dim3(256), 0, st, (const SortRec*)rA, (const uint32_t*)d_size, nl, d_off);
-    SRUN(launch_exscan(d_off, nl, d_off + nl, st));
-    uint64_t total = 0;
-    SRUN(hipMemcpyAsync(&total, d_off + nl, sizeof total, hipMemcpyDeviceToHost, st));
-    SRUN(hipStreamSynchronize(st));
-    SALLOC(d_idx, (nl + 1) * sizeof(BamIdx));
+    if ((rc = own.alloc(d_idx, (nl + 1) * sizeof(BamIdx)))) return rc;
     if (sorted) {
         uint8_t* d_raw = nullptr;
         SpillRec* d_rec = nullptr;
-        SALLOC(d_raw, total + 64);
-        SALLOC(d_rec, (nl + 1) * sizeof(SpillRec));
-        hipLaunchKernelGGL(k_bam_write, dim3(lgrid), dim3(256), 0, st, text, (const uint64_t*)d_starts, nl, s->rt, (const SortRec*)rA, (const uint64_t*)d_off, d_raw, d_idx, s->d_err);
-        hipLaunchKernelGGL(k_spill_recs, dim3(lgrid), dim3(256), 0, st, (const SortRec*)rA, (const uint32_t*)d_size, (const BamIdx*)d_idx, nl, d_rec);
-        SRUN(hipGetLastError());
+        if ((rc = own.alloc(d_raw, total + 64)) || (rc = own.alloc(d_rec, (nl + 1) * sizeof(SpillRec)))) return rc;
+        bam_write(s, text, R, d_raw, d_idx);
+        hipLaunchKernelGGL(k_spill_recs, dim3(R.grid()), dim3(256), 0, st, (const SortRec*)R.rA, (const uint32_t*)R.d_size, (const BamIdx*)d_idx, nl, d_rec);
+        BCHK(s, hipGetLastError());
         SpillRun r;
         r.data_off = (uint64_t)lseek(s->tmp_fd[0], 0, SEEK_CUR);
         r.key_off = (uint64_t)lseek(s->tmp_fd[1], 0, SEEK_CUR);
         r.nrec = nl;
-        rc = write_dev(s, 0, d_raw, total);
-        if (!rc) rc = write_dev(s, 1, d_rec, nl * sizeof(SpillRec));
-        cleanup();
-        if (rc) return rc;
+        if ((rc = write_dev(s, 0, d_raw, total)) || (rc = write_dev(s, 1, d_rec, nl * sizeof(SpillRec)))) return rc;
         s->runs.push_back(r);
     } else {
         if (!s->spilled) {                                         // the first piece: the header goes first
-            if ((rc = bs_reserve(s, s->H.hdr.size()))) { cleanup(); return rc; }
-            SRUN(hipMemcpyAsync(s->bs.d_win, s->H.hdr.data(), s->H.hdr.size(), hipMemcpyHostToDevice, st));
+            if ((rc = bs_reserve(s, s->H.hdr.size()))) return rc;
+            BCHK(s, hipMemcpyAsync(s->bs.d_win, s->H.hdr.data(), s->H.hdr.size(), hipMemcpyHostToDevice, st));
             s->bs.carry = s->H.hdr.size();
         }
-        if ((rc = bs_reserve(s, total))) { cleanup(); return rc; }
-        hipLaunchKernelGGL(k_bam_write, dim3(lgrid), dim3(256), 0, st, text, (const uint64_t*)d_starts, nl, s->rt, (const SortRec*)rA, (const uint64_t*)d_off,
-                           s->bs.d_win + s->bs.carry, d_idx, s->d_err);
-        SRUN(hipGetLastError());
-        rc = bs_commit(s, total, false, nullptr);
-        cleanup();
-        if (rc) return rc;
+        if ((rc = bs_reserve(s, total))) return rc;
+        bam_write(s, text, R, s->bs.d_win + s->bs.carry, d_idx);
+        BCHK(s, hipGetLastError());
+        if ((rc = bs_commit(s, total, false, nullptr))) return rc;
     }
-#undef SALLOC
-#undef SRUN
     s->spilled = true;
     s->records += nl;
     ++s->nruns;
@@ -1727,30 +1840,10 @@ static uint64_t merge_window_bytes(const mkt_bam* s) {             // record byt
 // the merge is set up: the last run is on disk, the text is gone
 static int merge_begin(mkt_bam* s) {
     const BamHeader& H = s->H;
-    const uint32_t nref = (uint32_t)H.names.size();
     hipStream_t st = s->stream;
     s->cur.assign(s->runs.size(), SpillCur());
-    BaiAcc& x = s->bx;
-    x.on = bai_possible(H);
-    if (!x.on) s->note = kNoIndexLongRef;
-    if (x.on) {
-        bai_lin_off(H, x.lin_off);
-        const uint64_t nlin = x.lin_off[nref];
-        std::vector<BaiRef> init(nref);
-        for (auto& r : init) { r.n_mapped = 0; r.n_unmapped = 0; r.beg = ~0ull; r.end = 0; }
-        BCHK(s, dalloc(s, (void**)&x.d_lin_off, (nref + 1) * sizeof(uint64_t)));
-        BCHK(s, dalloc(s, (void**)&x.d_lin, (nlin + 1) * sizeof(unsigned long long)));
-        BCHK(s, dalloc(s, (void**)&x.d_refs, (nref + 1) * sizeof(BaiRef)));
-        BCHK(s, dalloc(s, (void**)&x.d_nocoor, 256));
-        BCHK(s, dalloc(s, (void**)&x.d_prev, sizeof(BamIdx) + 64));
-        BCHK(s, hipMemcpyAsync(x.d_lin_off, x.lin_off.data(), (nref + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        BCHK(s, hipMemsetAsync(x.d_lin, 0xFF, (nlin + 1) * sizeof(unsigned long long), st));
-        if (nref) BCHK(s, hipMemcpyAsync(x.d_refs, init.data(), nref * sizeof(BaiRef), hipMemcpyHostToDevice, st));
-        BCHK(s, hipMemsetAsync(x.d_nocoor, 0, 256, st));
-        BCHK(s, hipMemsetAsync(x.d_nocoor + 2, 0xFF, sizeof(unsigned long long), st));
-    }
-    int rc = bs_reserve(s, H.hdr.size());
-    if (rc) return rc;
+    int rc = bai_begin(s);
+    if (rc || (rc = bs_reserve(s, H.hdr.size()))) return rc;
     BCHK(s, hipMemcpyAsync(s->bs.d_win, H.hdr.data(), H.hdr.size(), hipMemcpyHostToDevice, st));
     BCHK(s, hipStreamSynchronize(st));
     s->bs.carry = H.hdr.size();
@@ -1758,25 +1851,10 @@ static int merge_begin(mkt_bam* s) {
     return MKT_OK;
 }
 static int merge_finish(mkt_bam* s) {
-    BaiAcc& x = s->bx;
-    if (x.on) {
-        const BamHeader& H = s->H;
-        const uint32_t nref = (uint32_t)H.names.size();
-        std::vector<BaiRef> refs(nref);
-        std::vector<unsigned long long> lin(x.lin_off[nref]);
-        unsigned long long nc[3] = {0, 0, 0};
-        hipStream_t st = s->stream;
-        if (nref) BCHK(s, hipMemcpyAsync(refs.data(), x.d_refs, nref * sizeof(BaiRef), hipMemcpyDeviceToHost, st));
-        if (!lin.empty()) BCHK(s, hipMemcpyAsync(lin.data(), x.d_lin, lin.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        BCHK(s, hipMemcpyAsync(nc, x.d_nocoor, sizeof nc, hipMemcpyDeviceToHost, st));
-        BCHK(s, hipStreamSynchronize(st));
-        const uint64_t off_end = nc[0] ? nc[2] : x.end_voff;        // the first record without coordinates, or the end of the data
-        s->bai.clear();
-        bai_assemble(s, nref, x.lin_off, refs, lin, x.heads, nc[0], nc[1], off_end);
-        std::vector<BaiHead>().swap(x.heads);
-    }
+    const int rc = bai_end(s);
+    if (rc) return rc;
     spill_remove(s);
-    spill_free_device(s);
+    bam_free_device(s);
     s->merging = false;
     s->done = true;
     if (getenv("MKT_VERBOSE"))
@@ -1841,7 +1919,6 @@ static int merge_round(mkt_bam* s) {
     const uint64_t n = hrec.size();
     hipStream_t st = s->stream;
     MergeBufs& m = s->mb;
-    uint64_t ubase = s->bs.blk0 * BGZF_RAW + s->bs.carry;
     if (n) {
         if ((rc = dgrow(s, m.rec, m.rec_cap, (n + 1) * sizeof(SpillRec))) || (rc = dgrow(s, m.src, m.src_cap, (n + 1) * sizeof(uint64_t))) ||
             (rc = dgrow(s, m.bytes, m.bytes_cap, nb + 64)) || (rc = dgrow(s, m.rA, m.rA_cap, (n + 1) * sizeof(SortRec))) ||
@@ -1859,10 +1936,8 @@ static int merge_round(mkt_bam* s) {
         BCHK(s, hipStreamSynchronize(st));
         const unsigned grid = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(k_merge_keys, dim3(grid), dim3(256), 0, st, (const SpillRec*)m.rec, n, m.rA);
-        int tbits = 1;
-        while ((1ull << tbits) <= (uint64_t)s->rt.nref) ++tbits;
         SortRec *rA = m.rA, *rB = m.rB;
-        sort_radix_passes(rA, rB, n, m.hist, 1, 0, 33 + tbits, st);
+        sort_radix_passes(rA, rB, n, m.hist, 1, 0, bam_key_bits(s), st);
         hipLaunchKernelGGL(k_merge_sizes, dim3(grid), dim3(256), 0, st, (const SortRec*)rA, (const SpillRec*)m.rec, n, m.off, m.idx);
         BCHK(s, launch_exscan(m.off, n, m.off + n, st));
         hipLaunchKernelGGL(k_merge_gather, dim3((unsigned)((n + MG_WAVES - 1) / MG_WAVES)), dim3(64 * MG_WAVES), 0, st, (const uint8_t*)m.bytes, (const uint64_t*)m.src,
@@ -1874,7 +1949,7 @@ static int merge_round(mkt_bam* s) {
         c.keys.erase(c.keys.begin(), c.keys.begin() + take[r].first);
         c.bytes.erase(0, take[r].second);
     }
-    const BaiWin w{m.idx, m.off, n, ubase};
+    const BaiWin w{m.idx, m.off, n};
     if ((rc = bs_commit(s, nb, final, &w))) return rc;
     ++s->rounds;
     s->t_merge += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1902,7 +1977,7 @@ void mkt_bam_destroy(mkt_bam* s) {
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     spill_remove(s);
-    spill_free_device(s);
+    bam_free_device(s);
     if (s->d_text) dfree(s, s->d_text);
     if (s->d_bam) dfree(s, s->d_bam);
     for (int k = 0; k < 2; ++k) { if (s->h_io[k]) (void)hipHostFree(s->h_io[k]); if (s->ev_io[k]) (void)hipEventDestroy(s->ev_io[k]); }
@@ -2036,7 +2111,7 @@ static int spill_run_end(mkt_bam* s) {
         fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", (std::to_string(s->nruns) + (s->sp_sorted ? " runs formed" : " pieces converted")).c_str(), s->t_form);
     if (s->sp_sorted) return merge_begin(s);
     if ((rc = bs_commit(s, 0, true, nullptr))) return rc;
-    spill_free_device(s);
+    bam_free_device(s);
     s->done = true;
     return MKT_OK;
 }
@@ -2078,6 +2153,7 @@ static int bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_
         rc = spill_cut(s, true);
         if (!rc && !s->spilled) rc = bfail(s, MKT_E_NOMEM, "no run could be formed");
     }
+    if (!s->spilled) bam_free_device(s);                           // the single pass has ended: only the BAM stays
     if (rc) return rc;
     if (s->spilled) {
         if ((rc = spill_run_end(s))) return rc;
@@ -2093,101 +2169,14 @@ static int bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_
 // the single pass: everything resident
 static int bam_single(mkt_bam* s, int sorted, int level, bool verbose) {
     hipStream_t st = s->stream;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {                            // (call sites follow a stream synchronisation)
-        if (!verbose) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
-    // ---- header: text (with @HD SO:coordinate when sorting), the reference dictionary from @SQ, the name table
-    BamHeader H;
-    {
-        int rc = bam_parse_header(s, sorted != 0, H);
-        if (rc) return rc;
-    }
-    const std::vector<std::string>& names = H.names;
-    const std::string& hdr = H.hdr;
-    const uint32_t nref = (uint32_t)names.size();
-    const uint64_t hdr_len = hdr.size();
-    const uint32_t tcap = H.tcap;
-    const std::vector<unsigned long long>& th = H.th;
-    const std::vector<int32_t>& tidv = H.tidv;
-    const std::vector<uint32_t>& noff = H.noff;
-    const std::string& blob = H.blob;
-    (void)names;
-
-    std::vector<void*> owned;
-    auto cleanup = [&]() { for (void* p : owned) dfree(s, p); owned.clear(); };
-#define BALLOC(ptr, bytes_) do { hipError_t e_ = dalloc(s, (void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } owned.push_back((void*)(ptr)); } while (0)
-#define BRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    auto drop = [&](void* p) { dfree(s, p); owned.erase(std::remove(owned.begin(), owned.end(), p), owned.end()); };
-    unsigned long long* d_th = nullptr; int32_t* d_tid = nullptr; uint32_t* d_noff = nullptr; uint8_t* d_blob = nullptr;
-    CrcTabs* d_ct = nullptr;
-    uint32_t* d_err = nullptr;
-    BALLOC(d_th, tcap * sizeof(unsigned long long));
-    BALLOC(d_tid, tcap * sizeof(int32_t));
-    BALLOC(d_noff, (nref + 1) * sizeof(uint32_t));
-    BALLOC(d_blob, blob.size() + 16);
-    BALLOC(d_ct, sizeof(CrcTabs));
-    BALLOC(d_err, 256);
-    CrcTabs ct;
-    crc_tables(&ct);
-    BRUN(hipMemcpyAsync(d_th, th.data(), tcap * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    BRUN(hipMemcpyAsync(d_tid, tidv.data(), tcap * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    BRUN(hipMemcpyAsync(d_noff, noff.data(), (nref + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (!blob.empty()) BRUN(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    BRUN(hipMemcpyAsync(d_ct, &ct, sizeof ct, hipMemcpyHostToDevice, st));
-    BRUN(hipMemsetAsync(d_err, 0, 256, st));
-    BRUN(hipStreamSynchronize(st));
-    RefTab rt;
-    rt.hash = d_th; rt.id = d_tid; rt.name_off = d_noff; rt.names = d_blob; rt.mask = tcap - 1; rt.nref = nref;
-
-    // ---- lines, keys, order
-    uint64_t nl = 0;
-    uint64_t* d_starts = nullptr;
-    if (s->len) {
-        const hipError_t eli = sort_line_index(s->d_text, s->len, st, &d_starts, &nl);
-        if (eli == hipErrorOutOfMemory) { (void)hipGetLastError(); cleanup(); return bfail(s, MKT_E_NOMEM, "the line index does not fit beside the text"); }
-        BRUN(eli);
-        dtrack(s, d_starts, (nl + 2) * sizeof(uint64_t));
-        owned.push_back(d_starts);
-    }
-    mark("header + line index");
-    if (nl >= (1ull << 32) - 1) { cleanup(); return bfail(s, MKT_E_ARG, "%llu lines: records are indexed with 32 bits", (unsigned long long)nl); }
-    SortRec *rA = nullptr, *rB = nullptr;
-    uint32_t *d_size = nullptr, *d_hist = nullptr;
-    uint64_t* d_off = nullptr;
-    BamIdx* d_idx = nullptr;
-    uint8_t* d_raw = nullptr;
-    uint64_t total = 0;
-    const unsigned lgrid = (unsigned)((nl + 255) / 256);
-    if (nl) {
-        BALLOC(rA, (nl + 1) * sizeof(SortRec));
-        BALLOC(d_size, (nl + 1) * sizeof(uint32_t));
-        BALLOC(d_off, (nl + 2) * sizeof(uint64_t));
-        hipLaunchKernelGGL(k_bam_keys, dim3(lgrid), dim3(256), 0, st, (const uint8_t*)s->d_text, (const uint64_t*)d_starts, nl, rt, rA, d_size, d_err);
-        if (sorted) {
-            BALLOC(rB, (nl + 1) * sizeof(SortRec));
-            BALLOC(d_hist, kSortHistBytes);
-            int tbits = 1;
-            while ((1ull << tbits) <= (uint64_t)nref) ++tbits;
-            sort_radix_passes(rA, rB, nl, d_hist, 1, 0, 33 + tbits, st);
-        }
-        uint32_t herr = 0;
-        BRUN(hipMemcpyAsync(&herr, d_err, sizeof herr, hipMemcpyDeviceToHost, st));
-        BRUN(hipStreamSynchronize(st));
-        if (herr) {
-            cleanup();
-            return bfail(s, MKT_E_ARG, "not SAM alignment text (error bits 0x%x: 1 fewer than 11 fields, 2 reference name not in the header, 4 number, 8 CIGAR, 16 optional field, 32 SEQ / QUAL lengths, 64 QNAME length)", herr);
-        }
-        mark(sorted ? "keys + radix sort" : "keys");
-        hipLaunchKernelGGL(k_bam_sizes, dim3(lgrid), dim3(256), 0, st, (const SortRec*)rA, (const uint32_t*)d_size, nl, d_off);
-        BRUN(launch_exscan(d_off, nl, d_off + nl, st));
-        BRUN(hipMemcpyAsync(&total, d_off + nl, sizeof total, hipMemcpyDeviceToHost, st));
-        BRUN(hipStreamSynchronize(st));
-    }
-    const uint64_t nraw = hdr_len + total;
+    PhaseMarks mark{verbose};
+    int rc = bam_setup(s, sorted != 0);
+    if (rc) return rc;
+    const uint64_t hdr_len = s->H.hdr.size();
+    DevScope own(s);
+    BamRecs R;
+    if ((rc = bam_records(s, own, s->d_text, s->len, sorted != 0, mark, &R))) return rc;
+    const uint64_t nl = R.nl, nraw = hdr_len + R.total;
     if (s->autob) {
         // "auto": does the rest of the pass fit?  Next the records and their index fields beside the text and the sort records; then,
         // with those gone, the compressed blocks, the deflate scratch, the packed BAM and the index's head flags.
@@ -2198,128 +2187,60 @@ static int bam_single(mkt_bam* s, int sorted, int level, bool verbose) {
         const uint64_t freed = s->cap + 64 + (nl + 2) * sizeof(uint64_t) + (nl + 1) * (2 * sizeof(SortRec) + sizeof(uint32_t)) + kSortHistBytes;
         const uint64_t later = 2 * nblk * (uint64_t)BGZF_STRIDE + (nblk + 2) * sizeof(uint64_t) + (level > 0 ? batch * kDzPerBlock : 0) + (nl + 2) * sizeof(uint64_t);
         const uint64_t fr = device_free(s), slack = ((uint64_t)1 << 20) + (next + later) / 20;
-        if (next + slack > fr || next + later + slack > fr + freed) {
-            cleanup();
+        if (next + slack > fr || next + later + slack > fr + freed)
             return bfail(s, MKT_E_NOMEM, "the single pass does not fit this GPU (%.2f GB free beside the text)", (double)fr / 1e9);
-        }
     }
-    BALLOC(d_raw, nraw + 64);
-    BRUN(hipMemcpyAsync(d_raw, hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
+    uint8_t* d_raw = nullptr;
+    BamIdx* d_idx = nullptr;
+    if ((rc = own.alloc(d_raw, nraw + 64))) return rc;
+    BCHK(s, hipMemcpyAsync(d_raw, s->H.hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
     if (nl) {
-        BALLOC(d_idx, (nl + 1) * sizeof(BamIdx));
-        hipLaunchKernelGGL(k_bam_write, dim3(lgrid), dim3(256), 0, st, (const uint8_t*)s->d_text, (const uint64_t*)d_starts, nl, rt, (const SortRec*)rA, (const uint64_t*)d_off, d_raw + hdr_len, d_idx, d_err);
-        BRUN(hipGetLastError());
-        BRUN(hipStreamSynchronize(st));
+        if ((rc = own.alloc(d_idx, (nl + 1) * sizeof(BamIdx)))) return rc;
+        bam_write(s, s->d_text, R, d_raw + hdr_len, d_idx);
+        BCHK(s, hipGetLastError());
+        BCHK(s, hipStreamSynchronize(st));
         mark("records");
         // the text and the sort records are no longer needed
-        drop(rA); if (rB) drop(rB); drop(d_size); drop(d_starts);
-        rA = rB = nullptr;
+        own.drop(R.rA); if (R.rB) own.drop(R.rB); own.drop(R.d_size); own.drop(R.d_starts);
     }
     dfree(s, s->d_text); s->d_text = nullptr; s->cap = s->len = 0;
 
-    // ---- BGZF
+    // ---- BGZF: the whole file at once, the packed bytes stay on the device (mkt_bam_fetch / _read)
     const uint64_t nblocks = (nraw + BGZF_RAW - 1) / BGZF_RAW;
     uint8_t* d_comp = nullptr;
     uint64_t* d_csize = nullptr;
     uint32_t* d_scratch = nullptr;
-    BALLOC(d_comp, nblocks * (uint64_t)BGZF_STRIDE + 64);
-    BALLOC(d_csize, (nblocks + 2) * sizeof(uint64_t));
+    if ((rc = own.alloc(d_comp, nblocks * (uint64_t)BGZF_STRIDE + 64)) || (rc = own.alloc(d_csize, (nblocks + 2) * sizeof(uint64_t)))) return rc;
     // the token lists and bit streams of the blocks of one launch (levels 1, 2): at most 8 GB of scratch
     uint64_t batch = ((uint64_t)8 << 30) / kDzPerBlock;
     if (batch > nblocks) batch = nblocks;
     if (batch < 1) batch = 1;
-    if (level > 0) BALLOC(d_scratch, batch * kDzPerBlock + 64);
-    bgzf_launch(d_raw, nraw, nblocks, level, d_ct, d_comp, d_csize, d_scratch, batch, st);
-    BRUN(hipGetLastError());
-    BRUN(launch_exscan(d_csize, nblocks, d_csize + nblocks, st));
+    if (level > 0 && (rc = own.alloc(d_scratch, batch * kDzPerBlock + 64))) return rc;
     uint64_t clen = 0;
-    BRUN(hipMemcpyAsync(&clen, d_csize + nblocks, sizeof clen, hipMemcpyDeviceToHost, st));
-    BRUN(hipStreamSynchronize(st));
+    if ((rc = bgzf_compress(s, d_raw, nraw, nblocks, level, d_comp, d_csize, d_scratch, batch, &clen))) return rc;
+    BCHK(s, hipStreamSynchronize(st));
     mark(level > 0 ? "BGZF deflate" : "BGZF stored");
-    drop(d_raw);
-    if (d_scratch) drop(d_scratch);
-    { hipError_t e_ = dalloc(s, (void**)&s->d_bam, clen + 28 + 64); if (e_ != hipSuccess) { cleanup(); return bfail(s, MKT_E_NOMEM, "hipMalloc of the BAM failed: %s", hipGetErrorString(e_)); } }
+    own.drop(d_raw);
+    if (d_scratch) own.drop(d_scratch);
+    { hipError_t e_ = dalloc(s, (void**)&s->d_bam, clen + 28 + 64); if (e_ != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of the BAM failed: %s", hipGetErrorString(e_)); }
     hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)nblocks), dim3(BWG), 0, st, (const uint8_t*)d_comp, (const uint64_t*)d_csize, nblocks, s->d_bam);
-    BRUN(hipMemcpyAsync(s->d_bam + clen, kBgzfEof, 28, hipMemcpyHostToDevice, st));
-    BRUN(hipGetLastError());
-    BRUN(hipStreamSynchronize(st));
+    BCHK(s, hipMemcpyAsync(s->d_bam + clen, kBgzfEof, 28, hipMemcpyHostToDevice, st));
+    BCHK(s, hipGetLastError());
+    BCHK(s, hipStreamSynchronize(st));
     s->bam_len = clen + 28;
     s->records = nl;
     s->nruns = nl ? 1 : 0;
-    drop(d_comp);
+    own.drop(d_comp);
     mark("pack");
 
-    // ---- BAI (coordinate order only; the format ends at 2^29 bases per reference -- longer ones would need a CSI index: none is made then)
+    // ---- BAI: one window over the whole file (after the compression: the virtual offsets need d_csize)
     s->bai.clear();
     s->note.clear();
-    const bool bai_ok = bai_possible(H);
-    if (sorted && bai_ok) {
-        std::vector<uint64_t> lin_off;
-        bai_lin_off(H, lin_off);
-        const uint64_t nlin = lin_off[nref];
-        uint64_t* d_lin_off = nullptr;
-        unsigned long long *d_lin = nullptr, *d_nocoor = nullptr;
-        BaiRef* d_refs = nullptr;
-        BaiHead* d_heads = nullptr;
-        uint64_t* d_hflag = nullptr;
-        std::vector<BaiRef> refs(nref);
-        std::vector<unsigned long long> lin(nlin);
-        std::vector<BaiHead> heads;
-        unsigned long long no_coor = 0, beyond = 0;
-        std::vector<BaiRef> init(nref);
-        for (auto& r : init) { r.n_mapped = 0; r.n_unmapped = 0; r.beg = ~0ull; r.end = 0; }
-        BALLOC(d_lin_off, (nref + 1) * sizeof(uint64_t));
-        BALLOC(d_lin, (nlin + 1) * sizeof(unsigned long long));
-        BALLOC(d_refs, (nref + 1) * sizeof(BaiRef));
-        BALLOC(d_nocoor, 256);
-        BALLOC(d_hflag, (nl + 2) * sizeof(uint64_t));
-        BRUN(hipMemcpyAsync(d_lin_off, lin_off.data(), (nref + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        BRUN(hipMemsetAsync(d_lin, 0xFF, (nlin + 1) * sizeof(unsigned long long), st));
-        if (nref) BRUN(hipMemcpyAsync(d_refs, init.data(), nref * sizeof(BaiRef), hipMemcpyHostToDevice, st));
-        BRUN(hipMemsetAsync(d_nocoor, 0, 256, st));
-        uint64_t nheads = 0;
-        if (nl) {
-            hipLaunchKernelGGL(k_bai, dim3(lgrid), dim3(256), 0, st, (const BamIdx*)d_idx, (const uint64_t*)d_off, nl, VoffMap{hdr_len, 0, 0}, (const uint64_t*)d_csize, (const uint64_t*)d_lin_off, nref,
-                               d_lin, d_refs, d_hflag, d_nocoor, (const BamIdx*)nullptr);
-            BRUN(hipGetLastError());
-            BRUN(launch_exscan(d_hflag, nl, d_hflag + nl, st));
-            BRUN(hipMemcpyAsync(&nheads, d_hflag + nl, sizeof nheads, hipMemcpyDeviceToHost, st));
-        }
-        BRUN(hipMemcpyAsync(&no_coor, d_nocoor, sizeof no_coor, hipMemcpyDeviceToHost, st));
-        BRUN(hipMemcpyAsync(&beyond, d_nocoor + 1, sizeof beyond, hipMemcpyDeviceToHost, st));
-        if (nref) BRUN(hipMemcpyAsync(refs.data(), d_refs, nref * sizeof(BaiRef), hipMemcpyDeviceToHost, st));
-        if (nlin) BRUN(hipMemcpyAsync(lin.data(), d_lin, nlin * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        BRUN(hipStreamSynchronize(st));
-        heads.resize(nheads);
-        if (nheads) {
-            BALLOC(d_heads, ((size_t)nheads + 1) * sizeof(BaiHead));
-            hipLaunchKernelGGL(k_bai_heads, dim3(lgrid), dim3(256), 0, st, (const BamIdx*)d_idx, (const uint64_t*)d_off, nl, VoffMap{hdr_len, 0, 0}, (const uint64_t*)d_csize, (const uint64_t*)d_hflag, d_heads,
-                               (const BamIdx*)nullptr);
-            BRUN(hipGetLastError());
-            BRUN(hipMemcpyAsync(heads.data(), d_heads, (size_t)nheads * sizeof(BaiHead), hipMemcpyDeviceToHost, st));
-            BRUN(hipStreamSynchronize(st));
-        }
-        // the end of a run of records in one bin = the start of the record after it
-        const uint64_t n_coor = nl - no_coor;
-        uint64_t off_end = 0;
-        {
-            // virtual offset of the first record without coordinates (or of the end of the data)
-            uint64_t uo = 0;
-            if (nl) BRUN(hipMemcpy(&uo, d_off + n_coor, sizeof uo, hipMemcpyDeviceToHost));
-            uo += hdr_len;
-            const uint64_t b = uo / BGZF_RAW;
-            uint64_t cb = 0;
-            BRUN(hipMemcpy(&cb, d_csize + b, sizeof cb, hipMemcpyDeviceToHost));
-            off_end = (cb << 16) | (uo - b * BGZF_RAW);
-        }
-        bai_assemble(s, nref, lin_off, refs, lin, heads, no_coor, beyond, off_end);
-        mark("BAI");
-    } else if (sorted) {
-        s->note = kNoIndexLongRef;
+    if (sorted) {
+        const VoffMap vm{hdr_len, 0, 0};
+        if ((rc = bai_begin(s)) || (rc = bai_window(s, BaiWin{d_idx, R.d_off, nl}, vm, d_csize)) || (rc = bai_data_end(s, nraw, vm, d_csize)) || (rc = bai_end(s))) return rc;
+        if (s->bx.on) mark("BAI");
     }
-    cleanup();
-#undef BALLOC
-#undef BRUN
     return MKT_OK;
 }
 

@@ -102,6 +102,22 @@ def test_edges(tmp_path):
         st = {}
         u = m.sam_to_bam(hdr + body, sorted=False, level=level, run_bytes=20000, piece=7000, tmp=pre, stats=st)
         assert u == m.sam_to_bam(hdr + body, sorted=False, level=level) and st["runs"] >= 4 and st["tmp_bytes"] == 0
+    # the data ends exactly on a BGZF block boundary and every record has coordinates: the last chunk of the index ends at the
+    # virtual offset of the end of the data, which then is the start of the block after the last one.  Records of this shape take
+    # 52 bytes (4 + 32 fixed, 7 name, 4 CIGAR, 2 SEQ, 3 QUAL); an @CO line pads the header.
+    lines = [b"r%05d\t0\tchr1\t%d\t60\t3M\t*\t0\t0\tACG\tIII" % (i, 1 + i * 300) for i in range(3000)]
+    body = b"\n".join(lines) + b"\n"
+    h0, order = header_for(body)
+    fixed = 12 + len("@HD\tVN:1.6\tSO:coordinate\n") + len(h0) + sum(9 + len(c) for c in order) + 52 * len(lines)
+    pad = -(fixed + 5) % 0xff00
+    hdr = h0 + b"@CO\t" + b"x" * pad + b"\n"
+    ref = m.sam_to_bam(hdr + body)
+    bam = check_bam(hdr, body, ref[0], ref[1], ref[2], True, order)
+    assert bam.raw_len == fixed + 5 + pad and bam.raw_len % 0xff00 == 0
+    assert bamio.Bai(ref[1]).n_no_coor == 0
+    st = {}
+    assert m.sam_to_bam(hdr + body, run_bytes=len(body) // 3 + 200, tmp=pre, stats=st, piece=4096) == ref
+    assert st["runs"] == 3 and _leftovers(pre) == []
 
 
 @pytest.mark.parametrize("groups,limit_mb,case", [(64000, 48, "the text does not fit"), (16000, 48, "the text fits, the single pass does not")])
