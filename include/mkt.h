@@ -298,7 +298,8 @@ int mkt_group_count(mkt_ctx* ctx, uint64_t* groups);
 
 /* ---- pairs -> binned contact matrix at several resolutions (the driver's last stage, microcket:520-554) -------------------
  * What `juicer_tools pre -r ...` and `cooler cload pairix` spend their time on: the sparse binned matrix.  The containers they
- * write (.hic, .cool), balancing and zoomify are out of scope; parity with those tools is unpinned.  Bin drop-in: bin/pairs2matrix.
+ * write (.hic, .cool) and zoomify are out of scope; parity with those tools is unpinned.  Bin drop-in: bin/pairs2matrix.
+ * Balancing (iterative correction) of each resolution's matrix is defined below, behind mkt_matrix_balance.
  *
  * Definition.  chromsizes: lines name<TAB>length (anno/<genome>.info; empty and '#' lines ignored); FILE ORDER IS BIN ORDER.
  * For a resolution r >= 1: chromosome i of length L_i owns n_i = ceil(L_i / r) bins, off_i = n_0 + .. + n_(i-1), nbins = sum n_i;
@@ -338,6 +339,65 @@ int mkt_matrix_info(const mkt_matrix* m, uint32_t res_index, uint64_t* nbins, ui
 int mkt_matrix_fetch(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint32_t* bin1, uint32_t* bin2, uint32_t* count);
 int mkt_matrix_fetch_text(mkt_matrix* m, uint32_t res_index, uint64_t off, char* out, size_t n);
 int mkt_matrix_timing(const mkt_matrix* m, uint32_t res_index, double* ms);
+
+/* ---- matrix balancing: iterative correction (ICE) of one resolution's cells, on the GPU -----------------------------------
+ * The definition is this project's own, modelled on the genome-wide `cooler balance`; parity with cooler is UNPINNED (cooler is not
+ * run anywhere here; in particular its convergence criterion may differ in scale from the one below -- it was not compared).
+ * tests/balancedef.py restates the definition in numpy.  All arithmetic is float64.
+ *
+ * Definition, for the cells (bin1 <= bin2, count) of one resolution, nbins, and the per-chromosome bin ranges [off_i, off_i + n_i):
+ *  1. USED cells: bin2 - bin1 >= ignore_diags (global bin ids).  marg(x)[k] = sum of x over used cells with bin1 == k + sum of x
+ *     over used cells with bin2 == k (a diagonal cell counts twice; that only matters when ignore_diags == 0).
+ *  2. bias = 1 for every bin.  min_nnz > 0: bias = 0 where marg(1) < min_nnz.  m = marg(count * bias[bin1] * bias[bin2]).
+ *     min_count > 0: bias = 0 where m < min_count.
+ *  3. mad_max > 0: within each chromosome's bin range m is divided by the median of its positive entries (a range with none is
+ *     left alone); lg = log(m[m > 0]); cut = exp(median(lg) - mad_max * median(|lg - median(lg)|)); bias = 0 where m < cut.
+ *     A median of an even number of values is the mean of the two middle ones.
+ *  4. for it = 1 .. max_iters: m = marg(count * bias[bin1] * bias[bin2]); nz = m[m != 0]; nz empty: every weight is NaN, scale and
+ *     var are NaN, stop (not converged).  mean = mean(nz); var = population variance of nz / mean (scale-free);
+ *     m /= mean; m[m == 0] = 1; bias /= m; var < tol: converged, stop.
+ *  5. weight = bias / sqrt(mean) with the last mean; bins with bias == 0 get NaN.  iterations = the last it, scale = the last mean,
+ *     masked = the number of NaN weights.  The balanced value of a cell is count * weight[bin1] * weight[bin2].
+ * Out of scope: cis_only / trans_only (per-chromosome loops), KR / VC vectors, the .cool / .hic containers, a text dump of balanced
+ * values.
+ *
+ * Determinism: no floating-point atomics anywhere; every sum has a fixed shape that depends on (nbins, cells) only, so the weights
+ * are the same bits from call to call, process to process and whatever route the pairs came by.  Against the numpy restatement
+ * the mask, the iteration count and the stopping decision are identical and the weights agree to summation-order rounding.
+ *
+ *   mkt_balance_opts_default   ignore_diags 2, min_nnz 10, min_count 0, mad_max 5.0, tol 1e-5, max_iters 200
+ *   mkt_matrix_balance         valid after mkt_matrix_run (MKT_E_STATE before); opts NULL = the defaults; MKT_E_ARG with a message for
+ *                              a bad index, a negative or NaN option, max_iters == 0 or a non-zero reserved.  stats may be NULL.
+ *                              The filters of steps 2-3 run on the host from one nbins-sized copy; step 4 stays on the device.
+ *                              Cells and COO text are untouched; a later mkt_matrix_run (or add) discards the weights.
+ *   mkt_matrix_fetch_weights   weights [first, first + n) of resolution res_index (MKT_E_STATE "balance first" without them)
+ *   mkt_matrix_balance_timing  device time (ms, HIP events) of the last balance of res_index: the one-time setup (row pointers and the
+ *                              transposed copy, 8 bytes per cell, kept until the next run; 0 when it was reused) and the whole
+ *                              iteration loop of step 4: the host looks at the device's state once per 4 iterations, so up to 3
+ *                              iterations of empty launches behind the last one and the looks themselves are in iter_ms.  Like
+ *                              mkt_matrix_timing it takes a const handle: a bad index is MKT_E_ARG without a message.
+ * Limit: fewer than 2^32 cells per resolution (MKT_E_CAPACITY with a message; implied today by the matrix stage's own limit of fewer
+ * than 2^32 pairs per object). */
+typedef struct mkt_balance_opts {
+    int32_t ignore_diags;
+    int32_t min_nnz;
+    double min_count;
+    double mad_max;
+    double tol;
+    int32_t max_iters;
+    uint32_t reserved;       /* 0 */
+} mkt_balance_opts;
+typedef struct mkt_balance_stats {
+    uint32_t iterations;
+    int32_t converged;       /* 0 / 1 */
+    double var;              /* of the last iteration */
+    double scale;            /* the last mean */
+    uint64_t masked;         /* NaN weights */
+} mkt_balance_stats;
+void mkt_balance_opts_default(mkt_balance_opts* o);
+int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts* opts, mkt_balance_stats* stats);
+int mkt_matrix_fetch_weights(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, double* out);
+int mkt_matrix_balance_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* iter_ms);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,8 @@ ctypes binding used by the tests and by ``bench.py``; it never computes anything
 CPU fallback: without the built library or without a GPU every call raises.
 """
 from .capi import (  # noqa: F401
+    BalanceOpts,
+    BalanceStats,
     Context,
     EXT_KEYS,
     EXT_LANES,
@@ -28,6 +30,6 @@ from .capi import (  # noqa: F401
 )
 
 __all__ = [
-    "Context", "EXT_KEYS", "EXT_LANES", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
+    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
     "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam",
 ]

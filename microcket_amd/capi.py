@@ -1,4 +1,5 @@
 """ctypes binding of include/mkt.h (libmkt_hip.so).  Plumbing only: no record is ever touched here."""
+import collections
 import ctypes as C
 import os
 import sys
@@ -23,6 +24,7 @@ EXPORTS = [
     "mkt_bam_reserve", "mkt_bam_window", "mkt_bam_commit", "mkt_bam_read", "mkt_bam_spill", "mkt_bam_pull", "mkt_bam_stats",
     "mkt_matrix_create", "mkt_matrix_destroy", "mkt_matrix_error", "mkt_matrix_add", "mkt_matrix_add_device", "mkt_matrix_add_keys", "mkt_matrix_run",
     "mkt_matrix_info", "mkt_matrix_fetch", "mkt_matrix_fetch_text", "mkt_matrix_timing",
+    "mkt_balance_opts_default", "mkt_matrix_balance", "mkt_matrix_fetch_weights", "mkt_matrix_balance_timing",
 ]
 
 
@@ -47,6 +49,19 @@ class Stats(C.Structure):
 
 class Out(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("pairs_len", C.c_size_t), ("sam", C.c_void_p), ("sam_len", C.c_size_t)]
+
+
+class BalanceOpts(C.Structure):
+    """mkt_balance_opts of include/mkt.h"""
+    _fields_ = [("ignore_diags", C.c_int32), ("min_nnz", C.c_int32), ("min_count", C.c_double), ("mad_max", C.c_double), ("tol", C.c_double),
+                ("max_iters", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _BalanceStatsC(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("converged", C.c_int32), ("var", C.c_double), ("scale", C.c_double), ("masked", C.c_uint64)]
+
+
+BalanceStats = collections.namedtuple("BalanceStats", "iterations converged var scale masked")
 
 
 class Timing(C.Structure):
@@ -191,6 +206,11 @@ def load_library():
     L.mkt_matrix_fetch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mkt_matrix_fetch_text.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_size_t]
     L.mkt_matrix_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
+    L.mkt_balance_opts_default.argtypes = [C.POINTER(BalanceOpts)]
+    L.mkt_balance_opts_default.restype = None
+    L.mkt_matrix_balance.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BalanceOpts), C.POINTER(_BalanceStatsC)]
+    L.mkt_matrix_fetch_weights.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_balance_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -582,6 +602,32 @@ class Matrix:
         ms = C.c_double()
         self._chk(self.L.mkt_matrix_timing(self.h, res, C.byref(ms)), "mkt_matrix_timing")
         return ms.value
+
+    def balance(self, res, **opts):
+        """Iterative correction of resolution index res after run() (the definition: mkt_matrix_balance in include/mkt.h).
+        opts: ignore_diags, min_nnz, min_count, mad_max, tol, max_iters; returns BalanceStats."""
+        o = BalanceOpts()
+        self.L.mkt_balance_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("ignore_diags", "min_nnz", "min_count", "mad_max", "tol", "max_iters"):
+                raise TypeError(f"balance: unknown option {k}")
+            setattr(o, k, v)
+        s = _BalanceStatsC()
+        self._chk(self.L.mkt_matrix_balance(self.h, res, C.byref(o), C.byref(s)), "mkt_matrix_balance")
+        return BalanceStats(s.iterations, bool(s.converged), s.var, s.scale, s.masked)
+
+    def weights(self, res):
+        """the balancing weights of resolution index res: numpy float64[nbins], NaN for a masked bin"""
+        import numpy as np
+        out = np.zeros(self.info(res)[0], dtype=np.float64)
+        self._chk(self.L.mkt_matrix_fetch_weights(self.h, res, 0, out.size, out.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_weights")
+        return out
+
+    def balance_timing_ms(self, res):
+        """(setup ms, iteration loop ms) of the last balance(res): device time, HIP events"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_balance_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_balance_timing")
+        return a.value, b.value
 
     def close(self):
         if self.h:

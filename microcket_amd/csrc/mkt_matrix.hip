@@ -17,11 +17,14 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/mkt.h"
+#include "mkt_balance.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
 
@@ -271,6 +274,11 @@ struct MxRes {
     uint32_t *d_b1 = nullptr, *d_b2 = nullptr, *d_cnt = nullptr;
     uint8_t* d_text = nullptr;
     double ms = 0;
+    // balancing (mkt_matrix_balance): the setup lives as long as the cells, the weights until the next balance or run
+    BalSetup bal;
+    double* d_w = nullptr;
+    bool balanced = false;
+    double bal_setup_ms = 0, bal_iter_ms = 0;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -339,6 +347,9 @@ static void mx_free_results(mkt_matrix* m) {
         if (r.d_cnt) (void)hipFree(r.d_cnt);
         if (r.d_text) (void)hipFree(r.d_text);
         r.d_b1 = r.d_b2 = r.d_cnt = nullptr; r.d_text = nullptr; r.nnz = 0; r.text_bytes = 0; r.ms = 0;
+        bal_free(r.bal);
+        if (r.d_w) (void)hipFree(r.d_w);
+        r.d_w = nullptr; r.balanced = false; r.bal_setup_ms = r.bal_iter_ms = 0;
     }
     m->ran = false;
 }
@@ -653,6 +664,150 @@ int mkt_matrix_fetch_text(mkt_matrix* m, uint32_t res_index, uint64_t off, char*
     if (off > r.text_bytes || n > r.text_bytes - off) return mfail(m, MKT_E_ARG, "range past the end of the COO text");
     MCHK(m, hipSetDevice(m->device));
     if (n) MCHK(m, hipMemcpy(out, r.d_text + off, n, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+
+// ---- balancing: the entry points; the kernels are mkt_balance.hip, the definition is in include/mkt.h ------------------------
+void mkt_balance_opts_default(mkt_balance_opts* o) {
+    if (!o) return;
+    o->ignore_diags = 2; o->min_nnz = 10; o->min_count = 0.0; o->mad_max = 5.0; o->tol = 1e-5; o->max_iters = 200; o->reserved = 0;
+}
+
+int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts* opts, mkt_balance_stats* stats) {
+    if (!m) return MKT_E_ARG;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    mkt_balance_opts o;
+    mkt_balance_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "balance: ignore_diags %d is negative", o.ignore_diags);
+    if (o.min_nnz < 0) return mfail(m, MKT_E_ARG, "balance: min_nnz %d is negative", o.min_nnz);
+    if (!(o.min_count >= 0.0)) return mfail(m, MKT_E_ARG, "balance: min_count %g is negative or NaN", o.min_count);
+    if (!(o.mad_max >= 0.0)) return mfail(m, MKT_E_ARG, "balance: mad_max %g is negative or NaN", o.mad_max);
+    if (!(o.tol >= 0.0)) return mfail(m, MKT_E_ARG, "balance: tol %g is negative or NaN", o.tol);
+    if (o.max_iters <= 0) return mfail(m, MKT_E_ARG, "balance: max_iters %d (at least 1 is needed)", o.max_iters);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "balance: the reserved field is not 0");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "balance before run");
+    if (m->res[res_index].nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "balance: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)m->res[res_index].nnz);
+    MCHK(m, hipSetDevice(m->device));
+    MxRes& r = m->res[res_index];
+    hipStream_t st = m->stream;
+    const uint64_t nb = r.nbins;
+    if (r.d_w) { (void)hipFree(r.d_w); r.d_w = nullptr; }
+    r.balanced = false; r.bal_iter_ms = 0;
+    double *d_bias = nullptr, *d_m = nullptr, *d_part = nullptr;
+    BalState* d_state = nullptr;
+    auto cleanup = [&]() {
+        if (d_bias) (void)hipFree(d_bias);
+        if (d_m) (void)hipFree(d_m);
+        if (d_part) (void)hipFree(d_part);
+        if (d_state) (void)hipFree(d_state);
+        if (!r.balanced && r.d_w) { (void)hipFree(r.d_w); r.d_w = nullptr; }
+    };
+#define BRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "balance: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+    if (!r.bal.built) {
+        BRUN(hipEventRecord(m->ev0, st));
+        BRUN(bal_setup(r.bal, r.d_b1, r.d_b2, r.d_cnt, r.nnz, nb, r.B, st));
+        BRUN(hipEventRecord(m->ev1, st));
+        BRUN(hipEventSynchronize(m->ev1));
+        float ms = 0;
+        BRUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+        r.bal_setup_ms = ms;
+    } else r.bal_setup_ms = 0;
+    const size_t vbytes = (size_t)nb * 8 + 64;
+    BRUN(hipMalloc((void**)&d_bias, vbytes));
+    BRUN(hipMalloc((void**)&d_m, vbytes));
+    BRUN(hipMalloc((void**)&r.d_w, vbytes));
+    BRUN(hipMalloc((void**)&d_part, bal_partial_bytes(nb)));
+    BRUN(hipMalloc((void**)&d_state, sizeof(BalState)));
+    BRUN(hipMemsetAsync(d_state, 0, sizeof(BalState), st));
+
+    // steps 2 and 3 on the host, from one nbins-sized copy of the exact (integer-valued) marginals
+    std::vector<double> bias(nb, 1.0), hm(nb);
+    const uint32_t ig = (uint32_t)o.ignore_diags;
+    if (o.min_nnz > 0) {
+        BRUN(bal_marginal(r.bal, r.d_b2, r.d_cnt, nb, ig, true, nullptr, d_m, st));
+        BRUN(hipMemcpyAsync(hm.data(), d_m, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+        BRUN(hipStreamSynchronize(st));
+        for (uint64_t k = 0; k < nb; ++k) if (hm[k] < (double)o.min_nnz) bias[k] = 0.0;
+    }
+    BRUN(hipMemcpyAsync(d_bias, bias.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+    BRUN(bal_marginal(r.bal, r.d_b2, r.d_cnt, nb, ig, false, d_bias, d_m, st));
+    BRUN(hipMemcpyAsync(hm.data(), d_m, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    BRUN(hipStreamSynchronize(st));
+    if (o.min_count > 0.0)
+        for (uint64_t k = 0; k < nb; ++k) if (hm[k] < o.min_count) bias[k] = 0.0;
+    if (o.mad_max > 0.0) {
+        auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); const size_t n = v.size(); return n & 1 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0; };
+        std::vector<double> tmp;
+        const size_t nc = r.off.size();
+        for (size_t i = 0; i < nc; ++i) {
+            const uint64_t lo = r.off[i], hi = i + 1 < nc ? r.off[i + 1] : nb;
+            tmp.clear();
+            for (uint64_t k = lo; k < hi; ++k) if (hm[k] > 0.0) tmp.push_back(hm[k]);
+            if (tmp.empty()) continue;
+            const double med = median(tmp);
+            for (uint64_t k = lo; k < hi; ++k) hm[k] /= med;
+        }
+        tmp.clear();
+        for (uint64_t k = 0; k < nb; ++k) if (hm[k] > 0.0) tmp.push_back(std::log(hm[k]));
+        if (!tmp.empty()) {
+            const double med = median(tmp);
+            for (double& x : tmp) x = std::fabs(x - med);
+            const double dev = median(tmp), cut = std::exp(med - o.mad_max * dev);
+            for (uint64_t k = 0; k < nb; ++k) if (hm[k] < cut) bias[k] = 0.0;
+        }
+    }
+    uint64_t masked = 0;
+    for (uint64_t k = 0; k < nb; ++k) masked += bias[k] == 0.0;
+    BRUN(hipMemcpyAsync(d_bias, bias.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+
+    // step 4 on the device: a few iterations per look at the state (an iteration behind `done` is a no-op: five empty launches).
+    // $MKT_BALANCE_BATCH (1 .. 64) is there to measure other batch sizes (tools/balance_bench.py); the result does not depend on it.
+    BalState hs;
+    memset(&hs, 0, sizeof hs);
+    uint32_t per_look = 4;
+    if (const char* e = getenv("MKT_BALANCE_BATCH")) { const int v = atoi(e); if (v >= 1 && v <= 64) per_look = (uint32_t)v; }
+    BRUN(hipEventRecord(m->ev0, st));
+    for (uint32_t left = (uint32_t)o.max_iters; left && !hs.done;) {
+        const uint32_t batch = left < per_look ? left : per_look;
+        BRUN(bal_iterate(r.bal, r.d_b2, r.d_cnt, nb, ig, o.tol, batch, d_bias, d_m, d_part, d_state, st));
+        BRUN(hipMemcpyAsync(&hs, d_state, sizeof hs, hipMemcpyDeviceToHost, st));
+        BRUN(hipStreamSynchronize(st));
+        left -= batch;
+    }
+    BRUN(hipEventRecord(m->ev1, st));
+    BRUN(bal_weights(d_bias, nb, d_state, r.d_w, st));
+    BRUN(hipStreamSynchronize(st));
+    float ms = 0;
+    BRUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+#undef BRUN
+    r.bal_iter_ms = ms;
+    r.balanced = true;
+    cleanup();
+    if (stats) {
+        stats->iterations = hs.iters; stats->converged = hs.converged ? 1 : 0; stats->var = hs.var; stats->scale = hs.mean;
+        stats->masked = hs.empty ? nb : masked;
+    }
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_weights(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, double* out) {
+    if (!m || (n && !out)) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    const MxRes& r = m->res[res_index];
+    if (!m->ran || !r.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    if (first > r.nbins || n > r.nbins - first) return mfail(m, MKT_E_ARG, "weights [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nbins);
+    MCHK(m, hipSetDevice(m->device));
+    if (n) MCHK(m, hipMemcpy(out, r.d_w + first, n * 8, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+
+int mkt_matrix_balance_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* iter_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const MxRes& r = m->res[res_index];
+    if (setup_ms) *setup_ms = m->ran && r.balanced ? r.bal_setup_ms : 0.0;
+    if (iter_ms) *iter_ms = m->ran && r.balanced ? r.bal_iter_ms : 0.0;
     return MKT_OK;
 }
 

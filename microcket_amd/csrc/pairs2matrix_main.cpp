@@ -4,10 +4,15 @@
 // The work is mkt_matrix_* of libmkt_hip.so (include/mkt.h, where the binning is defined); this file only moves bytes.
 //
 //   pairs2matrix -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]        (no input file: stdin; $MKT_DEVICE: GPU ordinal)
+//                [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
 // (Pairs, Binned, Skipped, then nnz.<r> per resolution).
+// With --balance (iterative correction, mkt_matrix_balance of include/mkt.h) also per resolution <prefix>.<r>.weights.bed (the lines of
+// .bins.bed with a fourth column: the bin's weight as %.17g, nan for a masked bin) and <prefix>.balance.stat (per resolution
+// r, iterations, converged 0/1, var, scale, masked bins); a resolution that did not converge is a warning.  Without --balance nothing
+// of this is written and every other byte is the same.  A sub-option without --balance is a usage error, a malformed value exit 12.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -18,7 +23,8 @@
 #include "../../include/mkt.h"
 
 static int usage(const char* me) {
-    fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n", me);
+    fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n"
+                    "       [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -81,17 +87,54 @@ static bool write_file(const std::string& fn, const char* p, size_t n, const cha
     return (fclose(f) == 0) && ok;
 }
 
+// a whole non-negative decimal integer below 2^31 / a whole non-negative finite number
+static bool parse_int(const char* s, int32_t& out) {
+    if (!*s) return false;
+    uint64_t v = 0;
+    for (const char* p = s; *p; ++p) { if (*p < '0' || *p > '9' || p - s >= 10) return false; v = v * 10 + (uint64_t)(*p - '0'); }
+    if (v > 0x7FFFFFFFull) return false;
+    out = (int32_t)v;
+    return true;
+}
+static bool parse_num(const char* s, double& out) {
+    if (!*s || !((*s >= '0' && *s <= '9') || *s == '.')) return false;           // no sign, no inf / nan, no leading blank
+    for (const char* p = s; *p; ++p)                                              // plain decimal, with or without an exponent: no hexadecimal float
+        if (!((*p >= '0' && *p <= '9') || *p == '.' || *p == 'e' || *p == 'E' || ((*p == '+' || *p == '-') && (p[-1] == 'e' || p[-1] == 'E')))) return false;
+    char* end = nullptr;
+    errno = 0;
+    const double v = strtod(s, &end);
+    if (errno || *end || !(v >= 0.0) || v > 1.7976931348623157e308) return false;
+    out = v;
+    return true;
+}
+
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
+    bool balance = false;
+    const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
-        if (!strcmp(argv[i], "-g") && i + 1 < argc) table = argv[++i];
+        int b = -1;
+        for (int k = 0; k < 6; ++k) if (!strcmp(argv[i], bname[k])) b = k;
+        if (b >= 0) { if (i + 1 >= argc) return usage(argv[0]); bopt[b] = argv[++i]; }
+        else if (!strcmp(argv[i], "--balance")) balance = true;
+        else if (!strcmp(argv[i], "-g") && i + 1 < argc) table = argv[++i];
         else if (!strcmp(argv[i], "-r") && i + 1 < argc) rlist = argv[++i];
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) prefix = argv[++i];
         else if (argv[i][0] == '-' && argv[i][1] != '\0') return usage(argv[0]);
         else files.push_back(argv[i]);
     }
     if (!table || !rlist || !prefix) return usage(argv[0]);
+    mkt_balance_opts bo;
+    mkt_balance_opts_default(&bo);
+    for (int k = 0; k < 6; ++k) {
+        if (!bopt[k]) continue;
+        if (!balance) { fprintf(stderr, "Error: %s needs --balance\n", bname[k]); return usage(argv[0]); }
+        const bool ok = k == 0 ? parse_int(bopt[k], bo.ignore_diags) : k == 1 ? parse_int(bopt[k], bo.min_nnz) : k == 2 ? parse_num(bopt[k], bo.min_count)
+                      : k == 3 ? parse_num(bopt[k], bo.mad_max) : k == 4 ? parse_num(bopt[k], bo.tol) : (parse_int(bopt[k], bo.max_iters) && bo.max_iters >= 1);
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", bopt[k], bname[k], k == 5 ? "a whole number, at least 1" : k < 2 ? "a whole number, 0 or more" : "a number, 0 or more"); return 12; }
+    }
     std::string ttxt, why;
     if (!read_file(table, ttxt)) { fprintf(stderr, "Error: read chromosome table failed!\n"); return 10; }
     std::vector<Chrom> chroms;
@@ -134,6 +177,8 @@ int main(int argc, char* argv[]) {
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
 
     const std::string pre = prefix;
+    std::string bstat;
+    std::vector<double> weights;
     std::string stat = "Pairs\t" + std::to_string(pairs) + "\nBinned\t" + std::to_string(pairs - skipped) + "\nSkipped\t" + std::to_string(skipped) + "\n";
     for (uint32_t k = 0; k < res.size(); ++k) {
         uint64_t nbins = 0, nnz = 0, tb = 0;
@@ -148,19 +193,43 @@ int main(int argc, char* argv[]) {
             if (fwrite(buf.data(), 1, n, f) != n) { fclose(f); fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         }
         if (fclose(f) != 0) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
-        std::string bed;
+        if (balance) {
+            mkt_balance_stats bs;
+            if ((rc = mkt_matrix_balance(m, k, &bo, &bs)) != MKT_OK) return lib_fail("GPU matrix balance");
+            weights.resize(nbins);
+            if ((rc = mkt_matrix_fetch_weights(m, k, 0, nbins, weights.data())) != MKT_OK) return lib_fail("GPU matrix balance");
+            char line[160];
+            snprintf(line, sizeof line, "%u\t%u\t%d\t%.17g\t%.17g\t%llu\n", res[k], bs.iterations, bs.converged, bs.var, bs.scale, (unsigned long long)bs.masked);
+            bstat += line;
+            if (!bs.converged) fprintf(stderr, "WARN: balancing at resolution %u did not converge in %u iterations (var %g).\n", res[k], bs.iterations, bs.var);
+        }
+        std::string bed, wbed;
         const uint64_t r = res[k];
-        const char* mode = "wb";                                                  // the first piece truncates, the others append
+        const char *mode = "wb", *wmode = "wb";                                   // the first piece truncates, the others append
+        uint64_t bin = 0;
         for (const Chrom& c : chroms)
             for (uint64_t s = 0; s < c.len; s += r) {
+                const size_t at = bed.size();
                 bed += c.name; bed += '\t'; bed += std::to_string(s); bed += '\t'; bed += std::to_string(s + r < c.len ? s + r : c.len); bed += '\n';
+                if (balance) {
+                    char num[40];
+                    const double w = weights[bin++];
+                    if (w != w) strcpy(num, "nan"); else snprintf(num, sizeof num, "%.17g", w);
+                    wbed.append(bed, at, bed.size() - at - 1); wbed += '\t'; wbed += num; wbed += '\n';
+                    if (wbed.size() > ((size_t)32 << 20)) {
+                        if (!write_file(pre + "." + std::to_string(res[k]) + ".weights.bed", wbed.data(), wbed.size(), wmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+                        wbed.clear(); wmode = "ab";
+                    }
+                }
                 if (bed.size() > ((size_t)32 << 20)) {
                     if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
                     bed.clear(); mode = "ab";
                 }
             }
         if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        if (balance && !write_file(pre + "." + std::to_string(res[k]) + ".weights.bed", wbed.data(), wbed.size(), wmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
+    if (balance && !write_file(pre + ".balance.stat", bstat.data(), bstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (!write_file(pre + ".matrix.stat", stat.data(), stat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     mkt_matrix_destroy(m);
     return 0;
