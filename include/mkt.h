@@ -299,7 +299,8 @@ int mkt_group_count(mkt_ctx* ctx, uint64_t* groups);
 /* ---- pairs -> binned contact matrix at several resolutions (the driver's last stage, microcket:520-554) -------------------
  * What `juicer_tools pre -r ...` and `cooler cload pairix` spend their time on: the sparse binned matrix.  The containers they
  * write (.hic, .cool) and zoomify are out of scope; parity with those tools is unpinned.  Bin drop-in: bin/pairs2matrix.
- * Balancing (iterative correction) of each resolution's matrix is defined below, behind mkt_matrix_balance.
+ * Balancing (iterative correction) of each resolution's matrix is defined below, behind mkt_matrix_balance, and the expected
+ * (distance decay) tables and observed / expected values behind mkt_matrix_expected.
  *
  * Definition.  chromsizes: lines name<TAB>length (anno/<genome>.info; empty and '#' lines ignored); FILE ORDER IS BIN ORDER.
  * For a resolution r >= 1: chromosome i of length L_i owns n_i = ceil(L_i / r) bins, off_i = n_0 + .. + n_(i-1), nbins = sum n_i;
@@ -358,8 +359,9 @@ int mkt_matrix_timing(const mkt_matrix* m, uint32_t res_index, double* ms);
  *     m /= mean; m[m == 0] = 1; bias /= m; var < tol: converged, stop.
  *  5. weight = bias / sqrt(mean) with the last mean; bins with bias == 0 get NaN.  iterations = the last it, scale = the last mean,
  *     masked = the number of NaN weights.  The balanced value of a cell is count * weight[bin1] * weight[bin2].
- * Out of scope: cis_only / trans_only (per-chromosome loops), KR / VC vectors, the .cool / .hic containers, a text dump of balanced
- * values.
+ * Out of scope: cis_only / trans_only (per-chromosome loops), KR / VC vectors, the .cool / .hic containers.  What follows the
+ * weights (expected tables, balanced and observed / expected values of the cells) is defined below, behind mkt_matrix_expected; a
+ * per-cell TEXT dump of those values stays out of scope.
  *
  * Determinism: no floating-point atomics anywhere; every sum has a fixed shape that depends on (nbins, cells) only, so the weights
  * are the same bits from call to call, process to process and whatever route the pairs came by.  Against the numpy restatement
@@ -398,6 +400,67 @@ void mkt_balance_opts_default(mkt_balance_opts* o);
 int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts* opts, mkt_balance_stats* stats);
 int mkt_matrix_fetch_weights(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, double* out);
 int mkt_matrix_balance_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* iter_ms);
+
+/* ---- expected contacts: distance decay per chromosome and genome-wide, trans block means, observed / expected values ------------
+ * What `juicer_tools pre` keeps next to the counts (an expected-value vector per resolution) and what cooltools `expected-cis` /
+ * `expected-trans` compute.  The definition is this project's own, modelled on those; parity with cooltools and juicer is UNPINNED
+ * (neither is run anywhere here).  tests/expecteddef.py restates the definition in numpy.  All arithmetic is float64.
+ *
+ * Definition, for the cells (bin1 <= bin2, count) of one resolution, nbins, the chromosome ranges [off_c, off_c + n_c) and use_weights:
+ *  1. valid(k).  use_weights == 0: every bin is valid and w[k] = 1.  use_weights == 1: w = the weights of the last mkt_matrix_balance
+ *     of that resolution, valid(k) = w[k] is not NaN (without weights: MKT_E_STATE "balance first").
+ *  2. v = ((double)count * w[bin1]) * w[bin2]: two float64 multiplications in this order.  A cell is USED when both bins are valid.
+ *  3. CIS table, exactly nbins rows: row off_c + d is (chromosome c, diagonal d), 0 <= d < n_c.
+ *     n_valid = #{i in [off_c, off_c + n_c - d): valid(i) and valid(i + d)}; count_sum (uint64, exact) = sum of count over the used
+ *     cells with both bins in c and bin2 - bin1 == d; balanced_sum = the sum of v over the same cells.  No diagonal is left out:
+ *     consumers drop the first ignore_diags rows themselves.
+ *  4. TRANS table, one row per chromosome pair a < b in file order, row a * (2 * n_chr - a - 1) / 2 + (b - a - 1):
+ *     n_valid = nvalid_a * nvalid_b (valid bins of a times valid bins of b), count_sum and balanced_sum over the used cells of the
+ *     block, expected = balanced_sum / n_valid, NaN when n_valid == 0.
+ *  5. GENOME-WIDE table, one row per d in [0, max n_c): N[d], C[d], S[d] = the cis rows added over the chromosomes IN FILE ORDER
+ *     (done on the host); expected[d] = S[d] / N[d], NaN when N[d] == 0.
+ *  6. SMOOTHED expected, group edges in integers only: diagonal 0 is a group of its own; after it e_0 = 1,
+ *     e_(j+1) = e_j + max(1, e_j >> 3) (1 .. 8, 9, .., 16, 18, 20, 22, 24, 27, 30, 33, 37, ..), group j = [e_j, e_(j+1)) clipped to the
+ *     table.  expected_smooth[d] = (sum of S over d's group) / (sum of N over d's group), both sums in ascending d; NaN when the sum
+ *     of N is 0.
+ *  7. Per-cell VALUES in cell order: MKT_VALUE_BALANCED is v; MKT_VALUE_OE is v / expected[bin2 - bin1] for a cis cell and
+ *     v / expected(block) for a trans cell; MKT_VALUE_OE_SMOOTH the same with expected_smooth for cis cells.  A cell with a masked
+ *     bin is NaN.  A used cell's divisor is > 0 (its own v is in S), so a used cell is finite.
+ *
+ * Determinism: no floating-point atomics; every float64 sum has a shape fixed by (nbins, cells) only (a fixed number of lanes with a
+ * fixed stride and a fixed tree per segment, long segments in fixed chunks), so tables and values are the same bits from call to call,
+ * process to process and whatever route the pairs came by (add, add_device, add_keys).  Against the numpy restatement the integers
+ * and the NaN pattern are identical and the float sums agree to summation-order rounding.
+ *
+ *   mkt_expected_opts_default         use_weights 1
+ *   mkt_matrix_expected               valid after mkt_matrix_run (MKT_E_STATE before; with use_weights == 1 also before
+ *                                     mkt_matrix_balance of that resolution); opts NULL = the defaults; MKT_E_ARG with a message for a
+ *                                     bad index, use_weights other than 0 / 1 or a non-zero reserved.  info may be NULL.  The tables stay
+ *                                     resident (with a host mirror for the fetches) until the cells or the weights go away: a later
+ *                                     mkt_matrix_run, add or mkt_matrix_balance of that resolution discards them.
+ *   mkt_matrix_fetch_expected_cis / _trans / _genome   rows [first, first + n) of a table; any output pointer may be NULL.
+ *                                     MKT_E_STATE without tables, MKT_E_ARG with a message for a bad index or range.
+ *   mkt_matrix_fetch_values           values of cells [first, first + n) in the order of mkt_matrix_fetch.  OE and OE_SMOOTH need the
+ *                                     tables; BALANCED needs only the weights (it follows the tables' use_weights when there are tables:
+ *                                     with use_weights == 0 it is the count as a double).  MKT_E_ARG for a bad kind or range.
+ *   mkt_matrix_expected_timing        device time (ms, HIP events) of the last mkt_matrix_expected of res_index: the one-time grouping of
+ *                                     the cells by segment (12 bytes per cell, kept until the next run; 0 when it was reused) and the
+ *                                     sums (validity bits, n_valid, the segment sums).  A bad index is MKT_E_ARG without a message.
+ * Out of scope: a per-cell text dump, per-chromosome smoothing, the .hic / .cool containers.
+ * Limit: bits of (nbins + trans rows) + bits of the cell count <= 64 (MKT_E_CAPACITY with a message). */
+typedef struct mkt_expected_opts { int32_t use_weights; uint32_t reserved; /* 0 */ } mkt_expected_opts;
+typedef struct mkt_expected_info { uint64_t cis_rows, trans_rows, genome_rows; uint32_t n_chrom, smooth_groups; } mkt_expected_info;
+void mkt_expected_opts_default(mkt_expected_opts* o);
+int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_opts* opts, mkt_expected_info* info);
+int mkt_matrix_fetch_expected_cis(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum);
+int mkt_matrix_fetch_expected_trans(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum, double* expected);
+int mkt_matrix_fetch_expected_genome(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum, double* expected,
+                                     double* expected_smooth);
+#define MKT_VALUE_BALANCED 0
+#define MKT_VALUE_OE 1
+#define MKT_VALUE_OE_SMOOTH 2
+int mkt_matrix_fetch_values(mkt_matrix* m, uint32_t res_index, int kind, uint64_t first, uint64_t n, double* out);
+int mkt_matrix_expected_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sums_ms);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,8 @@ EXPORTS = [
     "mkt_matrix_create", "mkt_matrix_destroy", "mkt_matrix_error", "mkt_matrix_add", "mkt_matrix_add_device", "mkt_matrix_add_keys", "mkt_matrix_run",
     "mkt_matrix_info", "mkt_matrix_fetch", "mkt_matrix_fetch_text", "mkt_matrix_timing",
     "mkt_balance_opts_default", "mkt_matrix_balance", "mkt_matrix_fetch_weights", "mkt_matrix_balance_timing",
+    "mkt_expected_opts_default", "mkt_matrix_expected", "mkt_matrix_fetch_expected_cis", "mkt_matrix_fetch_expected_trans", "mkt_matrix_fetch_expected_genome",
+    "mkt_matrix_fetch_values", "mkt_matrix_expected_timing",
 ]
 
 
@@ -62,6 +64,22 @@ class _BalanceStatsC(C.Structure):
 
 
 BalanceStats = collections.namedtuple("BalanceStats", "iterations converged var scale masked")
+
+
+class ExpectedOpts(C.Structure):
+    """mkt_expected_opts of include/mkt.h"""
+    _fields_ = [("use_weights", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _ExpectedInfoC(C.Structure):
+    _fields_ = [("cis_rows", C.c_uint64), ("trans_rows", C.c_uint64), ("genome_rows", C.c_uint64), ("n_chrom", C.c_uint32), ("smooth_groups", C.c_uint32)]
+
+
+ExpectedCis = collections.namedtuple("ExpectedCis", "n_valid count_sum balanced_sum")
+ExpectedTrans = collections.namedtuple("ExpectedTrans", "n_valid count_sum balanced_sum expected")
+ExpectedGenome = collections.namedtuple("ExpectedGenome", "n_valid count_sum balanced_sum expected expected_smooth")
+Expected = collections.namedtuple("Expected", "cis trans genome n_chrom smooth_groups")
+VALUE_KINDS = {"balanced": 0, "oe": 1, "oe_smooth": 2}
 
 
 class Timing(C.Structure):
@@ -211,6 +229,14 @@ def load_library():
     L.mkt_matrix_balance.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(BalanceOpts), C.POINTER(_BalanceStatsC)]
     L.mkt_matrix_fetch_weights.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mkt_matrix_balance_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_expected_opts_default.argtypes = [C.POINTER(ExpectedOpts)]
+    L.mkt_expected_opts_default.restype = None
+    L.mkt_matrix_expected.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ExpectedOpts), C.POINTER(_ExpectedInfoC)]
+    L.mkt_matrix_fetch_expected_cis.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3
+    L.mkt_matrix_fetch_expected_trans.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 4
+    L.mkt_matrix_fetch_expected_genome.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
+    L.mkt_matrix_fetch_values.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_expected_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -627,6 +653,42 @@ class Matrix:
         """(setup ms, iteration loop ms) of the last balance(res): device time, HIP events"""
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_balance_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_balance_timing")
+        return a.value, b.value
+
+    def expected(self, res, use_weights=True):
+        """Expected-contact tables of resolution index res after run() (and balance(res) when use_weights): the definition is
+        mkt_matrix_expected in include/mkt.h.  Returns Expected(cis, trans, genome, n_chrom, smooth_groups), the three tables as
+        namedtuples of numpy arrays (n_valid and count_sum uint64, the others float64)."""
+        import numpy as np
+        o = ExpectedOpts()
+        self.L.mkt_expected_opts_default(C.byref(o))
+        o.use_weights = 1 if use_weights else 0
+        info = _ExpectedInfoC()
+        self._chk(self.L.mkt_matrix_expected(self.h, res, C.byref(o), C.byref(info)), "mkt_matrix_expected")
+
+        def table(fn, what, rows, cls):
+            cols = [np.zeros(rows, dtype=np.uint64 if k < 2 else np.float64) for k in range(len(cls._fields))]
+            self._chk(fn(self.h, res, 0, rows, *[a.ctypes.data_as(C.c_void_p) for a in cols]), what)
+            return cls(*cols)
+        return Expected(table(self.L.mkt_matrix_fetch_expected_cis, "mkt_matrix_fetch_expected_cis", info.cis_rows, ExpectedCis),
+                        table(self.L.mkt_matrix_fetch_expected_trans, "mkt_matrix_fetch_expected_trans", info.trans_rows, ExpectedTrans),
+                        table(self.L.mkt_matrix_fetch_expected_genome, "mkt_matrix_fetch_expected_genome", info.genome_rows, ExpectedGenome),
+                        info.n_chrom, info.smooth_groups)
+
+    def values(self, res, kind="balanced"):
+        """per-cell values in the order of cells(res): numpy float64[nnz]; kind "balanced" (count * w[bin1] * w[bin2]), "oe" or
+        "oe_smooth" (divided by the expected / smoothed expected of the last expected(res)); NaN for a cell with a masked bin"""
+        import numpy as np
+        if kind not in VALUE_KINDS:
+            raise ValueError(f"values: kind {kind!r} (one of {', '.join(VALUE_KINDS)})")
+        out = np.zeros(self.info(res)[1], dtype=np.float64)
+        self._chk(self.L.mkt_matrix_fetch_values(self.h, res, VALUE_KINDS[kind], 0, out.size, out.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_values")
+        return out
+
+    def expected_timing_ms(self, res):
+        """(setup ms, sums ms) of the last expected(res): device time, HIP events"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_expected_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_expected_timing")
         return a.value, b.value
 
     def close(self):

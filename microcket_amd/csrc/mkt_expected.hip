@@ -1,0 +1,358 @@
+// mkt_expected.hip -- expected-contact tables and observed / expected values of one resolution's binned contact matrix on the GPU;
+// include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_expected, mkt_matrix_fetch_*).
+//
+// A cell belongs to one SEGMENT: a cis cell of chromosome c on diagonal d to segment off_c + d (the row of the cis table), a trans
+// cell to segment nbins + its row of the trans table.  Once per resolution the cells are grouped by segment: the stable radix passes
+// of the duplicate marker over the segment bits of segment << Bc | cell index (Bc = bits of the cell count), a grouped copy of
+// (bin1, bin2, count), segment pointers by lower bound.  The sums then read 12 bytes per cell in order and gather w[] (nbins doubles,
+// meant to stay in cache).
+//
+// Nothing depends on the order anything ran in: there are no floating-point atomics.  A segment's sum is formed by a fixed number of
+// lanes (ExpSetup::width, from cells / segments) walking it with a fixed stride, and a fixed shuffle tree.  A segment of more than
+// kExpLong cells is cut into chunks of kExpChunk cells: one workgroup per chunk with the same shape one level up, then one workgroup
+// per segment over its chunks' partial sums in chunk order.  count_sum rides along as a uint64 (exact in any order).
+// n_valid of (chromosome, diagonal) is a popcount over the chromosome's validity bits: M & (M >> d), word by word.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <limits>
+
+#include "mkt_expected.h"
+#include "mkt_launch.h"
+
+namespace mkt {
+
+constexpr int EXWG = 256;
+typedef unsigned long long ex_u64;
+
+__global__ __launch_bounds__(EXWG) void k_ex_chr(const uint32_t* off, uint32_t nchr, uint64_t nbins, uint16_t* chr) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nbins) return;
+    uint32_t lo = 0, hi = nchr;                                          // first c with off[c] > k; off[0] == 0, so lo >= 1
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= k) lo = mid + 1; else hi = mid; }
+    chr[k] = (uint16_t)(lo - 1u);
+}
+__device__ inline uint64_t ex_trans_row(uint32_t a, uint32_t b, uint32_t nchr) { return (uint64_t)a * (2ull * nchr - a - 1ull) / 2ull + (b - a - 1u); }
+__device__ inline uint64_t ex_seg(uint32_t b1, uint32_t b2, const uint16_t* chr, const uint32_t* off, uint32_t nchr, uint64_t nbins) {
+    const uint32_t a = chr[b1], b = chr[b2];                             // bin1 <= bin2, so a <= b
+    return a == b ? (uint64_t)off[a] + (b2 - b1) : nbins + ex_trans_row(a, b, nchr);
+}
+__global__ __launch_bounds__(EXWG) void k_ex_keys(const uint32_t* b1, const uint32_t* b2, uint32_t nnz, const uint16_t* chr, const uint32_t* off, uint32_t nchr, uint64_t nbins,
+                                                  int Bc, uint64_t* key) {
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nnz) key[s] = (ex_seg(b1[s], b2[s], chr, off, nchr, nbins) << Bc) | s;
+}
+__global__ __launch_bounds__(EXWG) void k_ex_gather(const uint64_t* key, int Bc, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint32_t nnz,
+                                                    uint32_t* sb1, uint32_t* sb2, uint32_t* scnt) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nnz) return;
+    const uint32_t s = (uint32_t)(key[j] & ((1ull << Bc) - 1ull));
+    sb1[j] = b1[s]; sb2[j] = b2[s]; scnt[j] = cnt[s];
+}
+__global__ __launch_bounds__(EXWG) void k_ex_segptr(const uint64_t* key, int Bc, uint32_t nnz, uint64_t nseg, uint32_t* ptr) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > nseg) return;
+    uint32_t lo = 0, hi = nnz;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((key[mid] >> Bc) < k) lo = mid + 1; else hi = mid; }
+    ptr[k] = k == nseg ? nnz : lo;
+}
+
+// ---- validity bits, word-aligned per chromosome, and n_valid of every (chromosome, diagonal) --------------------------------
+__global__ __launch_bounds__(EXWG) void k_ex_mask(const double* w, uint64_t nbins, const uint16_t* chr, const uint32_t* off, const uint64_t* moff, ex_u64* mask) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nbins) return;
+    if (w) { const double x = w[k]; if (x != x) return; }
+    const uint32_t c = chr[k], i = (uint32_t)k - off[c];
+    atomicOr(&mask[moff[c] + (i >> 6)], 1ull << (i & 63u));            // an integer OR: the same word in any order
+}
+__global__ __launch_bounds__(EXWG) void k_ex_nvalid(const ex_u64* mask, uint64_t nbins, const uint16_t* chr, const uint32_t* off, const uint64_t* moff, ex_u64* nvalid) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nbins) return;
+    const uint32_t c = chr[k], d = (uint32_t)k - off[c];
+    const ex_u64* M = mask + moff[c];
+    const uint32_t words = (uint32_t)(moff[c + 1] - moff[c]), q = d >> 6, r = d & 63u;
+    ex_u64 acc = 0, lo = M[q];                                           // d < n_c, so q < words; bits past n_c are 0: i < n_c - d needs no test
+    for (uint32_t j = 0; j + q < words; ++j) {
+        const ex_u64 hi = j + q + 1u < words ? M[j + q + 1u] : 0ull;
+        const ex_u64 sh = r ? (lo >> r) | (hi << (64u - r)) : lo;      // bits [64 j + d, 64 j + d + 64) of M
+        acc += (ex_u64)__popcll(M[j] & sh);
+        lo = hi;
+    }
+    nvalid[k] = acc;
+}
+
+// ---- the sums ---------------------------------------------------------------------------------------------------------------
+// lane `l` of `W` walks elements p0 + l, p0 + l + W, ... of the grouped copy
+template <bool UNIT>
+__device__ inline void ex_walk(uint32_t l, uint32_t W, uint32_t p0, uint32_t p1, const uint32_t* sb1, const uint32_t* sb2, const uint32_t* scnt, const double* w, double& s, ex_u64& c) {
+    for (uint32_t j = p0 + l; j < p1; j += W) {
+        const uint32_t n = scnt[j];
+        if (UNIT) { s = __dadd_rn(s, (double)n); c += n; }
+        else {
+            const double wa = w[sb1[j]], wb = w[sb2[j]];
+            if (wa == wa && wb == wb) { s = __dadd_rn(s, __dmul_rn(__dmul_rn((double)n, wa), wb)); c += n; }    // v is rounded before it is added: no fused multiply-add
+        }
+    }
+}
+// W lanes per segment (W = 8 .. 64, a power of two): the tree adds lane l + d to lane l for d = W / 2 .. 1
+template <bool UNIT, int W>
+__global__ __launch_bounds__(EXWG) void k_ex_sums(const uint32_t* segptr, const uint32_t* sb1, const uint32_t* sb2, const uint32_t* scnt, uint64_t nseg, const double* w, double* S, ex_u64* C) {
+    const uint64_t g = ((uint64_t)blockIdx.x * EXWG + threadIdx.x) / W;
+    const uint32_t l = threadIdx.x & (W - 1);
+    double s = 0.0;
+    ex_u64 c = 0;
+    bool mine = false;
+    if (g < nseg) {
+        const uint32_t p0 = segptr[g], p1 = segptr[g + 1];
+        mine = p1 - p0 <= kExpLong;
+        if (mine) ex_walk<UNIT>(l, W, p0, p1, sb1, sb2, scnt, w, s, c);
+    }
+#pragma unroll
+    for (int d = W / 2; d >= 1; d >>= 1) { s = __dadd_rn(s, __shfl_down(s, d, W)); c += __shfl_down(c, d, W); }
+    if (mine && l == 0) { S[g] = s; C[g] = c; }
+}
+// a workgroup's sums: lane tree, then the four wave sums in wave order; valid in thread 0
+__device__ inline void ex_wgsum(double& s, ex_u64& c, double* shs, ex_u64* shc /* [EXWG / 64] each */) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { s = __dadd_rn(s, __shfl_down(s, d, 64)); c += __shfl_down(c, d, 64); }
+    if ((threadIdx.x & 63) == 0) { shs[threadIdx.x >> 6] = s; shc[threadIdx.x >> 6] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s = __dadd_rn(__dadd_rn(__dadd_rn(shs[0], shs[1]), shs[2]), shs[3]);
+        c = shc[0] + shc[1] + shc[2] + shc[3];
+    }
+}
+// one workgroup per chunk of a long segment: the same walk with 256 lanes
+template <bool UNIT>
+__global__ __launch_bounds__(EXWG) void k_ex_chunk(const uint2* ltask, const uint32_t* sb1, const uint32_t* sb2, const uint32_t* scnt, const double* w, double* ps, ex_u64* pc) {
+    __shared__ double shs[EXWG / 64];
+    __shared__ ex_u64 shc[EXWG / 64];
+    const uint2 t = ltask[blockIdx.x];
+    double s = 0.0;
+    ex_u64 c = 0;
+    ex_walk<UNIT>(threadIdx.x, EXWG, t.x, t.y, sb1, sb2, scnt, w, s, c);
+    ex_wgsum(s, c, shs, shc);
+    if (threadIdx.x == 0) { ps[blockIdx.x] = s; pc[blockIdx.x] = c; }
+}
+// one workgroup per long segment: its chunks' partial sums, lane l taking chunks l, l + 256, ..., the same tree
+__global__ __launch_bounds__(EXWG) void k_ex_long(const uint64_t* lseg, const double* ps, const ex_u64* pc, double* S, ex_u64* C) {
+    __shared__ double shs[EXWG / 64];
+    __shared__ ex_u64 shc[EXWG / 64];
+    const uint64_t g = lseg[3 * (uint64_t)blockIdx.x], t0 = lseg[3 * (uint64_t)blockIdx.x + 1], nt = lseg[3 * (uint64_t)blockIdx.x + 2];
+    double s = 0.0;
+    ex_u64 c = 0;
+    for (uint64_t t = threadIdx.x; t < nt; t += EXWG) { s = __dadd_rn(s, ps[t0 + t]); c += pc[t0 + t]; }
+    ex_wgsum(s, c, shs, shc);
+    if (threadIdx.x == 0) { S[g] = s; C[g] = c; }
+}
+
+// ---- per-cell values, in cell order -------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(EXWG) void k_ex_values(const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t first, uint64_t n, const double* w, int kind,
+                                                    const uint16_t* chr, const uint32_t* off, uint32_t nchr, const double* cis_div, const double* tr_div, double* out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = b1[first + i], y = b2[first + i];
+    const double wa = w ? w[x] : 1.0, wb = w ? w[y] : 1.0;
+    double v = __longlong_as_double(0x7FF8000000000000ll);               // a cell with a masked bin
+    if (wa == wa && wb == wb) {
+        v = __dmul_rn(__dmul_rn((double)cnt[first + i], wa), wb);
+        if (kind != 0) {
+            const uint32_t a = chr[x], b = chr[y];
+            v = v / (a == b ? cis_div[y - x] : tr_div[ex_trans_row(a, b, nchr)]);
+        }
+    }
+    out[i] = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+void exp_free(ExpSetup& s) {
+    void* p[] = {s.chr, s.sb1, s.sb2, s.scnt, s.segptr, s.ltask, s.lseg, s.moff};
+    for (void* q : p) if (q) (void)hipFree(q);
+    s = ExpSetup();
+}
+void exp_free_tables(ExpTables& t) {
+    void* p[] = {t.d_n, t.d_c, t.d_s, t.d_mask, t.d_part, t.d_cis_e, t.d_cis_sm, t.d_tr_e};
+    for (void* q : p) if (q) (void)hipFree(q);
+    t = ExpTables();
+}
+
+hipError_t exp_setup(ExpSetup& s, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t nnz, uint64_t nbins, const uint32_t* d_off,
+                     const std::vector<uint32_t>& off, hipStream_t st) {
+    exp_free(s);
+    const uint32_t nchr = (uint32_t)off.size();
+    if (nnz >= (1ull << 32) || nbins >= (1ull << 32) || nchr == 0 || nchr > 8192u) return hipErrorInvalidValue;
+    s.trans_rows = (uint64_t)nchr * (nchr - 1ull) / 2ull;
+    s.nseg = nbins + s.trans_rows;
+    int Bc = 0, Bs = 0;
+    while ((1ull << Bc) < nnz) ++Bc;                                     // a cell index fits Bc bits, a segment id Bs
+    while ((1ull << Bs) < s.nseg) ++Bs;
+    if (Bc + Bs > 64) return hipErrorInvalidValue;
+    std::vector<uint64_t> moff(nchr + 1, 0);
+    for (uint32_t c = 0; c < nchr; ++c) {
+        const uint64_t n_c = (c + 1 < nchr ? off[c + 1] : nbins) - off[c];
+        moff[c + 1] = moff[c] + (n_c + 63) / 64;
+        if (n_c > s.genome_rows) s.genome_rows = n_c;
+    }
+    s.mwords = moff[nchr];
+    hipError_t e;
+    uint64_t *kA = nullptr, *kB = nullptr;
+    uint32_t* d_radix = nullptr;
+    auto done = [&](hipError_t r) {
+        if (kA) (void)hipFree(kA);
+        if (kB) (void)hipFree(kB);
+        if (d_radix) (void)hipFree(d_radix);
+        if (r != hipSuccess) exp_free(s);
+        return r;
+    };
+    const size_t cbytes = (size_t)nnz * 4 + 64, pbytes = (size_t)(s.nseg + 1) * 4;
+    if ((e = hipMalloc((void**)&s.chr, (size_t)nbins * 2 + 64)) != hipSuccess) return done(e);
+    if ((e = hipMalloc((void**)&s.moff, (size_t)(nchr + 1) * 8)) != hipSuccess) return done(e);
+    if ((e = hipMalloc((void**)&s.sb1, cbytes)) != hipSuccess) return done(e);
+    if ((e = hipMalloc((void**)&s.sb2, cbytes)) != hipSuccess) return done(e);
+    if ((e = hipMalloc((void**)&s.scnt, cbytes)) != hipSuccess) return done(e);
+    if ((e = hipMalloc((void**)&s.segptr, pbytes)) != hipSuccess) return done(e);
+    if ((e = hipMemcpyAsync(s.moff, moff.data(), (size_t)(nchr + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return done(e);
+    if (nbins) hipLaunchKernelGGL(k_ex_chr, dim3((unsigned)((nbins + EXWG - 1) / EXWG)), dim3(EXWG), 0, st, d_off, nchr, nbins, s.chr);
+    if (nnz == 0) {
+        if ((e = hipMemsetAsync(s.segptr, 0, pbytes, st)) != hipSuccess) return done(e);
+    } else {
+        const unsigned cgrid = (unsigned)((nnz + EXWG - 1) / EXWG), pgrid = (unsigned)((s.nseg + 1 + EXWG - 1) / EXWG);
+        if ((e = hipMalloc((void**)&kA, (size_t)nnz * 8 + 64)) != hipSuccess) return done(e);
+        if ((e = hipMalloc((void**)&kB, (size_t)nnz * 8 + 64)) != hipSuccess) return done(e);
+        if ((e = hipMalloc((void**)&d_radix, radix64_count_bytes(nnz))) != hipSuccess) return done(e);
+        hipLaunchKernelGGL(k_ex_keys, dim3(cgrid), dim3(EXWG), 0, st, b1, b2, (uint32_t)nnz, (const uint16_t*)s.chr, d_off, nchr, nbins, Bc, kA);
+        if ((e = launch_radix64(kA, kB, nnz, Bc, Bs, d_radix, st)) != hipSuccess) return done(e);           // stable: (segment, cell index) order
+        hipLaunchKernelGGL(k_ex_gather, dim3(cgrid), dim3(EXWG), 0, st, (const uint64_t*)kA, Bc, b1, b2, cnt, (uint32_t)nnz, s.sb1, s.sb2, s.scnt);
+        hipLaunchKernelGGL(k_ex_segptr, dim3(pgrid), dim3(EXWG), 0, st, (const uint64_t*)kA, Bc, (uint32_t)nnz, s.nseg, s.segptr);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return done(e);
+    // the long segments and their chunks, from the pointers (once per resolution)
+    std::vector<uint32_t> sp(s.nseg + 1);
+    if ((e = hipMemcpyAsync(sp.data(), s.segptr, pbytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return done(e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return done(e);
+    std::vector<uint2> tasks;
+    std::vector<uint64_t> ls;
+    for (uint64_t g = 0; g < s.nseg; ++g) {
+        const uint32_t p0 = sp[g], p1 = sp[g + 1];
+        if (p1 - p0 <= kExpLong) continue;
+        ls.push_back(g); ls.push_back(tasks.size()); ls.push_back(((uint64_t)(p1 - p0) + kExpChunk - 1) / kExpChunk);
+        for (uint64_t p = p0; p < p1; p += kExpChunk) tasks.push_back(make_uint2((uint32_t)p, (uint32_t)(p + kExpChunk < p1 ? p + kExpChunk : p1)));
+    }
+    s.nlong = (uint32_t)(ls.size() / 3);
+    s.ntask = (uint32_t)tasks.size();
+    if (s.nlong) {
+        if ((e = hipMalloc((void**)&s.ltask, tasks.size() * sizeof(uint2))) != hipSuccess) return done(e);
+        if ((e = hipMalloc((void**)&s.lseg, ls.size() * 8)) != hipSuccess) return done(e);
+        if ((e = hipMemcpy(s.ltask, tasks.data(), tasks.size() * sizeof(uint2), hipMemcpyHostToDevice)) != hipSuccess) return done(e);
+        if ((e = hipMemcpy(s.lseg, ls.data(), ls.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return done(e);
+    }
+    const uint64_t avg = s.nseg ? nnz / s.nseg : 0;                      // cells a segment holds on average
+    s.width = avg >= 48 ? 64 : avg >= 24 ? 32 : avg >= 12 ? 16 : 8;
+    s.built = true;
+    return done(hipSuccess);
+}
+
+template <bool UNIT>
+static hipError_t ex_launch_sums(const ExpSetup& s, ExpTables& t, const double* w, hipStream_t st) {
+    if (s.nseg == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((s.nseg * (uint64_t)s.width + EXWG - 1) / EXWG);
+    ex_u64* C = (ex_u64*)t.d_c;
+#define EX_SUMS(W) hipLaunchKernelGGL((k_ex_sums<UNIT, W>), dim3(grid), dim3(EXWG), 0, st, (const uint32_t*)s.segptr, (const uint32_t*)s.sb1, (const uint32_t*)s.sb2, (const uint32_t*)s.scnt, s.nseg, w, t.d_s, C)
+    switch (s.width) {
+        case 64: EX_SUMS(64); break;
+        case 32: EX_SUMS(32); break;
+        case 16: EX_SUMS(16); break;
+        default: EX_SUMS(8); break;
+    }
+#undef EX_SUMS
+    if (s.nlong) {
+        ex_u64* pc = (ex_u64*)(t.d_part + s.ntask);
+        hipLaunchKernelGGL((k_ex_chunk<UNIT>), dim3(s.ntask), dim3(EXWG), 0, st, (const uint2*)s.ltask, (const uint32_t*)s.sb1, (const uint32_t*)s.sb2, (const uint32_t*)s.scnt, w, t.d_part, pc);
+        hipLaunchKernelGGL(k_ex_long, dim3(s.nlong), dim3(EXWG), 0, st, (const uint64_t*)s.lseg, (const double*)t.d_part, (const ex_u64*)pc, t.d_s, C);
+    }
+    return hipGetLastError();
+}
+
+hipError_t exp_sums(const ExpSetup& s, ExpTables& t, uint64_t nbins, const uint32_t* d_off, const double* w, hipStream_t st) {
+    exp_free_tables(t);
+    hipError_t e;
+    if ((e = hipMalloc((void**)&t.d_n, (size_t)nbins * 8 + 64)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&t.d_c, (size_t)s.nseg * 8 + 64)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&t.d_s, (size_t)s.nseg * 8 + 64)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&t.d_mask, (size_t)s.mwords * 8 + 64)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&t.d_part, (size_t)s.ntask * 16 + 64)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(t.d_mask, 0, (size_t)s.mwords * 8 + 64, st)) != hipSuccess) return e;
+    if (nbins) {
+        const unsigned bgrid = (unsigned)((nbins + EXWG - 1) / EXWG);
+        hipLaunchKernelGGL(k_ex_mask, dim3(bgrid), dim3(EXWG), 0, st, w, nbins, (const uint16_t*)s.chr, d_off, (const uint64_t*)s.moff, (ex_u64*)t.d_mask);
+        hipLaunchKernelGGL(k_ex_nvalid, dim3(bgrid), dim3(EXWG), 0, st, (const ex_u64*)t.d_mask, nbins, (const uint16_t*)s.chr, d_off, (const uint64_t*)s.moff, (ex_u64*)t.d_n);
+    }
+    return w ? ex_launch_sums<false>(s, t, w, st) : ex_launch_sums<true>(s, t, w, st);
+}
+
+hipError_t exp_finish(const ExpSetup& s, ExpTables& t, uint64_t nbins, const std::vector<uint32_t>& off, hipStream_t st) {
+    const uint32_t nchr = (uint32_t)off.size();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    hipError_t e;
+    std::vector<uint64_t> c(s.nseg);
+    std::vector<double> sm(s.nseg);
+    t.cis_n.assign(nbins, 0);
+    if (nbins && (e = hipMemcpyAsync(t.cis_n.data(), t.d_n, (size_t)nbins * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if (s.nseg && (e = hipMemcpyAsync(c.data(), t.d_c, (size_t)s.nseg * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if (s.nseg && (e = hipMemcpyAsync(sm.data(), t.d_s, (size_t)s.nseg * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    t.cis_c.assign(c.begin(), c.begin() + nbins);
+    t.cis_s.assign(sm.begin(), sm.begin() + nbins);
+    t.tr_c.assign(c.begin() + nbins, c.end());
+    t.tr_s.assign(sm.begin() + nbins, sm.end());
+    auto n_of = [&](uint32_t k) { return (uint64_t)(k + 1 < nchr ? off[k + 1] : nbins) - off[k]; };
+    // trans: n_valid = valid bins of a x valid bins of b (diagonal 0 of the cis table), rows in (a, b) order
+    t.tr_n.assign(s.trans_rows, 0);
+    t.tr_e.assign(s.trans_rows, nan);
+    uint64_t row = 0;
+    for (uint32_t a = 0; a < nchr; ++a) {
+        const uint64_t va = n_of(a) ? t.cis_n[off[a]] : 0;
+        for (uint32_t b = a + 1; b < nchr; ++b, ++row) {
+            const uint64_t n = va * (n_of(b) ? t.cis_n[off[b]] : 0);
+            t.tr_n[row] = n;
+            if (n) t.tr_e[row] = t.tr_s[row] / (double)n;
+        }
+    }
+    // genome-wide: the cis rows added over the chromosomes in file order
+    const uint64_t G = s.genome_rows;
+    t.g_n.assign(G, 0); t.g_c.assign(G, 0); t.g_s.assign(G, 0.0); t.g_e.assign(G, nan); t.g_sm.assign(G, nan);
+    for (uint32_t k = 0; k < nchr; ++k)
+        for (uint64_t d = 0, n = n_of(k); d < n; ++d) { t.g_n[d] += t.cis_n[off[k] + d]; t.g_c[d] += t.cis_c[off[k] + d]; t.g_s[d] += t.cis_s[off[k] + d]; }
+    for (uint64_t d = 0; d < G; ++d) if (t.g_n[d]) t.g_e[d] = t.g_s[d] / (double)t.g_n[d];
+    // smoothed: diagonal 0 alone, then groups [e, e + max(1, e >> 3)), both sums in ascending d
+    t.smooth_groups = 0;
+    for (uint64_t a = 0, b = 1; a < G;) {
+        const uint64_t end = b < G ? b : G;
+        double ss = 0.0;
+        uint64_t nn = 0;
+        for (uint64_t d = a; d < end; ++d) { ss += t.g_s[d]; nn += t.g_n[d]; }
+        if (nn) for (uint64_t d = a; d < end; ++d) t.g_sm[d] = ss / (double)nn;
+        ++t.smooth_groups;
+        a = b;
+        b = a + ((a >> 3) > 1 ? (a >> 3) : 1);
+    }
+    if ((e = hipMalloc((void**)&t.d_cis_e, (size_t)G * 8 + 64)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&t.d_cis_sm, (size_t)G * 8 + 64)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&t.d_tr_e, (size_t)s.trans_rows * 8 + 64)) != hipSuccess) return e;
+    if (G && (e = hipMemcpy(t.d_cis_e, t.g_e.data(), (size_t)G * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    if (G && (e = hipMemcpy(t.d_cis_sm, t.g_sm.data(), (size_t)G * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    if (s.trans_rows && (e = hipMemcpy(t.d_tr_e, t.tr_e.data(), (size_t)s.trans_rows * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    t.built = true;
+    return hipSuccess;
+}
+
+hipError_t exp_values(const ExpSetup* s, const ExpTables* t, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t first, uint64_t n,
+                      const uint32_t* d_off, uint32_t nchr, const double* w, int kind, double* out, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (kind != 0 && (!s || !t)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ex_values, dim3((unsigned)((n + EXWG - 1) / EXWG)), dim3(EXWG), 0, st, b1, b2, cnt, first, n, w, kind, s ? (const uint16_t*)s->chr : nullptr, d_off, nchr,
+                       t ? (const double*)(kind == 2 ? t->d_cis_sm : t->d_cis_e) : nullptr, t ? (const double*)t->d_tr_e : nullptr, out);
+    return hipGetLastError();
+}
+
+}  // namespace mkt

@@ -25,6 +25,7 @@
 
 #include "../../include/mkt.h"
 #include "mkt_balance.h"
+#include "mkt_expected.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
 
@@ -279,6 +280,10 @@ struct MxRes {
     double* d_w = nullptr;
     bool balanced = false;
     double bal_setup_ms = 0, bal_iter_ms = 0;
+    // expected tables (mkt_matrix_expected): the grouping lives as long as the cells, the tables until the next balance or run
+    ExpSetup exs;
+    ExpTables ext;
+    double exp_setup_ms = 0, exp_sums_ms = 0;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -350,6 +355,9 @@ static void mx_free_results(mkt_matrix* m) {
         bal_free(r.bal);
         if (r.d_w) (void)hipFree(r.d_w);
         r.d_w = nullptr; r.balanced = false; r.bal_setup_ms = r.bal_iter_ms = 0;
+        exp_free(r.exs);
+        exp_free_tables(r.ext);
+        r.exp_setup_ms = r.exp_sums_ms = 0;
     }
     m->ran = false;
 }
@@ -695,6 +703,7 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     const uint64_t nb = r.nbins;
     if (r.d_w) { (void)hipFree(r.d_w); r.d_w = nullptr; }
     r.balanced = false; r.bal_iter_ms = 0;
+    exp_free_tables(r.ext);                                             // tables of other weights
     double *d_bias = nullptr, *d_m = nullptr, *d_part = nullptr;
     BalState* d_state = nullptr;
     auto cleanup = [&]() {
@@ -808,6 +817,132 @@ int mkt_matrix_balance_timing(const mkt_matrix* m, uint32_t res_index, double* s
     const MxRes& r = m->res[res_index];
     if (setup_ms) *setup_ms = m->ran && r.balanced ? r.bal_setup_ms : 0.0;
     if (iter_ms) *iter_ms = m->ran && r.balanced ? r.bal_iter_ms : 0.0;
+    return MKT_OK;
+}
+
+// ---- expected tables and observed / expected values: the entry points; the kernels are mkt_expected.hip, the definition is in include/mkt.h
+void mkt_expected_opts_default(mkt_expected_opts* o) {
+    if (!o) return;
+    o->use_weights = 1; o->reserved = 0;
+}
+
+int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_opts* opts, mkt_expected_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    mkt_expected_opts o;
+    mkt_expected_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.use_weights != 0 && o.use_weights != 1) return mfail(m, MKT_E_ARG, "expected: use_weights %d (0 or 1)", o.use_weights);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "expected: the reserved field is not 0");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "expected before run");
+    MxRes& r = m->res[res_index];
+    if (o.use_weights && !r.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    if (r.nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "expected: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)r.nnz);
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    exp_free_tables(r.ext);
+    r.exp_sums_ms = 0;
+#define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { exp_free_tables(r.ext); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "expected: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+    float ms = 0;
+    if (!r.exs.built) {
+        ERUN(hipEventRecord(m->ev0, st));
+        const hipError_t e = exp_setup(r.exs, r.d_b1, r.d_b2, r.d_cnt, r.nnz, r.nbins, r.d_off, r.off, st);
+        if (e == hipErrorInvalidValue) return mfail(m, MKT_E_CAPACITY, "expected: segment ids and cell indices of resolution index %u do not fit 64 bits together", res_index);
+        ERUN(e);
+        ERUN(hipEventRecord(m->ev1, st));
+        ERUN(hipEventSynchronize(m->ev1));
+        ERUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+        r.exp_setup_ms = ms;
+    } else r.exp_setup_ms = 0;
+    ERUN(hipEventRecord(m->ev0, st));
+    ERUN(exp_sums(r.exs, r.ext, r.nbins, r.d_off, o.use_weights ? r.d_w : nullptr, st));
+    ERUN(hipEventRecord(m->ev1, st));
+    ERUN(exp_finish(r.exs, r.ext, r.nbins, r.off, st));
+    ERUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+#undef ERUN
+    r.exp_sums_ms = ms;
+    r.ext.use_weights = o.use_weights;
+    if (info) {
+        info->cis_rows = r.nbins; info->trans_rows = r.exs.trans_rows; info->genome_rows = r.exs.genome_rows;
+        info->n_chrom = (uint32_t)r.off.size(); info->smooth_groups = r.ext.smooth_groups;
+    }
+    return MKT_OK;
+}
+
+}  // extern "C"
+
+// the tables of res_index for a fetch of rows [first, first + n) of table `which` (0 cis, 1 trans, 2 genome), or the error
+static int mx_expected_tables(mkt_matrix* m, uint32_t res_index, const char* what, uint64_t first, uint64_t n, int which, const ExpTables** out) {
+    if (!m) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    const MxRes& r = m->res[res_index];
+    if (!m->ran || !r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    const uint64_t rows = which == 0 ? r.nbins : which == 1 ? r.exs.trans_rows : r.exs.genome_rows;
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "%s rows [%llu, +%llu) of %llu", what, (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    *out = &r.ext;
+    return MKT_OK;
+}
+template <typename T>
+static void mx_copy_rows(T* out, const std::vector<T>& v, uint64_t first, uint64_t n) { if (out && n) memcpy(out, v.data() + first, (size_t)n * sizeof(T)); }
+
+extern "C" {
+
+int mkt_matrix_fetch_expected_cis(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum) {
+    const ExpTables* t = nullptr;
+    const int rc = mx_expected_tables(m, res_index, "cis", first, n, 0, &t);
+    if (rc) return rc;
+    mx_copy_rows(n_valid, t->cis_n, first, n); mx_copy_rows(count_sum, t->cis_c, first, n); mx_copy_rows(balanced_sum, t->cis_s, first, n);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_expected_trans(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum, double* expected) {
+    const ExpTables* t = nullptr;
+    const int rc = mx_expected_tables(m, res_index, "trans", first, n, 1, &t);
+    if (rc) return rc;
+    mx_copy_rows(n_valid, t->tr_n, first, n); mx_copy_rows(count_sum, t->tr_c, first, n); mx_copy_rows(balanced_sum, t->tr_s, first, n); mx_copy_rows(expected, t->tr_e, first, n);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_expected_genome(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum, double* expected,
+                                     double* expected_smooth) {
+    const ExpTables* t = nullptr;
+    const int rc = mx_expected_tables(m, res_index, "genome", first, n, 2, &t);
+    if (rc) return rc;
+    mx_copy_rows(n_valid, t->g_n, first, n); mx_copy_rows(count_sum, t->g_c, first, n); mx_copy_rows(balanced_sum, t->g_s, first, n);
+    mx_copy_rows(expected, t->g_e, first, n); mx_copy_rows(expected_smooth, t->g_sm, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_values(mkt_matrix* m, uint32_t res_index, int kind, uint64_t first, uint64_t n, double* out) {
+    if (!m) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    if (kind != MKT_VALUE_BALANCED && kind != MKT_VALUE_OE && kind != MKT_VALUE_OE_SMOOTH) return mfail(m, MKT_E_ARG, "values: kind %d (0 balanced, 1 oe, 2 oe_smooth)", kind);
+    const MxRes& r = m->res[res_index];
+    if (!m->ran) return mfail(m, MKT_E_STATE, "values before run");
+    if (kind != MKT_VALUE_BALANCED && !r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    if (!r.ext.built && !r.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    if (first > r.nnz || n > r.nnz - first) return mfail(m, MKT_E_ARG, "values of cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nnz);
+    if (!out || n == 0) return MKT_OK;
+    MCHK(m, hipSetDevice(m->device));
+    const double* w = r.ext.built && !r.ext.use_weights ? nullptr : r.d_w;       // the tables' own option; without tables, the weights
+    const uint64_t piece = n < (1ull << 24) ? n : (1ull << 24);
+    double* d_out = nullptr;
+    { hipError_t e_ = hipMalloc((void**)&d_out, (size_t)piece * 8); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "values: hipMalloc of %llu doubles failed: %s", (unsigned long long)piece, hipGetErrorString(e_)); }
+    for (uint64_t at = 0; at < n; at += piece) {
+        const uint64_t k = n - at < piece ? n - at : piece;
+        hipError_t e = exp_values(r.ext.built ? &r.exs : nullptr, r.ext.built ? &r.ext : nullptr, r.d_b1, r.d_b2, r.d_cnt, first + at, k, r.d_off, (uint32_t)r.off.size(), w, kind, d_out, m->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + at, d_out, (size_t)k * 8, hipMemcpyDeviceToHost, m->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+        if (e != hipSuccess) { (void)hipFree(d_out); return mfail(m, MKT_E_HIP, "values: cells [%llu, +%llu) failed: %s", (unsigned long long)(first + at), (unsigned long long)k, hipGetErrorString(e)); }
+    }
+    (void)hipFree(d_out);
+    return MKT_OK;
+}
+
+int mkt_matrix_expected_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sums_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const MxRes& r = m->res[res_index];
+    if (setup_ms) *setup_ms = m->ran && r.ext.built ? r.exp_setup_ms : 0.0;
+    if (sums_ms) *sums_ms = m->ran && r.ext.built ? r.exp_sums_ms : 0.0;
     return MKT_OK;
 }
 

@@ -4,7 +4,7 @@
 // The work is mkt_matrix_* of libmkt_hip.so (include/mkt.h, where the binning is defined); this file only moves bytes.
 //
 //   pairs2matrix -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]        (no input file: stdin; $MKT_DEVICE: GPU ordinal)
-//                [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]]
+//                [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -13,6 +13,13 @@
 // .bins.bed with a fourth column: the bin's weight as %.17g, nan for a masked bin) and <prefix>.balance.stat (per resolution
 // r, iterations, converged 0/1, var, scale, masked bins); a resolution that did not converge is a warning.  Without --balance nothing
 // of this is written and every other byte is the same.  A sub-option without --balance is a usage error, a malformed value exit 12.
+// With --expected (mkt_matrix_expected of include/mkt.h; with --balance from the weights, without it raw: every bin valid, weight 1)
+// also per resolution, each with a header line, doubles as %.17g and nan for NaN:
+//   <prefix>.<r>.expected.tsv         diag, dist_bp = diag * r, n_valid, count_sum, balanced_sum, expected, expected_smooth (genome-wide)
+//   <prefix>.<r>.expected.chrom.tsv   chrom, diag, n_valid, count_sum, balanced_sum (every diagonal of every chromosome)
+//   <prefix>.<r>.expected.trans.tsv   chrom1, chrom2, n_valid, count_sum, balanced_sum, expected (every pair in table order)
+// Without --expected none of these appears and every other byte is the same.  A per-cell text dump of balanced or observed / expected
+// values is out of scope (mkt_matrix_fetch_values hands them back as arrays).
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -24,7 +31,7 @@
 
 static int usage(const char* me) {
     fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n"
-                    "       [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]]\n", me);
+                    "       [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -108,10 +115,16 @@ static bool parse_num(const char* s, double& out) {
     return true;
 }
 
+static void put_num(std::string& out, double x) {
+    char num[40];
+    if (x != x) strcpy(num, "nan"); else snprintf(num, sizeof num, "%.17g", x);
+    out += num;
+}
+
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
-    bool balance = false;
+    bool balance = false, expected = false;
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -119,6 +132,7 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 6; ++k) if (!strcmp(argv[i], bname[k])) b = k;
         if (b >= 0) { if (i + 1 >= argc) return usage(argv[0]); bopt[b] = argv[++i]; }
         else if (!strcmp(argv[i], "--balance")) balance = true;
+        else if (!strcmp(argv[i], "--expected")) expected = true;
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) table = argv[++i];
         else if (!strcmp(argv[i], "-r") && i + 1 < argc) rlist = argv[++i];
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) prefix = argv[++i];
@@ -202,6 +216,59 @@ int main(int argc, char* argv[]) {
             snprintf(line, sizeof line, "%u\t%u\t%d\t%.17g\t%.17g\t%llu\n", res[k], bs.iterations, bs.converged, bs.var, bs.scale, (unsigned long long)bs.masked);
             bstat += line;
             if (!bs.converged) fprintf(stderr, "WARN: balancing at resolution %u did not converge in %u iterations (var %g).\n", res[k], bs.iterations, bs.var);
+        }
+        if (expected) {
+            mkt_expected_opts eo;
+            mkt_expected_opts_default(&eo);
+            eo.use_weights = balance ? 1 : 0;
+            mkt_expected_info ei;
+            if ((rc = mkt_matrix_expected(m, k, &eo, &ei)) != MKT_OK) return lib_fail("GPU matrix expected");
+            const std::string base = pre + "." + std::to_string(res[k]) + ".expected";
+            std::vector<uint64_t> nv, cs;
+            std::vector<double> bs, ex, sm;
+            auto size = [&](uint64_t rows) { nv.resize(rows); cs.resize(rows); bs.resize(rows); ex.resize(rows); sm.resize(rows); };
+            auto flush = [&](const std::string& fn, std::string& t, const char*& md, bool last) {      // the first piece truncates, the others append
+                if (!last && t.size() <= ((size_t)32 << 20)) return true;
+                const bool ok = write_file(fn, t.data(), t.size(), md);
+                t.clear(); md = "ab";
+                return ok;
+            };
+            std::string t = "diag\tdist_bp\tn_valid\tcount_sum\tbalanced_sum\texpected\texpected_smooth\n";
+            const char* md = "wb";
+            bool ok = true;
+            size(ei.genome_rows);
+            if ((rc = mkt_matrix_fetch_expected_genome(m, k, 0, ei.genome_rows, nv.data(), cs.data(), bs.data(), ex.data(), sm.data())) != MKT_OK) return lib_fail("GPU matrix expected");
+            for (uint64_t d = 0; d < ei.genome_rows && ok; ++d) {
+                t += std::to_string(d); t += '\t'; t += std::to_string(d * res[k]); t += '\t'; t += std::to_string(nv[d]); t += '\t'; t += std::to_string(cs[d]); t += '\t';
+                put_num(t, bs[d]); t += '\t'; put_num(t, ex[d]); t += '\t'; put_num(t, sm[d]); t += '\n';
+                ok = flush(base + ".tsv", t, md, false);
+            }
+            ok = ok && flush(base + ".tsv", t, md, true);
+            t = "chrom\tdiag\tn_valid\tcount_sum\tbalanced_sum\n";
+            md = "wb";
+            size(ei.cis_rows);
+            if ((rc = mkt_matrix_fetch_expected_cis(m, k, 0, ei.cis_rows, nv.data(), cs.data(), bs.data())) != MKT_OK) return lib_fail("GPU matrix expected");
+            uint64_t row = 0;
+            for (const Chrom& c : chroms)
+                for (uint64_t d = 0, n = (c.len + res[k] - 1) / res[k]; d < n && ok; ++d, ++row) {
+                    t += c.name; t += '\t'; t += std::to_string(d); t += '\t'; t += std::to_string(nv[row]); t += '\t'; t += std::to_string(cs[row]); t += '\t';
+                    put_num(t, bs[row]); t += '\n';
+                    ok = flush(base + ".chrom.tsv", t, md, false);
+                }
+            ok = ok && flush(base + ".chrom.tsv", t, md, true);
+            t = "chrom1\tchrom2\tn_valid\tcount_sum\tbalanced_sum\texpected\n";
+            md = "wb";
+            size(ei.trans_rows);
+            if ((rc = mkt_matrix_fetch_expected_trans(m, k, 0, ei.trans_rows, nv.data(), cs.data(), bs.data(), ex.data())) != MKT_OK) return lib_fail("GPU matrix expected");
+            row = 0;
+            for (size_t a = 0; a < chroms.size(); ++a)
+                for (size_t b = a + 1; b < chroms.size() && ok; ++b, ++row) {
+                    t += chroms[a].name; t += '\t'; t += chroms[b].name; t += '\t'; t += std::to_string(nv[row]); t += '\t'; t += std::to_string(cs[row]); t += '\t';
+                    put_num(t, bs[row]); t += '\t'; put_num(t, ex[row]); t += '\n';
+                    ok = flush(base + ".trans.tsv", t, md, false);
+                }
+            ok = ok && flush(base + ".trans.tsv", t, md, true);
+            if (!ok) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         }
         std::string bed, wbed;
         const uint64_t r = res[k];
