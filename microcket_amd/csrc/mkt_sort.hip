@@ -115,9 +115,13 @@ __global__ void k_sort_keys(const uint8_t* text, uint64_t n, const uint64_t* sta
     if (nt < 4) { atomicOr(err, (uint32_t)SE_FIELDS); rec[j] = r; return; }
     const uint64_t p5 = nt >= 5 ? tabs[4] : le;
     auto num = [&](uint64_t a, uint64_t b) -> uint32_t {                      // sort -n on a plain decimal field
-        uint64_t v = 0;
-        for (uint64_t p = a; p < b; ++p) { const uint32_t d = (uint32_t)text[p] - (uint32_t)'0'; if (d > 9u) { atomicOr(err, (uint32_t)SE_FIELDS); break; } v = v * 10 + d; }
-        if (v > 0xFFFFFFFFull) atomicOr(err, (uint32_t)SE_FIELDS);
+        uint64_t v = 0;                                                       // checked per digit: v <= 2^32 - 1 before each step, so 64 bits never wrap
+        for (uint64_t p = a; p < b; ++p) {                                    // (leading zeros add nothing: a zero-padded field of any length is fine)
+            const uint32_t d = (uint32_t)text[p] - (uint32_t)'0';
+            if (d > 9u) { atomicOr(err, (uint32_t)SE_FIELDS); break; }
+            v = v * 10 + d;
+            if (v > 0xFFFFFFFFull) { atomicOr(err, (uint32_t)SE_FIELDS); break; }
+        }
         return (uint32_t)v;
     };
     auto slot = [&](uint64_t a, uint64_t b) -> uint32_t {
@@ -520,7 +524,7 @@ int mkt_sorter_sort(mkt_sorter* s, uint64_t* lines, uint64_t* bytes) {
     SRUN(hipMemcpyAsync(names.data(), d_tab->name, names.size(), hipMemcpyDeviceToHost, st));
     SRUN(hipMemcpyAsync(herr, d_err, sizeof herr, hipMemcpyDeviceToHost, st));
     SRUN(hipStreamSynchronize(st));
-    if (herr[0]) { cleanup(); return sfail(s, MKT_E_ARG, "not .pairs text (error bits 0x%x: 1 = fewer than five fields / non-decimal position, 2 = chromosome name longer than 62 bytes)", herr[0]); }
+    if (herr[0]) { cleanup(); return sfail(s, MKT_E_ARG, "not .pairs text (error bits 0x%x: 1 = fewer than five fields / position not decimal or beyond 32 bits, 2 = chromosome name longer than 62 bytes)", herr[0]); }
     std::vector<std::pair<std::string, uint32_t>> used;            // (name as sort -d sees it, slot)
     for (uint32_t k = 0; k < kChrSlots; ++k) if (hh[k]) {
         std::string f;

@@ -11,11 +11,7 @@ import util
 pytestmark = pytest.mark.gpu
 
 
-def _gnu_sort(data: bytes, tmp_path) -> bytes:
-    p = tmp_path / "in.pairs"
-    p.write_bytes(data)
-    e = dict(os.environ, LANG="C", LC_ALL="C")
-    return subprocess.run(["sort", "-k2,2d", "-k4,4d", "-k3,3n", "-k5,5n", str(p)], stdout=subprocess.PIPE, env=e, check=True).stdout
+_gnu_sort = util.gnu_sort                                          # shared with test_gpu_sort_edges.py and test_sortdef_host.py
 
 
 def _pairs(profile, seed, groups, mode, **kw):

@@ -168,6 +168,14 @@ def canon(b: bytes) -> bytes:
     return b"\n".join(lines) + (b"\n" if lines else b"")
 
 
+def gnu_sort(data: bytes, tmp_path) -> bytes:
+    """The system's sort, run exactly as the driver runs it (microcket:480,514): the checker of the .pairs sorter."""
+    p = tmp_path / "in.pairs"
+    p.write_bytes(data)
+    e = dict(os.environ, LANG="C", LC_ALL="C")
+    return subprocess.run(["sort", "-k2,2d", "-k4,4d", "-k3,3n", "-k5,5n", str(p)], stdout=subprocess.PIPE, env=e, check=True).stdout
+
+
 def sha(b: bytes) -> str:
     return hashlib.sha256(b).hexdigest()
 
