@@ -186,6 +186,11 @@ def build_test_tools():
     src = os.path.join(ROOT, "tests", "host", "tile_emul.cpp")
     if _newer(emul, [src] + _headers()):
         _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fPIC", "-shared", "-o", emul, src])
+    # host driver of the deflate code construction (mkt_deflate_codes.h); a tree that carries an older tests/ has no such source
+    dzc = os.path.join(out, "deflate_codes")
+    dsrc = os.path.join(ROOT, "tests", "host", "deflate_codes.cpp")
+    if os.path.exists(dsrc) and _newer(dzc, [dsrc, os.path.join(CSRC, "mkt_deflate_codes.h")]):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-o", dzc, dsrc])
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
     synth = os.path.join(tout, "synth_sam")

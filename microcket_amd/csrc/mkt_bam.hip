@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/mkt.h"
+#include "mkt_deflate_codes.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
 
@@ -464,72 +465,7 @@ constexpr uint32_t DZ_WAVE_SCRATCH = DZ_Q + DZ_QWORDS;            // words per w
 constexpr int DZ_STAGE = 104;                            // one step's bits of a wave: 64 tokens of <= 48 bits + the carry
 constexpr int DZ_HDRW = 176;                             // dynamic block header: <= 3 + 14 + 57 + 316 * 14 bits
 
-__device__ inline uint32_t bitrev(uint32_t v, int n) { return __brev(v) >> (32 - n); }
-__device__ inline void len_code(uint32_t len, uint32_t& sym, uint32_t& eb, uint32_t& ev) {       // 3..258
-    if (len == 258) { sym = 285; eb = 0; ev = 0; return; }
-    const uint32_t l = len - 3;
-    if (l < 8) { sym = 257 + l; eb = 0; ev = 0; return; }
-    const uint32_t k = 31u - (uint32_t)__clz((int)l);          // 3..7
-    eb = k - 2;
-    sym = 257 + 4 * eb + 4 + ((l >> eb) & 3u);
-    ev = l & ((1u << eb) - 1u);
-}
-__device__ inline void dist_code(uint32_t dist, uint32_t& sym, uint32_t& eb, uint32_t& ev) {     // 1..32768
-    const uint32_t d = dist - 1;
-    if (d < 4) { sym = d; eb = 0; ev = 0; return; }
-    const uint32_t k = 31u - (uint32_t)__clz((int)d);
-    eb = k - 1;
-    sym = 2 * k + ((d >> eb) & 1u);
-    ev = d & ((1u << eb) - 1u);
-}
-// code lengths for n symbols whose counts stand in A[0, n) in ascending order (Moffat & Katajainen, "In-place calculation of
-// minimum-redundancy codes", 1995): A[i] becomes the length of the i-th rarest symbol's code.  One lane.
-__device__ inline void mk_lengths(uint32_t* A, int n) {
-    if (n == 0) return;
-    if (n == 1) { A[0] = 1; return; }
-    A[0] += A[1];
-    int root = 0, leaf = 2, next;
-    for (next = 1; next < n - 1; ++next) {
-        if (leaf >= n || A[root] < A[leaf]) { A[next] = A[root]; A[root++] = (uint32_t)next; } else A[next] = A[leaf++];
-        if (leaf >= n || (root < next && A[root] < A[leaf])) { A[next] += A[root]; A[root++] = (uint32_t)next; } else A[next] += A[leaf++];
-    }
-    A[n - 2] = 0;
-    for (next = n - 3; next >= 0; --next) A[next] = A[A[next]] + 1;
-    int avbl = 1, used = 0, dpth = 0;
-    root = n - 2; next = n - 1;
-    while (avbl > 0) {
-        while (root >= 0 && (int)A[root] == dpth) { ++used; --root; }
-        while (avbl > used) { A[next--] = (uint32_t)dpth; --avbl; }
-        avbl = 2 * used; ++dpth; used = 0;
-    }
-}
-// One lane: lengths (<= maxbits) and canonical codes for the n used symbols listed rarest first in ssym (their counts in skey);
-// table[sym] = bit-reversed code | length << 16 (0 for unused symbols).
-__device__ inline void huff_codes(uint32_t* skey, const uint16_t* ssym, int n, int maxbits, uint32_t* table, int nsym) {
-    uint32_t num[33];
-    for (int i = 0; i <= 32; ++i) num[i] = 0;
-    mk_lengths(skey, n);
-    for (int i = 0; i < n; ++i) num[skey[i] > 32u ? 32u : skey[i]]++;
-    for (int i = maxbits + 1; i <= 32; ++i) { num[maxbits] += num[i]; num[i] = 0; }
-    uint32_t total = 0;
-    for (int i = maxbits; i > 0; --i) total += num[i] << (maxbits - i);
-    while (total > (1u << maxbits)) {                    // too many long codes: one leaves the deepest level, one code one level up splits
-        num[maxbits]--;
-        for (int i = maxbits - 1; i > 0; --i) if (num[i]) { num[i]--; num[i + 1] += 2; break; }
-        --total;
-    }
-    for (int s = 0; s < nsym; ++s) table[s] = 0;
-    int j = n;
-    for (int i = 1; i <= maxbits; ++i) for (uint32_t l = num[i]; l > 0; --l) table[ssym[--j]] = (uint32_t)i << 16;      // short codes to the frequent
-    uint32_t next_code[17];
-    uint32_t code = 0;
-    next_code[0] = 0;
-    for (int i = 1; i <= maxbits; ++i) { code = (code + num[i - 1]) << 1; next_code[i] = code; }
-    for (int s = 0; s < nsym; ++s) {
-        const uint32_t l = table[s] >> 16;
-        if (l) table[s] |= bitrev(next_code[l]++, (int)l);
-    }
-}
+// len_code, dist_code, mk_lengths, huff_codes, bitrev: mkt_deflate_codes.h (shared with the host test driver)
 struct BitSink {                                         // one lane appends bits to words in LDS
     uint32_t* w; uint32_t n;
     __device__ inline void put(uint32_t v, uint32_t nb) {
