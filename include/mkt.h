@@ -462,6 +462,91 @@ int mkt_matrix_fetch_expected_genome(mkt_matrix* m, uint32_t res_index, uint64_t
 int mkt_matrix_fetch_values(mkt_matrix* m, uint32_t res_index, int kind, uint64_t first, uint64_t n, double* out);
 int mkt_matrix_expected_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sums_ms);
 
+/* ---- loop calling: donut enrichment of every cell against its local neighbourhood, FDR thresholds, clustering --------------------
+ * The last hot loop of the Hi-C toolchain: what the reference's own benchmarking runs on its .hic files (HiCCUPS at 10 kb).  The
+ * definition is this project's own, modelled on HiCCUPS (Rao et al. 2014); parity with juicer_tools is UNPINNED (it is not run
+ * anywhere here).  tests/loopsdef.py restates the definition in numpy.  All arithmetic is float64.
+ *
+ * Inputs, for one resolution: the cells (bin1 <= bin2, count), the chromosome ranges [off_c, off_c + n_c) and the state of the last
+ * mkt_matrix_expected: its use_weights, w[k] and valid(k), E[d] = the genome-wide expected_smooth, v = ((double)count * w[bin1]) * w[bin2].
+ * Options (mkt_loops_opts): peak p, window, window_max, min_ll_count, min_dist, max_dist (0 = none), fdr, cluster_radius.
+ *  1. CANDIDATE cell (i, j): both bins in one chromosome c, both valid, min_dist <= j - i (and j - i <= max_dist when that is set).
+ *     A candidate is TESTED when step 4 leaves every region defined and step 5 leaves every r_R <= 512.
+ *  2. KEPT positions of an offset (a, b): (i + a, j + b) with both bins inside c's range, both valid and (j + b) - (i + a) >= 1.
+ *     Regions for a window w:   DONUT  max(|a|, |b|) <= w, not (|a| <= p and |b| <= p), a != 0, b != 0
+ *                               LL     1 <= a <= w, -w <= b <= -1, not (a <= p and b >= -p)           (towards the diagonal)
+ *                               H      |a| <= 1, p < |b| <= w
+ *                               V      p < |a| <= w, |b| <= 1
+ *  3. WINDOW: w = window; while Csum_LL(w) < min_ll_count and w < window_max: w += 1.  Csum_LL = the exact integer sum of the counts of
+ *     the stored cells at LL's kept positions.  All four regions use the final w, which is reported per cell.
+ *  4. Per region R: Bsum_R = the sum of v over the stored cells at kept positions, Esum_R = the sum of E[(j + b) - (i + a)] over ALL kept
+ *     positions.  Esum_R == 0 or no kept position: the region is UNDEFINED (status MKT_LOOP_UNDEFINED, r_R = e_R = NaN).
+ *     e_R = (Bsum_R / Esum_R) * E[j - i]; the raw expected r_R = e_R / (w[i] * w[j]).
+ *  5. CHUNKS: 28 edges, edge_k = ldexp(C[k % 3], k / 3) with C = {1.0, 1.2599210498948732, 1.5874010519681994} as those decimal
+ *     literals (edge_27 = 512).  chunk_R = the smallest k with r_R <= edge_k, by comparisons only.  r_R > 512 (or not a number) in any
+ *     region: status MKT_LOOP_OVER, counted, not tested.  The chunk of an undefined or over region is reported as 255.
+ *  6. HISTOGRAM H_R[k][x] (uint64) = the tested cells with chunk_R == k and min(count, 2047) == x.
+ *  7. THRESHOLDS, on the host, per (R, k) with lambda = edge_k: pmf_0 = exp(-lambda), pmf_x = (pmf_(x-1) * lambda) / x, cdf_x ascending,
+ *     Q(0) = 1, Q(x) = max(0, 1 - cdf_(x-1)); n = sum_x H, O(x) = sum_(x' >= x) H; T_R[k] = the smallest x >= 1 with O(x) > 0 and
+ *     n * Q(x) <= fdr * O(x); 2048 when there is none.
+ *  8. ENRICHED: a tested cell with count >= T_R[chunk_R] for all four R.
+ *  9. LOOPS: enriched cells of one chromosome are linked when max(|d bin1|, |d bin2|) <= cluster_radius; a loop is a connected component:
+ *     its peak cell (the largest count, ties to the smallest cell index) with count, window and the four r_R, the number of cells and
+ *     the bounding box.  Loops ascend by peak cell index.  (Done on the host: enriched cells are few.)
+ * Out of scope: HiCCUPS's post-filter ratio thresholds, merging across resolutions, per-chromosome expected, a .hic reader.
+ *
+ * Determinism: no floating-point atomics (the histogram's are integers); a region's sums are formed by a fixed number of lanes, each
+ * taking the rows a = -w + lane, + lanes, .. in ascending b, and a fixed shuffle tree: the same bits from call to call, process to
+ * process and whatever route the pairs came by.  Against the numpy restatement (which adds in ascending (a, b)) Csum_LL, the window,
+ * the kept positions and integer-valued Bsum are identical; Esum, e_R and r_R agree to summation-order rounding.
+ *
+ *   mkt_loops_opts_default        peak 2, window 5, window_max 20, min_ll_count 16, min_dist 8, max_dist 0, fdr 0.1, cluster_radius 2
+ *   mkt_matrix_loops              valid after mkt_matrix_expected of that resolution (MKT_E_STATE "expected first" without tables, and
+ *                                 before mkt_matrix_run); opts NULL = the defaults; MKT_E_ARG with a message for a bad index, a negative
+ *                                 option, window <= peak, window_max < window or > 20, fdr outside (0, 1) or NaN, or a non-zero reserved.
+ *                                 info may be NULL.  A later mkt_matrix_run, add, balance or expected of that resolution discards the results.
+ *   mkt_matrix_fetch_loop_cells   per-cell results of cells [first, first + n) in the order of mkt_matrix_fetch; any pointer may be NULL;
+ *                                 chunk, kept, r, e, bsum and esum hold 4 values per cell (DONUT, LL, H, V).  A cell that is no candidate
+ *                                 has window 0, chunks 255, NaN and zeros.
+ *   mkt_matrix_fetch_loop_hist    H as [4][28][2048] uint64
+ *   mkt_matrix_fetch_loop_thresholds   T as [4][28] uint32
+ *   mkt_matrix_fetch_loops        loops [first, first + n)
+ *   mkt_matrix_loops_timing       device time (ms, HIP events) of the neighbourhood pass (both launches), the histogram and the flagging
+ *                                 of the last mkt_matrix_loops of res_index.  A bad index is MKT_E_ARG without a message.
+ * Memory: 151 bytes per cell stay resident with the results (7 GB for 46.5 M cells), non-candidates included; 104 of them are the
+ * intermediate values (csum_ll, kept, bsum, esum, e) that mkt_matrix_fetch_loop_cells hands out for checking. */
+#define MKT_LOOP_NONE 0        /* not a candidate */
+#define MKT_LOOP_TESTED 1
+#define MKT_LOOP_UNDEFINED 2
+#define MKT_LOOP_OVER 3
+typedef struct mkt_loops_opts {
+    int32_t peak, window, window_max, min_ll_count, min_dist, max_dist;
+    double fdr;
+    int32_t cluster_radius;
+    uint32_t reserved;       /* 0 */
+} mkt_loops_opts;
+typedef struct mkt_loops_info {
+    uint64_t cells, candidates, tested, undefined, over;
+    uint64_t grew;           /* candidates whose window is larger than opts.window */
+    uint64_t at_max;         /* ... that stopped at window_max with Csum_LL < min_ll_count */
+    uint64_t enriched, loops;
+} mkt_loops_info;
+typedef struct mkt_loop {
+    uint64_t cell;           /* index of the peak cell in the order of mkt_matrix_fetch */
+    uint32_t bin1, bin2, count, window, n_cells;
+    uint32_t box[4];         /* min bin1, max bin1, min bin2, max bin2 of the component */
+    uint32_t reserved;
+    double r[4];             /* raw expected of the peak: DONUT, LL, H, V */
+} mkt_loop;
+void mkt_loops_opts_default(mkt_loops_opts* o);
+int mkt_matrix_loops(mkt_matrix* m, uint32_t res_index, const mkt_loops_opts* opts, mkt_loops_info* info);
+int mkt_matrix_fetch_loop_cells(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status, uint8_t* window, uint8_t* chunk, double* r,
+                                uint8_t* enriched, uint64_t* csum_ll, uint16_t* kept, double* bsum, double* esum, double* e);
+int mkt_matrix_fetch_loop_hist(mkt_matrix* m, uint32_t res_index, uint64_t* hist);
+int mkt_matrix_fetch_loop_thresholds(mkt_matrix* m, uint32_t res_index, uint32_t* thresholds);
+int mkt_matrix_fetch_loops(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, mkt_loop* out);
+int mkt_matrix_loops_timing(const mkt_matrix* m, uint32_t res_index, double* pass_ms, double* hist_ms, double* flag_ms);
+
 #ifdef __cplusplus
 }
 #endif

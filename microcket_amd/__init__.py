@@ -13,6 +13,11 @@ from .capi import (  # noqa: F401
     EXT_LANES,
     Expected,
     ExpectedOpts,
+    Loop,
+    LoopCells,
+    Loops,
+    LoopsInfo,
+    LoopsOpts,
     Matrix,
     MktError,
     MODE_FLASH,
@@ -32,6 +37,6 @@ from .capi import (  # noqa: F401
 )
 
 __all__ = [
-    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Expected", "ExpectedOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
+    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Expected", "ExpectedOpts", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
     "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam",
 ]

@@ -45,10 +45,13 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_matrix.hip", "mkt_balance.hip", "mkt_expected.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_matrix.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
+# sources whose host arithmetic is compared bit for bit with a numpy restatement: no fused multiply-add
+EXACT_SOURCES = ("mkt_loops.hip",)
+NO_CONTRACT = ("-ffp-contract=off",)
 
 
 def _compile_objects(srcs, tag, flags):
@@ -60,7 +63,8 @@ def _compile_objects(srcs, tag, flags):
         o = os.path.join(OBJ, tag + os.path.basename(s) + ".o")
         objs.append(o)
         if _newer(o, [s] + hdrs):
-            cmd = [hipcc(), "-c", "-fPIC", f"--offload-arch={ARCH}", "-O3", "-std=c++17", *flags, "-Wno-unused-function", "-I" + CSRC, s, "-o", o]
+            own = NO_CONTRACT if os.path.basename(s) in EXACT_SOURCES else ()
+            cmd = [hipcc(), "-c", "-fPIC", f"--offload-arch={ARCH}", "-O3", "-std=c++17", *flags, *own, "-Wno-unused-function", "-I" + CSRC, s, "-o", o]
             print("+", " ".join(cmd), flush=True)
             procs.append((cmd, subprocess.Popen(cmd)))
     for cmd, pr in procs:

@@ -27,6 +27,8 @@ EXPORTS = [
     "mkt_balance_opts_default", "mkt_matrix_balance", "mkt_matrix_fetch_weights", "mkt_matrix_balance_timing",
     "mkt_expected_opts_default", "mkt_matrix_expected", "mkt_matrix_fetch_expected_cis", "mkt_matrix_fetch_expected_trans", "mkt_matrix_fetch_expected_genome",
     "mkt_matrix_fetch_values", "mkt_matrix_expected_timing",
+    "mkt_loops_opts_default", "mkt_matrix_loops", "mkt_matrix_fetch_loop_cells", "mkt_matrix_fetch_loop_hist", "mkt_matrix_fetch_loop_thresholds",
+    "mkt_matrix_fetch_loops", "mkt_matrix_loops_timing",
 ]
 
 
@@ -80,6 +82,28 @@ ExpectedTrans = collections.namedtuple("ExpectedTrans", "n_valid count_sum balan
 ExpectedGenome = collections.namedtuple("ExpectedGenome", "n_valid count_sum balanced_sum expected expected_smooth")
 Expected = collections.namedtuple("Expected", "cis trans genome n_chrom smooth_groups")
 VALUE_KINDS = {"balanced": 0, "oe": 1, "oe_smooth": 2}
+
+
+class LoopsOpts(C.Structure):
+    """mkt_loops_opts of include/mkt.h"""
+    _fields_ = [("peak", C.c_int32), ("window", C.c_int32), ("window_max", C.c_int32), ("min_ll_count", C.c_int32), ("min_dist", C.c_int32),
+                ("max_dist", C.c_int32), ("fdr", C.c_double), ("cluster_radius", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _LoopsInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("cells", "candidates", "tested", "undefined", "over", "grew", "at_max", "enriched", "loops")]
+
+
+class _LoopC(C.Structure):
+    _fields_ = [("cell", C.c_uint64), ("bin1", C.c_uint32), ("bin2", C.c_uint32), ("count", C.c_uint32), ("window", C.c_uint32), ("n_cells", C.c_uint32),
+                ("box", C.c_uint32 * 4), ("reserved", C.c_uint32), ("r", C.c_double * 4)]
+
+
+LoopsInfo = collections.namedtuple("LoopsInfo", "cells candidates tested undefined over grew at_max enriched loops")
+Loop = collections.namedtuple("Loop", "cell bin1 bin2 count window r n_cells box")
+Loops = collections.namedtuple("Loops", "loops info")
+LoopCells = collections.namedtuple("LoopCells", "status window chunk r enriched csum_ll kept bsum esum e")
+LOOP_NONE, LOOP_TESTED, LOOP_UNDEFINED, LOOP_OVER = 0, 1, 2, 3
 
 
 class Timing(C.Structure):
@@ -237,6 +261,14 @@ def load_library():
     L.mkt_matrix_fetch_expected_genome.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
     L.mkt_matrix_fetch_values.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mkt_matrix_expected_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_loops_opts_default.argtypes = [C.POINTER(LoopsOpts)]
+    L.mkt_loops_opts_default.restype = None
+    L.mkt_matrix_loops.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(LoopsOpts), C.POINTER(_LoopsInfoC)]
+    L.mkt_matrix_fetch_loop_cells.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 10
+    L.mkt_matrix_fetch_loop_hist.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.mkt_matrix_fetch_loop_thresholds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    L.mkt_matrix_fetch_loops.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_loops_timing.argtypes = [C.c_void_p, C.c_uint32] + [C.POINTER(C.c_double)] * 3
     _lib = L
     return L
 
@@ -690,6 +722,53 @@ class Matrix:
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_expected_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_expected_timing")
         return a.value, b.value
+
+    def loops(self, res, **opts):
+        """Loop calling on resolution index res after expected(res): the definition is mkt_matrix_loops in include/mkt.h.  opts: peak,
+        window, window_max, min_ll_count, min_dist, max_dist, fdr, cluster_radius.  Returns Loops(loops, info): the loop table as a list
+        of Loop(cell, bin1, bin2, count, window, r, n_cells, box) ascending by peak cell index, and LoopsInfo."""
+        o = LoopsOpts()
+        self.L.mkt_loops_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("peak", "window", "window_max", "min_ll_count", "min_dist", "max_dist", "fdr", "cluster_radius"):
+                raise TypeError(f"loops: unknown option {k}")
+            setattr(o, k, v)
+        info = _LoopsInfoC()
+        self._chk(self.L.mkt_matrix_loops(self.h, res, C.byref(o), C.byref(info)), "mkt_matrix_loops")
+        rows = (_LoopC * max(info.loops, 1))()
+        self._chk(self.L.mkt_matrix_fetch_loops(self.h, res, 0, info.loops, rows), "mkt_matrix_fetch_loops")
+        table = [Loop(x.cell, x.bin1, x.bin2, x.count, x.window, tuple(x.r), x.n_cells, tuple(x.box)) for x in rows[:info.loops]]
+        return Loops(table, LoopsInfo(*[getattr(info, k) for k in LoopsInfo._fields]))
+
+    def loop_cells(self, res):
+        """per-cell results of the last loops(res) in the order of cells(res): LoopCells of numpy arrays (status, window, enriched uint8 [nnz];
+        chunk uint8, kept uint16, r, bsum, esum, e float64 [nnz, 4] for DONUT, LL, H, V; csum_ll uint64 [nnz])"""
+        import numpy as np
+        nnz = self.info(res)[1]
+        out = LoopCells(np.zeros(nnz, np.uint8), np.zeros(nnz, np.uint8), np.zeros((nnz, 4), np.uint8), np.zeros((nnz, 4), np.float64), np.zeros(nnz, np.uint8),
+                        np.zeros(nnz, np.uint64), np.zeros((nnz, 4), np.uint16), np.zeros((nnz, 4), np.float64), np.zeros((nnz, 4), np.float64), np.zeros((nnz, 4), np.float64))
+        self._chk(self.L.mkt_matrix_fetch_loop_cells(self.h, res, 0, nnz, *[a.ctypes.data_as(C.c_void_p) for a in out]), "mkt_matrix_fetch_loop_cells")
+        return out
+
+    def loop_hist(self, res):
+        """the histogram of the last loops(res): numpy uint64 [4, 28, 2048] (region, expected chunk, min(count, 2047))"""
+        import numpy as np
+        out = np.zeros((4, 28, 2048), dtype=np.uint64)
+        self._chk(self.L.mkt_matrix_fetch_loop_hist(self.h, res, out.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_loop_hist")
+        return out
+
+    def loop_thresholds(self, res):
+        """the count thresholds of the last loops(res): numpy uint32 [4, 28]; 2048 = none"""
+        import numpy as np
+        out = np.zeros((4, 28), dtype=np.uint32)
+        self._chk(self.L.mkt_matrix_fetch_loop_thresholds(self.h, res, out.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_loop_thresholds")
+        return out
+
+    def loops_timing_ms(self, res):
+        """(neighbourhood pass ms, histogram ms, flagging ms) of the last loops(res): device time, HIP events"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_loops_timing(self.h, res, C.byref(a), C.byref(b), C.byref(c)), "mkt_matrix_loops_timing")
+        return a.value, b.value, c.value
 
     def close(self):
         if self.h:

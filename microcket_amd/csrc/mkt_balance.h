@@ -25,6 +25,8 @@ struct BalState {
 };
 
 void bal_free(BalSetup& s);
+// the row pointers alone, into rowptr[nbins + 1] (what the loop caller needs when no balance has built a BalSetup)
+hipError_t bal_rowptr(uint32_t* rowptr, const uint32_t* b1, uint64_t nnz, uint64_t nbins, hipStream_t st);
 // rowptr, the transposed copy and colptr.  b1 / b2 / cnt: the nnz cells ascending in (bin1, bin2).  Synchronises the stream.
 hipError_t bal_setup(BalSetup& s, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t nnz, uint64_t nbins, int B, hipStream_t st);
 // m[k] = marg(x)[k] over the used cells; unit: x = 1 (bias is not read), else x = count * bias[bin1] * bias[bin2]

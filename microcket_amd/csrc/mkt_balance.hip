@@ -188,6 +188,13 @@ void bal_free(BalSetup& s) {
     s = BalSetup();
 }
 
+hipError_t bal_rowptr(uint32_t* rowptr, const uint32_t* b1, uint64_t nnz, uint64_t nbins, hipStream_t st) {
+    if (nnz >= (1ull << 32) || nbins >= (1ull << 32)) return hipErrorInvalidValue;
+    if (nnz == 0) return hipMemsetAsync(rowptr, 0, (size_t)(nbins + 1) * 4, st);
+    hipLaunchKernelGGL(k_bl_rowptr, dim3((unsigned)((nbins + 1 + BLWG - 1) / BLWG)), dim3(BLWG), 0, st, b1, (uint32_t)nnz, nbins, rowptr);
+    return hipGetLastError();
+}
+
 hipError_t bal_setup(BalSetup& s, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t nnz, uint64_t nbins, int B, hipStream_t st) {
     bal_free(s);
     if (nnz >= (1ull << 32) || nbins >= (1ull << 32)) return hipErrorInvalidValue;
@@ -213,7 +220,7 @@ hipError_t bal_setup(BalSetup& s, const uint32_t* b1, const uint32_t* b2, const 
         if ((e = hipMalloc((void**)&kA, (size_t)nnz * 8 + 64)) != hipSuccess) return done(e);
         if ((e = hipMalloc((void**)&kB, (size_t)nnz * 8 + 64)) != hipSuccess) return done(e);
         if ((e = hipMalloc((void**)&d_radix, radix64_count_bytes(nnz))) != hipSuccess) return done(e);
-        hipLaunchKernelGGL(k_bl_rowptr, dim3(pgrid), dim3(BLWG), 0, st, b1, (uint32_t)nnz, nbins, s.rowptr);
+        if ((e = bal_rowptr(s.rowptr, b1, nnz, nbins, st)) != hipSuccess) return done(e);
         hipLaunchKernelGGL(k_bl_tkeys, dim3(cgrid), dim3(BLWG), 0, st, b2, (uint32_t)nnz, kA);
         if ((e = launch_radix64(kA, kB, nnz, 32, B, d_radix, st)) != hipSuccess) return done(e);       // stable: (bin2, bin1) order from (bin1, bin2) order
         hipLaunchKernelGGL(k_bl_gather, dim3(cgrid), dim3(BLWG), 0, st, (const uint64_t*)kA, b1, cnt, (uint32_t)nnz, s.tr);

@@ -26,6 +26,7 @@
 #include "../../include/mkt.h"
 #include "mkt_balance.h"
 #include "mkt_expected.h"
+#include "mkt_loops.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
 
@@ -284,6 +285,8 @@ struct MxRes {
     ExpSetup exs;
     ExpTables ext;
     double exp_setup_ms = 0, exp_sums_ms = 0;
+    // loop calling (mkt_matrix_loops): the results live until the next expected, balance or run
+    LoopsState lps;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -358,6 +361,7 @@ static void mx_free_results(mkt_matrix* m) {
         exp_free(r.exs);
         exp_free_tables(r.ext);
         r.exp_setup_ms = r.exp_sums_ms = 0;
+        loops_free(r.lps);
     }
     m->ran = false;
 }
@@ -704,6 +708,7 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     if (r.d_w) { (void)hipFree(r.d_w); r.d_w = nullptr; }
     r.balanced = false; r.bal_iter_ms = 0;
     exp_free_tables(r.ext);                                             // tables of other weights
+    loops_free(r.lps);
     double *d_bias = nullptr, *d_m = nullptr, *d_part = nullptr;
     BalState* d_state = nullptr;
     auto cleanup = [&]() {
@@ -842,6 +847,7 @@ int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_op
     MCHK(m, hipSetDevice(m->device));
     hipStream_t st = m->stream;
     exp_free_tables(r.ext);
+    loops_free(r.lps);                                                  // loops of other tables
     r.exp_sums_ms = 0;
 #define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { exp_free_tables(r.ext); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "expected: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
     float ms = 0;
@@ -943,6 +949,118 @@ int mkt_matrix_expected_timing(const mkt_matrix* m, uint32_t res_index, double* 
     const MxRes& r = m->res[res_index];
     if (setup_ms) *setup_ms = m->ran && r.ext.built ? r.exp_setup_ms : 0.0;
     if (sums_ms) *sums_ms = m->ran && r.ext.built ? r.exp_sums_ms : 0.0;
+    return MKT_OK;
+}
+
+}  // extern "C"
+
+// ---- loop calling: the entry points; the kernels, thresholds and clustering are mkt_loops.hip, the definition is in include/mkt.h
+extern "C" {
+
+void mkt_loops_opts_default(mkt_loops_opts* o) {
+    if (!o) return;
+    o->peak = 2; o->window = 5; o->window_max = 20; o->min_ll_count = 16; o->min_dist = 8; o->max_dist = 0; o->fdr = 0.1; o->cluster_radius = 2; o->reserved = 0;
+}
+
+int mkt_matrix_loops(mkt_matrix* m, uint32_t res_index, const mkt_loops_opts* opts, mkt_loops_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    mkt_loops_opts o;
+    mkt_loops_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.peak < 0) return mfail(m, MKT_E_ARG, "loops: peak %d is negative", o.peak);
+    if (o.window <= o.peak) return mfail(m, MKT_E_ARG, "loops: window %d is not larger than peak %d", o.window, o.peak);
+    if (o.window_max < o.window || o.window_max > kLpWmax) return mfail(m, MKT_E_ARG, "loops: window_max %d (window %d .. %d)", o.window_max, o.window, kLpWmax);
+    if (o.min_ll_count < 0) return mfail(m, MKT_E_ARG, "loops: min_ll_count %d is negative", o.min_ll_count);
+    if (o.min_dist < 0 || o.max_dist < 0) return mfail(m, MKT_E_ARG, "loops: min_dist %d / max_dist %d is negative", o.min_dist, o.max_dist);
+    if (!(o.fdr > 0.0 && o.fdr < 1.0)) return mfail(m, MKT_E_ARG, "loops: fdr %g is not inside (0, 1)", o.fdr);
+    if (o.cluster_radius < 0) return mfail(m, MKT_E_ARG, "loops: cluster_radius %d is negative", o.cluster_radius);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "loops: the reserved field is not 0");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "loops before run");
+    MxRes& r = m->res[res_index];
+    if (!r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    loops_free(r.lps);
+#define LRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { loops_free(r.lps); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "loops: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
+    const uint32_t* rowptr = r.bal.built ? r.bal.rowptr : nullptr;
+    if (!rowptr) {                                                      // no balance has run: the row pointers alone
+        LRUN(hipMalloc((void**)&r.lps.rowptr, (size_t)(r.nbins + 1) * 4));
+        LRUN(bal_rowptr(r.lps.rowptr, r.d_b1, r.nnz, r.nbins, st));
+        rowptr = r.lps.rowptr;
+    }
+    LoopsIn in;
+    in.b1 = r.d_b1; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = rowptr; in.off = r.d_off; in.chr = r.exs.chr;
+    in.w = r.ext.use_weights ? r.d_w : nullptr; in.E = r.ext.d_cis_sm;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.genome_rows = r.exs.genome_rows; in.nchr = (uint32_t)r.off.size();
+    LRUN(loops_run(r.lps, in, r.off, o, st));
+#undef LRUN
+    if (info) *info = r.lps.info;
+    return MKT_OK;
+}
+
+// the results of res_index for a fetch, or the error
+static int mx_loops_state(mkt_matrix* m, uint32_t res_index, const LoopsState** out) {
+    if (!m) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    const MxRes& r = m->res[res_index];
+    if (!m->ran || !r.lps.built) return mfail(m, MKT_E_STATE, "no loops for resolution index %u: loops first", res_index);
+    *out = &r.lps;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_loop_cells(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status, uint8_t* window, uint8_t* chunk, double* r,
+                                uint8_t* enriched, uint64_t* csum_ll, uint16_t* kept, double* bsum, double* esum, double* e) {
+    const LoopsState* s = nullptr;
+    const int rc = mx_loops_state(m, res_index, &s);
+    if (rc) return rc;
+    const uint64_t nnz = m->res[res_index].nnz;
+    if (first > nnz || n > nnz - first) return mfail(m, MKT_E_ARG, "loop cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nnz);
+    MCHK(m, hipSetDevice(m->device));
+    if (n == 0) return MKT_OK;
+    if (status) MCHK(m, hipMemcpy(status, s->status + first, n, hipMemcpyDeviceToHost));
+    if (window) MCHK(m, hipMemcpy(window, s->window + first, n, hipMemcpyDeviceToHost));
+    if (chunk) MCHK(m, hipMemcpy(chunk, s->chunk + 4 * first, 4 * n, hipMemcpyDeviceToHost));
+    if (r) MCHK(m, hipMemcpy(r, s->r + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (enriched) MCHK(m, hipMemcpy(enriched, s->enriched + first, n, hipMemcpyDeviceToHost));
+    if (csum_ll) MCHK(m, hipMemcpy(csum_ll, s->csum + first, 8 * n, hipMemcpyDeviceToHost));
+    if (kept) MCHK(m, hipMemcpy(kept, s->kept + 4 * first, 8 * n, hipMemcpyDeviceToHost));
+    if (bsum) MCHK(m, hipMemcpy(bsum, s->bsum + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (esum) MCHK(m, hipMemcpy(esum, s->esum + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (e) MCHK(m, hipMemcpy(e, s->e + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+int mkt_matrix_fetch_loop_hist(mkt_matrix* m, uint32_t res_index, uint64_t* hist) {
+    const LoopsState* s = nullptr;
+    const int rc = mx_loops_state(m, res_index, &s);
+    if (rc) return rc;
+    if (hist) memcpy(hist, s->hist.data(), s->hist.size() * 8);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_loop_thresholds(mkt_matrix* m, uint32_t res_index, uint32_t* thresholds) {
+    const LoopsState* s = nullptr;
+    const int rc = mx_loops_state(m, res_index, &s);
+    if (rc) return rc;
+    if (thresholds) memcpy(thresholds, s->thr.data(), s->thr.size() * 4);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_loops(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, mkt_loop* out) {
+    const LoopsState* s = nullptr;
+    const int rc = mx_loops_state(m, res_index, &s);
+    if (rc) return rc;
+    const uint64_t rows = s->loops.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "loops [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    if (out && n) memcpy(out, s->loops.data() + first, (size_t)n * sizeof(mkt_loop));
+    return MKT_OK;
+}
+int mkt_matrix_loops_timing(const mkt_matrix* m, uint32_t res_index, double* pass_ms, double* hist_ms, double* flag_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const LoopsState& s = m->res[res_index].lps;
+    const bool have = m->ran && s.built;
+    if (pass_ms) *pass_ms = have ? s.pass_ms : 0.0;
+    if (hist_ms) *hist_ms = have ? s.hist_ms : 0.0;
+    if (flag_ms) *flag_ms = have ? s.flag_ms : 0.0;
     return MKT_OK;
 }
 

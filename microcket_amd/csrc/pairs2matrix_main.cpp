@@ -5,6 +5,8 @@
 //
 //   pairs2matrix -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]        (no input file: stdin; $MKT_DEVICE: GPU ordinal)
 //                [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]
+//                [--loops [--loop-peak N] [--loop-window N] [--loop-window-max N] [--loop-min-ll-count N] [--loop-min-dist N]
+//                         [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -20,6 +22,12 @@
 //   <prefix>.<r>.expected.trans.tsv   chrom1, chrom2, n_valid, count_sum, balanced_sum, expected (every pair in table order)
 // Without --expected none of these appears and every other byte is the same.  A per-cell text dump of balanced or observed / expected
 // values is out of scope (mkt_matrix_fetch_values hands them back as arrays).
+// With --loops (mkt_matrix_loops of include/mkt.h; it implies --expected and, like it, uses the weights with --balance and raw counts
+// without) also per resolution <prefix>.<r>.loops.bedpe: a header line, then per loop in the order of the library chrom, start, end of
+// the peak's two bins, count, the four raw expected values (donut, ll, h, v; %.17g), window, cells of the component and its bounding box
+// (start1, end1, start2, end2); and <prefix>.loops.stat (per resolution r, cells, candidates, tested, undefined, over, grew, at_max,
+// enriched, loops).  Without --loops neither appears and every other byte is the same.  A sub-option without --loops is a usage error, a
+// malformed value or a window outside peak < window <= window-max <= 20 exit 12, before anything is read.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -31,7 +39,9 @@
 
 static int usage(const char* me) {
     fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n"
-                    "       [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]\n", me);
+                    "       [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]\n"
+                    "       [--loops [--loop-peak N] [--loop-window N] [--loop-window-max N] [--loop-min-ll-count N] [--loop-min-dist N]\n"
+                    "                [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -124,13 +134,19 @@ static void put_num(std::string& out, double x) {
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
-    bool balance = false, expected = false;
+    bool balance = false, expected = false, loops = false;
+    const char* lopt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    static const char* const lname[8] = {"--loop-peak", "--loop-window", "--loop-window-max", "--loop-min-ll-count", "--loop-min-dist", "--loop-max-dist", "--loop-fdr", "--loop-cluster-radius"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
         int b = -1;
         for (int k = 0; k < 6; ++k) if (!strcmp(argv[i], bname[k])) b = k;
+        int l = -1;
+        for (int k = 0; k < 8; ++k) if (!strcmp(argv[i], lname[k])) l = k;
         if (b >= 0) { if (i + 1 >= argc) return usage(argv[0]); bopt[b] = argv[++i]; }
+        else if (l >= 0) { if (i + 1 >= argc) return usage(argv[0]); lopt[l] = argv[++i]; }
+        else if (!strcmp(argv[i], "--loops")) loops = expected = true;
         else if (!strcmp(argv[i], "--balance")) balance = true;
         else if (!strcmp(argv[i], "--expected")) expected = true;
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) table = argv[++i];
@@ -149,6 +165,18 @@ int main(int argc, char* argv[]) {
                       : k == 3 ? parse_num(bopt[k], bo.mad_max) : k == 4 ? parse_num(bopt[k], bo.tol) : (parse_int(bopt[k], bo.max_iters) && bo.max_iters >= 1);
         if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", bopt[k], bname[k], k == 5 ? "a whole number, at least 1" : k < 2 ? "a whole number, 0 or more" : "a number, 0 or more"); return 12; }
     }
+    mkt_loops_opts lo;
+    mkt_loops_opts_default(&lo);
+    for (int k = 0; k < 8; ++k) {
+        if (!lopt[k]) continue;
+        if (!loops) { fprintf(stderr, "Error: %s needs --loops\n", lname[k]); return usage(argv[0]); }
+        int32_t* const ip[8] = {&lo.peak, &lo.window, &lo.window_max, &lo.min_ll_count, &lo.min_dist, &lo.max_dist, nullptr, &lo.cluster_radius};
+        const bool ok = k == 6 ? (parse_num(lopt[k], lo.fdr) && lo.fdr > 0.0 && lo.fdr < 1.0) : parse_int(lopt[k], *ip[k]);
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", lopt[k], lname[k], k == 6 ? "a number inside (0, 1)" : "a whole number, 0 or more"); return 12; }
+    }
+    // the combinations the library would refuse, before anything is read or written
+    if (loops && lo.window <= lo.peak) { fprintf(stderr, "Error: --loop-window %d is not larger than --loop-peak %d\n", lo.window, lo.peak); return 12; }
+    if (loops && (lo.window_max < lo.window || lo.window_max > 20)) { fprintf(stderr, "Error: --loop-window-max %d (--loop-window %d .. 20)\n", lo.window_max, lo.window); return 12; }
     std::string ttxt, why;
     if (!read_file(table, ttxt)) { fprintf(stderr, "Error: read chromosome table failed!\n"); return 10; }
     std::vector<Chrom> chroms;
@@ -191,7 +219,7 @@ int main(int argc, char* argv[]) {
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
 
     const std::string pre = prefix;
-    std::string bstat;
+    std::string bstat, lstat;
     std::vector<double> weights;
     std::string stat = "Pairs\t" + std::to_string(pairs) + "\nBinned\t" + std::to_string(pairs - skipped) + "\nSkipped\t" + std::to_string(skipped) + "\n";
     for (uint32_t k = 0; k < res.size(); ++k) {
@@ -270,6 +298,33 @@ int main(int argc, char* argv[]) {
             ok = ok && flush(base + ".trans.tsv", t, md, true);
             if (!ok) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         }
+        if (loops) {
+            mkt_loops_info li;
+            if ((rc = mkt_matrix_loops(m, k, &lo, &li)) != MKT_OK) return lib_fail("GPU matrix loops");
+            std::vector<mkt_loop> rows(li.loops);
+            if ((rc = mkt_matrix_fetch_loops(m, k, 0, li.loops, rows.data())) != MKT_OK) return lib_fail("GPU matrix loops");
+            lstat += std::to_string(res[k]);
+            for (uint64_t v : {li.cells, li.candidates, li.tested, li.undefined, li.over, li.grew, li.at_max, li.enriched, li.loops}) { lstat += '\t'; lstat += std::to_string(v); }
+            lstat += '\n';
+            std::vector<uint64_t> first;                                          // first bin of every chromosome at this resolution
+            uint64_t nb = 0;
+            for (const Chrom& c : chroms) { first.push_back(nb); nb += (c.len + res[k] - 1) / res[k]; }
+            auto chrom_of = [&](uint64_t bin) { size_t c = chroms.size() - 1; while (first[c] > bin) --c; return c; };
+            auto span = [&](std::string& t, size_t c, uint64_t b0, uint64_t b1) {       // start of bin b0 and clipped end of bin b1, both in chromosome c
+                const uint64_t s = (b0 - first[c]) * res[k], e = (b1 - first[c] + 1) * res[k];
+                t += std::to_string(s); t += '\t'; t += std::to_string(e < chroms[c].len ? e : chroms[c].len);
+            };
+            std::string t = "#chrom1\tstart1\tend1\tchrom2\tstart2\tend2\tcount\texpected_donut\texpected_ll\texpected_h\texpected_v\twindow\tcells\tbox_start1\tbox_end1\tbox_start2\tbox_end2\n";
+            for (const mkt_loop& L : rows) {
+                const size_t c = chrom_of(L.bin1);
+                t += chroms[c].name; t += '\t'; span(t, c, L.bin1, L.bin1); t += '\t'; t += chroms[c].name; t += '\t'; span(t, c, L.bin2, L.bin2); t += '\t';
+                t += std::to_string(L.count);
+                for (int R = 0; R < 4; ++R) { t += '\t'; put_num(t, L.r[R]); }
+                t += '\t'; t += std::to_string(L.window); t += '\t'; t += std::to_string(L.n_cells); t += '\t';
+                span(t, c, L.box[0], L.box[1]); t += '\t'; span(t, c, L.box[2], L.box[3]); t += '\n';
+            }
+            if (!write_file(pre + "." + std::to_string(res[k]) + ".loops.bedpe", t.data(), t.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        }
         std::string bed, wbed;
         const uint64_t r = res[k];
         const char *mode = "wb", *wmode = "wb";                                   // the first piece truncates, the others append
@@ -297,6 +352,7 @@ int main(int argc, char* argv[]) {
         if (balance && !write_file(pre + "." + std::to_string(res[k]) + ".weights.bed", wbed.data(), wbed.size(), wmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
     if (balance && !write_file(pre + ".balance.stat", bstat.data(), bstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+    if (loops && !write_file(pre + ".loops.stat", lstat.data(), lstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (!write_file(pre + ".matrix.stat", stat.data(), stat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     mkt_matrix_destroy(m);
     return 0;
