@@ -547,6 +547,70 @@ int mkt_matrix_fetch_loop_thresholds(mkt_matrix* m, uint32_t res_index, uint32_t
 int mkt_matrix_fetch_loops(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, mkt_loop* out);
 int mkt_matrix_loops_timing(const mkt_matrix* m, uint32_t res_index, double* pass_ms, double* hist_ms, double* flag_ms);
 
+/* ---- compartments: the leading eigenvectors of each chromosome's cis observed / expected - 1 matrix ------------------------------
+ * What `juicer_tools eigenvector` and cooltools `eigs-cis` compute from the .hic / .cool.  The definition is this project's own,
+ * modelled on cooltools eigs-cis; parity with cooltools and juicer_tools is UNPINNED (neither is run anywhere here).
+ * tests/eigsdef.py restates the definition in numpy.  All arithmetic is float64.
+ *
+ * Inputs, for one resolution: the cells, the chromosome ranges [off_c, off_c + n_c) and the state of the last mkt_matrix_expected: its
+ * use_weights, w[k] and valid(k), E[d] = the genome-wide expected_smooth, v = ((double)count * w[bin1]) * w[bin2].
+ * Options (mkt_eigs_opts): n_eigs (1 .. 4), ignore_diags, clip, min_good, tol, max_iters; an optional phasing track p[nbins] (NaN = no value).
+ *  1. GOOD bin of chromosome c: valid(k) and at least one stored cell (k, j) or (j, k) with j in c, valid(j) and |j - k| >= ignore_diags.
+ *     n_good(c) counts them.  A chromosome with n_good < max(min_good, 9) is SKIPPED: eigenvalues NaN, vector entries NaN,
+ *     iterations 0, converged 0.
+ *  2. MATRIX A_c (symmetric, n_c x n_c, never formed on the GPU): for good i, j in c with |i - j| >= ignore_diags A[i][j] = oe - 1,
+ *     where oe = v / E[|i - j|] for a stored cell, replaced by min(oe, clip) when clip > 0, and oe = 0 for an absent cell.  Every other
+ *     entry is 0.  Equivalently A = S - (g g^T - B): S holds oe at the stored eligible positions, g is the 0/1 good indicator and
+ *     B[i][j] = g_i g_j for |i - j| < ignore_diags, so (A x)_i = (S x)_i - g_i (g^T x) + g_i sum_{|i - j| < ignore_diags, j in c} g_j x_j.
+ *  3. EIGENPAIRS: the n_eigs eigenpairs of A_c largest in |lambda|, in descending |lambda|; each vector has unit 2-norm over the good
+ *     bins and is NaN elsewhere.  A chromosome is CONVERGED when every reported pair has ||A x - lambda x||_2 <= tol * |lambda_1| as
+ *     computed on the device; otherwise the iteration stops after max_iters sweeps with converged = 0 and the pairs it has are still
+ *     reported, normalised.  The procedure: a block of 8 columns, X_0 a fixed integer hash of (bin - off_c, column) zeroed on the
+ *     other bins and orthonormalised; per iteration ONE sweep Y = A X, H = X^T Y (8 x 8 per chromosome), Rayleigh-Ritz
+ *     H = S Theta S^T by a cyclic Jacobi with a fixed number of sweeps, Ritz vectors X S, residual columns Y S - X S Theta, the next
+ *     X = orth(Y S).  A chromosome that is done freezes (a device-side flag per chromosome).
+ *  4. ORIENTATION.  With a track: when sum x_i (p_i - pbar) over the good bins with a value (pbar their mean) is negative, the vector is
+ *     flipped.  Without a track, or when that sum is exactly 0 or has no terms: the entry of largest |x_i| (ties to the lowest bin)
+ *     is made positive.
+ * An absent cell counts as -1: where the cis matrix is mostly empty the leading vector is the all-ones direction with
+ * lambda ~ -n_good.  Compartments are meant for resolutions where cis is dense (100 kb .. 1 Mb).
+ * Out of scope: percentile clipping (it needs a selection), per-arm views, trans eigenvectors, Pearson-correlation (juicer-style)
+ * vectors, Lanczos, a saddle plot.
+ *
+ * Determinism: no floating-point atomics; a row's sum is formed by a fixed number of lanes with a fixed stride and a fixed shuffle
+ * tree (rows of more than 1024 cells: one workgroup, the four wave sums added in wave order); the per-chromosome dot products use
+ * fixed chunks of 256 bins whose partial sums are added in chunk order; the 8 x 8 step runs on the host in a fixed order.  Everything
+ * depends on (nbins, cells, options) only: the same bits from call to call, process to process and whatever route the pairs came by.
+ *
+ *   mkt_eigs_opts_default       n_eigs 3, ignore_diags 2, min_good 9, max_iters 300, tol 1e-8, clip 0 (none)
+ *   mkt_matrix_eigs             valid after mkt_matrix_expected of that resolution (MKT_E_STATE "expected first" without tables); opts
+ *                               NULL = the defaults; phasing: nbins doubles or NULL; MKT_E_ARG with a message for a bad index, n_eigs
+ *                               outside 1 .. 4, a negative option, tol not inside (0, 1) or NaN, a NaN or negative clip or a non-zero
+ *                               reserved.  info may be NULL.  A later mkt_matrix_run, add, balance or expected of that resolution
+ *                               discards the results; loops and eigenvectors of one resolution do not disturb each other.
+ *   mkt_matrix_fetch_eigvecs    vector k (0 .. n_eigs - 1) for bins [first, first + n)
+ *   mkt_matrix_fetch_eigvals    chromosomes [first_chrom, first_chrom + n): lambda and resid as [n][n_eigs] (resid = the device's
+ *                               ||A x - lambda x||_2), n_good, iterations, converged; any pointer may be NULL
+ *   mkt_matrix_eigs_apply       y = A x for all chromosomes at once through the sweep kernel of the iteration: x and y are
+ *                               [nbins][ncols], 1 <= ncols <= 8; x is used as given on good bins and treated as 0 elsewhere; y is 0 on
+ *                               the other bins and on skipped chromosomes.  Needs the tables like mkt_matrix_eigs; keeps no result.
+ *   mkt_matrix_eigs_timing      of the last mkt_matrix_eigs of res_index (ms, HIP events): the setup (row pointers and transposed copy
+ *                               when no balance built them, good flags, X_0), the sweeps alone, and the rest of the iteration loop
+ *                               (reductions, the 8 x 8 step on the host with its copies).  A bad index is MKT_E_ARG without a message. */
+typedef struct mkt_eigs_opts {
+    int32_t n_eigs, ignore_diags, min_good, max_iters;
+    double tol, clip;
+    uint32_t reserved;       /* 0 */
+} mkt_eigs_opts;
+typedef struct mkt_eigs_info { uint32_t n_chrom, solved, converged, skipped, max_iterations; } mkt_eigs_info;
+void mkt_eigs_opts_default(mkt_eigs_opts* o);
+int mkt_matrix_eigs(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* phasing, mkt_eigs_info* info);
+int mkt_matrix_fetch_eigvecs(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, double* out);
+int mkt_matrix_fetch_eigvals(mkt_matrix* m, uint32_t res_index, uint32_t first_chrom, uint32_t n, double* lambda, double* resid, uint32_t* n_good,
+                             uint32_t* iterations, uint8_t* converged);
+int mkt_matrix_eigs_apply(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* x, uint32_t ncols, double* y);
+int mkt_matrix_eigs_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms, double* small_ms);
+
 #ifdef __cplusplus
 }
 #endif

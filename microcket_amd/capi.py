@@ -29,6 +29,7 @@ EXPORTS = [
     "mkt_matrix_fetch_values", "mkt_matrix_expected_timing",
     "mkt_loops_opts_default", "mkt_matrix_loops", "mkt_matrix_fetch_loop_cells", "mkt_matrix_fetch_loop_hist", "mkt_matrix_fetch_loop_thresholds",
     "mkt_matrix_fetch_loops", "mkt_matrix_loops_timing",
+    "mkt_eigs_opts_default", "mkt_matrix_eigs", "mkt_matrix_fetch_eigvecs", "mkt_matrix_fetch_eigvals", "mkt_matrix_eigs_apply", "mkt_matrix_eigs_timing",
 ]
 
 
@@ -104,6 +105,21 @@ Loop = collections.namedtuple("Loop", "cell bin1 bin2 count window r n_cells box
 Loops = collections.namedtuple("Loops", "loops info")
 LoopCells = collections.namedtuple("LoopCells", "status window chunk r enriched csum_ll kept bsum esum e")
 LOOP_NONE, LOOP_TESTED, LOOP_UNDEFINED, LOOP_OVER = 0, 1, 2, 3
+
+
+class EigsOpts(C.Structure):
+    """mkt_eigs_opts of include/mkt.h"""
+    _fields_ = [("n_eigs", C.c_int32), ("ignore_diags", C.c_int32), ("min_good", C.c_int32), ("max_iters", C.c_int32), ("tol", C.c_double), ("clip", C.c_double),
+                ("reserved", C.c_uint32)]
+
+
+class _EigsInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("n_chrom", "solved", "converged", "skipped", "max_iterations")]
+
+
+EigsInfo = collections.namedtuple("EigsInfo", "n_chrom solved converged skipped max_iterations")
+Eigs = collections.namedtuple("Eigs", "info vectors lambdas resid n_good iterations converged")
+EIGS_OPTS = ("n_eigs", "ignore_diags", "min_good", "max_iters", "tol", "clip")
 
 
 class Timing(C.Structure):
@@ -269,6 +285,13 @@ def load_library():
     L.mkt_matrix_fetch_loop_thresholds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.mkt_matrix_fetch_loops.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mkt_matrix_loops_timing.argtypes = [C.c_void_p, C.c_uint32] + [C.POINTER(C.c_double)] * 3
+    L.mkt_eigs_opts_default.argtypes = [C.POINTER(EigsOpts)]
+    L.mkt_eigs_opts_default.restype = None
+    L.mkt_matrix_eigs.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(EigsOpts), C.c_void_p, C.POINTER(_EigsInfoC)]
+    L.mkt_matrix_fetch_eigvecs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_fetch_eigvals.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
+    L.mkt_matrix_eigs_apply.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(EigsOpts), C.c_void_p, C.c_uint32, C.c_void_p]
+    L.mkt_matrix_eigs_timing.argtypes = [C.c_void_p, C.c_uint32] + [C.POINTER(C.c_double)] * 3
     _lib = L
     return L
 
@@ -768,6 +791,57 @@ class Matrix:
         """(neighbourhood pass ms, histogram ms, flagging ms) of the last loops(res): device time, HIP events"""
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_loops_timing(self.h, res, C.byref(a), C.byref(b), C.byref(c)), "mkt_matrix_loops_timing")
+        return a.value, b.value, c.value
+
+    def _eigs_opts(self, what, opts):
+        o = EigsOpts()
+        self.L.mkt_eigs_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in EIGS_OPTS:
+                raise TypeError(f"{what}: unknown option {k}")
+            setattr(o, k, v)
+        return o
+
+    def eigs(self, res, phasing=None, **opts):
+        """Compartment eigenvectors of resolution index res after expected(res): the definition is mkt_matrix_eigs in include/mkt.h.
+        phasing: nbins values (NaN = none) that fix the sign, or None.  opts: n_eigs, ignore_diags, min_good, max_iters, tol, clip.
+        Returns Eigs(info, vectors [n_eigs, nbins], lambdas and resid [n_chrom, n_eigs], n_good, iterations, converged [n_chrom])."""
+        import numpy as np
+        o = self._eigs_opts("eigs", opts)
+        nb = self.info(res)[0]
+        p = None
+        if phasing is not None:
+            p = np.ascontiguousarray(phasing, dtype=np.float64)
+            if p.shape != (nb,):
+                raise ValueError(f"eigs: phasing has shape {p.shape}, ({nb},) is needed")
+        info = _EigsInfoC()
+        self._chk(self.L.mkt_matrix_eigs(self.h, res, C.byref(o), p.ctypes.data_as(C.c_void_p) if p is not None else None, C.byref(info)), "mkt_matrix_eigs")
+        vec = np.zeros((o.n_eigs, nb), dtype=np.float64)
+        for k in range(o.n_eigs):
+            self._chk(self.L.mkt_matrix_fetch_eigvecs(self.h, res, k, 0, nb, vec[k].ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_eigvecs")
+        nc = info.n_chrom
+        lam, rs = np.zeros((nc, o.n_eigs), dtype=np.float64), np.zeros((nc, o.n_eigs), dtype=np.float64)
+        ng, it, cv = np.zeros(nc, dtype=np.uint32), np.zeros(nc, dtype=np.uint32), np.zeros(nc, dtype=np.uint8)
+        self._chk(self.L.mkt_matrix_fetch_eigvals(self.h, res, 0, nc, *[a.ctypes.data_as(C.c_void_p) for a in (lam, rs, ng, it, cv)]), "mkt_matrix_fetch_eigvals")
+        return Eigs(EigsInfo(*[getattr(info, k) for k in EigsInfo._fields]), vec, lam, rs, ng, it, cv.astype(bool))
+
+    def eigs_apply(self, res, x, **opts):
+        """y = A x for every chromosome at once through the sweep kernel of eigs(): x is [nbins] or [nbins, ncols <= 8], used as given
+        on good bins and as 0 elsewhere; y has x's shape and is 0 on the other bins and on skipped chromosomes."""
+        import numpy as np
+        o = self._eigs_opts("eigs_apply", opts)
+        x = np.asarray(x, dtype=np.float64)
+        x2 = np.ascontiguousarray(x.reshape(x.shape[0], -1))
+        if x2.shape[0] != self.info(res)[0]:
+            raise ValueError(f"eigs_apply: x has {x2.shape[0]} rows, {self.info(res)[0]} are needed")
+        y = np.zeros_like(x2)
+        self._chk(self.L.mkt_matrix_eigs_apply(self.h, res, C.byref(o), x2.ctypes.data_as(C.c_void_p), x2.shape[1], y.ctypes.data_as(C.c_void_p)), "mkt_matrix_eigs_apply")
+        return y.reshape(x.shape)
+
+    def eigs_timing_ms(self, res):
+        """(setup ms, sweeps ms, rest of the iteration loop ms) of the last eigs(res)"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_eigs_timing(self.h, res, C.byref(a), C.byref(b), C.byref(c)), "mkt_matrix_eigs_timing")
         return a.value, b.value, c.value
 
     def close(self):

@@ -27,6 +27,7 @@
 #include "mkt_balance.h"
 #include "mkt_expected.h"
 #include "mkt_loops.h"
+#include "mkt_eigs.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
 
@@ -287,6 +288,8 @@ struct MxRes {
     double exp_setup_ms = 0, exp_sums_ms = 0;
     // loop calling (mkt_matrix_loops): the results live until the next expected, balance or run
     LoopsState lps;
+    // compartment eigenvectors (mkt_matrix_eigs): the results live until the next expected, balance or run
+    EigsState egs;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -362,6 +365,7 @@ static void mx_free_results(mkt_matrix* m) {
         exp_free_tables(r.ext);
         r.exp_setup_ms = r.exp_sums_ms = 0;
         loops_free(r.lps);
+        eigs_free(r.egs);
     }
     m->ran = false;
 }
@@ -709,6 +713,7 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     r.balanced = false; r.bal_iter_ms = 0;
     exp_free_tables(r.ext);                                             // tables of other weights
     loops_free(r.lps);
+    eigs_free(r.egs);
     double *d_bias = nullptr, *d_m = nullptr, *d_part = nullptr;
     BalState* d_state = nullptr;
     auto cleanup = [&]() {
@@ -848,6 +853,7 @@ int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_op
     hipStream_t st = m->stream;
     exp_free_tables(r.ext);
     loops_free(r.lps);                                                  // loops of other tables
+    eigs_free(r.egs);
     r.exp_sums_ms = 0;
 #define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { exp_free_tables(r.ext); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "expected: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
     float ms = 0;
@@ -1061,6 +1067,132 @@ int mkt_matrix_loops_timing(const mkt_matrix* m, uint32_t res_index, double* pas
     if (pass_ms) *pass_ms = have ? s.pass_ms : 0.0;
     if (hist_ms) *hist_ms = have ? s.hist_ms : 0.0;
     if (flag_ms) *flag_ms = have ? s.flag_ms : 0.0;
+    return MKT_OK;
+}
+
+}  // extern "C"
+
+// ---- compartment eigenvectors: the entry points; the kernels and the iteration are mkt_eigs.hip, the definition is in include/mkt.h
+extern "C" {
+
+void mkt_eigs_opts_default(mkt_eigs_opts* o) {
+    if (!o) return;
+    o->n_eigs = 3; o->ignore_diags = 2; o->min_good = 9; o->max_iters = 300; o->tol = 1e-8; o->clip = 0.0; o->reserved = 0;
+}
+
+}  // extern "C"
+
+// the options checked, the tables there and the balance setup built (without a balance when none has run): what eigs and apply share
+static int mx_eigs_ready(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, mkt_eigs_opts& o, EigsIn& in, double* setup_ms) {
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    mkt_eigs_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.n_eigs < 1 || o.n_eigs > 4) return mfail(m, MKT_E_ARG, "eigs: n_eigs %d (1 .. 4)", o.n_eigs);
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "eigs: ignore_diags %d is negative", o.ignore_diags);
+    if (o.min_good < 0) return mfail(m, MKT_E_ARG, "eigs: min_good %d is negative", o.min_good);
+    if (o.max_iters < 0) return mfail(m, MKT_E_ARG, "eigs: max_iters %d is negative", o.max_iters);
+    if (!(o.tol > 0.0 && o.tol < 1.0)) return mfail(m, MKT_E_ARG, "eigs: tol %g is not inside (0, 1)", o.tol);
+    if (!(o.clip >= 0.0)) return mfail(m, MKT_E_ARG, "eigs: clip %g is negative or NaN", o.clip);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "eigs: the reserved field is not 0");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "eigs before run");
+    MxRes& r = m->res[res_index];
+    if (!r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    if (setup_ms) *setup_ms = 0;
+    if (!r.bal.built) {                                                 // raw counts: the row pointers and the transposed copy without a balance
+        MCHK(m, hipEventRecord(m->ev0, st));
+        const hipError_t e = bal_setup(r.bal, r.d_b1, r.d_b2, r.d_cnt, r.nnz, r.nbins, r.B, st);
+        if (e != hipSuccess) return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs: bal_setup failed: %s", hipGetErrorString(e));
+        MCHK(m, hipEventRecord(m->ev1, st));
+        MCHK(m, hipEventSynchronize(m->ev1));
+        float ms = 0;
+        MCHK(m, hipEventElapsedTime(&ms, m->ev0, m->ev1));
+        r.bal_setup_ms = ms;
+        if (setup_ms) *setup_ms = ms;
+    }
+    in.bal = &r.bal; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.off = r.d_off; in.chr = r.exs.chr;
+    in.w = r.ext.use_weights ? r.d_w : nullptr; in.E = r.ext.d_cis_sm;
+    in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    return MKT_OK;
+}
+
+extern "C" {
+
+int mkt_matrix_eigs(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* phasing, mkt_eigs_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    mkt_eigs_opts o;
+    EigsIn in;
+    double setup_ms = 0;
+    const int rc = mx_eigs_ready(m, res_index, opts, o, in, &setup_ms);
+    if (rc) return rc;
+    MxRes& r = m->res[res_index];
+    const hipError_t e = eigs_run(r.egs, in, r.off, o, phasing, m->stream);
+    if (e != hipSuccess) { eigs_free(r.egs); return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs: %s", hipGetErrorString(e)); }
+    r.egs.setup_ms += setup_ms;
+    if (info) *info = r.egs.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_eigs_apply(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* x, uint32_t ncols, double* y) {
+    if (!m) return MKT_E_ARG;
+    mkt_eigs_opts o;
+    EigsIn in;
+    const int rc = mx_eigs_ready(m, res_index, opts, o, in, nullptr);
+    if (rc) return rc;
+    if (ncols < 1 || ncols > (uint32_t)kEgCols) return mfail(m, MKT_E_ARG, "eigs apply: ncols %u (1 .. 8)", ncols);
+    if (!x || !y) return mfail(m, MKT_E_ARG, "eigs apply: x and y are needed");
+    const hipError_t e = eigs_apply(in, m->res[res_index].off, o, x, ncols, y, m->stream);
+    if (e != hipSuccess) return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs apply: %s", hipGetErrorString(e));
+    return MKT_OK;
+}
+
+// the results of res_index for a fetch, or the error
+static int mx_eigs_state(mkt_matrix* m, uint32_t res_index, const EigsState** out) {
+    if (!m) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    const MxRes& r = m->res[res_index];
+    if (!m->ran || !r.egs.built) return mfail(m, MKT_E_STATE, "no eigenvectors for resolution index %u: eigs first", res_index);
+    *out = &r.egs;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_eigvecs(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, double* out) {
+    const EigsState* s = nullptr;
+    const int rc = mx_eigs_state(m, res_index, &s);
+    if (rc) return rc;
+    const uint64_t nb = m->res[res_index].nbins;
+    if (k >= (uint32_t)s->n_eigs) return mfail(m, MKT_E_ARG, "eigenvector %u of %d", k, s->n_eigs);
+    if (first > nb || n > nb - first) return mfail(m, MKT_E_ARG, "eigenvector bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nb);
+    if (out && n) memcpy(out, s->vec.data() + (size_t)k * nb + first, (size_t)n * 8);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_eigvals(mkt_matrix* m, uint32_t res_index, uint32_t first_chrom, uint32_t n, double* lambda, double* resid, uint32_t* n_good,
+                             uint32_t* iterations, uint8_t* converged) {
+    const EigsState* s = nullptr;
+    const int rc = mx_eigs_state(m, res_index, &s);
+    if (rc) return rc;
+    const uint32_t nchr = (uint32_t)s->n_good.size();
+    if (first_chrom > nchr || n > nchr - first_chrom) return mfail(m, MKT_E_ARG, "eigenvalues of chromosomes [%u, +%u) of %u", first_chrom, n, nchr);
+    if (n == 0) return MKT_OK;
+    const size_t ne = (size_t)s->n_eigs;
+    if (lambda) memcpy(lambda, s->lambda.data() + first_chrom * ne, n * ne * 8);
+    if (resid) memcpy(resid, s->resid.data() + first_chrom * ne, n * ne * 8);
+    if (n_good) memcpy(n_good, s->n_good.data() + first_chrom, (size_t)n * 4);
+    if (iterations) memcpy(iterations, s->iterations.data() + first_chrom, (size_t)n * 4);
+    if (converged) memcpy(converged, s->converged.data() + first_chrom, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_eigs_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms, double* small_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const EigsState& s = m->res[res_index].egs;
+    const bool have = m->ran && s.built;
+    if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
+    if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;
+    if (small_ms) *small_ms = have ? s.small_ms : 0.0;
     return MKT_OK;
 }
 

@@ -7,6 +7,8 @@
 //                [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]
 //                [--loops [--loop-peak N] [--loop-window N] [--loop-window-max N] [--loop-min-ll-count N] [--loop-min-dist N]
 //                         [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]
+//                [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]
+//                        [--eigs-track FILE]]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -28,6 +30,13 @@
 // (start1, end1, start2, end2); and <prefix>.loops.stat (per resolution r, cells, candidates, tested, undefined, over, grew, at_max,
 // enriched, loops).  Without --loops neither appears and every other byte is the same.  A sub-option without --loops is a usage error, a
 // malformed value or a window outside peak < window <= window-max <= 20 exit 12, before anything is read.
+// With --eigs (mkt_matrix_eigs of include/mkt.h: compartment eigenvectors; it implies --expected and, like it, uses the weights with
+// --balance and raw counts without) also per resolution <prefix>.<r>.eigs.tsv: a header line, then the columns of .bins.bed plus E1 .. Ek
+// as %.17g (nan for NaN); and <prefix>.eigs.stat, one row per resolution and chromosome: r, chrom, bins, good, iterations, converged,
+// lambda1 .. lambdak.  A chromosome that did not converge is a warning.  --eigs-track FILE: a four-column bed with exactly the bins of
+// .bins.bed in order whose fourth column (a number or nan) fixes the sign; only with a single resolution (a usage error otherwise), a row
+// that does not match is exit 12.  Without --eigs neither file appears and every other byte is the same.  A sub-option without --eigs is
+// a usage error, a malformed value exit 12.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -41,7 +50,9 @@ static int usage(const char* me) {
     fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n"
                     "       [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]\n"
                     "       [--loops [--loop-peak N] [--loop-window N] [--loop-window-max N] [--loop-min-ll-count N] [--loop-min-dist N]\n"
-                    "                [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]\n", me);
+                    "                [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]\n"
+                    "       [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]\n"
+                    "               [--eigs-track FILE]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -134,7 +145,9 @@ static void put_num(std::string& out, double x) {
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
-    bool balance = false, expected = false, loops = false;
+    bool balance = false, expected = false, loops = false, eigs = false;
+    const char* gopt[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    static const char* const gname[7] = {"--eigs-n", "--eigs-ignore-diags", "--eigs-min-good", "--eigs-max-iters", "--eigs-tol", "--eigs-clip", "--eigs-track"};
     const char* lopt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const lname[8] = {"--loop-peak", "--loop-window", "--loop-window-max", "--loop-min-ll-count", "--loop-min-dist", "--loop-max-dist", "--loop-fdr", "--loop-cluster-radius"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -144,7 +157,11 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 6; ++k) if (!strcmp(argv[i], bname[k])) b = k;
         int l = -1;
         for (int k = 0; k < 8; ++k) if (!strcmp(argv[i], lname[k])) l = k;
-        if (b >= 0) { if (i + 1 >= argc) return usage(argv[0]); bopt[b] = argv[++i]; }
+        int g = -1;
+        for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], gname[k])) g = k;
+        if (g >= 0) { if (i + 1 >= argc) return usage(argv[0]); gopt[g] = argv[++i]; }
+        else if (!strcmp(argv[i], "--eigs")) eigs = expected = true;
+        else if (b >= 0) { if (i + 1 >= argc) return usage(argv[0]); bopt[b] = argv[++i]; }
         else if (l >= 0) { if (i + 1 >= argc) return usage(argv[0]); lopt[l] = argv[++i]; }
         else if (!strcmp(argv[i], "--loops")) loops = expected = true;
         else if (!strcmp(argv[i], "--balance")) balance = true;
@@ -177,12 +194,47 @@ int main(int argc, char* argv[]) {
     // the combinations the library would refuse, before anything is read or written
     if (loops && lo.window <= lo.peak) { fprintf(stderr, "Error: --loop-window %d is not larger than --loop-peak %d\n", lo.window, lo.peak); return 12; }
     if (loops && (lo.window_max < lo.window || lo.window_max > 20)) { fprintf(stderr, "Error: --loop-window-max %d (--loop-window %d .. 20)\n", lo.window_max, lo.window); return 12; }
+    mkt_eigs_opts go;
+    mkt_eigs_opts_default(&go);
+    for (int k = 0; k < 7; ++k) {
+        if (!gopt[k]) continue;
+        if (!eigs) { fprintf(stderr, "Error: %s needs --eigs\n", gname[k]); return usage(argv[0]); }
+        if (k == 6) continue;
+        int32_t* const ip[4] = {&go.n_eigs, &go.ignore_diags, &go.min_good, &go.max_iters};
+        const bool ok = k == 0 ? (parse_int(gopt[k], go.n_eigs) && go.n_eigs >= 1 && go.n_eigs <= 4) : k < 4 ? parse_int(gopt[k], *ip[k])
+                      : k == 4 ? (parse_num(gopt[k], go.tol) && go.tol > 0.0 && go.tol < 1.0) : parse_num(gopt[k], go.clip);
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", gopt[k], gname[k], k == 0 ? "a whole number, 1 .. 4" : k < 4 ? "a whole number, 0 or more" : k == 4 ? "a number inside (0, 1)" : "a number, 0 or more"); return 12; }
+    }
     std::string ttxt, why;
     if (!read_file(table, ttxt)) { fprintf(stderr, "Error: read chromosome table failed!\n"); return 10; }
     std::vector<Chrom> chroms;
     if (!parse_table(ttxt, chroms, why)) { fprintf(stderr, "Error: bad chromosome table: %s\n", why.c_str()); return 12; }
     std::vector<uint32_t> res;
     if (!parse_res(rlist, res)) { fprintf(stderr, "Error: bad resolution list '%s' (1 .. 16 different positive numbers, comma separated)\n", rlist); return 12; }
+    if (gopt[6] && res.size() != 1) { fprintf(stderr, "Error: --eigs-track needs a single resolution\n"); return usage(argv[0]); }
+    std::vector<double> track;
+    if (gopt[6]) {                                                            // the bins of .bins.bed in order, with a value each
+        std::string txt;
+        if (!read_file(gopt[6], txt)) { fprintf(stderr, "Error: read track file failed!\n"); return 10; }
+        size_t p = 0;
+        const uint64_t r = res[0];
+        for (const Chrom& c : chroms)
+            for (uint64_t s0 = 0; s0 < c.len; s0 += r) {
+                size_t q = txt.find('\n', p);
+                if (p >= txt.size()) { fprintf(stderr, "Error: track file: %zu rows, more bins\n", track.size()); return 12; }
+                if (q == std::string::npos) q = txt.size();
+                const std::string want = c.name + "\t" + std::to_string(s0) + "\t" + std::to_string(s0 + r < c.len ? s0 + r : c.len) + "\t";
+                if (txt.compare(p, want.size(), want) != 0) { fprintf(stderr, "Error: track file row %zu is not bin %s\n", track.size() + 1, want.c_str()); return 12; }
+                std::string v = txt.substr(p + want.size(), q - p - want.size());
+                if (!v.empty() && v.back() == '\r') v.pop_back();
+                char* end = nullptr;
+                const double x = strtod(v.c_str(), &end);
+                if (v.empty() || *end) { fprintf(stderr, "Error: track file row %zu: '%s' is not a number\n", track.size() + 1, v.c_str()); return 12; }
+                track.push_back(x);
+                p = q + 1;
+            }
+        if (p < txt.size()) { fprintf(stderr, "Error: track file has rows past the last bin\n"); return 12; }
+    }
     for (uint32_t r : res) {
         uint64_t nb = 0;
         for (const Chrom& c : chroms) nb += (c.len + r - 1) / r;
@@ -219,7 +271,9 @@ int main(int argc, char* argv[]) {
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
 
     const std::string pre = prefix;
-    std::string bstat, lstat;
+    std::string bstat, lstat, gstat;
+    std::vector<double> evec;
+    uint32_t ne = 0;
     std::vector<double> weights;
     std::string stat = "Pairs\t" + std::to_string(pairs) + "\nBinned\t" + std::to_string(pairs - skipped) + "\nSkipped\t" + std::to_string(skipped) + "\n";
     for (uint32_t k = 0; k < res.size(); ++k) {
@@ -325,9 +379,29 @@ int main(int argc, char* argv[]) {
             }
             if (!write_file(pre + "." + std::to_string(res[k]) + ".loops.bedpe", t.data(), t.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         }
-        std::string bed, wbed;
+        if (eigs) {
+            mkt_eigs_info gi;
+            if ((rc = mkt_matrix_eigs(m, k, &go, track.empty() ? nullptr : track.data(), &gi)) != MKT_OK) return lib_fail("GPU matrix eigs");
+            ne = (uint32_t)go.n_eigs;
+            evec.resize((size_t)ne * nbins);
+            for (uint32_t j = 0; j < ne; ++j)
+                if ((rc = mkt_matrix_fetch_eigvecs(m, k, j, 0, nbins, evec.data() + (size_t)j * nbins)) != MKT_OK) return lib_fail("GPU matrix eigs");
+            std::vector<double> lam((size_t)gi.n_chrom * ne);
+            std::vector<uint32_t> ng(gi.n_chrom), it(gi.n_chrom);
+            std::vector<uint8_t> cv(gi.n_chrom);
+            if ((rc = mkt_matrix_fetch_eigvals(m, k, 0, gi.n_chrom, lam.data(), nullptr, ng.data(), it.data(), cv.data())) != MKT_OK) return lib_fail("GPU matrix eigs");
+            for (uint32_t c = 0; c < gi.n_chrom; ++c) {
+                gstat += std::to_string(res[k]); gstat += '\t'; gstat += chroms[c].name; gstat += '\t'; gstat += std::to_string((chroms[c].len + res[k] - 1) / res[k]);
+                gstat += '\t'; gstat += std::to_string(ng[c]); gstat += '\t'; gstat += std::to_string(it[c]); gstat += '\t'; gstat += cv[c] ? '1' : '0';
+                for (uint32_t j = 0; j < ne; ++j) { gstat += '\t'; put_num(gstat, lam[(size_t)c * ne + j]); }
+                gstat += '\n';
+                if (it[c] && !cv[c]) fprintf(stderr, "WARN: eigenvectors of %s at resolution %u did not converge in %u iterations.\n", chroms[c].name.c_str(), res[k], it[c]);
+            }
+        }
+        std::string bed, wbed, gbed;
         const uint64_t r = res[k];
-        const char *mode = "wb", *wmode = "wb";                                   // the first piece truncates, the others append
+        const char *mode = "wb", *wmode = "wb", *gmode = "wb";             // the first piece truncates, the others append
+        if (eigs) { gbed = "chrom\tstart\tend"; for (uint32_t j = 0; j < ne; ++j) { gbed += "\tE"; gbed += std::to_string(j + 1); } gbed += '\n'; }
         uint64_t bin = 0;
         for (const Chrom& c : chroms)
             for (uint64_t s = 0; s < c.len; s += r) {
@@ -335,7 +409,7 @@ int main(int argc, char* argv[]) {
                 bed += c.name; bed += '\t'; bed += std::to_string(s); bed += '\t'; bed += std::to_string(s + r < c.len ? s + r : c.len); bed += '\n';
                 if (balance) {
                     char num[40];
-                    const double w = weights[bin++];
+                    const double w = weights[bin];
                     if (w != w) strcpy(num, "nan"); else snprintf(num, sizeof num, "%.17g", w);
                     wbed.append(bed, at, bed.size() - at - 1); wbed += '\t'; wbed += num; wbed += '\n';
                     if (wbed.size() > ((size_t)32 << 20)) {
@@ -343,14 +417,26 @@ int main(int argc, char* argv[]) {
                         wbed.clear(); wmode = "ab";
                     }
                 }
+                if (eigs) {
+                    gbed.append(bed, at, bed.size() - at - 1);
+                    for (uint32_t j = 0; j < ne; ++j) { gbed += '\t'; put_num(gbed, evec[(size_t)j * nbins + bin]); }
+                    gbed += '\n';
+                    if (gbed.size() > ((size_t)32 << 20)) {
+                        if (!write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+                        gbed.clear(); gmode = "ab";
+                    }
+                }
                 if (bed.size() > ((size_t)32 << 20)) {
                     if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
                     bed.clear(); mode = "ab";
                 }
+                ++bin;
             }
         if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (balance && !write_file(pre + "." + std::to_string(res[k]) + ".weights.bed", wbed.data(), wbed.size(), wmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        if (eigs && !write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
+    if (eigs && !write_file(pre + ".eigs.stat", gstat.data(), gstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (balance && !write_file(pre + ".balance.stat", bstat.data(), bstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (loops && !write_file(pre + ".loops.stat", lstat.data(), lstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (!write_file(pre + ".matrix.stat", stat.data(), stat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
