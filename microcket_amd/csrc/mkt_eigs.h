@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../../include/mkt.h"
-#include "mkt_balance.h"
+#include "mkt_layout.h"
 
 namespace mkt {
 
@@ -16,12 +16,11 @@ constexpr int kEgCols = 8;                        // columns of the block: X and
 constexpr uint32_t kEgChunk = 256;                // bins per chunk of the per-chromosome dot products
 constexpr int kEgJacobiSweeps = 12;               // cyclic Jacobi sweeps of the 8 x 8 Rayleigh-Ritz step
 
-// what the sweep reads: the cells sorted by (bin1, bin2) with the row pointers and the transposed copy of the balance setup, the
-// chromosome of a bin and the ranges, the weights (nullptr: every bin valid, weight 1) and E = expected_smooth of the genome-wide table
+// what the sweep reads: the cells sorted by (bin1, bin2) with their full layout (row pointers, transposed copy, chromosome of a bin),
+// the ranges, the weights (nullptr: every bin valid, weight 1) and E = expected_smooth of the genome-wide table
 struct EigsIn {
-    const BalSetup* bal;
+    const MxLayout* lay;
     const uint32_t *b2, *cnt, *off;
-    const uint16_t* chr;
     const double *w, *E;
     uint64_t nbins;
     uint32_t nchr;
@@ -39,7 +38,6 @@ struct EigsState {
     bool built = false;
 };
 
-void eigs_free(EigsState& s);
 // steps 1 .. 4.  phasing: nbins doubles on the host or nullptr.  Synchronises the stream.
 hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>& off, const mkt_eigs_opts& o, const double* phasing, hipStream_t st);
 // y = A x through the sweep kernel of the iteration; x, y: [nbins][ncols] on the host.  Synchronises the stream.

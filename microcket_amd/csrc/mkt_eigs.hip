@@ -2,14 +2,13 @@
 // GPU; include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_eigs, mkt_matrix_eigs_apply, the fetches).
 //
 // The matrix A = S - (g g^T - B) is never formed.  One sweep Y = A X multiplies a block of 8 columns: bin k's lanes walk its row
-// segment of the cells and its column segment of the balance setup's transposed copy (as the balance sweep does), form oe from the
+// segment of the cells and its column segment of the layout's transposed copy (as the balance sweep does), form oe from the
 // count, the two weights and E[d], gather the 64 contiguous bytes X[other bin][0 .. 8) and keep 8 accumulators; the rank-one term
 // g (g^T X) comes from the previous reduction and the band term B X from the up to 2 ignore_diags - 1 neighbouring rows of X.
 // Cis, good bins and d >= ignore_diags are compares in the walk.
 //
-// Nothing depends on the order anything ran in: there are no floating-point atomics.  A row's sums are formed by a fixed number of
-// lanes (BalSetup::width) with a fixed stride and a fixed shuffle tree; rows of more than kBalLong cells get one workgroup, the four
-// wave sums added in wave order.  Per-chromosome dot products (X^T Y, Y^T Y, norms, g^T X) are sums over chunks of kEgChunk bins, four
+// Nothing depends on the order anything ran in.  A row's sums are formed by MxLayout::width lanes with a fixed stride
+// and the lane tree; rows of more than kBalLong cells get one workgroup and the workgroup tree.  Per-chromosome dot products (X^T Y, Y^T Y, norms, g^T X) are sums over chunks of kEgChunk bins, four
 // interleaved slices per chunk added in slice order, then the chunks of a chromosome in chunk order.  The 8 x 8 Rayleigh-Ritz step and
 // the Cholesky factor that re-orthonormalises the block run on the host, per chromosome, between two launches: two looks at the
 // device per iteration (DESIGN.md 7e has what that costs).  A chromosome that is done is skipped by every kernel through done[c].
@@ -21,6 +20,7 @@
 #include <limits>
 
 #include "mkt_eigs.h"
+#include "mkt_segred.h"
 
 namespace mkt {
 
@@ -91,7 +91,7 @@ __device__ inline void eg_finish(const EgArgs& a, uint32_t k, uint32_t c, uint32
     y[2] = make_double2((acc[4] - g[4]) + band[4], (acc[5] - g[5]) + band[5]);
     y[3] = make_double2((acc[6] - g[6]) + band[6], (acc[7] - g[7]) + band[7]);
 }
-// W lanes per bin (W = 8 .. 64, a power of two): the tree adds lane l + d to lane l for d = W / 2 .. 1
+// W lanes per bin (W = 8 .. 64, a power of two)
 template <bool HASW, int W>
 __global__ __launch_bounds__(EGWG) void k_eg_sweep(EgArgs a) {
     const uint64_t k64 = ((uint64_t)blockIdx.x * EGWG + threadIdx.x) / W;
@@ -108,14 +108,10 @@ __global__ __launch_bounds__(EGWG) void k_eg_sweep(EgArgs a) {
             if (mine && a.act[k]) eg_walk<HASW>(a, k, l, W, lo, hi, acc);
         }
     }
-#pragma unroll
-    for (int d = W / 2; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += __shfl_down(acc[j], d, W);
-    }
+    lane_tree_n<W>(acc);
     if (mine && l == 0) eg_finish(a, k, c, lo, hi, acc);
 }
-// one workgroup per long bin: the same walk with 256 lanes, the tree per wave, the four wave sums added in wave order
+// one workgroup per long bin: the same walk with 256 lanes
 template <bool HASW>
 __global__ __launch_bounds__(EGWG) void k_eg_sweep_long(EgArgs a, const uint32_t* longbins) {
     __shared__ double sh[EGWG / 64][8];
@@ -124,21 +120,8 @@ __global__ __launch_bounds__(EGWG) void k_eg_sweep_long(EgArgs a, const uint32_t
     const uint32_t lo = a.off[c], hi = c + 1u < a.nchr ? a.off[c + 1] : (uint32_t)a.nbins;
     double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (a.act[k]) eg_walk<HASW>(a, k, threadIdx.x, EGWG, lo, hi, acc);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] += __shfl_down(acc[j], d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sh[threadIdx.x >> 6][j] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
-        eg_finish(a, k, c, lo, hi, acc);
-    }
+    wg_tree_n(acc, &sh[0][0]);
+    if (threadIdx.x == 0) eg_finish(a, k, c, lo, hi, acc);
 }
 
 // good(k): valid and one stored cell to a valid bin of its chromosome at a distance of ignore_diags or more.  One lane per bin; the
@@ -208,7 +191,7 @@ __global__ __launch_bounds__(EGWG) void k_eg_dots(const uint4* chunks, const dou
     }
     sh[q][p] = h; sh[q][64 + p] = m;
     __syncthreads();
-    if (threadIdx.x < EG_HM) partial[(size_t)blockIdx.x * EG_HM + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+    if (threadIdx.x < EG_HM) partial[(size_t)blockIdx.x * EG_HM + threadIdx.x] = sum4(sh[0][threadIdx.x], sh[1][threadIdx.x], sh[2][threadIdx.x], sh[3][threadIdx.x]);
 }
 // lanes 0 .. 7: |R_j|^2 (R is in Y's place), 8 .. 15: |V_j|^2, 16 .. 23: g^T X_j
 __global__ __launch_bounds__(EGWG) void k_eg_norms(const uint4* chunks, const double* R, const double* V, const double* X, const uint32_t* done, double* partial) {
@@ -223,7 +206,7 @@ __global__ __launch_bounds__(EGWG) void k_eg_norms(const uint4* chunks, const do
         sh[q][p] = s;
     }
     __syncthreads();
-    if (threadIdx.x < EG_NR) partial[(size_t)blockIdx.x * EG_NR + threadIdx.x] = ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
+    if (threadIdx.x < EG_NR) partial[(size_t)blockIdx.x * EG_NR + threadIdx.x] = sum4(sh[0][threadIdx.x], sh[1][threadIdx.x], sh[2][threadIdx.x], sh[3][threadIdx.x]);
 }
 __global__ __launch_bounds__(EG_HM) void k_eg_chrsum(const uint2* cchunks, const double* partial, const uint32_t* done, uint32_t width, double* out) {
     const uint32_t c = blockIdx.x;
@@ -259,40 +242,28 @@ __global__ __launch_bounds__(EGWG) void k_eg_transform(const uint16_t* chr, cons
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------------
-void eigs_free(EigsState& s) { s = EigsState(); }
-
 namespace {
 
 // everything one call holds on the device; freed when it goes out of scope
 struct EgWork {
-    double *X = nullptr, *Y = nullptr, *V = nullptr, *partial = nullptr, *HM = nullptr, *NR = nullptr, *T = nullptr, *io = nullptr;
-    uint8_t *good = nullptr, *act = nullptr;
-    uint32_t* done = nullptr;
-    uint4* chunks = nullptr;
-    uint2* cchunks = nullptr;
+    DevBuf<double> X, Y, V, partial, HM, NR, T, io;
+    DevBuf<uint8_t> good, act;
+    DevBuf<uint32_t> done;
+    DevBuf<uint4> chunks;
+    DevBuf<uint2> cchunks;
     uint32_t nchunks = 0;
     std::vector<uint8_t> h_good, h_act;
     std::vector<uint32_t> n_good, h_done;
     EgArgs a;
-    ~EgWork() {
-        void* p[] = {X, Y, V, partial, HM, NR, T, io, good, act, done, chunks, cchunks};
-        for (void* q : p) if (q) (void)hipFree(q);
-    }
 };
-
-#define EG(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 
 template <bool HASW>
 hipError_t eg_launch_sweep(const EigsIn& in, const EgArgs& a, hipStream_t st) {
     if (in.nbins == 0) return hipSuccess;
-    const BalSetup& s = *in.bal;
-    const unsigned grid = (unsigned)((in.nbins * (uint64_t)s.width + EGWG - 1) / EGWG);
-    switch (s.width) {
-        case 64: hipLaunchKernelGGL((k_eg_sweep<HASW, 64>), dim3(grid), dim3(EGWG), 0, st, a); break;
-        case 32: hipLaunchKernelGGL((k_eg_sweep<HASW, 32>), dim3(grid), dim3(EGWG), 0, st, a); break;
-        case 16: hipLaunchKernelGGL((k_eg_sweep<HASW, 16>), dim3(grid), dim3(EGWG), 0, st, a); break;
-        default: hipLaunchKernelGGL((k_eg_sweep<HASW, 8>), dim3(grid), dim3(EGWG), 0, st, a); break;
-    }
+    const MxLayout& s = *in.lay;
+    dispatch_width(s.width, [&](auto W) {
+        hipLaunchKernelGGL((k_eg_sweep<HASW, decltype(W)::value>), dim3(grid_for(in.nbins * (uint64_t)s.width, EGWG)), dim3(EGWG), 0, st, a);
+    });
     if (s.nlong) hipLaunchKernelGGL((k_eg_sweep_long<HASW>), dim3(s.nlong), dim3(EGWG), 0, st, a, (const uint32_t*)s.longbins);
     return hipGetLastError();
 }
@@ -315,23 +286,23 @@ hipError_t eg_prepare(EgWork& k, const EigsIn& in, const std::vector<uint32_t>& 
     const uint64_t nb = in.nbins;
     const uint32_t nchr = in.nchr;
     const size_t vbytes = (size_t)nb * 64 + 64;
-    EG(hipMalloc((void**)&k.X, vbytes)); EG(hipMalloc((void**)&k.Y, vbytes)); EG(hipMalloc((void**)&k.V, vbytes));
-    EG(hipMalloc((void**)&k.good, nb + 64)); EG(hipMalloc((void**)&k.act, nb + 64));
-    EG(hipMalloc((void**)&k.done, (size_t)nchr * 4 + 64));
-    EG(hipMalloc((void**)&k.HM, (size_t)nchr * EG_HM * 8)); EG(hipMalloc((void**)&k.NR, (size_t)nchr * EG_NR * 8)); EG(hipMalloc((void**)&k.T, (size_t)nchr * EG_T * 8));
-    EG(hipMemsetAsync(k.X, 0, vbytes, st)); EG(hipMemsetAsync(k.Y, 0, vbytes, st)); EG(hipMemsetAsync(k.V, 0, vbytes, st));
-    EG(hipMemsetAsync(k.NR, 0, (size_t)nchr * EG_NR * 8, st)); EG(hipMemsetAsync(k.HM, 0, (size_t)nchr * EG_HM * 8, st));
+    MKT_TRY(k.X.alloc(nb * 8, 64)); MKT_TRY(k.Y.alloc(nb * 8, 64)); MKT_TRY(k.V.alloc(nb * 8, 64));
+    MKT_TRY(k.good.alloc(nb, 64)); MKT_TRY(k.act.alloc(nb, 64));
+    MKT_TRY(k.done.alloc(nchr, 64));
+    MKT_TRY(k.HM.alloc((size_t)nchr * EG_HM)); MKT_TRY(k.NR.alloc((size_t)nchr * EG_NR)); MKT_TRY(k.T.alloc((size_t)nchr * EG_T));
+    MKT_TRY(hipMemsetAsync(k.X, 0, vbytes, st)); MKT_TRY(hipMemsetAsync(k.Y, 0, vbytes, st)); MKT_TRY(hipMemsetAsync(k.V, 0, vbytes, st));
+    MKT_TRY(hipMemsetAsync(k.NR, 0, (size_t)nchr * EG_NR * 8, st)); MKT_TRY(hipMemsetAsync(k.HM, 0, (size_t)nchr * EG_HM * 8, st));
     EgArgs& a = k.a;
-    a.rowptr = in.bal->rowptr; a.colptr = in.bal->colptr; a.b2 = in.b2; a.cnt = in.cnt; a.off = in.off; a.done = k.done; a.tr = in.bal->tr;
-    a.act = k.act; a.chr = in.chr; a.w = in.w; a.E = in.E; a.X = k.X; a.gx = k.NR; a.Y = k.Y;
+    a.rowptr = in.lay->rowptr; a.colptr = in.lay->colptr; a.b2 = in.b2; a.cnt = in.cnt; a.off = in.off; a.done = k.done; a.tr = in.lay->tr;
+    a.act = k.act; a.chr = in.lay->chr; a.w = in.w; a.E = in.E; a.X = k.X; a.gx = k.NR; a.Y = k.Y;
     a.nbins = nb; a.nchr = nchr; a.ig = (uint32_t)o.ignore_diags; a.clip = o.clip;
     k.h_good.assign(nb, 0);
     if (nb) {
-        hipLaunchKernelGGL(k_eg_good, dim3((unsigned)((nb + EGWG - 1) / EGWG)), dim3(EGWG), 0, st, a, k.good);
-        EG(hipGetLastError());
-        EG(hipMemcpyAsync(k.h_good.data(), k.good, nb, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_eg_good, dim3(grid_for(nb, EGWG)), dim3(EGWG), 0, st, a, k.good);
+        MKT_TRY(hipGetLastError());
+        MKT_TRY(hipMemcpyAsync(k.h_good.data(), k.good, nb, hipMemcpyDeviceToHost, st));
     }
-    EG(hipStreamSynchronize(st));
+    MKT_TRY(hipStreamSynchronize(st));
     const uint32_t need = (uint32_t)(o.min_good > 9 ? o.min_good : 9);
     k.n_good.assign(nchr, 0); k.h_done.assign(nchr, 0); k.h_act = k.h_good;
     std::vector<uint4> chunks;
@@ -349,13 +320,13 @@ hipError_t eg_prepare(EgWork& k, const EigsIn& in, const std::vector<uint32_t>& 
         cc[c].y = (uint32_t)chunks.size() - cc[c].x;
     }
     k.nchunks = (uint32_t)chunks.size();
-    EG(hipMalloc((void**)&k.chunks, (size_t)(k.nchunks + 1) * sizeof(uint4)));
-    EG(hipMalloc((void**)&k.cchunks, (size_t)nchr * sizeof(uint2)));
-    EG(hipMalloc((void**)&k.partial, (size_t)(k.nchunks + 1) * EG_HM * 8));
-    if (k.nchunks) EG(hipMemcpyAsync(k.chunks, chunks.data(), (size_t)k.nchunks * sizeof(uint4), hipMemcpyHostToDevice, st));
-    EG(hipMemcpyAsync(k.cchunks, cc.data(), (size_t)nchr * sizeof(uint2), hipMemcpyHostToDevice, st));
-    EG(hipMemcpyAsync(k.done, k.h_done.data(), (size_t)nchr * 4, hipMemcpyHostToDevice, st));
-    if (nb) EG(hipMemcpyAsync(k.act, k.h_act.data(), nb, hipMemcpyHostToDevice, st));
+    MKT_TRY(k.chunks.alloc(k.nchunks + 1));
+    MKT_TRY(k.cchunks.alloc(nchr));
+    MKT_TRY(k.partial.alloc((size_t)(k.nchunks + 1) * EG_HM));
+    if (k.nchunks) MKT_TRY(hipMemcpyAsync(k.chunks, chunks.data(), (size_t)k.nchunks * sizeof(uint4), hipMemcpyHostToDevice, st));
+    MKT_TRY(hipMemcpyAsync(k.cchunks, cc.data(), (size_t)nchr * sizeof(uint2), hipMemcpyHostToDevice, st));
+    MKT_TRY(hipMemcpyAsync(k.done, k.h_done.data(), (size_t)nchr * 4, hipMemcpyHostToDevice, st));
+    if (nb) MKT_TRY(hipMemcpyAsync(k.act, k.h_act.data(), nb, hipMemcpyHostToDevice, st));
     return hipStreamSynchronize(st);                                      // the vectors above are read by the copies
 }
 
@@ -405,34 +376,33 @@ bool eg_orth(const double S[8][8], const double M[8][8], double T2[8][8]) {
 
 hipError_t eigs_apply(const EigsIn& in, const std::vector<uint32_t>& off, const mkt_eigs_opts& o, const double* x, uint32_t ncols, double* y, hipStream_t st) {
     EgWork k;
-    EG(eg_prepare(k, in, off, o, st));
+    MKT_TRY(eg_prepare(k, in, off, o, st));
     const uint64_t nb = in.nbins;
     if (nb == 0) return hipSuccess;
     const size_t iobytes = (size_t)nb * ncols * 8;
-    EG(hipMalloc((void**)&k.io, iobytes));
-    EG(hipMemcpyAsync(k.io, x, iobytes, hipMemcpyHostToDevice, st));
-    const unsigned grid8 = (unsigned)((nb * 8 + EGWG - 1) / EGWG);
+    MKT_TRY(k.io.alloc((size_t)nb * ncols));
+    MKT_TRY(hipMemcpyAsync(k.io, x, iobytes, hipMemcpyHostToDevice, st));
+    const unsigned grid8 = grid_for(nb * 8, EGWG);
     hipLaunchKernelGGL(k_eg_load, dim3(grid8), dim3(EGWG), 0, st, (const uint8_t*)k.act, (const double*)k.io, ncols, nb, k.X);
-    EG(eg_norms(k, in.nchr, st));                                         // g^T X
-    EG(eg_sweep(in, k.a, st));
-    hipLaunchKernelGGL(k_eg_store, dim3((unsigned)((nb * ncols + EGWG - 1) / EGWG)), dim3(EGWG), 0, st, (const double*)k.Y, ncols, nb, k.io);
-    EG(hipGetLastError());
-    EG(hipMemcpyAsync(y, k.io, iobytes, hipMemcpyDeviceToHost, st));
+    MKT_TRY(eg_norms(k, in.nchr, st));                                         // g^T X
+    MKT_TRY(eg_sweep(in, k.a, st));
+    hipLaunchKernelGGL(k_eg_store, dim3(grid_for(nb * ncols, EGWG)), dim3(EGWG), 0, st, (const double*)k.Y, ncols, nb, k.io);
+    MKT_TRY(hipGetLastError());
+    MKT_TRY(hipMemcpyAsync(y, k.io, iobytes, hipMemcpyDeviceToHost, st));
     return hipStreamSynchronize(st);
 }
 
 hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>& off, const mkt_eigs_opts& o, const double* phasing, hipStream_t st) {
-    eigs_free(s);
+    s = EigsState();
     const uint64_t nb = in.nbins;
     const uint32_t nchr = in.nchr;
     const int ne = o.n_eigs;
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    for (int i = 0; i < 4; ++i) EG(hipEventCreate(&ev[i]));
+    DevEvents<4> ev;
+    MKT_TRY(ev.create());
     EgWork k;
-    EG(hipEventRecord(ev[0], st));
-    EG(eg_prepare(k, in, off, o, st));
+    MKT_TRY(hipEventRecord(ev[0], st));
+    MKT_TRY(eg_prepare(k, in, off, o, st));
     s.vec.assign((size_t)ne * nb, nan);
     s.lambda.assign((size_t)nchr * ne, nan); s.resid.assign((size_t)nchr * ne, nan);
     s.n_good = k.n_good; s.iterations.assign(nchr, 0); s.converged.assign(nchr, 0);
@@ -440,24 +410,24 @@ hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>&
     std::vector<double> hm((size_t)nchr * EG_HM), nr((size_t)nchr * EG_NR), T((size_t)nchr * EG_T, 0.0);
     std::vector<uint8_t> broke(nchr, 0);
     std::vector<uint32_t>& done = k.h_done;
-    const unsigned bgrid = (unsigned)((nb + EGWG - 1) / EGWG);
+    const unsigned bgrid = grid_for(nb, EGWG);
     auto live = [&]() { for (uint32_t c = 0; c < nchr; ++c) if (!done[c]) return true; return false; };
     auto transform = [&]() -> hipError_t {
-        EG(hipMemcpyAsync(k.T, T.data(), T.size() * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_eg_transform, dim3(bgrid), dim3(EGWG), 0, st, in.chr, (const uint32_t*)k.done, (const double*)k.T, nb, k.X, k.Y, k.V);
-        EG(eg_norms(k, nchr, st));
-        EG(hipMemcpyAsync(nr.data(), k.NR, nr.size() * 8, hipMemcpyDeviceToHost, st));
+        MKT_TRY(hipMemcpyAsync(k.T, T.data(), T.size() * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_eg_transform, dim3(bgrid), dim3(EGWG), 0, st, (const uint16_t*)in.lay->chr, (const uint32_t*)k.done, (const double*)k.T, nb, k.X.get(), k.Y.get(), k.V.get());
+        MKT_TRY(eg_norms(k, nchr, st));
+        MKT_TRY(hipMemcpyAsync(nr.data(), k.NR, nr.size() * 8, hipMemcpyDeviceToHost, st));
         return hipStreamSynchronize(st);
     };
     auto fetch_hm = [&]() -> hipError_t {
-        EG(eg_dots(k, nchr, st));
-        EG(hipMemcpyAsync(hm.data(), k.HM, hm.size() * 8, hipMemcpyDeviceToHost, st));
+        MKT_TRY(eg_dots(k, nchr, st));
+        MKT_TRY(hipMemcpyAsync(hm.data(), k.HM, hm.size() * 8, hipMemcpyDeviceToHost, st));
         return hipStreamSynchronize(st);
     };
     // X_0 and its orthonormalisation: the Gram matrix is M of the dot products with Y = X, S = I
     if (nb && live()) {
-        hipLaunchKernelGGL(k_eg_init, dim3((unsigned)((nb * 8 + EGWG - 1) / EGWG)), dim3(EGWG), 0, st, k.a, k.X, k.Y);
-        EG(fetch_hm());
+        hipLaunchKernelGGL(k_eg_init, dim3(grid_for(nb * 8, EGWG)), dim3(EGWG), 0, st, k.a, k.X, k.Y);
+        MKT_TRY(fetch_hm());
         for (uint32_t c = 0; c < nchr; ++c) {
             if (done[c]) continue;
             double S[8][8], M[8][8], T2[8][8];
@@ -467,24 +437,24 @@ hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>&
             for (int i = 0; i < 8; ++i) for (int j = 0; j < 8; ++j) { t[8 * i + j] = S[i][j]; t[72 + 8 * i + j] = T2[i][j]; }
             for (int j = 0; j < 8; ++j) t[64 + j] = 0.0;
         }
-        EG(transform());
+        MKT_TRY(transform());
         bool changed = false;
         for (uint32_t c = 0; c < nchr; ++c) if (broke[c] && !done[c]) { done[c] = 1; changed = true; }   // a start block without full rank: nothing to iterate
-        if (changed) EG(hipMemcpyAsync(k.done, done.data(), (size_t)nchr * 4, hipMemcpyHostToDevice, st));
+        if (changed) MKT_TRY(hipMemcpyAsync(k.done, done.data(), (size_t)nchr * 4, hipMemcpyHostToDevice, st));
     }
-    EG(hipEventRecord(ev[1], st));
-    EG(hipEventSynchronize(ev[1]));
+    MKT_TRY(hipEventRecord(ev[1], st));
+    MKT_TRY(hipEventSynchronize(ev[1]));
     float ms = 0;
-    EG(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    MKT_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     s.setup_ms = ms;
     double sweep_ms = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int it = 0; it < o.max_iters && live(); ++it) {
-        EG(hipEventRecord(ev[2], st));
-        EG(eg_sweep(in, k.a, st));
-        EG(hipEventRecord(ev[3], st));
-        EG(fetch_hm());
-        EG(hipEventElapsedTime(&ms, ev[2], ev[3]));
+        MKT_TRY(hipEventRecord(ev[2], st));
+        MKT_TRY(eg_sweep(in, k.a, st));
+        MKT_TRY(hipEventRecord(ev[3], st));
+        MKT_TRY(fetch_hm());
+        MKT_TRY(hipEventElapsedTime(&ms, ev[2], ev[3]));
         sweep_ms += ms;
         for (uint32_t c = 0; c < nchr; ++c) {
             if (done[c]) continue;
@@ -502,7 +472,7 @@ hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>&
             for (int i = 0; i < 8; ++i) for (int j = 0; j < 8; ++j) { t[8 * i + j] = S[i][j]; t[72 + 8 * i + j] = T2[i][j]; }
             for (int j = 0; j < 8; ++j) t[64 + j] = d[order[j]];
         }
-        EG(transform());
+        MKT_TRY(transform());
         bool changed = false;
         for (uint32_t c = 0; c < nchr; ++c) {
             if (done[c]) continue;
@@ -516,15 +486,15 @@ hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>&
             if (ok) { s.converged[c] = 1; done[c] = 1; changed = true; }
             else if (broke[c]) { done[c] = 1; changed = true; }           // the block lost rank: what it has is reported, not converged
         }
-        if (changed) EG(hipMemcpyAsync(k.done, done.data(), (size_t)nchr * 4, hipMemcpyHostToDevice, st));
+        if (changed) MKT_TRY(hipMemcpyAsync(k.done, done.data(), (size_t)nchr * 4, hipMemcpyHostToDevice, st));
     }
-    EG(hipStreamSynchronize(st));
+    MKT_TRY(hipStreamSynchronize(st));
     s.sweep_ms = sweep_ms;
     const double loop_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     s.small_ms = loop_ms > sweep_ms ? loop_ms - sweep_ms : 0.0;
     // the Ritz vectors of the last iteration of every chromosome: unit norm over the good bins, orientation, NaN elsewhere
     std::vector<double> V((size_t)nb * 8);
-    if (nb) EG(hipMemcpy(V.data(), k.V, (size_t)nb * 64, hipMemcpyDeviceToHost));
+    if (nb) MKT_TRY(hipMemcpy(V.data(), k.V, (size_t)nb * 64, hipMemcpyDeviceToHost));
     s.info.n_chrom = nchr;
     for (uint32_t c = 0; c < nchr; ++c) {
         const uint64_t lo = off[c], hi = c + 1 < nchr ? off[c + 1] : nb;

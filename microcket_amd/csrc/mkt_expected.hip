@@ -2,15 +2,14 @@
 // include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_expected, mkt_matrix_fetch_*).
 //
 // A cell belongs to one SEGMENT: a cis cell of chromosome c on diagonal d to segment off_c + d (the row of the cis table), a trans
-// cell to segment nbins + its row of the trans table.  Once per resolution the cells are grouped by segment: the stable radix passes
-// of the duplicate marker over the segment bits of segment << Bc | cell index (Bc = bits of the cell count), a grouped copy of
-// (bin1, bin2, count), segment pointers by lower bound.  The sums then read 12 bytes per cell in order and gather w[] (nbins doubles,
-// meant to stay in cache).
+// cell to segment nbins + its row of the trans table.  Once per resolution the cells are grouped by segment (KeyGroup, mkt_layout.h,
+// over segment << Bc | cell index, Bc = bits of the cell count) into a copy of (bin1, bin2, count).  The sums then read 12 bytes per
+// cell in order and gather w[] (nbins doubles, meant to stay in cache).
 //
-// Nothing depends on the order anything ran in: there are no floating-point atomics.  A segment's sum is formed by a fixed number of
-// lanes (ExpSetup::width, from cells / segments) walking it with a fixed stride, and a fixed shuffle tree.  A segment of more than
-// kExpLong cells is cut into chunks of kExpChunk cells: one workgroup per chunk with the same shape one level up, then one workgroup
-// per segment over its chunks' partial sums in chunk order.  count_sum rides along as a uint64 (exact in any order).
+// Nothing depends on the order anything ran in: a segment's sum is formed by ExpSetup::width lanes walking it with a
+// fixed stride, and the lane tree.  A segment of more than kExpLong cells is cut into chunks of kExpChunk cells: one workgroup and
+// the workgroup tree per chunk, then one workgroup per segment over its chunks' partial sums in chunk order.  count_sum rides along
+// as a uint64 (exact in any order).
 // n_valid of (chromosome, diagonal) is a popcount over the chromosome's validity bits: M & (M >> d), word by word.
 #include <hip/hip_runtime.h>
 
@@ -18,20 +17,13 @@
 #include <limits>
 
 #include "mkt_expected.h"
-#include "mkt_launch.h"
+#include "mkt_segred.h"
 
 namespace mkt {
 
 constexpr int EXWG = 256;
 typedef unsigned long long ex_u64;
 
-__global__ __launch_bounds__(EXWG) void k_ex_chr(const uint32_t* off, uint32_t nchr, uint64_t nbins, uint16_t* chr) {
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nbins) return;
-    uint32_t lo = 0, hi = nchr;                                          // first c with off[c] > k; off[0] == 0, so lo >= 1
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= k) lo = mid + 1; else hi = mid; }
-    chr[k] = (uint16_t)(lo - 1u);
-}
 __device__ inline uint64_t ex_trans_row(uint32_t a, uint32_t b, uint32_t nchr) { return (uint64_t)a * (2ull * nchr - a - 1ull) / 2ull + (b - a - 1u); }
 __device__ inline uint64_t ex_seg(uint32_t b1, uint32_t b2, const uint16_t* chr, const uint32_t* off, uint32_t nchr, uint64_t nbins) {
     const uint32_t a = chr[b1], b = chr[b2];                             // bin1 <= bin2, so a <= b
@@ -48,13 +40,6 @@ __global__ __launch_bounds__(EXWG) void k_ex_gather(const uint64_t* key, int Bc,
     if (j >= nnz) return;
     const uint32_t s = (uint32_t)(key[j] & ((1ull << Bc) - 1ull));
     sb1[j] = b1[s]; sb2[j] = b2[s]; scnt[j] = cnt[s];
-}
-__global__ __launch_bounds__(EXWG) void k_ex_segptr(const uint64_t* key, int Bc, uint32_t nnz, uint64_t nseg, uint32_t* ptr) {
-    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k > nseg) return;
-    uint32_t lo = 0, hi = nnz;
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((key[mid] >> Bc) < k) lo = mid + 1; else hi = mid; }
-    ptr[k] = k == nseg ? nnz : lo;
 }
 
 // ---- validity bits, word-aligned per chromosome, and n_valid of every (chromosome, diagonal) --------------------------------
@@ -94,7 +79,7 @@ __device__ inline void ex_walk(uint32_t l, uint32_t W, uint32_t p0, uint32_t p1,
         }
     }
 }
-// W lanes per segment (W = 8 .. 64, a power of two): the tree adds lane l + d to lane l for d = W / 2 .. 1
+// W lanes per segment (W = 8 .. 64, a power of two)
 template <bool UNIT, int W>
 __global__ __launch_bounds__(EXWG) void k_ex_sums(const uint32_t* segptr, const uint32_t* sb1, const uint32_t* sb2, const uint32_t* scnt, uint64_t nseg, const double* w, double* S, ex_u64* C) {
     const uint64_t g = ((uint64_t)blockIdx.x * EXWG + threadIdx.x) / W;
@@ -107,20 +92,8 @@ __global__ __launch_bounds__(EXWG) void k_ex_sums(const uint32_t* segptr, const 
         mine = p1 - p0 <= kExpLong;
         if (mine) ex_walk<UNIT>(l, W, p0, p1, sb1, sb2, scnt, w, s, c);
     }
-#pragma unroll
-    for (int d = W / 2; d >= 1; d >>= 1) { s = __dadd_rn(s, __shfl_down(s, d, W)); c += __shfl_down(c, d, W); }
+    lane_tree_v<W>(AddRn(), s, c);
     if (mine && l == 0) { S[g] = s; C[g] = c; }
-}
-// a workgroup's sums: lane tree, then the four wave sums in wave order; valid in thread 0
-__device__ inline void ex_wgsum(double& s, ex_u64& c, double* shs, ex_u64* shc /* [EXWG / 64] each */) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { s = __dadd_rn(s, __shfl_down(s, d, 64)); c += __shfl_down(c, d, 64); }
-    if ((threadIdx.x & 63) == 0) { shs[threadIdx.x >> 6] = s; shc[threadIdx.x >> 6] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s = __dadd_rn(__dadd_rn(__dadd_rn(shs[0], shs[1]), shs[2]), shs[3]);
-        c = shc[0] + shc[1] + shc[2] + shc[3];
-    }
 }
 // one workgroup per chunk of a long segment: the same walk with 256 lanes
 template <bool UNIT>
@@ -131,7 +104,7 @@ __global__ __launch_bounds__(EXWG) void k_ex_chunk(const uint2* ltask, const uin
     double s = 0.0;
     ex_u64 c = 0;
     ex_walk<UNIT>(threadIdx.x, EXWG, t.x, t.y, sb1, sb2, scnt, w, s, c);
-    ex_wgsum(s, c, shs, shc);
+    wg_tree2(AddRn(), s, shs, c, shc);
     if (threadIdx.x == 0) { ps[blockIdx.x] = s; pc[blockIdx.x] = c; }
 }
 // one workgroup per long segment: its chunks' partial sums, lane l taking chunks l, l + 256, ..., the same tree
@@ -142,7 +115,7 @@ __global__ __launch_bounds__(EXWG) void k_ex_long(const uint64_t* lseg, const do
     double s = 0.0;
     ex_u64 c = 0;
     for (uint64_t t = threadIdx.x; t < nt; t += EXWG) { s = __dadd_rn(s, ps[t0 + t]); c += pc[t0 + t]; }
-    ex_wgsum(s, c, shs, shc);
+    wg_tree2(AddRn(), s, shs, c, shc);
     if (threadIdx.x == 0) { S[g] = s; C[g] = c; }
 }
 
@@ -153,7 +126,7 @@ __global__ __launch_bounds__(EXWG) void k_ex_values(const uint32_t* b1, const ui
     if (i >= n) return;
     const uint32_t x = b1[first + i], y = b2[first + i];
     const double wa = w ? w[x] : 1.0, wb = w ? w[y] : 1.0;
-    double v = __longlong_as_double(0x7FF8000000000000ll);               // a cell with a masked bin
+    double v = dev_nan();                                                // a cell with a masked bin
     if (wa == wa && wb == wb) {
         v = __dmul_rn(__dmul_rn((double)cnt[first + i], wa), wb);
         if (kind != 0) {
@@ -165,20 +138,9 @@ __global__ __launch_bounds__(EXWG) void k_ex_values(const uint32_t* b1, const ui
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-void exp_free(ExpSetup& s) {
-    void* p[] = {s.chr, s.sb1, s.sb2, s.scnt, s.segptr, s.ltask, s.lseg, s.moff};
-    for (void* q : p) if (q) (void)hipFree(q);
-    s = ExpSetup();
-}
-void exp_free_tables(ExpTables& t) {
-    void* p[] = {t.d_n, t.d_c, t.d_s, t.d_mask, t.d_part, t.d_cis_e, t.d_cis_sm, t.d_tr_e};
-    for (void* q : p) if (q) (void)hipFree(q);
-    t = ExpTables();
-}
-
-hipError_t exp_setup(ExpSetup& s, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t nnz, uint64_t nbins, const uint32_t* d_off,
+static hipError_t ex_setup(ExpSetup& s, const uint16_t* chr, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t nnz, uint64_t nbins, const uint32_t* d_off,
                      const std::vector<uint32_t>& off, hipStream_t st) {
-    exp_free(s);
+    s = ExpSetup();
     const uint32_t nchr = (uint32_t)off.size();
     if (nnz >= (1ull << 32) || nbins >= (1ull << 32) || nchr == 0 || nchr > 8192u) return hipErrorInvalidValue;
     s.trans_rows = (uint64_t)nchr * (nchr - 1ull) / 2ull;
@@ -194,42 +156,26 @@ hipError_t exp_setup(ExpSetup& s, const uint32_t* b1, const uint32_t* b2, const 
         if (n_c > s.genome_rows) s.genome_rows = n_c;
     }
     s.mwords = moff[nchr];
-    hipError_t e;
-    uint64_t *kA = nullptr, *kB = nullptr;
-    uint32_t* d_radix = nullptr;
-    auto done = [&](hipError_t r) {
-        if (kA) (void)hipFree(kA);
-        if (kB) (void)hipFree(kB);
-        if (d_radix) (void)hipFree(d_radix);
-        if (r != hipSuccess) exp_free(s);
-        return r;
-    };
-    const size_t cbytes = (size_t)nnz * 4 + 64, pbytes = (size_t)(s.nseg + 1) * 4;
-    if ((e = hipMalloc((void**)&s.chr, (size_t)nbins * 2 + 64)) != hipSuccess) return done(e);
-    if ((e = hipMalloc((void**)&s.moff, (size_t)(nchr + 1) * 8)) != hipSuccess) return done(e);
-    if ((e = hipMalloc((void**)&s.sb1, cbytes)) != hipSuccess) return done(e);
-    if ((e = hipMalloc((void**)&s.sb2, cbytes)) != hipSuccess) return done(e);
-    if ((e = hipMalloc((void**)&s.scnt, cbytes)) != hipSuccess) return done(e);
-    if ((e = hipMalloc((void**)&s.segptr, pbytes)) != hipSuccess) return done(e);
-    if ((e = hipMemcpyAsync(s.moff, moff.data(), (size_t)(nchr + 1) * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return done(e);
-    if (nbins) hipLaunchKernelGGL(k_ex_chr, dim3((unsigned)((nbins + EXWG - 1) / EXWG)), dim3(EXWG), 0, st, d_off, nchr, nbins, s.chr);
-    if (nnz == 0) {
-        if ((e = hipMemsetAsync(s.segptr, 0, pbytes, st)) != hipSuccess) return done(e);
-    } else {
-        const unsigned cgrid = (unsigned)((nnz + EXWG - 1) / EXWG), pgrid = (unsigned)((s.nseg + 1 + EXWG - 1) / EXWG);
-        if ((e = hipMalloc((void**)&kA, (size_t)nnz * 8 + 64)) != hipSuccess) return done(e);
-        if ((e = hipMalloc((void**)&kB, (size_t)nnz * 8 + 64)) != hipSuccess) return done(e);
-        if ((e = hipMalloc((void**)&d_radix, radix64_count_bytes(nnz))) != hipSuccess) return done(e);
-        hipLaunchKernelGGL(k_ex_keys, dim3(cgrid), dim3(EXWG), 0, st, b1, b2, (uint32_t)nnz, (const uint16_t*)s.chr, d_off, nchr, nbins, Bc, kA);
-        if ((e = launch_radix64(kA, kB, nnz, Bc, Bs, d_radix, st)) != hipSuccess) return done(e);           // stable: (segment, cell index) order
-        hipLaunchKernelGGL(k_ex_gather, dim3(cgrid), dim3(EXWG), 0, st, (const uint64_t*)kA, Bc, b1, b2, cnt, (uint32_t)nnz, s.sb1, s.sb2, s.scnt);
-        hipLaunchKernelGGL(k_ex_segptr, dim3(pgrid), dim3(EXWG), 0, st, (const uint64_t*)kA, Bc, (uint32_t)nnz, s.nseg, s.segptr);
+    KeyGroup kg;                                                         // its scratch goes behind the synchronise below
+    const size_t pbytes = (size_t)(s.nseg + 1) * 4;
+    MKT_TRY(s.moff.alloc(nchr + 1));
+    MKT_TRY(s.sb1.alloc(nnz, 64));
+    MKT_TRY(s.sb2.alloc(nnz, 64));
+    MKT_TRY(s.scnt.alloc(nnz, 64));
+    MKT_TRY(s.segptr.alloc(s.nseg + 1));
+    MKT_TRY(hipMemcpyAsync(s.moff, moff.data(), (size_t)(nchr + 1) * 8, hipMemcpyHostToDevice, st));
+    if (nnz == 0) MKT_TRY(hipMemsetAsync(s.segptr, 0, pbytes, st));
+    else {
+        MKT_TRY(kg.alloc(nnz));
+        hipLaunchKernelGGL(k_ex_keys, dim3(grid_for(nnz, EXWG)), dim3(EXWG), 0, st, b1, b2, (uint32_t)nnz, chr, d_off, nchr, nbins, Bc, kg.keys());
+        MKT_TRY(kg.group(nnz, Bc, Bs, Bc, s.nseg + 1, s.segptr, st));         // stable: (segment, cell index) order
+        hipLaunchKernelGGL(k_ex_gather, dim3(grid_for(nnz, EXWG)), dim3(EXWG), 0, st, (const uint64_t*)kg.keys(), Bc, b1, b2, cnt, (uint32_t)nnz, s.sb1.get(), s.sb2.get(), s.scnt.get());
     }
-    if ((e = hipGetLastError()) != hipSuccess) return done(e);
+    MKT_TRY(hipGetLastError());
     // the long segments and their chunks, from the pointers (once per resolution)
     std::vector<uint32_t> sp(s.nseg + 1);
-    if ((e = hipMemcpyAsync(sp.data(), s.segptr, pbytes, hipMemcpyDeviceToHost, st)) != hipSuccess) return done(e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return done(e);
+    MKT_TRY(hipMemcpyAsync(sp.data(), s.segptr, pbytes, hipMemcpyDeviceToHost, st));
+    MKT_TRY(hipStreamSynchronize(st));
     std::vector<uint2> tasks;
     std::vector<uint64_t> ls;
     for (uint64_t g = 0; g < s.nseg; ++g) {
@@ -241,51 +187,51 @@ hipError_t exp_setup(ExpSetup& s, const uint32_t* b1, const uint32_t* b2, const 
     s.nlong = (uint32_t)(ls.size() / 3);
     s.ntask = (uint32_t)tasks.size();
     if (s.nlong) {
-        if ((e = hipMalloc((void**)&s.ltask, tasks.size() * sizeof(uint2))) != hipSuccess) return done(e);
-        if ((e = hipMalloc((void**)&s.lseg, ls.size() * 8)) != hipSuccess) return done(e);
-        if ((e = hipMemcpy(s.ltask, tasks.data(), tasks.size() * sizeof(uint2), hipMemcpyHostToDevice)) != hipSuccess) return done(e);
-        if ((e = hipMemcpy(s.lseg, ls.data(), ls.size() * 8, hipMemcpyHostToDevice)) != hipSuccess) return done(e);
+        MKT_TRY(s.ltask.alloc(tasks.size()));
+        MKT_TRY(s.lseg.alloc(ls.size()));
+        MKT_TRY(hipMemcpy(s.ltask, tasks.data(), tasks.size() * sizeof(uint2), hipMemcpyHostToDevice));
+        MKT_TRY(hipMemcpy(s.lseg, ls.data(), ls.size() * 8, hipMemcpyHostToDevice));
     }
-    const uint64_t avg = s.nseg ? nnz / s.nseg : 0;                      // cells a segment holds on average
-    s.width = avg >= 48 ? 64 : avg >= 24 ? 32 : avg >= 12 ? 16 : 8;
+    s.width = seg_width(s.nseg ? nnz / s.nseg : 0);                      // cells a segment holds on average
     s.built = true;
-    return done(hipSuccess);
+    return hipSuccess;
+}
+
+hipError_t exp_setup(ExpSetup& s, const uint16_t* chr, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t nnz, uint64_t nbins, const uint32_t* d_off,
+                     const std::vector<uint32_t>& off, hipStream_t st) {
+    const hipError_t e = ex_setup(s, chr, b1, b2, cnt, nnz, nbins, d_off, off, st);
+    if (e != hipSuccess) s = ExpSetup();                                 // nothing half built stays behind
+    return e;
 }
 
 template <bool UNIT>
 static hipError_t ex_launch_sums(const ExpSetup& s, ExpTables& t, const double* w, hipStream_t st) {
     if (s.nseg == 0) return hipSuccess;
-    const unsigned grid = (unsigned)((s.nseg * (uint64_t)s.width + EXWG - 1) / EXWG);
-    ex_u64* C = (ex_u64*)t.d_c;
-#define EX_SUMS(W) hipLaunchKernelGGL((k_ex_sums<UNIT, W>), dim3(grid), dim3(EXWG), 0, st, (const uint32_t*)s.segptr, (const uint32_t*)s.sb1, (const uint32_t*)s.sb2, (const uint32_t*)s.scnt, s.nseg, w, t.d_s, C)
-    switch (s.width) {
-        case 64: EX_SUMS(64); break;
-        case 32: EX_SUMS(32); break;
-        case 16: EX_SUMS(16); break;
-        default: EX_SUMS(8); break;
-    }
-#undef EX_SUMS
+    ex_u64* C = (ex_u64*)t.d_c.get();
+    dispatch_width(s.width, [&](auto W) {
+        hipLaunchKernelGGL((k_ex_sums<UNIT, decltype(W)::value>), dim3(grid_for(s.nseg * (uint64_t)s.width, EXWG)), dim3(EXWG), 0, st, (const uint32_t*)s.segptr,
+                           (const uint32_t*)s.sb1, (const uint32_t*)s.sb2, (const uint32_t*)s.scnt, s.nseg, w, t.d_s.get(), C);
+    });
     if (s.nlong) {
-        ex_u64* pc = (ex_u64*)(t.d_part + s.ntask);
-        hipLaunchKernelGGL((k_ex_chunk<UNIT>), dim3(s.ntask), dim3(EXWG), 0, st, (const uint2*)s.ltask, (const uint32_t*)s.sb1, (const uint32_t*)s.sb2, (const uint32_t*)s.scnt, w, t.d_part, pc);
-        hipLaunchKernelGGL(k_ex_long, dim3(s.nlong), dim3(EXWG), 0, st, (const uint64_t*)s.lseg, (const double*)t.d_part, (const ex_u64*)pc, t.d_s, C);
+        ex_u64* pc = (ex_u64*)(t.d_part.get() + s.ntask);
+        hipLaunchKernelGGL((k_ex_chunk<UNIT>), dim3(s.ntask), dim3(EXWG), 0, st, (const uint2*)s.ltask, (const uint32_t*)s.sb1, (const uint32_t*)s.sb2, (const uint32_t*)s.scnt, w, t.d_part.get(), pc);
+        hipLaunchKernelGGL(k_ex_long, dim3(s.nlong), dim3(EXWG), 0, st, (const uint64_t*)s.lseg, (const double*)t.d_part, (const ex_u64*)pc, t.d_s.get(), C);
     }
     return hipGetLastError();
 }
 
-hipError_t exp_sums(const ExpSetup& s, ExpTables& t, uint64_t nbins, const uint32_t* d_off, const double* w, hipStream_t st) {
-    exp_free_tables(t);
-    hipError_t e;
-    if ((e = hipMalloc((void**)&t.d_n, (size_t)nbins * 8 + 64)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&t.d_c, (size_t)s.nseg * 8 + 64)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&t.d_s, (size_t)s.nseg * 8 + 64)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&t.d_mask, (size_t)s.mwords * 8 + 64)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&t.d_part, (size_t)s.ntask * 16 + 64)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(t.d_mask, 0, (size_t)s.mwords * 8 + 64, st)) != hipSuccess) return e;
+hipError_t exp_sums(const ExpSetup& s, ExpTables& t, const uint16_t* chr, uint64_t nbins, const uint32_t* d_off, const double* w, hipStream_t st) {
+    t = ExpTables();
+    MKT_TRY(t.d_n.alloc(nbins, 64));
+    MKT_TRY(t.d_c.alloc(s.nseg, 64));
+    MKT_TRY(t.d_s.alloc(s.nseg, 64));
+    MKT_TRY(t.d_mask.alloc(s.mwords, 64));
+    MKT_TRY(t.d_part.alloc(2 * (size_t)s.ntask, 64));
+    MKT_TRY(hipMemsetAsync(t.d_mask, 0, (size_t)s.mwords * 8 + 64, st));
     if (nbins) {
-        const unsigned bgrid = (unsigned)((nbins + EXWG - 1) / EXWG);
-        hipLaunchKernelGGL(k_ex_mask, dim3(bgrid), dim3(EXWG), 0, st, w, nbins, (const uint16_t*)s.chr, d_off, (const uint64_t*)s.moff, (ex_u64*)t.d_mask);
-        hipLaunchKernelGGL(k_ex_nvalid, dim3(bgrid), dim3(EXWG), 0, st, (const ex_u64*)t.d_mask, nbins, (const uint16_t*)s.chr, d_off, (const uint64_t*)s.moff, (ex_u64*)t.d_n);
+        const unsigned bgrid = grid_for(nbins, EXWG);
+        hipLaunchKernelGGL(k_ex_mask, dim3(bgrid), dim3(EXWG), 0, st, w, nbins, chr, d_off, (const uint64_t*)s.moff, (ex_u64*)t.d_mask.get());
+        hipLaunchKernelGGL(k_ex_nvalid, dim3(bgrid), dim3(EXWG), 0, st, (const ex_u64*)t.d_mask.get(), nbins, chr, d_off, (const uint64_t*)s.moff, (ex_u64*)t.d_n.get());
     }
     return w ? ex_launch_sums<false>(s, t, w, st) : ex_launch_sums<true>(s, t, w, st);
 }
@@ -293,14 +239,13 @@ hipError_t exp_sums(const ExpSetup& s, ExpTables& t, uint64_t nbins, const uint3
 hipError_t exp_finish(const ExpSetup& s, ExpTables& t, uint64_t nbins, const std::vector<uint32_t>& off, hipStream_t st) {
     const uint32_t nchr = (uint32_t)off.size();
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    hipError_t e;
     std::vector<uint64_t> c(s.nseg);
     std::vector<double> sm(s.nseg);
     t.cis_n.assign(nbins, 0);
-    if (nbins && (e = hipMemcpyAsync(t.cis_n.data(), t.d_n, (size_t)nbins * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if (s.nseg && (e = hipMemcpyAsync(c.data(), t.d_c, (size_t)s.nseg * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if (s.nseg && (e = hipMemcpyAsync(sm.data(), t.d_s, (size_t)s.nseg * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    if (nbins) MKT_TRY(hipMemcpyAsync(t.cis_n.data(), t.d_n, (size_t)nbins * 8, hipMemcpyDeviceToHost, st));
+    if (s.nseg) MKT_TRY(hipMemcpyAsync(c.data(), t.d_c, (size_t)s.nseg * 8, hipMemcpyDeviceToHost, st));
+    if (s.nseg) MKT_TRY(hipMemcpyAsync(sm.data(), t.d_s, (size_t)s.nseg * 8, hipMemcpyDeviceToHost, st));
+    MKT_TRY(hipStreamSynchronize(st));
     t.cis_c.assign(c.begin(), c.begin() + nbins);
     t.cis_s.assign(sm.begin(), sm.begin() + nbins);
     t.tr_c.assign(c.begin() + nbins, c.end());
@@ -336,21 +281,21 @@ hipError_t exp_finish(const ExpSetup& s, ExpTables& t, uint64_t nbins, const std
         a = b;
         b = a + ((a >> 3) > 1 ? (a >> 3) : 1);
     }
-    if ((e = hipMalloc((void**)&t.d_cis_e, (size_t)G * 8 + 64)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&t.d_cis_sm, (size_t)G * 8 + 64)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&t.d_tr_e, (size_t)s.trans_rows * 8 + 64)) != hipSuccess) return e;
-    if (G && (e = hipMemcpy(t.d_cis_e, t.g_e.data(), (size_t)G * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if (G && (e = hipMemcpy(t.d_cis_sm, t.g_sm.data(), (size_t)G * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if (s.trans_rows && (e = hipMemcpy(t.d_tr_e, t.tr_e.data(), (size_t)s.trans_rows * 8, hipMemcpyHostToDevice)) != hipSuccess) return e;
+    MKT_TRY(t.d_cis_e.alloc(G, 64));
+    MKT_TRY(t.d_cis_sm.alloc(G, 64));
+    MKT_TRY(t.d_tr_e.alloc(s.trans_rows, 64));
+    if (G) MKT_TRY(hipMemcpy(t.d_cis_e, t.g_e.data(), (size_t)G * 8, hipMemcpyHostToDevice));
+    if (G) MKT_TRY(hipMemcpy(t.d_cis_sm, t.g_sm.data(), (size_t)G * 8, hipMemcpyHostToDevice));
+    if (s.trans_rows) MKT_TRY(hipMemcpy(t.d_tr_e, t.tr_e.data(), (size_t)s.trans_rows * 8, hipMemcpyHostToDevice));
     t.built = true;
     return hipSuccess;
 }
 
-hipError_t exp_values(const ExpSetup* s, const ExpTables* t, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t first, uint64_t n,
+hipError_t exp_values(const ExpTables* t, const uint16_t* chr, const uint32_t* b1, const uint32_t* b2, const uint32_t* cnt, uint64_t first, uint64_t n,
                       const uint32_t* d_off, uint32_t nchr, const double* w, int kind, double* out, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    if (kind != 0 && (!s || !t)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ex_values, dim3((unsigned)((n + EXWG - 1) / EXWG)), dim3(EXWG), 0, st, b1, b2, cnt, first, n, w, kind, s ? (const uint16_t*)s->chr : nullptr, d_off, nchr,
+    if (kind != 0 && (!chr || !t)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ex_values, dim3(grid_for(n, EXWG)), dim3(EXWG), 0, st, b1, b2, cnt, first, n, w, kind, chr, d_off, nchr,
                        t ? (const double*)(kind == 2 ? t->d_cis_sm : t->d_cis_e) : nullptr, t ? (const double*)t->d_tr_e : nullptr, out);
     return hipGetLastError();
 }

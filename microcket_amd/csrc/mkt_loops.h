@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/mkt.h"
+#include "mkt_devbuf.h"
 
 namespace mkt {
 
@@ -26,11 +27,10 @@ struct LoopsIn {
 
 // the results of the last mkt_matrix_loops of one resolution: per cell on the device, tables and loops on the host
 struct LoopsState {
-    uint8_t *status = nullptr, *window = nullptr, *chunk = nullptr, *enriched = nullptr;   // [nnz], [nnz], [4 nnz], [nnz]
-    uint16_t* kept = nullptr;                       // [4 nnz] kept positions of a region
-    uint64_t* csum = nullptr;                       // [nnz] Csum_LL of the final window
-    double *r = nullptr, *e = nullptr, *bsum = nullptr, *esum = nullptr;                   // [4 nnz] each, cell-major
-    uint32_t* rowptr = nullptr;                     // the pass's own row pointers when no balance built them
+    DevBuf<uint8_t> status, window, chunk, enriched;   // [nnz], [nnz], [4 nnz], [nnz]
+    DevBuf<uint16_t> kept;                          // [4 nnz] kept positions of a region
+    DevBuf<uint64_t> csum;                          // [nnz] Csum_LL of the final window
+    DevBuf<double> r, e, bsum, esum;                // [4 nnz] each, cell-major
     std::vector<uint64_t> hist;                     // [4][28][2048]
     std::vector<uint32_t> thr;                      // [4][28]
     std::vector<mkt_loop> loops;
@@ -39,7 +39,6 @@ struct LoopsState {
     bool built = false;
 };
 
-void loops_free(LoopsState& s);
 // edge_k of step 5
 double loops_edge(int k);
 // step 7 on the host: T[R][k] from H[R][k][x]

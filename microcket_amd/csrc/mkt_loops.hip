@@ -7,7 +7,7 @@
 // mask.  Lane l then takes the rows a = -w + l, -w + l + lanes, ..: for a valid row inside the chromosome it adds E over the kept
 // positions of the four regions in ascending b (that sum does not look at the cells), finds column j - w of row i + a by a binary
 // search between the row pointers and walks the short run of stored cells up to column j + w, adding v and (for LL) the count.
-// A fixed shuffle tree adds the lanes.  Nothing depends on the order anything ran in: the sums have one shape per (w, lanes).
+// The lane tree adds the lanes.  Nothing depends on the order anything ran in: the sums have one shape per (w, lanes).
 //
 // Window growth makes the work uneven, so there are two launches.  The first gives every cell 16 lanes and the starting window; a
 // candidate whose Csum_LL is below min_ll_count is appended to a list instead of being written (the list's order is arbitrary and
@@ -25,6 +25,7 @@
 #include <unordered_map>
 
 #include "mkt_loops.h"
+#include "mkt_segred.h"
 
 #pragma clang fp contract(off)
 
@@ -45,10 +46,6 @@ struct LpOpts { int p, window, wmax; lp_u64 min_ll; uint32_t min_dist, max_dist;
 
 __constant__ double c_lp_edges[kLpChunks];
 
-__device__ inline uint32_t lp_lower(const uint32_t* a, uint32_t lo, uint32_t hi, uint32_t v) {       // first s in [lo, hi) with a[s] >= v
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 __device__ inline bool lp_valid(const double* w, int64_t k, int64_t lo, int64_t hi) {
     if (k < lo || k >= hi) return false;
     if (!w) return true;
@@ -67,7 +64,7 @@ __device__ inline LpCell lp_cell(const LoopsIn& in, const LpOpts& o, uint64_t s)
     return c;
 }
 __device__ inline void lp_write_none(const LpOut& out, uint64_t s) {
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double nan = dev_nan();
     out.status[s] = MKT_LOOP_NONE; out.window[s] = 0; out.csum[s] = 0;
     for (int R = 0; R < 4; ++R) {
         out.chunk[4 * s + R] = kLpNoChunk; out.kept[4 * s + R] = 0;
@@ -78,7 +75,7 @@ __device__ inline void lp_write_none(const LpOut& out, uint64_t s) {
 // The sums of cell c at window w (w < 0: nothing to do, the group only keeps the barriers company) by the G lanes of its group, lane
 // gl.  E: the group's kLpE doubles of LDS.  Valid in lane 0 afterwards.  Every thread of the workgroup calls this.
 template <int G>
-__device__ inline void lp_sums(const LoopsIn& in, const LpOpts& o, const LpCell& c, int w, uint32_t gl, double* E, double* B, double* Es, uint32_t* P, lp_u64& cs) {
+__device__ inline void lp_sums(const LoopsIn& in, const LpOpts& o, const LpCell& c, int w, uint32_t gl, double* E, double (&B)[4], double (&Es)[4], uint32_t (&P)[4], lp_u64& cs) {
     const int64_t dmid = c.j - c.i;
     for (int t = (int)gl; t <= 4 * w; t += G) {
         const int64_t d = dmid - 2 * w + t;
@@ -109,7 +106,7 @@ __device__ inline void lp_sums(const LoopsIn& in, const LpOpts& o, const LpCell&
         }
         const uint32_t r1 = in.rowptr[row + 1];
         const int64_t c0 = c.j - w;
-        for (uint32_t s = lp_lower(in.b2, in.rowptr[row], r1, c0 < 0 ? 0u : (uint32_t)c0); s < r1; ++s) {       // the stored cells of the row, ascending b
+        for (uint32_t s = seg_lower_bound(in.b2, in.rowptr[row], r1, c0 < 0 ? 0u : (uint32_t)c0); s < r1; ++s) {       // the stored cells of the row, ascending b
             const int64_t col = in.b2[s];
             if (col > c.j + w) break;
             const int b = (int)(col - c.j);
@@ -124,15 +121,11 @@ __device__ inline void lp_sums(const LoopsIn& in, const LpOpts& o, const LpCell&
             if (aa > p && bb <= 1) B[3] += v;
         }
     }
-#pragma unroll
-    for (int d = G / 2; d >= 1; d >>= 1) {                                 // lane l + d is added to lane l
-        for (int R = 0; R < 4; ++R) { B[R] += __shfl_down(B[R], d, G); Es[R] += __shfl_down(Es[R], d, G); P[R] += __shfl_down(P[R], d, G); }
-        cs += __shfl_down(cs, d, G);
-    }
+    lane_tree_v<G>(AddPlain(), B[0], Es[0], P[0], B[1], Es[1], P[1], B[2], Es[2], P[2], B[3], Es[3], P[3], cs);
 }
 // lane 0 of the group: steps 4 and 5 from the sums.  Ecen = E[j - i].
 __device__ inline void lp_finish(const LoopsIn& in, const LpOut& out, const LpCell& c, uint64_t s, int w, double Ecen, const double* B, const double* Es, const uint32_t* P, lp_u64 cs) {
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double nan = dev_nan();
     const double ww = (in.w ? in.w[c.i] : 1.0) * (in.w ? in.w[c.j] : 1.0);
     bool undef = false, over = false;
     for (int R = 0; R < 4; ++R) {
@@ -187,7 +180,7 @@ __global__ __launch_bounds__(LPWG) void k_lp_grow(LoopsIn in, LpOpts o, LpOut ou
         if (lp_valid(in.w, row, c.lo, c.hi)) {
             const uint32_t r1 = in.rowptr[row + 1];
             const int64_t c0 = c.j - o.wmax < c.lo ? c.lo : c.j - o.wmax;
-            for (uint32_t q = lp_lower(in.b2, in.rowptr[row], r1, (uint32_t)c0); q < r1; ++q) {
+            for (uint32_t q = seg_lower_bound(in.b2, in.rowptr[row], r1, (uint32_t)c0); q < r1; ++q) {
                 const int64_t col = in.b2[q];
                 if (col >= c.j) break;
                 const int bb = (int)(c.j - col);
@@ -268,12 +261,6 @@ __global__ __launch_bounds__(LPWG) void k_lp_gather(const uint32_t* list, uint32
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-void loops_free(LoopsState& s) {
-    void* p[] = {s.status, s.window, s.chunk, s.enriched, s.kept, s.csum, s.r, s.e, s.bsum, s.esum, s.rowptr};
-    for (void* q : p) if (q) (void)hipFree(q);
-    s = LoopsState();
-}
-
 double loops_edge(int k) {
     static const double C[3] = {1.0, 1.2599210498948732, 1.5874010519681994};
     return std::ldexp(C[k % 3], k / 3);
@@ -356,87 +343,78 @@ static void lp_cluster(const std::vector<uint32_t>& cell, const std::vector<LpPe
 hipError_t loops_run(LoopsState& s, const LoopsIn& in, const std::vector<uint32_t>& off, const mkt_loops_opts& opts, hipStream_t st) {
     const uint64_t nnz = in.nnz;
     if (nnz >= (1ull << 32)) return hipErrorInvalidValue;
-    hipError_t e;
-    lp_u64 *d_H = nullptr, *d_counters = nullptr;
-    uint32_t *d_T = nullptr, *d_list = nullptr;
-    LpPeak* d_peaks = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto done = [&](hipError_t r) {
-        void* p[] = {d_H, d_counters, d_T, d_list, d_peaks};
-        for (void* q : p) if (q) (void)hipFree(q);
-        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-        return r;
-    };
-#define LRUN(call) do { if ((e = (call)) != hipSuccess) return done(e); } while (0)
-    for (hipEvent_t& x : ev) LRUN(hipEventCreate(&x));
+    DevBuf<lp_u64> d_H, d_counters;
+    DevBuf<uint32_t> d_T, d_list;
+    DevBuf<LpPeak> d_peaks;
+    DevEvents<6> ev;
+    MKT_TRY(ev.create());
     const size_t n1 = (size_t)nnz + 64, n4 = 4 * (size_t)nnz + 64, hbytes = (size_t)4 * kLpChunks * kLpCols * 8;
-    LRUN(hipMalloc((void**)&s.status, n1)); LRUN(hipMalloc((void**)&s.window, n1)); LRUN(hipMalloc((void**)&s.chunk, n4)); LRUN(hipMalloc((void**)&s.enriched, n1));
-    LRUN(hipMalloc((void**)&s.kept, n4 * 2)); LRUN(hipMalloc((void**)&s.csum, n1 * 8));
-    LRUN(hipMalloc((void**)&s.r, n4 * 8)); LRUN(hipMalloc((void**)&s.e, n4 * 8)); LRUN(hipMalloc((void**)&s.bsum, n4 * 8)); LRUN(hipMalloc((void**)&s.esum, n4 * 8));
-    LRUN(hipMalloc((void**)&d_H, hbytes)); LRUN(hipMalloc((void**)&d_counters, 8 * 8)); LRUN(hipMalloc((void**)&d_T, 4 * kLpChunks * 4));
-    LRUN(hipMalloc((void**)&d_list, n1 * 4));
-    LRUN(hipMemsetAsync(d_H, 0, hbytes, st)); LRUN(hipMemsetAsync(d_counters, 0, 8 * 8, st));
+    MKT_TRY(s.status.alloc(n1)); MKT_TRY(s.window.alloc(n1)); MKT_TRY(s.chunk.alloc(n4)); MKT_TRY(s.enriched.alloc(n1));
+    MKT_TRY(s.kept.alloc(n4)); MKT_TRY(s.csum.alloc(n1));
+    MKT_TRY(s.r.alloc(n4)); MKT_TRY(s.e.alloc(n4)); MKT_TRY(s.bsum.alloc(n4)); MKT_TRY(s.esum.alloc(n4));
+    MKT_TRY(d_H.alloc(4 * kLpChunks * kLpCols)); MKT_TRY(d_counters.alloc(8)); MKT_TRY(d_T.alloc(4 * kLpChunks));
+    MKT_TRY(d_list.alloc(n1));
+    MKT_TRY(hipMemsetAsync(d_H, 0, hbytes, st)); MKT_TRY(hipMemsetAsync(d_counters, 0, 8 * 8, st));
     double edges[kLpChunks];
     for (int k = 0; k < kLpChunks; ++k) edges[k] = loops_edge(k);
-    LRUN(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_lp_edges), edges, sizeof edges, 0, hipMemcpyHostToDevice, st));
+    MKT_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_lp_edges), edges, sizeof edges, 0, hipMemcpyHostToDevice, st));
     LpOpts o;
     o.p = opts.peak; o.window = opts.window; o.wmax = opts.window_max; o.min_ll = (lp_u64)opts.min_ll_count; o.min_dist = (uint32_t)opts.min_dist; o.max_dist = (uint32_t)opts.max_dist;
     LpOut out;
-    out.status = s.status; out.window = s.window; out.chunk = s.chunk; out.kept = s.kept; out.csum = (lp_u64*)s.csum;
+    out.status = s.status; out.window = s.window; out.chunk = s.chunk; out.kept = s.kept; out.csum = (lp_u64*)s.csum.get();
     out.r = s.r; out.e = s.e; out.bsum = s.bsum; out.esum = s.esum;
-    out.grow_list = d_list; out.grow_n = (uint32_t*)(d_counters + 7);
-    const unsigned cgrid = (unsigned)((nnz + LPWG - 1) / LPWG);
+    out.grow_list = d_list; out.grow_n = (uint32_t*)(d_counters.get() + 7);
+    const unsigned cgrid = grid_for(nnz, LPWG);
     uint32_t ngrow = 0;
-    LRUN(hipEventRecord(ev[0], st));
+    MKT_TRY(hipEventRecord(ev[0], st));
     if (nnz) {
-        hipLaunchKernelGGL(k_lp_pass, dim3((unsigned)((nnz + LPWG / 16 - 1) / (LPWG / 16))), dim3(LPWG), 0, st, in, o, out);
-        LRUN(hipMemcpyAsync(&ngrow, out.grow_n, 4, hipMemcpyDeviceToHost, st));
-        LRUN(hipStreamSynchronize(st));
-        if (ngrow) hipLaunchKernelGGL(k_lp_grow, dim3((ngrow + LPWG / 64 - 1) / (LPWG / 64)), dim3(LPWG), 0, st, in, o, out, ngrow);
+        hipLaunchKernelGGL(k_lp_pass, dim3(grid_for(nnz, LPWG / 16)), dim3(LPWG), 0, st, in, o, out);
+        MKT_TRY(hipMemcpyAsync(&ngrow, out.grow_n, 4, hipMemcpyDeviceToHost, st));
+        MKT_TRY(hipStreamSynchronize(st));
+        if (ngrow) hipLaunchKernelGGL(k_lp_grow, dim3(grid_for(ngrow, LPWG / 64)), dim3(LPWG), 0, st, in, o, out, ngrow);
     }
-    LRUN(hipEventRecord(ev[1], st));
-    LRUN(hipEventRecord(ev[2], st));
-    if (nnz) hipLaunchKernelGGL(k_lp_hist, dim3((unsigned)((nnz + kLpHistCells - 1) / kLpHistCells)), dim3(LPWG), 0, st, (const uint8_t*)s.status, (const uint8_t*)s.window, (const uint8_t*)s.chunk, (const lp_u64*)s.csum, in.cnt, nnz, o, d_H, d_counters);
-    LRUN(hipEventRecord(ev[3], st));
-    LRUN(hipGetLastError());
+    MKT_TRY(hipEventRecord(ev[1], st));
+    MKT_TRY(hipEventRecord(ev[2], st));
+    if (nnz) hipLaunchKernelGGL(k_lp_hist, dim3(grid_for(nnz, kLpHistCells)), dim3(LPWG), 0, st, (const uint8_t*)s.status, (const uint8_t*)s.window, (const uint8_t*)s.chunk, (const lp_u64*)s.csum.get(), in.cnt, nnz, o, d_H, d_counters);
+    MKT_TRY(hipEventRecord(ev[3], st));
+    MKT_TRY(hipGetLastError());
     s.hist.assign((size_t)4 * kLpChunks * kLpCols, 0);
     s.thr.assign(4 * kLpChunks, 0);
-    LRUN(hipMemcpyAsync(s.hist.data(), d_H, hbytes, hipMemcpyDeviceToHost, st));
-    LRUN(hipStreamSynchronize(st));
+    MKT_TRY(hipMemcpyAsync(s.hist.data(), d_H, hbytes, hipMemcpyDeviceToHost, st));
+    MKT_TRY(hipStreamSynchronize(st));
     loops_thresholds(s.hist.data(), opts.fdr, s.thr.data());
-    LRUN(hipMemcpyAsync(d_T, s.thr.data(), 4 * kLpChunks * 4, hipMemcpyHostToDevice, st));
-    LRUN(hipEventRecord(ev[4], st));
+    MKT_TRY(hipMemcpyAsync(d_T, s.thr.data(), 4 * kLpChunks * 4, hipMemcpyHostToDevice, st));
+    MKT_TRY(hipEventRecord(ev[4], st));
     if (nnz) hipLaunchKernelGGL(k_lp_flag, dim3(cgrid), dim3(LPWG), 0, st, (const uint8_t*)s.status, (const uint8_t*)s.chunk, in.cnt, nnz, (const uint32_t*)d_T, s.enriched, d_list, d_counters);
-    LRUN(hipEventRecord(ev[5], st));
-    LRUN(hipGetLastError());
+    MKT_TRY(hipEventRecord(ev[5], st));
+    MKT_TRY(hipGetLastError());
     lp_u64 hc[8];
-    LRUN(hipMemcpyAsync(hc, d_counters, sizeof hc, hipMemcpyDeviceToHost, st));
-    LRUN(hipStreamSynchronize(st));
+    MKT_TRY(hipMemcpyAsync(hc, d_counters, sizeof hc, hipMemcpyDeviceToHost, st));
+    MKT_TRY(hipStreamSynchronize(st));
     float ms = 0;
-    LRUN(hipEventElapsedTime(&ms, ev[0], ev[1])); s.pass_ms = ms;
-    LRUN(hipEventElapsedTime(&ms, ev[2], ev[3])); s.hist_ms = ms;
-    LRUN(hipEventElapsedTime(&ms, ev[4], ev[5])); s.flag_ms = ms;
+    MKT_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); s.pass_ms = ms;
+    MKT_TRY(hipEventElapsedTime(&ms, ev[2], ev[3])); s.hist_ms = ms;
+    MKT_TRY(hipEventElapsedTime(&ms, ev[4], ev[5])); s.flag_ms = ms;
     const uint32_t nen = (uint32_t)hc[6];
     std::vector<uint32_t> cell(nen);
     std::vector<LpPeak> pk(nen);
     if (nen) {
-        LRUN(hipMemcpyAsync(cell.data(), d_list, (size_t)nen * 4, hipMemcpyDeviceToHost, st));
-        LRUN(hipStreamSynchronize(st));
+        MKT_TRY(hipMemcpyAsync(cell.data(), d_list, (size_t)nen * 4, hipMemcpyDeviceToHost, st));
+        MKT_TRY(hipStreamSynchronize(st));
         std::sort(cell.begin(), cell.end());
-        LRUN(hipMemcpyAsync(d_list, cell.data(), (size_t)nen * 4, hipMemcpyHostToDevice, st));          // `cell` is not touched before the next synchronise
-        LRUN(hipMalloc((void**)&d_peaks, (size_t)nen * sizeof(LpPeak)));
-        hipLaunchKernelGGL(k_lp_gather, dim3((nen + LPWG - 1) / LPWG), dim3(LPWG), 0, st, (const uint32_t*)d_list, nen, in.b1, in.b2, in.cnt, (const uint8_t*)s.window, (const double*)s.r, d_peaks);
-        LRUN(hipGetLastError());
-        LRUN(hipMemcpyAsync(pk.data(), d_peaks, (size_t)nen * sizeof(LpPeak), hipMemcpyDeviceToHost, st));
-        LRUN(hipStreamSynchronize(st));
+        MKT_TRY(hipMemcpyAsync(d_list, cell.data(), (size_t)nen * 4, hipMemcpyHostToDevice, st));          // `cell` is not touched before the next synchronise
+        MKT_TRY(d_peaks.alloc(nen));
+        hipLaunchKernelGGL(k_lp_gather, dim3(grid_for(nen, LPWG)), dim3(LPWG), 0, st, (const uint32_t*)d_list, nen, in.b1, in.b2, in.cnt, (const uint8_t*)s.window, (const double*)s.r, d_peaks);
+        MKT_TRY(hipGetLastError());
+        MKT_TRY(hipMemcpyAsync(pk.data(), d_peaks, (size_t)nen * sizeof(LpPeak), hipMemcpyDeviceToHost, st));
+        MKT_TRY(hipStreamSynchronize(st));
     }
-#undef LRUN
     s.loops.clear();
     lp_cluster(cell, pk, off, in.nbins, opts.cluster_radius, s.loops);
     s.info.cells = nnz; s.info.candidates = hc[0]; s.info.tested = hc[1]; s.info.undefined = hc[2]; s.info.over = hc[3];
     s.info.grew = hc[4]; s.info.at_max = hc[5]; s.info.enriched = nen; s.info.loops = s.loops.size();
     s.built = true;
-    return done(hipSuccess);
+    return hipSuccess;
 }
 
 }  // namespace mkt

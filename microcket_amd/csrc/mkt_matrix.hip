@@ -29,6 +29,8 @@
 #include "mkt_loops.h"
 #include "mkt_eigs.h"
 #include "mkt_launch.h"
+#include "mkt_layout.h"
+#include "mkt_segred.h"
 #include "mkt_sortlib.h"
 
 using namespace mkt;
@@ -272,14 +274,14 @@ struct MxRes {
     uint64_t nbins = 0;
     int B = 0;
     std::vector<uint32_t> off;
-    uint32_t* d_off = nullptr;
+    DevBuf<uint32_t> d_off;
     uint64_t nnz = 0, text_bytes = 0;
-    uint32_t *d_b1 = nullptr, *d_b2 = nullptr, *d_cnt = nullptr;
-    uint8_t* d_text = nullptr;
+    DevBuf<uint32_t> d_b1, d_b2, d_cnt;
+    DevBuf<uint8_t> d_text;
     double ms = 0;
-    // balancing (mkt_matrix_balance): the setup lives as long as the cells, the weights until the next balance or run
-    BalSetup bal;
-    double* d_w = nullptr;
+    MxLayout lay;                                   // built on demand by whoever needs it first; lives as long as the cells
+    // balancing (mkt_matrix_balance): the weights live until the next balance or run
+    DevBuf<double> d_w;
     bool balanced = false;
     double bal_setup_ms = 0, bal_iter_ms = 0;
     // expected tables (mkt_matrix_expected): the grouping lives as long as the cells, the tables until the next balance or run
@@ -301,10 +303,10 @@ struct mkt_matrix {
     std::vector<std::string> names;
     std::vector<uint32_t> lens;
     std::unordered_map<std::string, uint32_t> index;
-    MxTab* d_tab = nullptr;
-    MxCounters* d_counters = nullptr;
-    MxRec* d_rec = nullptr; uint64_t rec_cap = 0, n = 0;
-    uint8_t* d_text = nullptr; size_t text_cap = 0;
+    DevBuf<MxTab> d_tab;
+    DevBuf<MxCounters> d_counters;
+    DevBuf<MxRec> d_rec; uint64_t rec_cap = 0, n = 0;
+    DevBuf<uint8_t> d_text; size_t text_cap = 0;
     std::string carry;                              // an incomplete last line of the text seen so far
     bool ran = false;
     uint64_t pairs = 0, skipped = 0;
@@ -321,7 +323,12 @@ static int mfail(mkt_matrix* m, int code, const char* fmt, ...) {
     if (m) m->err = buf; else g_mx_create_err = buf;
     return code;
 }
-#define MCHK(m, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mfail((m), MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
+// a HIP error of section `sec` ("balance: ", ...); oom_own: out of memory has its own code there (the analyses and the run)
+static int mx_hip(mkt_matrix* m, const char* sec, hipError_t e, bool oom_own) {
+    return mfail(m, oom_own && e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "%sHIP call failed: %s", sec, hipGetErrorString(e));
+}
+#define MX(m, sec, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mx_hip((m), (sec), e_, true); } while (0)
+#define MCHK(m, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return mx_hip((m), "", e_, false); } while (0)
 
 // lines name \t length [\t ...]; empty lines and '#' lines are ignored.  Returns an empty string or what is wrong.
 static std::string mx_parse_table(const char* txt, size_t len, std::vector<std::string>& names, std::vector<uint32_t>& lens) {
@@ -353,19 +360,13 @@ static std::string mx_parse_table(const char* txt, size_t len, std::vector<std::
 
 static void mx_free_results(mkt_matrix* m) {
     for (MxRes& r : m->res) {
-        if (r.d_b1) (void)hipFree(r.d_b1);
-        if (r.d_b2) (void)hipFree(r.d_b2);
-        if (r.d_cnt) (void)hipFree(r.d_cnt);
-        if (r.d_text) (void)hipFree(r.d_text);
-        r.d_b1 = r.d_b2 = r.d_cnt = nullptr; r.d_text = nullptr; r.nnz = 0; r.text_bytes = 0; r.ms = 0;
-        bal_free(r.bal);
-        if (r.d_w) (void)hipFree(r.d_w);
-        r.d_w = nullptr; r.balanced = false; r.bal_setup_ms = r.bal_iter_ms = 0;
-        exp_free(r.exs);
-        exp_free_tables(r.ext);
+        r.d_b1.reset(); r.d_b2.reset(); r.d_cnt.reset(); r.d_text.reset();
+        r.nnz = 0; r.text_bytes = 0; r.ms = 0;
+        r.lay = MxLayout();
+        r.d_w.reset(); r.balanced = false; r.bal_setup_ms = r.bal_iter_ms = 0;
+        r.exs = ExpSetup(); r.ext = ExpTables();
         r.exp_setup_ms = r.exp_sums_ms = 0;
-        loops_free(r.lps);
-        eigs_free(r.egs);
+        r.lps = LoopsState(); r.egs = EigsState();
     }
     m->ran = false;
 }
@@ -374,42 +375,122 @@ static int mx_reserve_rec(mkt_matrix* m, uint64_t need) {
     if (need <= m->rec_cap) return MKT_OK;
     uint64_t ncap = m->rec_cap ? m->rec_cap : (1ull << 20);
     while (ncap < need) ncap *= 2;
-    MxRec* nb = nullptr;
-    { hipError_t e_ = hipMalloc((void**)&nb, ncap * sizeof(MxRec)); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of %llu pair records failed: %s", (unsigned long long)ncap, hipGetErrorString(e_)); }
+    DevBuf<MxRec> nb;
+    { hipError_t e_ = nb.alloc(ncap); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of %llu pair records failed: %s", (unsigned long long)ncap, hipGetErrorString(e_)); }
     if (m->d_rec) {
         MCHK(m, hipStreamSynchronize(m->stream));
         if (m->n) MCHK(m, hipMemcpy(nb, m->d_rec, m->n * sizeof(MxRec), hipMemcpyDeviceToDevice));
-        MCHK(m, hipFree(m->d_rec));
     }
-    m->d_rec = nb; m->rec_cap = ncap;
+    m->d_rec = std::move(nb); m->rec_cap = ncap;
     return MKT_OK;
 }
 static int mx_reserve_text(mkt_matrix* m, size_t need) {
     if (need <= m->text_cap) return MKT_OK;
     size_t ncap = m->text_cap ? m->text_cap : ((size_t)64 << 20);
     while (ncap < need) ncap *= 2;
-    if (m->d_text) { MCHK(m, hipStreamSynchronize(m->stream)); MCHK(m, hipFree(m->d_text)); m->d_text = nullptr; m->text_cap = 0; }
-    { hipError_t e_ = hipMalloc((void**)&m->d_text, ncap + 64); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of %zu text bytes failed: %s", ncap, hipGetErrorString(e_)); }
+    if (m->d_text) { MCHK(m, hipStreamSynchronize(m->stream)); m->d_text.reset(); m->text_cap = 0; }
+    { hipError_t e_ = m->d_text.alloc(ncap, 64); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of %zu text bytes failed: %s", ncap, hipGetErrorString(e_)); }
     m->text_cap = ncap;
     return MKT_OK;
 }
 // d_text[0, n) holds whole lines: index them, one record per line behind the ones that are there
 static int mx_process_text(mkt_matrix* m, size_t n) {
     if (n == 0) return MKT_OK;
+    DevBuf<uint64_t> starts;
     uint64_t* d_starts = nullptr;
     uint64_t nl = 0;
     MCHK(m, sort_line_index(m->d_text, n, m->stream, &d_starts, &nl));
+    starts.adopt(d_starts);
     int rc = nl ? mx_reserve_rec(m, m->n + nl) : MKT_OK;
     if (rc == MKT_OK && nl) {
-        hipLaunchKernelGGL(k_mx_parse, dim3((unsigned)((nl + MXWG - 1) / MXWG)), dim3(MXWG), 0, m->stream, (const uint8_t*)m->d_text, (const uint64_t*)d_starts, nl,
-                           (const MxTab*)m->d_tab, m->d_rec + m->n, m->d_counters);
+        hipLaunchKernelGGL(k_mx_parse, dim3(grid_for(nl, MXWG)), dim3(MXWG), 0, m->stream, (const uint8_t*)m->d_text, (const uint64_t*)d_starts, nl,
+                           (const MxTab*)m->d_tab, m->d_rec.get() + m->n, m->d_counters.get());
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
         if (e != hipSuccess) rc = mfail(m, MKT_E_HIP, "parsing %llu .pairs lines failed: %s", (unsigned long long)nl, hipGetErrorString(e));
         else m->n += nl;
     }
-    (void)hipFree(d_starts);
     return rc;
+}
+
+// what an entry point needs of a resolution before it may go on; each has its message
+enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16 };
+static int mx_need(mkt_matrix* m, uint32_t res_index, const MxRes& r, int need, const char* what = nullptr) {
+    if ((need & MX_RAN) && !m->ran) return mfail(m, MKT_E_STATE, "%s before run", what);
+    if ((need & MX_WEIGHTS) && !(m->ran && r.balanced)) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    if ((need & MX_TABLES) && !(m->ran && r.ext.built)) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    if ((need & MX_LOOPS) && !(m->ran && r.lps.built)) return mfail(m, MKT_E_STATE, "no loops for resolution index %u: loops first", res_index);
+    if ((need & MX_EIGS) && !(m->ran && r.egs.built)) return mfail(m, MKT_E_STATE, "no eigenvectors for resolution index %u: eigs first", res_index);
+    return MKT_OK;
+}
+// the resolution of an entry point, or the error: the object, the index, then what it needs
+static int mx_res(mkt_matrix* m, uint32_t res_index, MxRes** r, int need = 0, const char* what = nullptr) {
+    if (!m) return MKT_E_ARG;
+    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    *r = &m->res[res_index];
+    return mx_need(m, res_index, **r, need, what);
+}
+#define MX_RES(...) do { const int rc_ = mx_res(__VA_ARGS__); if (rc_) return rc_; } while (0)
+// the resident cells of a resolution, as the layout and the analyses take them
+static MxCells mx_cells(const MxRes& r) {
+    MxCells c;
+    c.b1 = r.d_b1; c.b2 = r.d_b2; c.cnt = r.d_cnt; c.off = r.d_off;
+    c.nnz = r.nnz; c.nbins = r.nbins; c.nchr = (uint32_t)r.off.size(); c.B = r.B;
+    return c;
+}
+// device time of work() between the object's two events; the stream is idle when it returns
+template <typename F>
+static hipError_t mx_timed(mkt_matrix* m, double* ms_out, F&& work) {
+    MKT_TRY(hipEventRecord(m->ev0, m->stream));
+    MKT_TRY(work());
+    MKT_TRY(hipEventRecord(m->ev1, m->stream));
+    MKT_TRY(hipStreamSynchronize(m->stream));
+    float ms = 0;
+    MKT_TRY(hipEventElapsedTime(&ms, m->ev0, m->ev1));
+    *ms_out = ms;
+    return hipSuccess;
+}
+
+// the scratch of one mkt_matrix_run: the two key buffers and the counters of the radix passes, the sums of the scans
+struct MxScratch {
+    DevBuf<uint64_t> a, b, sums;
+    DevBuf<uint32_t> radix, pos;                                         // pos: a resolution's head positions, until its time is taken
+    hipError_t alloc(uint64_t n, uint64_t nv) {
+        MKT_TRY(a.alloc(n, 64));
+        MKT_TRY(b.alloc(n, 64));
+        MKT_TRY(radix.alloc(0, radix64_count_bytes(n)));
+        return sums.alloc((nv + MX_CPW - 1) / MX_CPW + 2);               // (at most nv cells: room for the text passes' sums, which are more than the head passes')
+    }
+};
+// one resolution's cells and COO text from the n records (nv of them binned).  A cell count that cannot be (0, or above nv) is left
+// in r.nnz for the caller and nothing more is done.
+static hipError_t mx_bin(mkt_matrix* m, MxRes& r, MxScratch& sc, uint64_t n, uint64_t nv) {
+    hipStream_t st = m->stream;
+    const uint64_t hblocks = (nv + MX_TILE - 1) / MX_TILE;
+    uint64_t *kA = sc.a, *kB = sc.b, *sums = sc.sums;                    // the passes swap the two as needed
+    hipLaunchKernelGGL(k_mx_keys, dim3(grid_for(n, MXWG)), dim3(MXWG), 0, st, (const MxRec*)m->d_rec, n, (const uint32_t*)r.d_off, r.r, r.B, r.nbins, kA);
+    MKT_TRY(launch_radix64(kA, kB, n, 0, 2 * r.B, sc.radix, st));
+    hipLaunchKernelGGL(k_mx_head_count, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, sums);
+    MKT_TRY(launch_exscan(sums, hblocks, sums + hblocks, st));
+    uint64_t nnz = 0, tb = 0;
+    MKT_TRY(hipMemcpyAsync(&nnz, sums + hblocks, 8, hipMemcpyDeviceToHost, st));
+    MKT_TRY(hipStreamSynchronize(st));
+    r.nnz = nnz;
+    if (nnz == 0 || nnz > nv) return hipSuccess;
+    DevBuf<uint32_t>& pos = sc.pos;
+    MKT_TRY(r.d_b1.alloc(nnz)); MKT_TRY(r.d_b2.alloc(nnz)); MKT_TRY(r.d_cnt.alloc(nnz));
+    MKT_TRY(pos.alloc(nnz));
+    hipLaunchKernelGGL(k_mx_cells, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, (const uint64_t*)sums, r.B, r.d_b1.get(), r.d_b2.get(), pos.get());
+    const uint64_t tblocks = (nnz + MX_CPW - 1) / MX_CPW;
+    hipLaunchKernelGGL(k_mx_counts, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)pos, nnz, nv, r.d_cnt.get(), sums);
+    MKT_TRY(launch_exscan(sums, tblocks, sums + tblocks, st));
+    MKT_TRY(hipMemcpyAsync(&tb, sums + tblocks, 8, hipMemcpyDeviceToHost, st));
+    MKT_TRY(hipStreamSynchronize(st));
+    MKT_TRY(r.d_text.alloc(tb, 64));
+    hipLaunchKernelGGL(k_mx_text, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)r.d_cnt, nnz, (const uint64_t*)sums, r.d_text.get());
+    MKT_TRY(hipGetLastError());
+    r.text_bytes = tb;
+    return hipSuccess;
 }
 
 extern "C" {
@@ -460,12 +541,12 @@ int mkt_matrix_create(int device, const char* chromsizes, size_t len, const uint
         while (ht->hash[s]) s = (s + 1u) & (kMxSlots - 1u);            // at most 8192 names in 16384 slots
         ht->hash[s] = h; ht->idx[s] = (uint16_t)i;
     }
-    if ((e = hipMalloc((void**)&m->d_tab, sizeof(MxTab))) != hipSuccess) return dfail("hipMalloc", e);
+    if ((e = m->d_tab.alloc(1)) != hipSuccess) return dfail("hipMalloc", e);
     if ((e = hipMemcpy(m->d_tab, ht, sizeof(MxTab), hipMemcpyHostToDevice)) != hipSuccess) return dfail("hipMemcpy", e);
-    if ((e = hipMalloc((void**)&m->d_counters, sizeof(MxCounters))) != hipSuccess) return dfail("hipMalloc", e);
+    if ((e = m->d_counters.alloc(1)) != hipSuccess) return dfail("hipMalloc", e);
     if ((e = hipMemset(m->d_counters, 0, sizeof(MxCounters))) != hipSuccess) return dfail("hipMemset", e);
     for (MxRes& r : m->res) {
-        if ((e = hipMalloc((void**)&r.d_off, (size_t)nc * 4)) != hipSuccess) return dfail("hipMalloc", e);
+        if ((e = r.d_off.alloc(nc)) != hipSuccess) return dfail("hipMalloc", e);
         if ((e = hipMemcpy(r.d_off, r.off.data(), (size_t)nc * 4, hipMemcpyHostToDevice)) != hipSuccess) return dfail("hipMemcpy", e);
     }
     *out = m;
@@ -476,12 +557,8 @@ void mkt_matrix_destroy(mkt_matrix* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    mx_free_results(m);
-    for (MxRes& r : m->res) if (r.d_off) (void)hipFree(r.d_off);
-    if (m->d_tab) (void)hipFree(m->d_tab);
-    if (m->d_counters) (void)hipFree(m->d_counters);
-    if (m->d_rec) (void)hipFree(m->d_rec);
-    if (m->d_text) (void)hipFree(m->d_text);
+    m->res.clear();                                                     // every device buffer goes with its owner, before the stream
+    m->d_tab.reset(); m->d_counters.reset(); m->d_rec.reset(); m->d_text.reset();
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -500,7 +577,7 @@ int mkt_matrix_add(mkt_matrix* m, const char* bytes, size_t n) {
     int rc = mx_reserve_text(m, c + end);
     if (rc) return rc;
     if (c) MCHK(m, hipMemcpyAsync(m->d_text, m->carry.data(), c, hipMemcpyHostToDevice, m->stream));
-    MCHK(m, hipMemcpyAsync(m->d_text + c, bytes, end, hipMemcpyHostToDevice, m->stream));
+    MCHK(m, hipMemcpyAsync(m->d_text.get() + c, bytes, end, hipMemcpyHostToDevice, m->stream));
     MCHK(m, hipStreamSynchronize(m->stream));                          // the caller may reuse `bytes`
     m->carry.assign(bytes + end, n - end);
     return mx_process_text(m, c + end);
@@ -515,9 +592,9 @@ int mkt_matrix_add_device(mkt_matrix* m, const void* d_bytes, size_t n) {
     if (rc) return rc;
     MCHK(m, hipMemcpyAsync(m->d_text, d_bytes, n, hipMemcpyDeviceToDevice, m->stream));
     char last = 0;
-    MCHK(m, hipMemcpyAsync(&last, m->d_text + n - 1, 1, hipMemcpyDeviceToHost, m->stream));
+    MCHK(m, hipMemcpyAsync(&last, m->d_text.get() + n - 1, 1, hipMemcpyDeviceToHost, m->stream));
     MCHK(m, hipStreamSynchronize(m->stream));
-    if (last != '\n') { const char nl = '\n'; MCHK(m, hipMemcpy(m->d_text + n, &nl, 1, hipMemcpyHostToDevice)); ++n; }
+    if (last != '\n') { const char nl = '\n'; MCHK(m, hipMemcpy(m->d_text.get() + n, &nl, 1, hipMemcpyHostToDevice)); ++n; }
     return mx_process_text(m, n);
 }
 int mkt_matrix_add_keys(mkt_matrix* m, mkt_ctx* ctx, int drop_last, const uint8_t* skip_flags, size_t n_flags) {
@@ -551,22 +628,20 @@ int mkt_matrix_add_keys(mkt_matrix* m, mkt_ctx* ctx, int drop_last, const uint8_
     MCHK(m, hipSetDevice(m->device));
     if (m->ran) mx_free_results(m);
     if ((rc = mx_reserve_rec(m, m->n + n))) return rc;
-    uint16_t* d_lut = nullptr;
-    uint8_t* d_flags = nullptr;
-    MCHK(m, hipMalloc((void**)&d_lut, kChrSlots * sizeof(uint16_t)));
+    DevBuf<uint16_t> d_lut;
+    DevBuf<uint8_t> d_flags;
+    MCHK(m, d_lut.alloc(kChrSlots));
     hipError_t e = hipMemcpyAsync(d_lut, lut.data(), kChrSlots * sizeof(uint16_t), hipMemcpyHostToDevice, m->stream);
     if (e == hipSuccess && skip_flags) {
-        e = hipMalloc((void**)&d_flags, n);
+        e = d_flags.alloc(n);
         if (e == hipSuccess) e = hipMemcpyAsync(d_flags, skip_flags, n, hipMemcpyHostToDevice, m->stream);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_mx_from_keys, dim3((unsigned)((n + MXWG - 1) / MXWG)), dim3(MXWG), 0, m->stream, (const KeyRec*)d_keys, n, (const uint16_t*)d_lut,
-                           (const uint8_t*)d_flags, (const MxTab*)m->d_tab, m->d_rec + m->n, m->d_counters);
+        hipLaunchKernelGGL(k_mx_from_keys, dim3(grid_for(n, MXWG)), dim3(MXWG), 0, m->stream, (const KeyRec*)d_keys, n, (const uint16_t*)d_lut,
+                           (const uint8_t*)d_flags, (const MxTab*)m->d_tab, m->d_rec.get() + m->n, m->d_counters.get());
         e = hipGetLastError();
     }
     const hipError_t e2 = hipStreamSynchronize(m->stream);             // the context may go on (and the host buffers be reused) when this returns
-    (void)hipFree(d_lut);
-    if (d_flags) (void)hipFree(d_flags);
     if (e != hipSuccess || e2 != hipSuccess) return mfail(m, MKT_E_HIP, "records from %llu keys failed: %s", (unsigned long long)n, hipGetErrorString(e != hipSuccess ? e : e2));
     m->n += n;
     return MKT_OK;
@@ -592,54 +667,19 @@ int mkt_matrix_run(mkt_matrix* m, uint64_t* pairs, uint64_t* skipped) {
     if (hc.err) return mfail(m, MKT_E_ARG, "not .pairs text (error bits 0x%x: 1 = fewer than five fields / non-decimal position)", hc.err);
     const uint64_t n = m->n, nv = n - hc.skipped - hc.none;
     m->pairs = n - hc.none; m->skipped = hc.skipped;
-    std::vector<void*> owned;
-    auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
-#define MALLOC(ptr, bytes_) do { hipError_t e_ = hipMalloc((void**)&(ptr), (bytes_)); if (e_ != hipSuccess) { cleanup(); mx_free_results(m); return mfail(m, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", (size_t)(bytes_), hipGetErrorString(e_)); } } while (0)
-#define MRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); mx_free_results(m); return mfail(m, MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    uint64_t *kA = nullptr, *kB = nullptr, *d_sums = nullptr;
-    uint32_t *d_radix = nullptr, *d_pos = nullptr;
-    const uint64_t hblocks = (nv + MX_TILE - 1) / MX_TILE;
-    if (nv) {
-        MALLOC(kA, n * 8 + 64); owned.push_back(kA);
-        MALLOC(kB, n * 8 + 64); owned.push_back(kB);
-        MALLOC(d_radix, radix64_count_bytes(n)); owned.push_back(d_radix);
-        MALLOC(d_sums, ((nv + MX_CPW - 1) / MX_CPW + 2) * 8); owned.push_back(d_sums);   // (at most nv cells: room for the text passes' sums, which are more than the head passes')
-    }
+    MxScratch sc;
+    const hipError_t ea = nv ? sc.alloc(n, nv) : hipSuccess;
+    if (ea != hipSuccess) return mfail(m, MKT_E_NOMEM, "hipMalloc of the sort scratch of %llu pairs failed: %s", (unsigned long long)n, hipGetErrorString(ea));
     for (MxRes& r : m->res) {
         if (nv == 0) continue;
-        MRUN(hipEventRecord(m->ev0, st));
-        hipLaunchKernelGGL(k_mx_keys, dim3((unsigned)((n + MXWG - 1) / MXWG)), dim3(MXWG), 0, st, (const MxRec*)m->d_rec, n, (const uint32_t*)r.d_off, r.r, r.B, r.nbins, kA);
-        MRUN(launch_radix64(kA, kB, n, 0, 2 * r.B, d_radix, st));
-        hipLaunchKernelGGL(k_mx_head_count, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, d_sums);
-        MRUN(launch_exscan(d_sums, hblocks, d_sums + hblocks, st));
-        uint64_t nnz = 0;
-        MRUN(hipMemcpyAsync(&nnz, d_sums + hblocks, 8, hipMemcpyDeviceToHost, st));
-        MRUN(hipStreamSynchronize(st));
-        if (nnz == 0 || nnz > nv) { cleanup(); mx_free_results(m); return mfail(m, MKT_E_KERNEL, "%llu cells from %llu binned pairs", (unsigned long long)nnz, (unsigned long long)nv); }
-        MALLOC(r.d_b1, nnz * 4); MALLOC(r.d_b2, nnz * 4); MALLOC(r.d_cnt, nnz * 4);
-        MALLOC(d_pos, nnz * 4);
-        owned.push_back(d_pos);
-        hipLaunchKernelGGL(k_mx_cells, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, (const uint64_t*)d_sums, r.B, r.d_b1, r.d_b2, d_pos);
-        const uint64_t tblocks = (nnz + MX_CPW - 1) / MX_CPW;
-        hipLaunchKernelGGL(k_mx_counts, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)d_pos, nnz, nv, r.d_cnt, d_sums);
-        MRUN(launch_exscan(d_sums, tblocks, d_sums + tblocks, st));
-        uint64_t tb = 0;
-        MRUN(hipMemcpyAsync(&tb, d_sums + tblocks, 8, hipMemcpyDeviceToHost, st));
-        MRUN(hipStreamSynchronize(st));
-        MALLOC(r.d_text, tb + 64);
-        hipLaunchKernelGGL(k_mx_text, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)r.d_cnt, nnz, (const uint64_t*)d_sums, r.d_text);
-        MRUN(hipGetLastError());
-        MRUN(hipEventRecord(m->ev1, st));
-        MRUN(hipStreamSynchronize(st));
-        float ms = 0;
-        MRUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
-        r.ms = ms; r.nnz = nnz; r.text_bytes = tb;
-        owned.pop_back();
-        (void)hipFree(d_pos); d_pos = nullptr;
+        const hipError_t e = mx_timed(m, &r.ms, [&] { return mx_bin(m, r, sc, n, nv); });
+        sc.pos.reset();
+        if (e == hipSuccess && r.nnz != 0 && r.nnz <= nv) continue;
+        const uint64_t nnz = r.nnz;
+        mx_free_results(m);                                              // a failure leaves no half-made result behind
+        if (e != hipSuccess) return mx_hip(m, "run: ", e, true);
+        return mfail(m, MKT_E_KERNEL, "%llu cells from %llu binned pairs", (unsigned long long)nnz, (unsigned long long)nv);
     }
-    cleanup();
-#undef MALLOC
-#undef MRUN
     m->ran = true;
     if (pairs) *pairs = m->pairs;
     if (skipped) *skipped = m->skipped;
@@ -660,26 +700,25 @@ int mkt_matrix_timing(const mkt_matrix* m, uint32_t res_index, double* ms) {
     return MKT_OK;
 }
 int mkt_matrix_fetch(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint32_t* bin1, uint32_t* bin2, uint32_t* count) {
-    if (!m) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
-    if (!m->ran) return mfail(m, MKT_E_STATE, "fetch before run");
-    const MxRes& r = m->res[res_index];
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_RAN, "fetch");
+    const MxRes& r = *rp;
     if (first > r.nnz || n > r.nnz - first) return mfail(m, MKT_E_ARG, "cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nnz);
     MCHK(m, hipSetDevice(m->device));
     if (n == 0) return MKT_OK;
-    if (bin1) MCHK(m, hipMemcpy(bin1, r.d_b1 + first, n * 4, hipMemcpyDeviceToHost));
-    if (bin2) MCHK(m, hipMemcpy(bin2, r.d_b2 + first, n * 4, hipMemcpyDeviceToHost));
-    if (count) MCHK(m, hipMemcpy(count, r.d_cnt + first, n * 4, hipMemcpyDeviceToHost));
+    if (bin1) MCHK(m, hipMemcpy(bin1, r.d_b1.get() + first, n * 4, hipMemcpyDeviceToHost));
+    if (bin2) MCHK(m, hipMemcpy(bin2, r.d_b2.get() + first, n * 4, hipMemcpyDeviceToHost));
+    if (count) MCHK(m, hipMemcpy(count, r.d_cnt.get() + first, n * 4, hipMemcpyDeviceToHost));
     return MKT_OK;
 }
 int mkt_matrix_fetch_text(mkt_matrix* m, uint32_t res_index, uint64_t off, char* out, size_t n) {
-    if (!m || (n && !out)) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
-    if (!m->ran) return mfail(m, MKT_E_STATE, "fetch before run");
-    const MxRes& r = m->res[res_index];
+    if (n && !out) return MKT_E_ARG;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_RAN, "fetch");
+    const MxRes& r = *rp;
     if (off > r.text_bytes || n > r.text_bytes - off) return mfail(m, MKT_E_ARG, "range past the end of the COO text");
     MCHK(m, hipSetDevice(m->device));
-    if (n) MCHK(m, hipMemcpy(out, r.d_text + off, n, hipMemcpyDeviceToHost));
+    if (n) MCHK(m, hipMemcpy(out, r.d_text.get() + off, n, hipMemcpyDeviceToHost));
     return MKT_OK;
 }
 
@@ -690,9 +729,9 @@ void mkt_balance_opts_default(mkt_balance_opts* o) {
 }
 
 int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts* opts, mkt_balance_stats* stats) {
-    if (!m) return MKT_E_ARG;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    if (m && stats) memset(stats, 0, sizeof *stats);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
     mkt_balance_opts o;
     mkt_balance_opts_default(&o);
     if (opts) o = *opts;
@@ -703,55 +742,39 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     if (!(o.tol >= 0.0)) return mfail(m, MKT_E_ARG, "balance: tol %g is negative or NaN", o.tol);
     if (o.max_iters <= 0) return mfail(m, MKT_E_ARG, "balance: max_iters %d (at least 1 is needed)", o.max_iters);
     if (o.reserved != 0) return mfail(m, MKT_E_ARG, "balance: the reserved field is not 0");
-    if (!m->ran) return mfail(m, MKT_E_STATE, "balance before run");
+    if (const int rc = mx_need(m, res_index, *rp, MX_RAN, "balance")) return rc;
     if (m->res[res_index].nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "balance: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)m->res[res_index].nnz);
     MCHK(m, hipSetDevice(m->device));
-    MxRes& r = m->res[res_index];
+    MxRes& r = *rp;
     hipStream_t st = m->stream;
     const uint64_t nb = r.nbins;
-    if (r.d_w) { (void)hipFree(r.d_w); r.d_w = nullptr; }
+    r.d_w.reset();
     r.balanced = false; r.bal_iter_ms = 0;
-    exp_free_tables(r.ext);                                             // tables of other weights
-    loops_free(r.lps);
-    eigs_free(r.egs);
-    double *d_bias = nullptr, *d_m = nullptr, *d_part = nullptr;
-    BalState* d_state = nullptr;
-    auto cleanup = [&]() {
-        if (d_bias) (void)hipFree(d_bias);
-        if (d_m) (void)hipFree(d_m);
-        if (d_part) (void)hipFree(d_part);
-        if (d_state) (void)hipFree(d_state);
-        if (!r.balanced && r.d_w) { (void)hipFree(r.d_w); r.d_w = nullptr; }
-    };
-#define BRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "balance: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    if (!r.bal.built) {
-        BRUN(hipEventRecord(m->ev0, st));
-        BRUN(bal_setup(r.bal, r.d_b1, r.d_b2, r.d_cnt, r.nnz, nb, r.B, st));
-        BRUN(hipEventRecord(m->ev1, st));
-        BRUN(hipEventSynchronize(m->ev1));
-        float ms = 0;
-        BRUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
-        r.bal_setup_ms = ms;
-    } else r.bal_setup_ms = 0;
-    const size_t vbytes = (size_t)nb * 8 + 64;
-    BRUN(hipMalloc((void**)&d_bias, vbytes));
-    BRUN(hipMalloc((void**)&d_m, vbytes));
-    BRUN(hipMalloc((void**)&r.d_w, vbytes));
-    BRUN(hipMalloc((void**)&d_part, bal_partial_bytes(nb)));
-    BRUN(hipMalloc((void**)&d_state, sizeof(BalState)));
+    r.ext = ExpTables();                                                // tables of other weights
+    r.lps = LoopsState(); r.egs = EigsState();
+    DevBuf<double> d_bias, d_m, d_part, d_w;                            // d_w becomes r.d_w at the end: a failure leaves no weights
+    DevBuf<BalState> d_state;
+#define BRUN(call) MX(m, "balance: ", call)
+    r.bal_setup_ms = 0;
+    if (!r.lay.has_full) BRUN(mx_timed(m, &r.bal_setup_ms, [&] { return layout_full(r.lay, mx_cells(r), st); }));
+    BRUN(d_bias.alloc(nb, 64));
+    BRUN(d_m.alloc(nb, 64));
+    BRUN(d_w.alloc(nb, 64));
+    BRUN(d_part.alloc(0, bal_partial_bytes(nb)));
+    BRUN(d_state.alloc(1));
     BRUN(hipMemsetAsync(d_state, 0, sizeof(BalState), st));
 
     // steps 2 and 3 on the host, from one nbins-sized copy of the exact (integer-valued) marginals
     std::vector<double> bias(nb, 1.0), hm(nb);
     const uint32_t ig = (uint32_t)o.ignore_diags;
     if (o.min_nnz > 0) {
-        BRUN(bal_marginal(r.bal, r.d_b2, r.d_cnt, nb, ig, true, nullptr, d_m, st));
+        BRUN(bal_marginal(r.lay, r.d_b2, r.d_cnt, nb, ig, true, nullptr, d_m, st));
         BRUN(hipMemcpyAsync(hm.data(), d_m, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
         BRUN(hipStreamSynchronize(st));
         for (uint64_t k = 0; k < nb; ++k) if (hm[k] < (double)o.min_nnz) bias[k] = 0.0;
     }
     BRUN(hipMemcpyAsync(d_bias, bias.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
-    BRUN(bal_marginal(r.bal, r.d_b2, r.d_cnt, nb, ig, false, d_bias, d_m, st));
+    BRUN(bal_marginal(r.lay, r.d_b2, r.d_cnt, nb, ig, false, d_bias, d_m, st));
     BRUN(hipMemcpyAsync(hm.data(), d_m, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
     BRUN(hipStreamSynchronize(st));
     if (o.min_count > 0.0)
@@ -787,23 +810,21 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     memset(&hs, 0, sizeof hs);
     uint32_t per_look = 4;
     if (const char* e = getenv("MKT_BALANCE_BATCH")) { const int v = atoi(e); if (v >= 1 && v <= 64) per_look = (uint32_t)v; }
-    BRUN(hipEventRecord(m->ev0, st));
-    for (uint32_t left = (uint32_t)o.max_iters; left && !hs.done;) {
-        const uint32_t batch = left < per_look ? left : per_look;
-        BRUN(bal_iterate(r.bal, r.d_b2, r.d_cnt, nb, ig, o.tol, batch, d_bias, d_m, d_part, d_state, st));
-        BRUN(hipMemcpyAsync(&hs, d_state, sizeof hs, hipMemcpyDeviceToHost, st));
-        BRUN(hipStreamSynchronize(st));
-        left -= batch;
-    }
-    BRUN(hipEventRecord(m->ev1, st));
-    BRUN(bal_weights(d_bias, nb, d_state, r.d_w, st));
+    BRUN(mx_timed(m, &r.bal_iter_ms, [&]() -> hipError_t {
+        for (uint32_t left = (uint32_t)o.max_iters; left && !hs.done;) {
+            const uint32_t batch = left < per_look ? left : per_look;
+            MKT_TRY(bal_iterate(r.lay, r.d_b2, r.d_cnt, nb, ig, o.tol, batch, d_bias, d_m, d_part, d_state, st));
+            MKT_TRY(hipMemcpyAsync(&hs, d_state, sizeof hs, hipMemcpyDeviceToHost, st));
+            MKT_TRY(hipStreamSynchronize(st));
+            left -= batch;
+        }
+        return hipSuccess;
+    }));
+    BRUN(bal_weights(d_bias, nb, d_state, d_w, st));
     BRUN(hipStreamSynchronize(st));
-    float ms = 0;
-    BRUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
 #undef BRUN
-    r.bal_iter_ms = ms;
+    r.d_w = std::move(d_w);
     r.balanced = true;
-    cleanup();
     if (stats) {
         stats->iterations = hs.iters; stats->converged = hs.converged ? 1 : 0; stats->var = hs.var; stats->scale = hs.mean;
         stats->masked = hs.empty ? nb : masked;
@@ -812,13 +833,13 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
 }
 
 int mkt_matrix_fetch_weights(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, double* out) {
-    if (!m || (n && !out)) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
-    const MxRes& r = m->res[res_index];
-    if (!m->ran || !r.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    if (n && !out) return MKT_E_ARG;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_WEIGHTS);
+    const MxRes& r = *rp;
     if (first > r.nbins || n > r.nbins - first) return mfail(m, MKT_E_ARG, "weights [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nbins);
     MCHK(m, hipSetDevice(m->device));
-    if (n) MCHK(m, hipMemcpy(out, r.d_w + first, n * 8, hipMemcpyDeviceToHost));
+    if (n) MCHK(m, hipMemcpy(out, r.d_w.get() + first, n * 8, hipMemcpyDeviceToHost));
     return MKT_OK;
 }
 
@@ -837,43 +858,34 @@ void mkt_expected_opts_default(mkt_expected_opts* o) {
 }
 
 int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_opts* opts, mkt_expected_info* info) {
-    if (!m) return MKT_E_ARG;
-    if (info) memset(info, 0, sizeof *info);
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
     mkt_expected_opts o;
     mkt_expected_opts_default(&o);
     if (opts) o = *opts;
     if (o.use_weights != 0 && o.use_weights != 1) return mfail(m, MKT_E_ARG, "expected: use_weights %d (0 or 1)", o.use_weights);
     if (o.reserved != 0) return mfail(m, MKT_E_ARG, "expected: the reserved field is not 0");
-    if (!m->ran) return mfail(m, MKT_E_STATE, "expected before run");
-    MxRes& r = m->res[res_index];
-    if (o.use_weights && !r.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | (o.use_weights ? MX_WEIGHTS : 0), "expected")) return rc;
     if (r.nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "expected: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)r.nnz);
     MCHK(m, hipSetDevice(m->device));
     hipStream_t st = m->stream;
-    exp_free_tables(r.ext);
-    loops_free(r.lps);                                                  // loops of other tables
-    eigs_free(r.egs);
-    r.exp_sums_ms = 0;
-#define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { exp_free_tables(r.ext); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "expected: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    float ms = 0;
-    if (!r.exs.built) {
-        ERUN(hipEventRecord(m->ev0, st));
-        const hipError_t e = exp_setup(r.exs, r.d_b1, r.d_b2, r.d_cnt, r.nnz, r.nbins, r.d_off, r.off, st);
+    r.ext = ExpTables();
+    r.lps = LoopsState(); r.egs = EigsState();                          // loops and eigenvectors of other tables
+    r.exp_sums_ms = r.exp_setup_ms = 0;
+#define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { r.ext = ExpTables(); return mx_hip(m, "expected: ", e_, true); } } while (0)
+    if (!r.exs.built) {                                                 // with the chromosome of a bin when nothing has built it yet
+        const hipError_t e = mx_timed(m, &r.exp_setup_ms, [&]() -> hipError_t {
+            MKT_TRY(layout_chr(r.lay, mx_cells(r), st));
+            return exp_setup(r.exs, r.lay.chr, r.d_b1, r.d_b2, r.d_cnt, r.nnz, r.nbins, r.d_off, r.off, st);
+        });
         if (e == hipErrorInvalidValue) return mfail(m, MKT_E_CAPACITY, "expected: segment ids and cell indices of resolution index %u do not fit 64 bits together", res_index);
         ERUN(e);
-        ERUN(hipEventRecord(m->ev1, st));
-        ERUN(hipEventSynchronize(m->ev1));
-        ERUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
-        r.exp_setup_ms = ms;
-    } else r.exp_setup_ms = 0;
-    ERUN(hipEventRecord(m->ev0, st));
-    ERUN(exp_sums(r.exs, r.ext, r.nbins, r.d_off, o.use_weights ? r.d_w : nullptr, st));
-    ERUN(hipEventRecord(m->ev1, st));
+    }
+    ERUN(mx_timed(m, &r.exp_sums_ms, [&] { return exp_sums(r.exs, r.ext, r.lay.chr, r.nbins, r.d_off, o.use_weights ? r.d_w.get() : nullptr, st); }));
     ERUN(exp_finish(r.exs, r.ext, r.nbins, r.off, st));
-    ERUN(hipEventElapsedTime(&ms, m->ev0, m->ev1));
 #undef ERUN
-    r.exp_sums_ms = ms;
     r.ext.use_weights = o.use_weights;
     if (info) {
         info->cis_rows = r.nbins; info->trans_rows = r.exs.trans_rows; info->genome_rows = r.exs.genome_rows;
@@ -886,10 +898,9 @@ int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_op
 
 // the tables of res_index for a fetch of rows [first, first + n) of table `which` (0 cis, 1 trans, 2 genome), or the error
 static int mx_expected_tables(mkt_matrix* m, uint32_t res_index, const char* what, uint64_t first, uint64_t n, int which, const ExpTables** out) {
-    if (!m) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
-    const MxRes& r = m->res[res_index];
-    if (!m->ran || !r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_TABLES);
+    const MxRes& r = *rp;
     const uint64_t rows = which == 0 ? r.nbins : which == 1 ? r.exs.trans_rows : r.exs.genome_rows;
     if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "%s rows [%llu, +%llu) of %llu", what, (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
     *out = &r.ext;
@@ -925,28 +936,26 @@ int mkt_matrix_fetch_expected_genome(mkt_matrix* m, uint32_t res_index, uint64_t
 }
 
 int mkt_matrix_fetch_values(mkt_matrix* m, uint32_t res_index, int kind, uint64_t first, uint64_t n, double* out) {
-    if (!m) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
     if (kind != MKT_VALUE_BALANCED && kind != MKT_VALUE_OE && kind != MKT_VALUE_OE_SMOOTH) return mfail(m, MKT_E_ARG, "values: kind %d (0 balanced, 1 oe, 2 oe_smooth)", kind);
-    const MxRes& r = m->res[res_index];
-    if (!m->ran) return mfail(m, MKT_E_STATE, "values before run");
-    if (kind != MKT_VALUE_BALANCED && !r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
-    if (!r.ext.built && !r.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
+    const MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | (kind != MKT_VALUE_BALANCED ? MX_TABLES : 0), "values")) return rc;
+    if (!r.ext.built) { if (const int rc = mx_need(m, res_index, r, MX_WEIGHTS)) return rc; }
     if (first > r.nnz || n > r.nnz - first) return mfail(m, MKT_E_ARG, "values of cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nnz);
     if (!out || n == 0) return MKT_OK;
     MCHK(m, hipSetDevice(m->device));
-    const double* w = r.ext.built && !r.ext.use_weights ? nullptr : r.d_w;       // the tables' own option; without tables, the weights
+    const double* w = r.ext.built && !r.ext.use_weights ? nullptr : r.d_w.get();       // the tables' own option; without tables, the weights
     const uint64_t piece = n < (1ull << 24) ? n : (1ull << 24);
-    double* d_out = nullptr;
-    { hipError_t e_ = hipMalloc((void**)&d_out, (size_t)piece * 8); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "values: hipMalloc of %llu doubles failed: %s", (unsigned long long)piece, hipGetErrorString(e_)); }
+    DevBuf<double> d_out;
+    { hipError_t e_ = d_out.alloc(piece); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "values: hipMalloc of %llu doubles failed: %s", (unsigned long long)piece, hipGetErrorString(e_)); }
     for (uint64_t at = 0; at < n; at += piece) {
         const uint64_t k = n - at < piece ? n - at : piece;
-        hipError_t e = exp_values(r.ext.built ? &r.exs : nullptr, r.ext.built ? &r.ext : nullptr, r.d_b1, r.d_b2, r.d_cnt, first + at, k, r.d_off, (uint32_t)r.off.size(), w, kind, d_out, m->stream);
+        hipError_t e = exp_values(r.ext.built ? &r.ext : nullptr, r.ext.built ? r.lay.chr.get() : nullptr, r.d_b1, r.d_b2, r.d_cnt, first + at, k, r.d_off, (uint32_t)r.off.size(), w, kind, d_out, m->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(out + at, d_out, (size_t)k * 8, hipMemcpyDeviceToHost, m->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-        if (e != hipSuccess) { (void)hipFree(d_out); return mfail(m, MKT_E_HIP, "values: cells [%llu, +%llu) failed: %s", (unsigned long long)(first + at), (unsigned long long)k, hipGetErrorString(e)); }
+        if (e != hipSuccess) return mfail(m, MKT_E_HIP, "values: cells [%llu, +%llu) failed: %s", (unsigned long long)(first + at), (unsigned long long)k, hipGetErrorString(e));
     }
-    (void)hipFree(d_out);
     return MKT_OK;
 }
 
@@ -969,9 +978,9 @@ void mkt_loops_opts_default(mkt_loops_opts* o) {
 }
 
 int mkt_matrix_loops(mkt_matrix* m, uint32_t res_index, const mkt_loops_opts* opts, mkt_loops_info* info) {
-    if (!m) return MKT_E_ARG;
-    if (info) memset(info, 0, sizeof *info);
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
     mkt_loops_opts o;
     mkt_loops_opts_default(&o);
     if (opts) o = *opts;
@@ -983,22 +992,16 @@ int mkt_matrix_loops(mkt_matrix* m, uint32_t res_index, const mkt_loops_opts* op
     if (!(o.fdr > 0.0 && o.fdr < 1.0)) return mfail(m, MKT_E_ARG, "loops: fdr %g is not inside (0, 1)", o.fdr);
     if (o.cluster_radius < 0) return mfail(m, MKT_E_ARG, "loops: cluster_radius %d is negative", o.cluster_radius);
     if (o.reserved != 0) return mfail(m, MKT_E_ARG, "loops: the reserved field is not 0");
-    if (!m->ran) return mfail(m, MKT_E_STATE, "loops before run");
-    MxRes& r = m->res[res_index];
-    if (!r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "loops")) return rc;
     MCHK(m, hipSetDevice(m->device));
     hipStream_t st = m->stream;
-    loops_free(r.lps);
-#define LRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { loops_free(r.lps); return mfail(m, e_ == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "loops: %s failed: %s", #call, hipGetErrorString(e_)); } } while (0)
-    const uint32_t* rowptr = r.bal.built ? r.bal.rowptr : nullptr;
-    if (!rowptr) {                                                      // no balance has run: the row pointers alone
-        LRUN(hipMalloc((void**)&r.lps.rowptr, (size_t)(r.nbins + 1) * 4));
-        LRUN(bal_rowptr(r.lps.rowptr, r.d_b1, r.nnz, r.nbins, st));
-        rowptr = r.lps.rowptr;
-    }
+    r.lps = LoopsState();
+#define LRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { r.lps = LoopsState(); return mx_hip(m, "loops: ", e_, true); } } while (0)
+    LRUN(layout_rows(r.lay, mx_cells(r), st));                          // the row pointers are all the pass needs
     LoopsIn in;
-    in.b1 = r.d_b1; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = rowptr; in.off = r.d_off; in.chr = r.exs.chr;
-    in.w = r.ext.use_weights ? r.d_w : nullptr; in.E = r.ext.d_cis_sm;
+    in.b1 = r.d_b1; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = r.lay.rowptr; in.off = r.d_off; in.chr = r.lay.chr;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr; in.E = r.ext.d_cis_sm;
     in.nnz = r.nnz; in.nbins = r.nbins; in.genome_rows = r.exs.genome_rows; in.nchr = (uint32_t)r.off.size();
     LRUN(loops_run(r.lps, in, r.off, o, st));
 #undef LRUN
@@ -1006,55 +1009,45 @@ int mkt_matrix_loops(mkt_matrix* m, uint32_t res_index, const mkt_loops_opts* op
     return MKT_OK;
 }
 
-// the results of res_index for a fetch, or the error
-static int mx_loops_state(mkt_matrix* m, uint32_t res_index, const LoopsState** out) {
-    if (!m) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
-    const MxRes& r = m->res[res_index];
-    if (!m->ran || !r.lps.built) return mfail(m, MKT_E_STATE, "no loops for resolution index %u: loops first", res_index);
-    *out = &r.lps;
-    return MKT_OK;
-}
-
 int mkt_matrix_fetch_loop_cells(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status, uint8_t* window, uint8_t* chunk, double* r,
                                 uint8_t* enriched, uint64_t* csum_ll, uint16_t* kept, double* bsum, double* esum, double* e) {
-    const LoopsState* s = nullptr;
-    const int rc = mx_loops_state(m, res_index, &s);
-    if (rc) return rc;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    const LoopsState* s = &rp->lps;
     const uint64_t nnz = m->res[res_index].nnz;
     if (first > nnz || n > nnz - first) return mfail(m, MKT_E_ARG, "loop cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nnz);
     MCHK(m, hipSetDevice(m->device));
     if (n == 0) return MKT_OK;
-    if (status) MCHK(m, hipMemcpy(status, s->status + first, n, hipMemcpyDeviceToHost));
-    if (window) MCHK(m, hipMemcpy(window, s->window + first, n, hipMemcpyDeviceToHost));
-    if (chunk) MCHK(m, hipMemcpy(chunk, s->chunk + 4 * first, 4 * n, hipMemcpyDeviceToHost));
-    if (r) MCHK(m, hipMemcpy(r, s->r + 4 * first, 32 * n, hipMemcpyDeviceToHost));
-    if (enriched) MCHK(m, hipMemcpy(enriched, s->enriched + first, n, hipMemcpyDeviceToHost));
-    if (csum_ll) MCHK(m, hipMemcpy(csum_ll, s->csum + first, 8 * n, hipMemcpyDeviceToHost));
-    if (kept) MCHK(m, hipMemcpy(kept, s->kept + 4 * first, 8 * n, hipMemcpyDeviceToHost));
-    if (bsum) MCHK(m, hipMemcpy(bsum, s->bsum + 4 * first, 32 * n, hipMemcpyDeviceToHost));
-    if (esum) MCHK(m, hipMemcpy(esum, s->esum + 4 * first, 32 * n, hipMemcpyDeviceToHost));
-    if (e) MCHK(m, hipMemcpy(e, s->e + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (status) MCHK(m, hipMemcpy(status, s->status.get() + first, n, hipMemcpyDeviceToHost));
+    if (window) MCHK(m, hipMemcpy(window, s->window.get() + first, n, hipMemcpyDeviceToHost));
+    if (chunk) MCHK(m, hipMemcpy(chunk, s->chunk.get() + 4 * first, 4 * n, hipMemcpyDeviceToHost));
+    if (r) MCHK(m, hipMemcpy(r, s->r.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (enriched) MCHK(m, hipMemcpy(enriched, s->enriched.get() + first, n, hipMemcpyDeviceToHost));
+    if (csum_ll) MCHK(m, hipMemcpy(csum_ll, s->csum.get() + first, 8 * n, hipMemcpyDeviceToHost));
+    if (kept) MCHK(m, hipMemcpy(kept, s->kept.get() + 4 * first, 8 * n, hipMemcpyDeviceToHost));
+    if (bsum) MCHK(m, hipMemcpy(bsum, s->bsum.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (esum) MCHK(m, hipMemcpy(esum, s->esum.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (e) MCHK(m, hipMemcpy(e, s->e.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
     return MKT_OK;
 }
 int mkt_matrix_fetch_loop_hist(mkt_matrix* m, uint32_t res_index, uint64_t* hist) {
-    const LoopsState* s = nullptr;
-    const int rc = mx_loops_state(m, res_index, &s);
-    if (rc) return rc;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    const LoopsState* s = &rp->lps;
     if (hist) memcpy(hist, s->hist.data(), s->hist.size() * 8);
     return MKT_OK;
 }
 int mkt_matrix_fetch_loop_thresholds(mkt_matrix* m, uint32_t res_index, uint32_t* thresholds) {
-    const LoopsState* s = nullptr;
-    const int rc = mx_loops_state(m, res_index, &s);
-    if (rc) return rc;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    const LoopsState* s = &rp->lps;
     if (thresholds) memcpy(thresholds, s->thr.data(), s->thr.size() * 4);
     return MKT_OK;
 }
 int mkt_matrix_fetch_loops(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, mkt_loop* out) {
-    const LoopsState* s = nullptr;
-    const int rc = mx_loops_state(m, res_index, &s);
-    if (rc) return rc;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    const LoopsState* s = &rp->lps;
     const uint64_t rows = s->loops.size();
     if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "loops [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
     if (out && n) memcpy(out, s->loops.data() + first, (size_t)n * sizeof(mkt_loop));
@@ -1082,9 +1075,10 @@ void mkt_eigs_opts_default(mkt_eigs_opts* o) {
 
 }  // extern "C"
 
-// the options checked, the tables there and the balance setup built (without a balance when none has run): what eigs and apply share
+// the options checked, the tables there and the full layout built: what eigs and apply share
 static int mx_eigs_ready(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, mkt_eigs_opts& o, EigsIn& in, double* setup_ms) {
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
     mkt_eigs_opts_default(&o);
     if (opts) o = *opts;
     if (o.n_eigs < 1 || o.n_eigs > 4) return mfail(m, MKT_E_ARG, "eigs: n_eigs %d (1 .. 4)", o.n_eigs);
@@ -1094,25 +1088,17 @@ static int mx_eigs_ready(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts*
     if (!(o.tol > 0.0 && o.tol < 1.0)) return mfail(m, MKT_E_ARG, "eigs: tol %g is not inside (0, 1)", o.tol);
     if (!(o.clip >= 0.0)) return mfail(m, MKT_E_ARG, "eigs: clip %g is negative or NaN", o.clip);
     if (o.reserved != 0) return mfail(m, MKT_E_ARG, "eigs: the reserved field is not 0");
-    if (!m->ran) return mfail(m, MKT_E_STATE, "eigs before run");
-    MxRes& r = m->res[res_index];
-    if (!r.ext.built) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "eigs")) return rc;
     MCHK(m, hipSetDevice(m->device));
     hipStream_t st = m->stream;
     if (setup_ms) *setup_ms = 0;
-    if (!r.bal.built) {                                                 // raw counts: the row pointers and the transposed copy without a balance
-        MCHK(m, hipEventRecord(m->ev0, st));
-        const hipError_t e = bal_setup(r.bal, r.d_b1, r.d_b2, r.d_cnt, r.nnz, r.nbins, r.B, st);
-        if (e != hipSuccess) return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs: bal_setup failed: %s", hipGetErrorString(e));
-        MCHK(m, hipEventRecord(m->ev1, st));
-        MCHK(m, hipEventSynchronize(m->ev1));
-        float ms = 0;
-        MCHK(m, hipEventElapsedTime(&ms, m->ev0, m->ev1));
-        r.bal_setup_ms = ms;
-        if (setup_ms) *setup_ms = ms;
+    if (!r.lay.has_full) {                                              // raw counts: the transposed half without a balance
+        MX(m, "eigs: ", mx_timed(m, &r.bal_setup_ms, [&] { return layout_full(r.lay, mx_cells(r), st); }));
+        if (setup_ms) *setup_ms = r.bal_setup_ms;
     }
-    in.bal = &r.bal; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.off = r.d_off; in.chr = r.exs.chr;
-    in.w = r.ext.use_weights ? r.d_w : nullptr; in.E = r.ext.d_cis_sm;
+    in.lay = &r.lay; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.off = r.d_off;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr; in.E = r.ext.d_cis_sm;
     in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
     return MKT_OK;
 }
@@ -1129,7 +1115,7 @@ int mkt_matrix_eigs(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts
     if (rc) return rc;
     MxRes& r = m->res[res_index];
     const hipError_t e = eigs_run(r.egs, in, r.off, o, phasing, m->stream);
-    if (e != hipSuccess) { eigs_free(r.egs); return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { r.egs = EigsState(); return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs: %s", hipGetErrorString(e)); }
     r.egs.setup_ms += setup_ms;
     if (info) *info = r.egs.info;
     return MKT_OK;
@@ -1148,20 +1134,10 @@ int mkt_matrix_eigs_apply(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts
     return MKT_OK;
 }
 
-// the results of res_index for a fetch, or the error
-static int mx_eigs_state(mkt_matrix* m, uint32_t res_index, const EigsState** out) {
-    if (!m) return MKT_E_ARG;
-    if (res_index >= m->res.size()) return mfail(m, MKT_E_ARG, "resolution index %u of %zu", res_index, m->res.size());
-    const MxRes& r = m->res[res_index];
-    if (!m->ran || !r.egs.built) return mfail(m, MKT_E_STATE, "no eigenvectors for resolution index %u: eigs first", res_index);
-    *out = &r.egs;
-    return MKT_OK;
-}
-
 int mkt_matrix_fetch_eigvecs(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, double* out) {
-    const EigsState* s = nullptr;
-    const int rc = mx_eigs_state(m, res_index, &s);
-    if (rc) return rc;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_EIGS);
+    const EigsState* s = &rp->egs;
     const uint64_t nb = m->res[res_index].nbins;
     if (k >= (uint32_t)s->n_eigs) return mfail(m, MKT_E_ARG, "eigenvector %u of %d", k, s->n_eigs);
     if (first > nb || n > nb - first) return mfail(m, MKT_E_ARG, "eigenvector bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nb);
@@ -1171,9 +1147,9 @@ int mkt_matrix_fetch_eigvecs(mkt_matrix* m, uint32_t res_index, uint32_t k, uint
 
 int mkt_matrix_fetch_eigvals(mkt_matrix* m, uint32_t res_index, uint32_t first_chrom, uint32_t n, double* lambda, double* resid, uint32_t* n_good,
                              uint32_t* iterations, uint8_t* converged) {
-    const EigsState* s = nullptr;
-    const int rc = mx_eigs_state(m, res_index, &s);
-    if (rc) return rc;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_EIGS);
+    const EigsState* s = &rp->egs;
     const uint32_t nchr = (uint32_t)s->n_good.size();
     if (first_chrom > nchr || n > nchr - first_chrom) return mfail(m, MKT_E_ARG, "eigenvalues of chromosomes [%u, +%u) of %u", first_chrom, n, nchr);
     if (n == 0) return MKT_OK;
