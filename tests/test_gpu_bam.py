@@ -4,14 +4,15 @@ The checker is tests/bamio.py (an independent reader written from the SAM/BAM sp
 block and verifies its CRC-32 / ISIZE).  samtools ships with the reference only as a prebuilt binary that is never run, so
 parity with samtools' exact bytes is UNPINNED; what is pinned: the decoded records equal the input lines, the order is
 (reference id, position, strand) with ties in input order, the header carries the @SQ dictionary and SO:coordinate, integer
-tags use the smallest type, `bin` is reg2bin of the alignment, and every query through the .bai finds exactly the records a
-scan finds."""
+tags use the smallest type, `bin` is reg2bin of the alignment, every query through the .bai finds the records a scan finds,
+and the .bai is byte for byte the index that DESIGN.md defines ("The index, exactly"; built independently by tests/baidef.py)."""
 import os
 import random
 import subprocess
 
 import pytest
 
+import baidef
 import bamio
 import util
 
@@ -38,33 +39,12 @@ def header_for(sam: bytes, extra=(), hd=None):
     return h.encode(), order
 
 
-def check_bam(sam_header: bytes, body: bytes, bam_bytes: bytes, bai_bytes: bytes, nrec, sorted_=True, order=None):
-    bam = bamio.Bam(bam_bytes)
-    lines = [ln for ln in body.decode().split("\n") if ln]
-    assert nrec == len(lines) == len(bam.records)
-    ids = {n: i for i, n in enumerate(order)}
-    assert [r[0] for r in bam.refs] == order
-    assert all(r[1] == 250000000 for r in bam.refs)
-    want_text = sam_header.decode()
-    if sorted_:
-        assert bam.text.split("\n")[0].startswith("@HD") and "SO:coordinate" in bam.text.split("\n")[0]
-        assert [ln for ln in bam.text.split("\n") if not ln.startswith("@HD")] == [ln for ln in want_text.split("\n") if not ln.startswith("@HD")]
-        lines = sorted(lines, key=lambda ln: bamio.sam_sort_key(ln, ids))          # Python's sort is stable: ties in input order
-    else:
-        assert bam.text == want_text
-    got = [bam.sam_line(r[2]) for r in bam.records]
-    assert got == [bamio.normalise_sam_line(ln) for ln in lines]
-    for _, _, r in bam.records:
-        b, e = bamio.ref_span(r)
-        assert r["bin"] == bamio.reg2bin(b, e)
-        for tag, ty, v in r["tags"]:
-            if ty in "cCsSiI":
-                assert ty == bamio.expected_int_type(v), (tag, ty, v)
-    if not sorted_:
-        assert bai_bytes == b""
-        return bam
+def check_index_loose(bam, bai_bytes):
+    """What an index must let a reader do, whatever its exact chunks: every record lies in a chunk of its bin, a region query visits
+    at least what a scan finds, no linear entry lies behind a record of its window.  (Many wrong indexes pass this: see
+    tests/test_baidef_host.py; check_bam adds the exact comparison.)"""
     bai = bamio.Bai(bai_bytes)
-    assert len(bai.refs) == len(order)
+    assert len(bai.refs) == len(bam.refs)
     assert bai.n_no_coor == sum(1 for _, _, r in bam.records if r["tid"] < 0)
     by_tid = {}
     for v0, v1, r in bam.records:
@@ -96,6 +76,38 @@ def check_bam(sam_header: bytes, body: bytes, bam_bytes: bytes, bai_bytes: bytes
         for (v0, v1, r), (b, e) in zip(recs, spans):
             for w in range(max(b, 0) >> 14, ((e - 1) >> 14) + 1):
                 assert w < len(lin) and lin[w] <= v0
+
+
+def check_bam(sam_header: bytes, body: bytes, bam_bytes: bytes, bai_bytes: bytes, nrec, sorted_=True, order=None, lens=None):
+    """lens: the references' LN where they are not the 250 Mb of header_for"""
+    bam = bamio.Bam(bam_bytes)
+    lines = [ln for ln in body.decode().split("\n") if ln]
+    assert nrec == len(lines) == len(bam.records)
+    ids = {n: i for i, n in enumerate(order)}
+    assert [r[0] for r in bam.refs] == order
+    assert [r[1] for r in bam.refs] == (lens if lens is not None else [250000000] * len(order))
+    want_text = sam_header.decode()
+    if sorted_:
+        assert bam.text.split("\n")[0].startswith("@HD") and "SO:coordinate" in bam.text.split("\n")[0]
+        assert [ln for ln in bam.text.split("\n") if not ln.startswith("@HD")] == [ln for ln in want_text.split("\n") if not ln.startswith("@HD")]
+        lines = sorted(lines, key=lambda ln: bamio.sam_sort_key(ln, ids))          # Python's sort is stable: ties in input order
+    else:
+        assert bam.text == want_text
+    got = [bam.sam_line(r[2]) for r in bam.records]
+    assert got == [bamio.normalise_sam_line(ln) for ln in lines]
+    for _, _, r in bam.records:
+        b, e = bamio.ref_span(r)
+        assert r["bin"] == bamio.reg2bin(b, e)
+        for tag, ty, v in r["tags"]:
+            if ty in "cCsSiI":
+                assert ty == bamio.expected_int_type(v), (tag, ty, v)
+    if not sorted_:
+        assert bai_bytes == b""
+        return bam
+    check_index_loose(bam, bai_bytes)
+    # ... and the index is exactly the one DESIGN.md defines ("The index, exactly"), byte for byte
+    want = baidef.bai_definition(bam)
+    assert baidef.bai_bytes(want) == bai_bytes, baidef.explain(bai_bytes, want)
     return bam
 
 
