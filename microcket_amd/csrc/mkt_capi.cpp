@@ -23,6 +23,9 @@ using namespace mkt;
 
 // block offsets are 32 bit, the ordered kernels pack byte counts into 31-bit fields
 static const size_t kMaxBlock = ((size_t)1 << 31) - 65536;
+// rounds of the lean kernel's tiles dealt by ticket at the end of a block (profiles/fast_dealing.txt has the sweep); 0: all static
+static const uint32_t kFastRoundsDefault = 8;
+static const size_t kStampWords = 20;        // diagnostic builds: 16 phase words + 4 span words (mkt_debug_stamps / mkt_debug_spans)
 
 static thread_local std::string g_create_error;
 
@@ -105,6 +108,7 @@ struct mkt_ctx {
     char* d_syn = nullptr; size_t syn_cap = 0;
     uint64_t* d_syn_sizes = nullptr; size_t syn_sizes_cap = 0;
     unsigned long long* d_stamps = nullptr;   // diagnostic builds (MKT_STAMPS) only
+    uint32_t fast_rounds = kFastRoundsDefault; // lean kernel: rounds of tiles dealt by ticket at the end of a block (MKT_FAST_ROUNDS)
     bool no_lean = false;                     // MKT_NO_LEAN=1: generic kernel only (debugging aid)
     int halo_widened = 0;                     // times adapt_geometry widened the halos of this input (at most twice)
     std::string err;
@@ -152,7 +156,8 @@ int mkt_device_count(void) {
 }
 
 // workspace of one block: descA | descB | descC | tile_last | tile_groups | defer_list |
-//                         region cursors (16 x 128 B) | ticket, defer_count, ticket of the deferred pass (256 B) | BlockResult
+//                         region cursors (16 x 128 B) | ticket, defer_count, ticket of the deferred pass, ticket of the lean kernel's
+//                         drawn tiles, ... (256 B) | BlockResult
 static size_t ws_tiles_bytes(uint32_t ntiles) {
     size_t b = (size_t)ntiles * (3 * sizeof(uint64_t) + sizeof(TileLast) + sizeof(uint64_t) + sizeof(uint32_t));
     return (b + 127) & ~(size_t)127;
@@ -202,6 +207,14 @@ int mkt_create(const mkt_params* p, mkt_ctx** out) {
     c->dims = c->cfg == CFG_SMALL ? small_dims() : max_dims();
     c->dims_probed = p->tiles != MKT_TILES_AUTO || p->ordered;
     { const char* e = getenv("MKT_NO_LEAN"); c->no_lean = e && e[0] == '1'; }
+    // rounds of the lean kernel's tiles held back for dealing by ticket: a number, or "all" = all but a workgroup's first tile
+    if (const char* e = getenv("MKT_FAST_ROUNDS")) {
+        char* end = nullptr;
+        const unsigned long v = strtoul(e, &end, 10);
+        if (!strcmp(e, "all")) c->fast_rounds = 0xFFFFFFFFu;
+        else if (e[0] && end && !*end && v < 0xFFFFFFFFul) c->fast_rounds = (uint32_t)v;
+        else { mkt_destroy(c); return fail(nullptr, MKT_E_ARG, "MKT_FAST_ROUNDS must be a number of rounds or \"all\""); }
+    }
     size_t bc = p->block_bytes ? (size_t)p->block_bytes : ((size_t)64 << 20);
     if (bc < 4096) bc = 4096;
     if (bc >= kMaxBlock) bc = kMaxBlock - 4096;
@@ -371,6 +384,7 @@ static int enqueue_block(mkt_ctx* c, const uint8_t* d_text, size_t n, int cfg, c
     a.ticket = (uint32_t*)w;
     a.defer_count = (uint32_t*)(w + 64);
     uint32_t* ticket2 = (uint32_t*)(w + 128);
+    a.fast_ticket = (uint32_t*)(w + 160);
     a.last_tile = (int*)(w + 192);
     a.scan_ticket = (uint32_t*)(w + 224);
     w += 256;
@@ -427,7 +441,7 @@ static int enqueue_block(mkt_ctx* c, const uint8_t* d_text, size_t n, int cfg, c
         a.key_list = c->d_key_list; a.key_list_cap = c->key_list_cap;
     }
 #if defined(MKT_STAMPS)
-    if (!c->d_stamps) { HIPCHK(c, hipMalloc((void**)&c->d_stamps, 16 * sizeof(unsigned long long))); HIPCHK(c, hipMemset(c->d_stamps, 0, 16 * sizeof(unsigned long long))); }
+    if (!c->d_stamps) { HIPCHK(c, hipMalloc((void**)&c->d_stamps, kStampWords * sizeof(unsigned long long))); HIPCHK(c, hipMemset(c->d_stamps, 0, kStampWords * sizeof(unsigned long long))); }
     a.stamps = getenv("MKT_NO_STAMPS") ? nullptr : c->d_stamps;
     { const char* e = getenv("MKT_DEBUG_STOP"); a.debug_stop = e ? atoi(e) : 0; }
 #endif
@@ -439,8 +453,18 @@ static int enqueue_block(mkt_ctx* c, const uint8_t* d_text, size_t n, int cfg, c
         HIPCHK(c, hipEventCreate(&e1));
         c->ev.push_back(e0); c->ev.push_back(e1); c->ev_bytes.push_back(n);
     }
-    const uint32_t max_wgs = fast_max_workgroups(cfg);       // every workgroup resident, tiles dealt statically
+    const uint32_t max_wgs = fast_max_workgroups(cfg);       // every workgroup resident
     int grid = (int)(ntiles < max_wgs ? ntiles : max_wgs);
+    // lean kernel: rounds 0 .. K-1 of its tiles are dealt statically (tile = workgroup + k * grid), K = max(1, ntiles / grid - R); the
+    // tiles behind them, R whole rounds and the partial one, by ticket.  R = 0 (or a block of one round): every tile static.
+    a.fast_dyn0 = kFastAllStatic;
+    if (c->fast_rounds && ntiles > (uint32_t)grid) {
+        const uint32_t rounds = ntiles / (uint32_t)grid, K = rounds > c->fast_rounds ? rounds - c->fast_rounds : 1u;
+        a.fast_dyn0 = K * (uint32_t)grid;
+    }
+#if defined(MKT_STAMPS)
+    if (a.debug_stop) a.fast_dyn0 = kFastAllStatic;                  // (the timing ladder leaves tiles early, before the next ticket is drawn)
+#endif
     const bool lean = !c->p.ordered && cfg != CFG_SMALL && !c->no_lean;
     HIPCHK(c, hipEventRecord(e0, c->stream));
     if (lean) {
@@ -1582,6 +1606,17 @@ int mkt_debug_stamps(mkt_ctx* c, unsigned long long* out16) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out16, c->d_stamps, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemset(c->d_stamps, 0, 16 * sizeof(unsigned long long)));
+    return MKT_OK;
+}
+// diagnostic build only: the workgroup spans of k_fast since the last call (STAMP_SPAN in mkt_kernels.hip), 100 MHz ticks:
+// sum of the spans, longest span, latest end, 2^62 - earliest first stamp
+int mkt_debug_spans(mkt_ctx* c, unsigned long long* out4) {
+    if (!c || !out4) return MKT_E_ARG;
+    memset(out4, 0, 4 * sizeof(unsigned long long));
+    if (!c->d_stamps) return MKT_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out4, c->d_stamps + 16, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemset(c->d_stamps + 16, 0, 4 * sizeof(unsigned long long)));
     return MKT_OK;
 }
 #endif

@@ -27,13 +27,25 @@ struct ScanScratch { uint64_t a[NT / 64], b[NT / 64]; };
 #if defined(MKT_STAMPS)
 // (accumulated in registers of lane 0 and added to a.stamps once per workgroup: an atomic per phase and tile would itself be
 //  the longest thing on lane 0's path)
-#define STAMP_DECL() unsigned long long stamp_prev_ = 0, stamp_acc_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+#define STAMP_DECL() unsigned long long stamp_prev_ = 0, stamp_first_ = 0, stamp_acc_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
 #define STAMP(k)                                                                        \
     do {                                                                                \
         if (tid == 0 && a.stamps) {                                                     \
             const unsigned long long now_ = __builtin_amdgcn_s_memtime();               \
             if ((k) > 0) stamp_acc_[(k)] += now_ - stamp_prev_;                         \
+            else if (!stamp_first_) stamp_first_ = __builtin_amdgcn_s_memrealtime();   \
             stamp_prev_ = now_;                                                         \
+        }                                                                               \
+    } while (0)
+// a workgroup's span, first stamp to the end (k_fast), on the 100 MHz clock all compute dies share, in four words of their own behind
+// the 16 phase words: the sum over all workgroups in stamps[16], the longest in [17], the latest end in [18] and 2^62 - the earliest
+// start in [19] -- read after ONE launch they show how long the machine waits for its slowest workgroup (tools/fast_tail.py)
+#define STAMP_SPAN(t0_)                                                                 \
+    do {                                                                                \
+        if ((t0_) == 0 && a.stamps && stamp_first_) {                                   \
+            const unsigned long long end_ = __builtin_amdgcn_s_memrealtime();           \
+            atomicAdd(&a.stamps[16], end_ - stamp_first_); atomicMax(&a.stamps[17], end_ - stamp_first_); \
+            atomicMax(&a.stamps[18], end_); atomicMax(&a.stamps[19], (1ull << 62) - stamp_first_); \
         }                                                                               \
     } while (0)
 #define STAMP_FLUSH(t0_)                                                                \
@@ -45,6 +57,7 @@ struct ScanScratch { uint64_t a[NT / 64], b[NT / 64]; };
 #define STAMP_DECL() do { } while (0)
 #define STAMP(k) do { } while (0)
 #define STAMP_FLUSH(t0_) do { } while (0)
+#define STAMP_SPAN(t0_) do { } while (0)
 #define STOP_AFTER(k)
 #endif
 
@@ -563,15 +576,34 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
     auto own = [&](uint32_t ws, uint32_t nws, uint32_t ke) { const uint32_t c = ws < ngrp ? (ngrp - ws + nws - 1u) / nws : 0u; return ke < c ? ke : c; };
     if (tid0 < (int)C_COUNT) wg_cnt[tid0] = 0;
     fast_init(st, (uint32_t)tid0);
-    // static tile assignment: no ticket atomic (30 k tiles per block would saturate one address)
+    // Tile dealing: the workgroup's first rounds are static (tile blockIdx.x + k * gridDim.x while that lies below a.fast_dyn0: no
+    // atomic at all), the block's last tiles [a.fast_dyn0, ntiles) are drawn from a.fast_ticket in the order the workgroups get
+    // there, so that a launch does not wait for the workgroup whose static share happened to be the slowest.  The scan pipeline
+    // needs a tile's id one tile ahead.  The next tile is never carried in a register (the kernel has none to spare): it is
+    // t + gridDim.x while that is a static tile, and otherwise stands in s_next[cur], where `cur` changes with every tile.  The
+    // ticket for the tile after the next one is drawn around the second half of the look-ahead scan (the answer is back no
+    // later than the scan's loads: nothing waits for it) and stored in s_next[cur ^ 1] before a barrier the phases have anyway.
+    // The drawing lane is lane 0 of the LAST wave, a scanning wave: lane 0 of wave 0 is on the critical path of every phase.
+    // a.fast_dyn0 = kFastAllStatic: every tile static, s_next is never touched.
     // the output pointers once per workgroup: the per-tile limits in s_out are all rewritten by every claim (the argument block
     // lives in scratch memory by now -- five dependent loads that used to sit in front of lane 0's scan of EVERY tile)
     if (tid0 == 0) s_out = a.out;
     uint32_t gdim = gridDim.x;                                   // (read once: the dispatch packet is a scalar memory load away)
     asm volatile("" : "+s"(gdim));
+    __shared__ uint32_t s_next[2];                                // drawn tiles: [cur] the next one, [cur ^ 1] the one after it
+    const bool ticket_lane = tid0 == NTW - 64;
+    // A block of a single static round (fast_dyn0 == gridDim.x) needs its first drawn tile before the first tile's look-ahead scan:
+    // one returning atomic and one barrier here, once per workgroup and launch, in front of the loop and of no phase of any tile.
+    if (blockIdx.x + gdim >= a.fast_dyn0) {
+        if (ticket_lane) s_next[0] = a.fast_dyn0 + atomicAdd(a.fast_ticket, 1u);
+        __syncthreads();
+    }
+    // the tile after x, the bitmap index being c ("none left" is any id >= ntiles, as a draw past the last tile gives).  s_next[c] is
+    // written one tile earlier and barriers lie between that and every read; it is written again only in the tile after next.
+    auto next_of = [&](uint32_t x, uint32_t c) { return x + gdim < a.fast_dyn0 ? x + gdim : (uint32_t)__builtin_amdgcn_readfirstlane((int)s_next[c]); };
     uint32_t cur = 0;                                             // bitmap of the current tile
     bool scanned = false;                                         // ... already filled by the previous iteration
-    for (uint32_t t = blockIdx.x; t < a.ntiles; t += gdim) {
+    for (uint32_t t = blockIdx.x; t < a.ntiles; t = next_of(t, cur ^ 1u)) {      // (cur has changed by then)
         int tid = tid0;
         asm volatile("" : "+v"(tid));                   // per-lane addresses are recomputed per tile, not kept live (and spilled) across the loop
         // (no barrier: the previous tile ended on one, and nothing below reads what lane 0 resets here before the barrier
@@ -693,8 +725,11 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
             if (NTW < 256 && tid < 4 && tid >= NTW / 64) { st.m_surv[tid] = 0; st.m_eqp[tid] = 0; st.m_r1[tid] = 0; st.m_r2[tid] = 0; st.m_start[tid] = 0; }
         }
         // the scanning waves: first half of the next tile's window (behind their own few lines, if the window has more than 128)
-        if (NSW && wave >= (uint32_t)(NWV - NSW) && t + gdim < a.ntiles)
-            fast_scan<Cfg, (NSW ? NSW : 1)>(a, t + gdim, s_hit[cur ^ 1u], wave - (uint32_t)(NWV - NSW), 0u, own(wave - (uint32_t)(NWV - NSW), NSW, lpt_a), tid & 63);
+        if (NSW && wave >= (uint32_t)(NWV - NSW)) {
+            const uint32_t nxt = next_of(t, cur);
+            if (nxt < a.ntiles)
+                fast_scan<Cfg, (NSW ? NSW : 1)>(a, nxt, s_hit[cur ^ 1u], wave - (uint32_t)(NWV - NSW), 0u, own(wave - (uint32_t)(NWV - NSW), NSW, lpt_a), tid & 63);
+        }
         __syncthreads();
         STAMP(3);
         STOP_AFTER(3)
@@ -721,18 +756,27 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
                 uint4* d = reinterpret_cast<uint4*>(a.out.sam + ((size_t)t * Cfg::LCAP + i) * 32u);
                 if (((size_t)t * Cfg::LCAP + i) * 32u + 32u <= a.out.sam_cap) { d[0] = r0; d[1] = r1; }
             }
-            if (NSW && wave >= (uint32_t)(NWV - NSW) && t + gdim < a.ntiles)
-                fast_scan<Cfg, (NSW ? NSW : 1)>(a, t + gdim, s_hit[cur ^ 1u], wave - (uint32_t)(NWV - NSW), lpt_a, own(wave - (uint32_t)(NWV - NSW), NSW, lpt_sw), tid & 63);
-            if (NSW && t + gdim < a.ntiles) { scanned = true; cur ^= 1u; }
+            const uint32_t nxt = next_of(t, cur);
+            if (NSW && wave >= (uint32_t)(NWV - NSW) && nxt < a.ntiles)
+                fast_scan<Cfg, (NSW ? NSW : 1)>(a, nxt, s_hit[cur ^ 1u], wave - (uint32_t)(NWV - NSW), lpt_a, own(wave - (uint32_t)(NWV - NSW), NSW, lpt_sw), tid & 63);
+            scanned = NSW && nxt < a.ntiles; cur ^= 1u;
             __syncthreads();
             continue;
         }
 #endif
         if (!st.abn) for (uint32_t i = first_idx + rr_id; i < end_idx; i += 64 * RR) fast_group(st, tv, P, G, i);
-        // the scanning waves: the rest of the next tile's window
-        if (NSW && wave >= (uint32_t)(NWV - NSW) && t + gdim < a.ntiles)
-            fast_scan<Cfg, (NSW ? NSW : 1)>(a, t + gdim, s_hit[cur ^ 1u], wave - (uint32_t)(NWV - NSW), lpt_a, own(wave - (uint32_t)(NWV - NSW), NSW, lpt_sw), tid & 63);
-        if (NSW && t + gdim < a.ntiles) { scanned = true; cur ^= 1u; }
+        // the scanning waves: the rest of the next tile's window; around it the ticket for the tile after that one, where it is a drawn one
+        // (the diagnostic early exits above never get here: the host deals statically when debug_stop is set)
+        {
+            const uint32_t nxt = next_of(t, cur);
+            const bool draw = nxt < a.ntiles && nxt + gdim >= a.fast_dyn0;      // (uniform)
+            uint32_t tk = 0;
+            if (draw && ticket_lane) tk = atomicAdd(a.fast_ticket, 1u);
+            if (NSW && wave >= (uint32_t)(NWV - NSW) && nxt < a.ntiles)
+                fast_scan<Cfg, (NSW ? NSW : 1)>(a, nxt, s_hit[cur ^ 1u], wave - (uint32_t)(NWV - NSW), lpt_a, own(wave - (uint32_t)(NWV - NSW), NSW, lpt_sw), tid & 63);
+            if (draw && ticket_lane) s_next[cur ^ 1u] = a.fast_dyn0 + tk;
+            scanned = NSW && nxt < a.ntiles; cur ^= 1u;                         // (every tile: s_next is indexed by it)
+        }
         __syncthreads();
         STAMP(4);
         STOP_AFTER(4)
@@ -894,6 +938,7 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
     }
     if (tid0 < (int)C_COUNT && wg_cnt[tid0]) atomicAdd(&a.res->counters[tid0], wg_cnt[tid0]);
     STAMP_FLUSH(tid0);
+    STAMP_SPAN(tid0);
 }
 
 // After the tiles, step 1 (one workgroup per 1024 tiles): exclusive scan of the per-tile group counts

@@ -22,16 +22,19 @@ constexpr int kMaxRegions = 16;
 constexpr int kCurShift = 36;
 constexpr unsigned long long kCurLow = (1ull << kCurShift) - 1ull;
 
+constexpr uint32_t kFastAllStatic = 0xFFFFFFFFu;
 struct KArgs {
     const uint8_t* text;        // block text, 16-byte aligned
     uint32_t n;                 // block bytes (< 2^31)
     uint32_t ntiles;
     TileDims dims;              // bytes per tile / back halo / forward halo (multiples of 16, within the kernels' capacities)
+    uint32_t fast_dyn0;         // lean kernel: tiles below it are dealt statically, [fast_dyn0, ntiles) by fast_ticket (kFastAllStatic: none)
     Params P;
     uint64_t* descA;            // per-tile look-back words: groups | emitted
     uint64_t* descB;            //                            pair_bytes | self-circles
     uint64_t* descC;            //                            sam_bytes
     uint32_t* ticket;
+    uint32_t* fast_ticket;      // lean kernel: the ticket of its drawn tiles (zeroed with the workspace, a word of its own)
     uint64_t* tile_groups;      // per tile: groups opened (low 32) | pairs emitted (high 32); k_finish_scan turns both into exclusive prefixes
     int32_t ordered;            // 1: outputs in input order (decoupled look-back); 0: one atomic range per tile
     TileLast* tile_last;
