@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -195,6 +195,11 @@ def build_test_tools():
     dsrc = os.path.join(ROOT, "tests", "host", "deflate_codes.cpp")
     if os.path.exists(dsrc) and _newer(dzc, [dsrc, os.path.join(CSRC, "mkt_deflate_codes.h")]):
         _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-o", dzc, dsrc])
+    # device check of the owning buffer types (mkt_devbuf.h): HIP runtime only; a tree that carries an older tests/ has no such source
+    dbc = os.path.join(out, "devbuf_check")
+    bsrc = os.path.join(ROOT, "tests", "host", "devbuf_check.cpp")
+    if os.path.exists(bsrc) and _newer(dbc, [bsrc, os.path.join(CSRC, "mkt_devbuf.h")]):
+        _run([hipcc(), f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-Wall", "-Wl,-rpath,/opt/rocm/lib", "-o", dbc, bsrc])
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
     synth = os.path.join(tout, "synth_sam")

@@ -59,7 +59,34 @@ struct KArgs {
     int32_t debug_stop;         // diagnostic builds only: leave every tile after phase k (timing ladder; outputs are wrong)
 };
 
-TileDims small_dims();                       // the 256-byte tiles of CFG_SMALL
+// The workspace of one block, zeroed before its kernels run (the one description of its layout):
+//   descA | descB | descC | tile_last | tile_groups | defer_list   (per tile; rounded up to 128 B)
+//   region cursors (16 x 128 B) | 256 B of counter words | 1024 scan words (one per 1024 tiles) | BlockResult
+struct BlockWs {
+    uint8_t* base;
+    uint32_t ntiles;
+    static constexpr size_t kScanWords = 1024;
+    size_t tiles_bytes() const { return ((size_t)ntiles * (3 * sizeof(uint64_t) + sizeof(TileLast) + sizeof(uint64_t) + sizeof(uint32_t)) + 127) & ~(size_t)127; }
+    size_t bytes() const { return tiles_bytes() + kMaxRegions * sizeof(RegionCur) + 256 + kScanWords * sizeof(uint64_t) + sizeof(BlockResult); }
+    uint64_t* descA() const { return (uint64_t*)base; }
+    uint64_t* descB() const { return descA() + ntiles; }
+    uint64_t* descC() const { return descB() + ntiles; }
+    TileLast* tile_last() const { return (TileLast*)(descC() + ntiles); }
+    uint64_t* tile_groups() const { return (uint64_t*)(tile_last() + ntiles); }
+    uint32_t* defer_list() const { return (uint32_t*)(tile_groups() + ntiles); }
+    RegionCur* cur() const { return (RegionCur*)(base + tiles_bytes()); }
+    uint8_t* counters() const { return (uint8_t*)(cur() + kMaxRegions); }
+    uint32_t* ticket() const { return (uint32_t*)counters(); }                       // generic kernel over all tiles
+    uint32_t* defer_count() const { return (uint32_t*)(counters() + 64); }
+    uint32_t* defer_ticket() const { return (uint32_t*)(counters() + 128); }         // generic kernel over the deferred tiles
+    uint32_t* fast_ticket() const { return (uint32_t*)(counters() + 160); }          // lean kernel's drawn tiles
+    int* last_tile() const { return (int*)(counters() + 192); }
+    uint32_t* scan_ticket() const { return (uint32_t*)(counters() + 224); }
+    uint64_t* scan_desc() const { return (uint64_t*)(counters() + 256); }
+    BlockResult* res() const { return (BlockResult*)(scan_desc() + kScanWords); }
+};
+
+TileDims small_dims();                    // the 256-byte tiles of CFG_SMALL
 TileDims max_dims();                         // the largest geometry the lean kernel (and the generic kernel behind it) takes
 uint32_t fast_max_workgroups(int cfg);      // grid of the lean kernel: the workgroups that are resident at once on 256 CUs
 // newlines in text[0, n): the host's line-length probe on device-resident text (one small launch; *out zeroed by the caller)

@@ -12,6 +12,7 @@ REF_EXE = os.path.join(ROOT, "oracle", "_ref", "sam2pairs.ref")
 EMUL_SO = os.path.join(ROOT, "tests", "host", "_build", "libmkt_emul.so")
 SYNTH_EXE = os.path.join(ROOT, "tools", "_build", "synth_sam")
 DEFLATE_CODES_EXE = os.path.join(ROOT, "tests", "host", "_build", "deflate_codes")
+DEVBUF_CHECK_EXE = os.path.join(ROOT, "tests", "host", "_build", "devbuf_check")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 MODES = {"flash": 0, "unc": 1}
@@ -31,7 +32,7 @@ def ensure_built():
     # mtime-checked (make / build._newer): an edited header rebuilds the emulation and the oracle instead of testing stale code
     build.build_oracle()
     build.build_test_tools()
-    for p in (ORACLE_SO, ORACLE_EXE, EMUL_SO, SYNTH_EXE, DEFLATE_CODES_EXE):
+    for p in (ORACLE_SO, ORACLE_EXE, EMUL_SO, SYNTH_EXE, DEFLATE_CODES_EXE, DEVBUF_CHECK_EXE):
         assert os.path.exists(p), p
     _built_once = True
 
