@@ -96,6 +96,16 @@ typedef struct mkt_timing {
     uint64_t deferred_tiles;   /* of those, tiles the lean kernel left to the generic kernel */
 } mkt_timing;
 
+/* how often a context had to run blocks again, by the cause it repaired first (tests read this to prove that an input took the
+ * path they are about).  Streaming path: every cause; resident path (mkt_sync): geometry only, everything else is an error. */
+typedef struct mkt_replays {
+    uint64_t geometry;         /* line table overflown: next smaller tile geometry */
+    uint64_t pairs_cap;        /* .pairs region too small: buffer grown */
+    uint64_t sam_cap;          /* .sam region too small: buffer grown */
+    uint64_t sc_cap;           /* self-circle slices or the run's lists too small: grown */
+    uint64_t jobs_rerun;       /* blocks launched again: the failed one and every block queued behind it */
+} mkt_replays;
+
 typedef struct mkt_ctx mkt_ctx;
 
 int mkt_abi_version(void);
@@ -158,7 +168,8 @@ int mkt_format_log(const mkt_stats* st, char* out, size_t cap);
 int mkt_reset(mkt_ctx* ctx);
 
 int mkt_get_timing(const mkt_ctx* ctx, mkt_timing* t);
-int mkt_reset_timing(mkt_ctx* ctx);
+int mkt_reset_timing(mkt_ctx* ctx);      /* clears mkt_replays as well; mkt_reset clears neither */
+int mkt_get_replays(const mkt_ctx* ctx, mkt_replays* r);
 
 /* ---- synthetic inputs (stand-in for util/simulation + BWA) ------------------------
  * Generates groups [first_group, first_group + n_groups) of the seeded data set straight into

@@ -15,7 +15,7 @@ EXPORTS = [
     "mkt_abi_version", "mkt_strerror", "mkt_last_error", "mkt_device_count", "mkt_create", "mkt_destroy",
     "mkt_input_window", "mkt_submit_window",
     "mkt_submit", "mkt_drain", "mkt_drain_wait", "mkt_submit_device", "mkt_sync", "mkt_fetch_last_block", "mkt_finish",
-    "mkt_format_log", "mkt_get_timing", "mkt_reset_timing", "mkt_synth_device", "mkt_copy_to_host", "mkt_device_text",
+    "mkt_format_log", "mkt_get_timing", "mkt_reset_timing", "mkt_get_replays", "mkt_synth_device", "mkt_copy_to_host", "mkt_device_text",
     "mkt_reset", "mkt_ext_dedup", "mkt_ext_chrstat", "mkt_ext_chr_names", "mkt_ext_keys_fetch", "mkt_ext_dedup_keys", "mkt_ext_keys_device", "mkt_ext_partition", "mkt_ext_dedup_device", "mkt_ext_unpartition", "mkt_ext_dedup_multi", "mkt_dataset_create", "mkt_dataset_info", "mkt_dataset_block", "mkt_dataset_destroy", "mkt_group_count",
     "mkt_sorter_create", "mkt_sorter_destroy", "mkt_sorter_error", "mkt_sorter_add", "mkt_sorter_add_device", "mkt_sorter_sort", "mkt_sorter_fetch",
     "mkt_rmdup_create", "mkt_rmdup_destroy", "mkt_rmdup_error", "mkt_rmdup_reserve", "mkt_rmdup_add", "mkt_rmdup_run", "mkt_rmdup_fetch",
@@ -127,6 +127,14 @@ class Timing(C.Structure):
                 ("tiles", C.c_uint64), ("deferred_tiles", C.c_uint64)]
 
 
+class _ReplaysC(C.Structure):
+    """mkt_replays of include/mkt.h"""
+    _fields_ = [(k, C.c_uint64) for k in ("geometry", "pairs_cap", "sam_cap", "sc_cap", "jobs_rerun")]
+
+
+Replays = collections.namedtuple("Replays", "geometry pairs_cap sam_cap sc_cap jobs_rerun")
+
+
 def lib_path():
     # MKT_LIB selects a diagnostic build (e.g. the phase-stamp build); never needed in production
     return os.environ.get("MKT_LIB") or os.path.join(HERE, "libmkt_hip.so")
@@ -192,6 +200,7 @@ def load_library():
     L.mkt_format_log.argtypes = [C.POINTER(Stats), C.c_char_p, C.c_size_t]
     L.mkt_get_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
     L.mkt_reset_timing.argtypes = [C.c_void_p]
+    L.mkt_get_replays.argtypes = [C.c_void_p, C.POINTER(_ReplaysC)]
     L.mkt_synth_device.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int,
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     L.mkt_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -557,6 +566,12 @@ class Context:
 
     def reset_timing(self):
         self._chk(self.L.mkt_reset_timing(self.h), "mkt_reset_timing")
+
+    def replays(self):
+        """Replays(geometry, pairs_cap, sam_cap, sc_cap, jobs_rerun): repairs by cause and blocks run again since reset_timing()"""
+        r = _ReplaysC()
+        self._chk(self.L.mkt_get_replays(self.h, C.byref(r)), "mkt_get_replays")
+        return Replays(*[getattr(r, k) for k in Replays._fields])
 
 
 class Dataset:

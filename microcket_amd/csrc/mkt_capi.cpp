@@ -419,17 +419,20 @@ static int stream_replay(mkt_ctx* c, const BlockResult& r) {
         smaller_geometry(c, c->in[j0.in_slot].d, j0.n);
         for (mkt_ctx::Job& q : c->jobs) { q.cfg = c->cfg; q.dims = c->dims; }
         if (c->cfg == CFG_SMALL) { c->cfg = keep_cfg; c->dims = keep; }      // (the 256-byte tiles are a last resort per block: the stream keeps its lean geometry)
+        ++c->replays.geometry;
         fixed = true;
     } else {
         const uint32_t nr = r.nregions ? r.nregions : 1;
         if (r.err & E_PAIRS_CAP) {
             uint64_t mx = 0; for (uint32_t q = 0; q < nr; ++q) if (r.rpair[q] > mx) mx = r.rpair[q];
             if ((rc = ensure_dev(c, c->d_pairs, (size_t)(mx * nr) + mx / 4 * nr + 65536))) return rc;
+            ++c->replays.pairs_cap;
             fixed = true;
         }
         if (r.err & E_SAM_CAP) {
             uint64_t mx = 0; for (uint32_t q = 0; q < nr; ++q) if (r.rsam[q] > mx) mx = r.rsam[q];
             if ((rc = ensure_dev(c, c->d_sam, (size_t)(mx * nr) + mx / 4 * nr + 65536))) return rc;
+            ++c->replays.sam_cap;
             fixed = true;
         }
         if (r.err & E_SC_CAP) {            // per-block raw entries: grow the slices, and the run's list with them
@@ -437,6 +440,7 @@ static int stream_replay(mkt_ctx* c, const BlockResult& r) {
             HIPCHK(c, c->d_sc_tmp.regrow(need * kMaxRegions));         // (idle already; whatever its size was)
             if ((rc = ensure_sc_list(c, (size_t)c->acc.sc + (c->jobs.size() + 1) * need))) return rc;
             c->key_density = 0;            // extension: the key list may be what overflowed: back to the worst-case reservation
+            ++c->replays.sc_cap;
             fixed = true;
         }
     }
@@ -446,6 +450,7 @@ static int stream_replay(mkt_ctx* c, const BlockResult& r) {
     for (const mkt_ctx::Job& q : c->jobs) {
         if ((rc = stream_launch(c, q))) return rc;
         c->bytes_unsynced += q.n;
+        ++c->replays.jobs_rerun;
     }
     return MKT_OK;
 }
@@ -762,6 +767,7 @@ int mkt_sync(mkt_ctx* c) {
         if (r.err) {
             if ((r.err & (E_LINE_TABLE | E_OVF_SLOTS)) && c->p.tiles == MKT_TILES_AUTO && c->cfg != CFG_SMALL && replays < 4 && c->res_text.size() > k) {
                 ++replays;
+                ++c->replays.geometry; c->replays.jobs_rerun += c->res_used - k;
                 smaller_geometry(c, c->res_text[k], c->res_n[k]);
                 c->last_dims = c->dims;
                 changed = true;
@@ -897,6 +903,14 @@ int mkt_get_timing(const mkt_ctx* c, mkt_timing* t) {
 int mkt_reset_timing(mkt_ctx* c) {
     if (!c) return MKT_E_ARG;
     c->folded_ms = 0; c->folded_launches = 0; c->folded_bytes = 0; c->tiles_total = 0; c->tiles_deferred = 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    c->replays = mkt_replays{0, 0, 0, 0, 0};
+    return MKT_OK;
+}
+int mkt_get_replays(const mkt_ctx* c, mkt_replays* r) {
+    if (!c || !r) return MKT_E_ARG;
+    std::lock_guard<std::mutex> g(const_cast<mkt_ctx*>(c)->mu);       // (the streaming worker counts under the same lock)
+    *r = c->replays;
     return MKT_OK;
 }
 

@@ -104,6 +104,7 @@ struct mkt_ctx {
     std::deque<Timed> ev;                // resident path: start / stop of the tile kernel of every block since the last sync
     double folded_ms = 0; uint64_t folded_launches = 0, folded_bytes = 0;
     uint64_t tiles_total = 0, tiles_deferred = 0;      // lean-kernel tiles / those it left to the generic kernel
+    mkt_replays replays = {0, 0, 0, 0, 0};             // repairs by cause and blocks run again (streaming: written by the worker under mu)
     // synth
     GrowBuf<char> d_syn;
     GrowBuf<uint64_t> d_syn_sizes;
