@@ -29,9 +29,16 @@ def bin_layout(table, r):
     return off[:-1], n, off[-1]
 
 
+POS_SAT = 1 << 40                                                   # see parse_pairs
+
+
 def parse_pairs(pairs_text: bytes, flags=None):
     """(chrA names, posA, chrB names, posB) of the pair lines ('#' lines ignored); flags: one per pair line, truthy = left out.
-    A line with fewer than five columns or a non-decimal position raises ValueError."""
+    A line with fewer than five columns or a non-decimal position raises ValueError (a position that ends in '\\r' is one: only
+    columns past the fifth may carry the '\\r' of a CRLF line).
+    A position is a decimal number of any length, leading zeros allowed; it is capped at POS_SAT = 2^40.  Every tabulated length is
+    below 2^32, so the cap changes no result: it only states that a number of 13 digits or more is "past every chromosome's end"
+    and nothing else, however many digits follow (int() here cannot wrap; a 64-bit accumulator without the cap would)."""
     ca, pa, cb, pb = [], [], [], []
     k = 0
     lines = pairs_text.split(b"\n")
@@ -46,7 +53,7 @@ def parse_pairs(pairs_text: bytes, flags=None):
         keep = flags is None or not flags[k]
         k += 1
         if keep:
-            ca.append(f[1]); pa.append(min(int(f[2]), 1 << 40)); cb.append(f[3]); pb.append(min(int(f[4]), 1 << 40))
+            ca.append(f[1]); pa.append(min(int(f[2]), POS_SAT)); cb.append(f[3]); pb.append(min(int(f[4]), POS_SAT))
     return ca, pa, cb, pb
 
 
