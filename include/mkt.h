@@ -622,6 +622,76 @@ int mkt_matrix_fetch_eigvals(mkt_matrix* m, uint32_t res_index, uint32_t first_c
 int mkt_matrix_eigs_apply(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* x, uint32_t ncols, double* y);
 int mkt_matrix_eigs_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms, double* small_ms);
 
+/* ---- domains: the diamond insulation score of every bin at up to four nested windows, and the boundaries called from it -----------
+ * What cooltools `insulation` computes from a .cool (Crane et al. 2015): the analysis the reference's own benchmarking runs on its
+ * .hic files besides loops.  The definition is this project's own, modelled on cooltools insulation; parity with cooltools is
+ * UNPINNED (it is not run anywhere here).  tests/insuldef.py restates the definition in numpy.  All floating point is float64.
+ *
+ * Inputs, for one resolution: the cells (bin1 <= bin2, count), the chromosome ranges [off_c, off_c + n_c) and use_weights: with 0
+ * every bin is valid and w = 1; with 1 w is the weights of the last mkt_matrix_balance and valid(k) means w[k] is not NaN.
+ * v = ((double)count * w[bin1]) * w[bin2]: two multiplications in this order, never fused with the addition that follows.
+ * Options (mkt_insulation_opts): n_windows (1 .. 4), window[4] in bins (strictly ascending, each 1 .. 1024), ignore_diags,
+ * use_weights, min_frac_valid, min_strength.
+ *  1. POSITIONS of bin i in chromosome c for a window W: (a, b) = (i - p, i + q) with 0 <= p, q < W, p + q >= ignore_diags, a >= off_c and
+ *     b < off_c + n_c.  A position is KEPT when valid(a) and valid(b) (valid(i) itself is not asked for).
+ *     n_full(W) = #{(p, q): 0 <= p, q < W, p + q >= ignore_diags}: the unclipped count, the same for every i.
+ *  2. Per (i, W): n_valid (uint64) = the kept positions; csum (uint64, exact) = the sum of count over the stored cells at kept
+ *     positions; bsum = the sum of v over the same cells.  An absent cell at a kept position adds 0 and still counts in n_valid.
+ *  3. SCORE = bsum / (double)n_valid; NaN when n_full == 0, n_valid == 0 or (double)n_valid < min_frac_valid * (double)n_full.  With
+ *     the default min_frac_valid the clipped diamonds at chromosome ends are therefore NaN; with min_frac_valid = 0 they are scored.
+ *  4. NORMALISATION, on the host, per chromosome and window: mean_c = the sum, in ascending bin order, of the scores that are finite
+ *     and > 0, divided by their number; L[i] = log2(score[i] / mean_c), NaN when the score is NaN or 0 or the chromosome has no such
+ *     score.
+ *  5. MINIMA, on the host: inside a chromosome a SEGMENT is a maximal run of consecutive bins with finite L.  A plateau [s, e] of equal
+ *     value x inside a segment is a minimum when s - 1 and e + 1 are in the segment and both hold values > x; it is reported at bin s.
+ *  6. STRENGTH of a minimum: walk left from s - 1 while in the segment and L[j] >= x and take the largest value seen, the same to the
+ *     right from e + 1; strength = min(left, right) - x.  NaN on every bin that is not a reported minimum.
+ *  7. BOUNDARY: a minimum with strength >= min_strength.
+ * Out of scope: Otsu / Li automatic thresholds, min_dist_bad_bin, per-arm views, merging boundaries across windows, a dense or
+ * sliding-sum path.
+ *
+ * Determinism: no floating-point atomics.  The summation order of bsum, with W_max the largest window: G lanes own bin i, G = 64 for
+ * X >= 48, 32 for X >= 24, 16 for X >= 12, else 8, where X = W_max when the matrix holds at least one cell per bin and W_max / 2
+ * (integer) otherwise.  Lane l takes the rows a = i - p for p = l, l + G, l + 2 G, .. (p < W_max, a >= off_c), each row's stored cells
+ * in ascending b, and adds every v to its partial sum of the cell's SHELL k = the smallest k with max(p, q) < window[k], starting
+ * from 0.0.  Per shell the lanes are added by the tree lane l += lane l + d for d = G / 2, G / 4, .. 1; window k's bsum is then
+ * shell 0 + shell 1 + .. + shell k, added in that order.  n_valid and csum are integers (n_valid from a prefix count of the valid
+ * bins, never through a float).  G, the stride, the tree and the order depend on (nbins, cells, options) only: the same bits from
+ * call to call, process to process and by every route (add, add_device, add_keys).  Against the numpy restatement (which adds in
+ * ascending (a, b)) n_valid, csum, the NaN pattern and integer-valued bsum are identical; other bsum agree to summation-order
+ * rounding.  Asking for several windows at once may round bsum differently from asking for one (the shells).
+ *
+ *   mkt_insulation_opts_default   n_windows 3, window {5, 10, 25}, ignore_diags 2, use_weights 1, min_frac_valid 0.66, min_strength 0.2
+ *   mkt_matrix_insulation         valid after mkt_matrix_run (MKT_E_STATE before it) and, with use_weights 1, after mkt_matrix_balance of
+ *                                 that resolution (MKT_E_STATE "balance first"); opts NULL = the defaults; MKT_E_ARG with a message
+ *                                 for a bad index, n_windows outside 1 .. 4, windows not strictly ascending or outside 1 .. 1024, a
+ *                                 negative ignore_diags, use_weights not 0 / 1, min_frac_valid outside [0, 1] or NaN, a negative or NaN
+ *                                 min_strength or a non-zero reserved.  info may be NULL.  A later mkt_matrix_run, add or balance of
+ *                                 that resolution discards the results; expected tables, loops, eigenvectors and insulation of one
+ *                                 resolution do not disturb each other.
+ *   mkt_matrix_fetch_insulation   window k (0 .. n_windows - 1) for bins [first, first + n); any pointer may be NULL; MKT_E_ARG with
+ *                                 a message for k >= n_windows or a bad range
+ *   mkt_matrix_insulation_timing  of the last mkt_matrix_insulation of res_index (ms, HIP events): the setup (the copy of the weights,
+ *                                 the prefix count on the host and its upload; 0 without weights) and the sweep.  A bad index is
+ *                                 MKT_E_ARG without a message. */
+typedef struct mkt_insulation_opts {
+    int32_t n_windows;
+    int32_t window[4];       /* bins; the first n_windows are used */
+    int32_t ignore_diags, use_weights;
+    uint32_t reserved;       /* 0 */
+    double min_frac_valid, min_strength;
+} mkt_insulation_opts;
+typedef struct mkt_insulation_info {
+    uint64_t defined[4];     /* per window: bins with a finite log2 score */
+    uint64_t minima[4], boundaries[4];
+    uint32_t n_chrom, reserved;
+} mkt_insulation_info;
+void mkt_insulation_opts_default(mkt_insulation_opts* o);
+int mkt_matrix_insulation(mkt_matrix* m, uint32_t res_index, const mkt_insulation_opts* opts, mkt_insulation_info* info);
+int mkt_matrix_fetch_insulation(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* csum, double* bsum,
+                                double* score, double* log2_score, double* strength, uint8_t* boundary);
+int mkt_matrix_insulation_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms);
+
 #ifdef __cplusplus
 }
 #endif

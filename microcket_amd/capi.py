@@ -30,6 +30,7 @@ EXPORTS = [
     "mkt_loops_opts_default", "mkt_matrix_loops", "mkt_matrix_fetch_loop_cells", "mkt_matrix_fetch_loop_hist", "mkt_matrix_fetch_loop_thresholds",
     "mkt_matrix_fetch_loops", "mkt_matrix_loops_timing",
     "mkt_eigs_opts_default", "mkt_matrix_eigs", "mkt_matrix_fetch_eigvecs", "mkt_matrix_fetch_eigvals", "mkt_matrix_eigs_apply", "mkt_matrix_eigs_timing",
+    "mkt_insulation_opts_default", "mkt_matrix_insulation", "mkt_matrix_fetch_insulation", "mkt_matrix_insulation_timing",
 ]
 
 
@@ -120,6 +121,21 @@ class _EigsInfoC(C.Structure):
 EigsInfo = collections.namedtuple("EigsInfo", "n_chrom solved converged skipped max_iterations")
 Eigs = collections.namedtuple("Eigs", "info vectors lambdas resid n_good iterations converged")
 EIGS_OPTS = ("n_eigs", "ignore_diags", "min_good", "max_iters", "tol", "clip")
+
+
+class InsulationOpts(C.Structure):
+    """mkt_insulation_opts of include/mkt.h"""
+    _fields_ = [("n_windows", C.c_int32), ("window", C.c_int32 * 4), ("ignore_diags", C.c_int32), ("use_weights", C.c_int32), ("reserved", C.c_uint32),
+                ("min_frac_valid", C.c_double), ("min_strength", C.c_double)]
+
+
+class _InsulationInfoC(C.Structure):
+    _fields_ = [("defined", C.c_uint64 * 4), ("minima", C.c_uint64 * 4), ("boundaries", C.c_uint64 * 4), ("n_chrom", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+InsulationInfo = collections.namedtuple("InsulationInfo", "n_chrom windows defined minima boundaries")
+InsulationTrack = collections.namedtuple("InsulationTrack", "n_valid csum bsum score log2_score strength boundary")
+INSULATION_OPTS = ("ignore_diags", "use_weights", "min_frac_valid", "min_strength")
 
 
 class Timing(C.Structure):
@@ -301,6 +317,11 @@ def load_library():
     L.mkt_matrix_fetch_eigvals.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
     L.mkt_matrix_eigs_apply.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(EigsOpts), C.c_void_p, C.c_uint32, C.c_void_p]
     L.mkt_matrix_eigs_timing.argtypes = [C.c_void_p, C.c_uint32] + [C.POINTER(C.c_double)] * 3
+    L.mkt_insulation_opts_default.argtypes = [C.POINTER(InsulationOpts)]
+    L.mkt_insulation_opts_default.restype = None
+    L.mkt_matrix_insulation.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(InsulationOpts), C.POINTER(_InsulationInfoC)]
+    L.mkt_matrix_fetch_insulation.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 7
+    L.mkt_matrix_insulation_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -858,6 +879,40 @@ class Matrix:
         a, b, c = C.c_double(), C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_eigs_timing(self.h, res, C.byref(a), C.byref(b), C.byref(c)), "mkt_matrix_eigs_timing")
         return a.value, b.value, c.value
+
+    def insulation(self, res, windows=(5, 10, 25), **opts):
+        """Insulation scores and boundaries of resolution index res after run() (and balance(res) unless use_weights=0): the definition
+        is mkt_matrix_insulation in include/mkt.h.  windows: 1 .. 4 sizes in bins, strictly ascending.  opts: ignore_diags, use_weights,
+        min_frac_valid, min_strength.  Returns InsulationInfo(n_chrom, windows, defined, minima, boundaries), the last three per window."""
+        o = InsulationOpts()
+        self.L.mkt_insulation_opts_default(C.byref(o))
+        windows = [int(w) for w in windows]
+        o.n_windows = len(windows)
+        for k in range(4):
+            o.window[k] = windows[k] if k < len(windows) else 0
+        for k, v in opts.items():
+            if k not in INSULATION_OPTS:
+                raise TypeError(f"insulation: unknown option {k}")
+            setattr(o, k, int(v) if k == "use_weights" else v)
+        info = _InsulationInfoC()
+        self._chk(self.L.mkt_matrix_insulation(self.h, res, C.byref(o), C.byref(info)), "mkt_matrix_insulation")
+        n = min(len(windows), 4)
+        return InsulationInfo(info.n_chrom, tuple(windows), tuple(info.defined[:n]), tuple(info.minima[:n]), tuple(info.boundaries[:n]))
+
+    def insulation_track(self, res, k):
+        """window k of the last insulation(res): InsulationTrack of numpy arrays over the bins (n_valid, csum uint64; bsum, score, log2_score,
+        strength float64, NaN where undefined; boundary bool)"""
+        import numpy as np
+        nb = self.info(res)[0]
+        cols = [np.zeros(nb, np.uint64), np.zeros(nb, np.uint64)] + [np.zeros(nb, np.float64) for _ in range(4)] + [np.zeros(nb, np.uint8)]
+        self._chk(self.L.mkt_matrix_fetch_insulation(self.h, res, k, 0, nb, *[a.ctypes.data_as(C.c_void_p) for a in cols]), "mkt_matrix_fetch_insulation")
+        return InsulationTrack(*cols[:6], cols[6].astype(bool))
+
+    def insulation_timing_ms(self, res):
+        """(setup ms, sweep ms) of the last insulation(res): device time, HIP events"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_insulation_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_insulation_timing")
+        return a.value, b.value
 
     def close(self):
         if self.h:

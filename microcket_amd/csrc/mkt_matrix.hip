@@ -28,6 +28,7 @@
 #include "mkt_expected.h"
 #include "mkt_loops.h"
 #include "mkt_eigs.h"
+#include "mkt_insulation.h"
 #include "mkt_launch.h"
 #include "mkt_layout.h"
 #include "mkt_segred.h"
@@ -292,6 +293,8 @@ struct MxRes {
     LoopsState lps;
     // compartment eigenvectors (mkt_matrix_eigs): the results live until the next expected, balance or run
     EigsState egs;
+    // insulation scores and boundaries (mkt_matrix_insulation): the results live until the next balance or run
+    InsState ins;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -367,6 +370,7 @@ static void mx_free_results(mkt_matrix* m) {
         r.exs = ExpSetup(); r.ext = ExpTables();
         r.exp_setup_ms = r.exp_sums_ms = 0;
         r.lps = LoopsState(); r.egs = EigsState();
+        r.ins = InsState();
     }
     m->ran = false;
 }
@@ -414,13 +418,14 @@ static int mx_process_text(mkt_matrix* m, size_t n) {
 }
 
 // what an entry point needs of a resolution before it may go on; each has its message
-enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16 };
+enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16, MX_INS = 32 };
 static int mx_need(mkt_matrix* m, uint32_t res_index, const MxRes& r, int need, const char* what = nullptr) {
     if ((need & MX_RAN) && !m->ran) return mfail(m, MKT_E_STATE, "%s before run", what);
     if ((need & MX_WEIGHTS) && !(m->ran && r.balanced)) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
     if ((need & MX_TABLES) && !(m->ran && r.ext.built)) return mfail(m, MKT_E_STATE, "no expected tables for resolution index %u: expected first", res_index);
     if ((need & MX_LOOPS) && !(m->ran && r.lps.built)) return mfail(m, MKT_E_STATE, "no loops for resolution index %u: loops first", res_index);
     if ((need & MX_EIGS) && !(m->ran && r.egs.built)) return mfail(m, MKT_E_STATE, "no eigenvectors for resolution index %u: eigs first", res_index);
+    if ((need & MX_INS) && !(m->ran && r.ins.built)) return mfail(m, MKT_E_STATE, "no insulation scores for resolution index %u: insulation first", res_index);
     return MKT_OK;
 }
 // the resolution of an entry point, or the error: the object, the index, then what it needs
@@ -752,6 +757,7 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     r.balanced = false; r.bal_iter_ms = 0;
     r.ext = ExpTables();                                                // tables of other weights
     r.lps = LoopsState(); r.egs = EigsState();
+    r.ins = InsState();                                                 // scores of other weights
     DevBuf<double> d_bias, d_m, d_part, d_w;                            // d_w becomes r.d_w at the end: a failure leaves no weights
     DevBuf<BalState> d_state;
 #define BRUN(call) MX(m, "balance: ", call)
@@ -1169,6 +1175,75 @@ int mkt_matrix_eigs_timing(const mkt_matrix* m, uint32_t res_index, double* setu
     if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
     if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;
     if (small_ms) *small_ms = have ? s.small_ms : 0.0;
+    return MKT_OK;
+}
+
+}  // extern "C"
+
+// ---- insulation scores and boundaries: the entry points; the sweep and the calling are mkt_insulation.hip, the definition is in include/mkt.h
+extern "C" {
+
+void mkt_insulation_opts_default(mkt_insulation_opts* o) {
+    if (!o) return;
+    o->n_windows = 3; o->window[0] = 5; o->window[1] = 10; o->window[2] = 25; o->window[3] = 0;
+    o->ignore_diags = 2; o->use_weights = 1; o->reserved = 0; o->min_frac_valid = 0.66; o->min_strength = 0.2;
+}
+
+int mkt_matrix_insulation(mkt_matrix* m, uint32_t res_index, const mkt_insulation_opts* opts, mkt_insulation_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    mkt_insulation_opts o;
+    mkt_insulation_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.n_windows < 1 || o.n_windows > kInsWindows) return mfail(m, MKT_E_ARG, "insulation: n_windows %d (1 .. 4)", o.n_windows);
+    for (int k = 0; k < o.n_windows; ++k) {
+        if (o.window[k] < 1 || o.window[k] > kInsWmax) return mfail(m, MKT_E_ARG, "insulation: window %d is outside 1 .. %d bins", o.window[k], kInsWmax);
+        if (k && o.window[k] <= o.window[k - 1]) return mfail(m, MKT_E_ARG, "insulation: windows %d, %d are not strictly ascending", o.window[k - 1], o.window[k]);
+    }
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "insulation: ignore_diags %d is negative", o.ignore_diags);
+    if (o.use_weights != 0 && o.use_weights != 1) return mfail(m, MKT_E_ARG, "insulation: use_weights %d (0 or 1)", o.use_weights);
+    if (!(o.min_frac_valid >= 0.0 && o.min_frac_valid <= 1.0)) return mfail(m, MKT_E_ARG, "insulation: min_frac_valid %g is not inside [0, 1]", o.min_frac_valid);
+    if (!(o.min_strength >= 0.0)) return mfail(m, MKT_E_ARG, "insulation: min_strength %g is negative or NaN", o.min_strength);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "insulation: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | (o.use_weights ? MX_WEIGHTS : 0), "insulation")) return rc;
+    if (r.nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "insulation: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)r.nnz);
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    r.ins = InsState();
+#define IRUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { r.ins = InsState(); return mx_hip(m, "insulation: ", e_, true); } } while (0)
+    IRUN(layout_rows(r.lay, mx_cells(r), st));                          // the row pointers and the chromosome of a bin are all the sweep needs
+    InsIn in;
+    in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = r.lay.rowptr; in.off = r.d_off; in.chr = r.lay.chr;
+    in.w = o.use_weights ? r.d_w.get() : nullptr;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    IRUN(insulation_run(r.ins, in, r.off, o, st));
+#undef IRUN
+    if (info) *info = r.ins.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_insulation(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* csum, double* bsum,
+                                double* score, double* log2_score, double* strength, uint8_t* boundary) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_INS);
+    const InsState* s = &rp->ins;
+    const uint64_t nb = rp->nbins;
+    if (k >= (uint32_t)s->n_windows) return mfail(m, MKT_E_ARG, "insulation window %u of %d", k, s->n_windows);
+    if (first > nb || n > nb - first) return mfail(m, MKT_E_ARG, "insulation bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nb);
+    const uint64_t at = (uint64_t)k * nb + first;
+    mx_copy_rows(n_valid, s->n_valid, at, n); mx_copy_rows(csum, s->csum, at, n); mx_copy_rows(bsum, s->bsum, at, n); mx_copy_rows(score, s->score, at, n);
+    mx_copy_rows(log2_score, s->log2_score, at, n); mx_copy_rows(strength, s->strength, at, n); mx_copy_rows(boundary, s->boundary, at, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_insulation_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const InsState& s = m->res[res_index].ins;
+    const bool have = m->ran && s.built;
+    if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
+    if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;
     return MKT_OK;
 }
 

@@ -9,6 +9,7 @@
 //                         [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]
 //                [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]
 //                        [--eigs-track FILE]]
+//                [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -37,6 +38,13 @@
 // .bins.bed in order whose fourth column (a number or nan) fixes the sign; only with a single resolution (a usage error otherwise), a row
 // that does not match is exit 12.  Without --eigs neither file appears and every other byte is the same.  A sub-option without --eigs is
 // a usage error, a malformed value exit 12.
+// With --insulation BP1[,BP2,..] (mkt_matrix_insulation of include/mkt.h: diamond insulation scores and boundaries; 1 .. 4 window sizes in
+// base pairs, strictly ascending, each a positive multiple of every -r and at most 1024 bins, otherwise exit 12 before anything is read;
+// from the weights with --balance, raw counts without) also per resolution <prefix>.<r>.insulation.tsv: a header line, then the columns
+// of .bins.bed plus per window n_valid_<bp>, score_<bp>, log2_insulation_score_<bp>, boundary_strength_<bp> (doubles as %.17g, nan for
+// NaN) and is_boundary_<bp> (0 / 1); and <prefix>.insulation.stat, one row per resolution and window: r, window_bp, bins, defined,
+// minima, boundaries.  Without --insulation neither appears and every other byte is the same.  A sub-option without --insulation is a
+// usage error, a malformed value exit 12.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -52,7 +60,8 @@ static int usage(const char* me) {
                     "       [--loops [--loop-peak N] [--loop-window N] [--loop-window-max N] [--loop-min-ll-count N] [--loop-min-dist N]\n"
                     "                [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]\n"
                     "       [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]\n"
-                    "               [--eigs-track FILE]]\n", me);
+                    "               [--eigs-track FILE]]\n"
+                    "       [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -150,6 +159,9 @@ int main(int argc, char* argv[]) {
     static const char* const gname[7] = {"--eigs-n", "--eigs-ignore-diags", "--eigs-min-good", "--eigs-max-iters", "--eigs-tol", "--eigs-clip", "--eigs-track"};
     const char* lopt[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const lname[8] = {"--loop-peak", "--loop-window", "--loop-window-max", "--loop-min-ll-count", "--loop-min-dist", "--loop-max-dist", "--loop-fdr", "--loop-cluster-radius"};
+    const char* ilist = nullptr;
+    const char* iopt[3] = {nullptr, nullptr, nullptr};
+    static const char* const iname[3] = {"--ins-ignore-diags", "--ins-min-frac-valid", "--ins-min-strength"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -159,7 +171,11 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 8; ++k) if (!strcmp(argv[i], lname[k])) l = k;
         int g = -1;
         for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], gname[k])) g = k;
+        int s = -1;
+        for (int k = 0; k < 3; ++k) if (!strcmp(argv[i], iname[k])) s = k;
         if (g >= 0) { if (i + 1 >= argc) return usage(argv[0]); gopt[g] = argv[++i]; }
+        else if (s >= 0) { if (i + 1 >= argc) return usage(argv[0]); iopt[s] = argv[++i]; }
+        else if (!strcmp(argv[i], "--insulation")) { if (i + 1 >= argc) return usage(argv[0]); ilist = argv[++i]; }
         else if (!strcmp(argv[i], "--eigs")) eigs = expected = true;
         else if (b >= 0) { if (i + 1 >= argc) return usage(argv[0]); bopt[b] = argv[++i]; }
         else if (l >= 0) { if (i + 1 >= argc) return usage(argv[0]); lopt[l] = argv[++i]; }
@@ -205,12 +221,28 @@ int main(int argc, char* argv[]) {
                       : k == 4 ? (parse_num(gopt[k], go.tol) && go.tol > 0.0 && go.tol < 1.0) : parse_num(gopt[k], go.clip);
         if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", gopt[k], gname[k], k == 0 ? "a whole number, 1 .. 4" : k < 4 ? "a whole number, 0 or more" : k == 4 ? "a number inside (0, 1)" : "a number, 0 or more"); return 12; }
     }
+    mkt_insulation_opts io;
+    mkt_insulation_opts_default(&io);
+    io.use_weights = balance ? 1 : 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!iopt[k]) continue;
+        if (!ilist) { fprintf(stderr, "Error: %s needs --insulation\n", iname[k]); return usage(argv[0]); }
+        const bool ok = k == 0 ? parse_int(iopt[k], io.ignore_diags) : k == 1 ? (parse_num(iopt[k], io.min_frac_valid) && io.min_frac_valid <= 1.0) : parse_num(iopt[k], io.min_strength);
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", iopt[k], iname[k], k == 0 ? "a whole number, 0 or more" : k == 1 ? "a number inside [0, 1]" : "a number, 0 or more"); return 12; }
+    }
+    std::vector<uint32_t> ibp;                                                // the windows in base pairs
+    if (ilist && (!parse_res(ilist, ibp) || ibp.size() > 4)) { fprintf(stderr, "Error: bad window list '%s' for --insulation (1 .. 4 different positive numbers, comma separated)\n", ilist); return 12; }
+    for (size_t k = 1; k < ibp.size(); ++k)
+        if (ibp[k] <= ibp[k - 1]) { fprintf(stderr, "Error: the windows of --insulation are not strictly ascending\n"); return 12; }
     std::string ttxt, why;
     if (!read_file(table, ttxt)) { fprintf(stderr, "Error: read chromosome table failed!\n"); return 10; }
     std::vector<Chrom> chroms;
     if (!parse_table(ttxt, chroms, why)) { fprintf(stderr, "Error: bad chromosome table: %s\n", why.c_str()); return 12; }
     std::vector<uint32_t> res;
     if (!parse_res(rlist, res)) { fprintf(stderr, "Error: bad resolution list '%s' (1 .. 16 different positive numbers, comma separated)\n", rlist); return 12; }
+    for (uint32_t r : res)
+        for (uint32_t bp : ibp)
+            if (bp % r != 0 || bp / r > 1024) { fprintf(stderr, "Error: --insulation window %u is not a multiple of resolution %u of at most 1024 bins\n", bp, r); return 12; }
     if (gopt[6] && res.size() != 1) { fprintf(stderr, "Error: --eigs-track needs a single resolution\n"); return usage(argv[0]); }
     std::vector<double> track;
     if (gopt[6]) {                                                            // the bins of .bins.bed in order, with a value each
@@ -271,7 +303,11 @@ int main(int argc, char* argv[]) {
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
 
     const std::string pre = prefix;
-    std::string bstat, lstat, gstat;
+    std::string bstat, lstat, gstat, istat;
+    const uint32_t ni = (uint32_t)ibp.size();
+    std::vector<uint64_t> inv;                                                // [ni][nbins] of the resolution at hand
+    std::vector<double> isc, ilg, ist;
+    std::vector<uint8_t> ibd;
     std::vector<double> evec;
     uint32_t ne = 0;
     std::vector<double> weights;
@@ -398,9 +434,30 @@ int main(int argc, char* argv[]) {
                 if (it[c] && !cv[c]) fprintf(stderr, "WARN: eigenvectors of %s at resolution %u did not converge in %u iterations.\n", chroms[c].name.c_str(), res[k], it[c]);
             }
         }
-        std::string bed, wbed, gbed;
+        if (ni) {
+            io.n_windows = (int32_t)ni;
+            for (uint32_t j = 0; j < 4; ++j) io.window[j] = j < ni ? (int32_t)(ibp[j] / res[k]) : 0;
+            mkt_insulation_info ii;
+            if ((rc = mkt_matrix_insulation(m, k, &io, &ii)) != MKT_OK) return lib_fail("GPU matrix insulation");
+            inv.resize((size_t)ni * nbins); isc.resize((size_t)ni * nbins); ilg.resize((size_t)ni * nbins); ist.resize((size_t)ni * nbins); ibd.resize((size_t)ni * nbins);
+            for (uint32_t j = 0; j < ni; ++j) {
+                const size_t at = (size_t)j * nbins;
+                if ((rc = mkt_matrix_fetch_insulation(m, k, j, 0, nbins, inv.data() + at, nullptr, nullptr, isc.data() + at, ilg.data() + at, ist.data() + at, ibd.data() + at)) != MKT_OK)
+                    return lib_fail("GPU matrix insulation");
+                istat += std::to_string(res[k]); istat += '\t'; istat += std::to_string(ibp[j]); istat += '\t'; istat += std::to_string(nbins);
+                for (uint64_t v : {ii.defined[j], ii.minima[j], ii.boundaries[j]}) { istat += '\t'; istat += std::to_string(v); }
+                istat += '\n';
+            }
+        }
+        std::string bed, wbed, gbed, ibed;
         const uint64_t r = res[k];
-        const char *mode = "wb", *wmode = "wb", *gmode = "wb";             // the first piece truncates, the others append
+        const char *mode = "wb", *wmode = "wb", *gmode = "wb", *imode = "wb";     // the first piece truncates, the others append
+        if (ni) {
+            ibed = "chrom\tstart\tend";
+            for (uint32_t j = 0; j < ni; ++j)
+                for (const char* col : {"n_valid_", "score_", "log2_insulation_score_", "boundary_strength_", "is_boundary_"}) { ibed += '\t'; ibed += col; ibed += std::to_string(ibp[j]); }
+            ibed += '\n';
+        }
         if (eigs) { gbed = "chrom\tstart\tend"; for (uint32_t j = 0; j < ne; ++j) { gbed += "\tE"; gbed += std::to_string(j + 1); } gbed += '\n'; }
         uint64_t bin = 0;
         for (const Chrom& c : chroms)
@@ -426,6 +483,19 @@ int main(int argc, char* argv[]) {
                         gbed.clear(); gmode = "ab";
                     }
                 }
+                if (ni) {
+                    ibed.append(bed, at, bed.size() - at - 1);
+                    for (uint32_t j = 0; j < ni; ++j) {
+                        const size_t x = (size_t)j * nbins + bin;
+                        ibed += '\t'; ibed += std::to_string(inv[x]); ibed += '\t'; put_num(ibed, isc[x]); ibed += '\t'; put_num(ibed, ilg[x]); ibed += '\t'; put_num(ibed, ist[x]);
+                        ibed += ibd[x] ? "\t1" : "\t0";
+                    }
+                    ibed += '\n';
+                    if (ibed.size() > ((size_t)32 << 20)) {
+                        if (!write_file(pre + "." + std::to_string(res[k]) + ".insulation.tsv", ibed.data(), ibed.size(), imode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+                        ibed.clear(); imode = "ab";
+                    }
+                }
                 if (bed.size() > ((size_t)32 << 20)) {
                     if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
                     bed.clear(); mode = "ab";
@@ -435,7 +505,9 @@ int main(int argc, char* argv[]) {
         if (!write_file(pre + "." + std::to_string(res[k]) + ".bins.bed", bed.data(), bed.size(), mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (balance && !write_file(pre + "." + std::to_string(res[k]) + ".weights.bed", wbed.data(), wbed.size(), wmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (eigs && !write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+        if (ni && !write_file(pre + "." + std::to_string(res[k]) + ".insulation.tsv", ibed.data(), ibed.size(), imode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
+    if (ni && !write_file(pre + ".insulation.stat", istat.data(), istat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (eigs && !write_file(pre + ".eigs.stat", gstat.data(), gstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (balance && !write_file(pre + ".balance.stat", bstat.data(), bstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (loops && !write_file(pre + ".loops.stat", lstat.data(), lstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
