@@ -692,6 +692,78 @@ int mkt_matrix_fetch_insulation(mkt_matrix* m, uint32_t res_index, uint32_t k, u
                                 double* score, double* log2_score, double* strength, uint8_t* boundary);
 int mkt_matrix_insulation_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms);
 
+/* ---- pileups: the average contact map in a small window around a list of features; aggregate peak analysis (APA) ------------------
+ * The step that judges the calls: with the called loops as the list it is `juicer_tools apa`, with the insulation boundaries the
+ * on-diagonal pileup of `cooltools pileup` / coolpup.py, with a user's pairs of anchors a comparison of matrices at known features.
+ * The definition is this project's own, modelled on those; parity with juicer_tools and cooltools is UNPINNED (neither is run anywhere
+ * here).  tests/piledef.py restates the definition in numpy.  All floating point is float64.
+ *
+ * Inputs, for one resolution: the cells (bin1 <= bin2, count), the chromosome ranges [off_c, off_c + n_c) and the state of the last
+ * mkt_matrix_expected: its use_weights, w[k] and valid(k), the genome-wide expected[d] and expected_smooth[d];
+ * v = ((double)count * w[bin1]) * w[bin2].  n features (a_f, b_f) as global bin ids in the order given; duplicates are allowed.
+ * Options (mkt_pileup_opts): flank (1 .. 32, side S = 2 * flank + 1), corner (1 .. flank), kind (MKT_VALUE_BALANCED, MKT_VALUE_OE or
+ * MKT_VALUE_OE_SMOOTH), ignore_diags, edges (0 / 1), min_dist, max_dist (0 = none).
+ *  1. STATUS of a feature: MKT_PILE_TRANS when the anchors lie in different chromosomes; else MKT_PILE_DIST when b - a < min_dist, or
+ *     b - a > max_dist when that is set; else MKT_PILE_EDGE when edges == 0 and some bin of a +- flank or b +- flank leaves the
+ *     chromosome's range; else MKT_PILE_USED.  Only USED features contribute.  a > b or a bin >= nbins is MKT_E_ARG with a message that
+ *     names the feature, and nothing is computed.
+ *  2. POSITIONS: (p, q) with -flank <= p, q <= flank denotes i = a + p, j = b + q.  The matrix is symmetric: the cell looked up is
+ *     (min(i, j), max(i, j)) and d = |j - i|.  A position is KEPT when both bins are inside the chromosome, both are valid and
+ *     d >= ignore_diags.
+ *  3. VALUE of a stored cell at a kept position: v for BALANCED, v / expected[d] for OE, v / expected_smooth[d] for OE_SMOOTH: one IEEE
+ *     division, never fused, no reciprocal approximation.  A stored cell with two valid bins has a divisor > 0 (expected, step 7).
+ *  4. Per position over the used features: n[p][q] (uint64) = the features where the position is kept; csum[p][q] (uint64, exact) = the
+ *     sum of count over the stored cells at kept positions; vsum[p][q] = the sum of the values over the same cells.  An absent cell at
+ *     a kept position adds nothing and still counts in n.  mean = vsum / (double)n, NaN when n == 0.
+ *  5. SUMMATION ORDER of vsum, which is part of the definition: chunk c holds the features [256 c, 256 c + 256) by their index as given
+ *     (features that are not used keep their slots); T_c[p][q] starts from 0.0 and takes the values of the chunk's used features in
+ *     ascending index; vsum starts from 0.0 and takes T_0, T_1, .. in ascending c.  No floating-point atomics.  The result is the same
+ *     bits from call to call, process to process and by every route (add, add_device, add_keys), and the same bits as
+ *     tests/piledef.py, which adds in this same order.
+ *  6. SCORES, on the host, from mean.  Boxes of corner x corner positions: LL p in [flank - corner + 1, flank], q in
+ *     [-flank, -flank + corner - 1] (the corner towards the diagonal, as in the loops stage); UL p low, q low; UR p low, q high; LR p
+ *     high, q high.  mean_B = the sum of the finite mean over the box in ascending (p, q), divided by their number; NaN when there are
+ *     none.  peak = mean[0][0]; p2ll = peak / mean_LL, p2ul, p2ur, p2lr the same; p2m = peak / (the mean of the finite values at all
+ *     positions but (0, 0)); z_ll = (peak - mean_LL) / sd_LL, sd_LL = the square root of the sum of (x - mean_LL)^2 in ascending (p, q)
+ *     over (k - 1), NaN with fewer than two finite values.
+ * Out of scope: shifted or random controls, rescaled (variable-size) features, by-strand or by-distance splitting, trans pileups,
+ * per-feature snippets, a .hic / .cool reader.
+ *
+ *   mkt_pileup_opts_default         flank 10, corner 6, kind OE_SMOOTH, ignore_diags 2, edges 0, min_dist 0, max_dist 0
+ *   mkt_matrix_pileup               valid after mkt_matrix_expected of that resolution (MKT_E_STATE "expected first" without tables,
+ *                                   "pileup before run" before mkt_matrix_run); opts NULL = the defaults; n == 0 is allowed (all counts
+ *                                   zero, mean and scores NaN).  MKT_E_ARG with a message for a bad index, flank outside 1 .. 32, corner
+ *                                   outside 1 .. flank, a bad kind, a negative option, edges not 0 / 1, max_dist set and below min_dist,
+ *                                   a non-zero reserved, a bad feature (step 1) or NULL bins with n > 0; MKT_E_CAPACITY for n >= 2^32.
+ *                                   info may be NULL.  A refused call leaves the previous results alone.  A later mkt_matrix_run, add,
+ *                                   balance or expected of that resolution discards the results; loops, eigenvectors, insulation and
+ *                                   pileup of one resolution do not disturb each other.  Features go to the device in batches of 4096
+ *                                   chunks (2^20 features), so the partial sums take at most 4096 * S^2 * 20 bytes whatever n is; the
+ *                                   bits do not depend on the batch.
+ *   mkt_matrix_fetch_pileup         n, csum, vsum, mean as [side][side], row p, column q (index [p + flank][q + flank]); any may be NULL
+ *   mkt_matrix_fetch_pileup_status  the MKT_PILE_* of features [first, first + n); MKT_E_ARG with a message for a bad range
+ *   mkt_matrix_pileup_timing        of the last mkt_matrix_pileup of res_index (ms, HIP events, added over the batches): the setup (the
+ *                                   upload of the features and their statuses) and the sweep (the chunk kernel and the fold).  A bad
+ *                                   index is MKT_E_ARG without a message; 0, 0 without results. */
+#define MKT_PILE_USED 1
+#define MKT_PILE_TRANS 2
+#define MKT_PILE_EDGE 3
+#define MKT_PILE_DIST 4
+typedef struct mkt_pileup_opts {
+    int32_t flank, corner, kind, ignore_diags, edges, min_dist, max_dist;
+    uint32_t reserved;       /* 0 */
+} mkt_pileup_opts;
+typedef struct mkt_pileup_info {
+    uint64_t features, used, trans, edge, dist;
+    uint32_t side, chunks;
+    double peak, p2ll, p2ul, p2ur, p2lr, p2m, z_ll;
+} mkt_pileup_info;
+void mkt_pileup_opts_default(mkt_pileup_opts* o);
+int mkt_matrix_pileup(mkt_matrix* m, uint32_t res_index, const uint32_t* bin1, const uint32_t* bin2, uint64_t n, const mkt_pileup_opts* opts, mkt_pileup_info* info);
+int mkt_matrix_fetch_pileup(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* csum, double* vsum, double* mean);
+int mkt_matrix_fetch_pileup_status(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status);
+int mkt_matrix_pileup_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms);
+
 #ifdef __cplusplus
 }
 #endif

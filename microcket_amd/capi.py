@@ -31,6 +31,7 @@ EXPORTS = [
     "mkt_matrix_fetch_loops", "mkt_matrix_loops_timing",
     "mkt_eigs_opts_default", "mkt_matrix_eigs", "mkt_matrix_fetch_eigvecs", "mkt_matrix_fetch_eigvals", "mkt_matrix_eigs_apply", "mkt_matrix_eigs_timing",
     "mkt_insulation_opts_default", "mkt_matrix_insulation", "mkt_matrix_fetch_insulation", "mkt_matrix_insulation_timing",
+    "mkt_pileup_opts_default", "mkt_matrix_pileup", "mkt_matrix_fetch_pileup", "mkt_matrix_fetch_pileup_status", "mkt_matrix_pileup_timing",
 ]
 
 
@@ -136,6 +137,23 @@ class _InsulationInfoC(C.Structure):
 InsulationInfo = collections.namedtuple("InsulationInfo", "n_chrom windows defined minima boundaries")
 InsulationTrack = collections.namedtuple("InsulationTrack", "n_valid csum bsum score log2_score strength boundary")
 INSULATION_OPTS = ("ignore_diags", "use_weights", "min_frac_valid", "min_strength")
+
+
+class PileupOpts(C.Structure):
+    """mkt_pileup_opts of include/mkt.h"""
+    _fields_ = [("flank", C.c_int32), ("corner", C.c_int32), ("kind", C.c_int32), ("ignore_diags", C.c_int32), ("edges", C.c_int32), ("min_dist", C.c_int32),
+                ("max_dist", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _PileupInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("features", "used", "trans", "edge", "dist")] + [("side", C.c_uint32), ("chunks", C.c_uint32)] + \
+               [(k, C.c_double) for k in ("peak", "p2ll", "p2ul", "p2ur", "p2lr", "p2m", "z_ll")]
+
+
+PileupInfo = collections.namedtuple("PileupInfo", "features used trans edge dist side chunks peak p2ll p2ul p2ur p2lr p2m z_ll")
+Pileup = collections.namedtuple("Pileup", "n csum vsum mean status")
+PILEUP_OPTS = ("flank", "corner", "kind", "ignore_diags", "edges", "min_dist", "max_dist")
+PILE_USED, PILE_TRANS, PILE_EDGE, PILE_DIST = 1, 2, 3, 4
 
 
 class Timing(C.Structure):
@@ -322,6 +340,12 @@ def load_library():
     L.mkt_matrix_insulation.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(InsulationOpts), C.POINTER(_InsulationInfoC)]
     L.mkt_matrix_fetch_insulation.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 7
     L.mkt_matrix_insulation_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_pileup_opts_default.argtypes = [C.POINTER(PileupOpts)]
+    L.mkt_pileup_opts_default.restype = None
+    L.mkt_matrix_pileup.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(PileupOpts), C.POINTER(_PileupInfoC)]
+    L.mkt_matrix_fetch_pileup.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
+    L.mkt_matrix_fetch_pileup_status.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_pileup_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -797,6 +821,8 @@ class Matrix:
         rows = (_LoopC * max(info.loops, 1))()
         self._chk(self.L.mkt_matrix_fetch_loops(self.h, res, 0, info.loops, rows), "mkt_matrix_fetch_loops")
         table = [Loop(x.cell, x.bin1, x.bin2, x.count, x.window, tuple(x.r), x.n_cells, tuple(x.box)) for x in rows[:info.loops]]
+        self._n_loops = getattr(self, "_n_loops", {})
+        self._n_loops[res] = info.loops                                     # pileup_loops reads the table again
         return Loops(table, LoopsInfo(*[getattr(info, k) for k in LoopsInfo._fields]))
 
     def loop_cells(self, res):
@@ -913,6 +939,65 @@ class Matrix:
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_insulation_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_insulation_timing")
         return a.value, b.value
+
+    def pileup(self, res, bin1, bin2, **opts):
+        """Pileup of resolution index res around the features (bin1[f], bin2[f]) (global bin ids, bin1 <= bin2) after expected(res): the
+        definition is mkt_matrix_pileup in include/mkt.h.  opts: flank, corner, kind ("balanced", "oe", "oe_smooth" or its number),
+        ignore_diags, edges, min_dist, max_dist.  Returns PileupInfo (the counts per status, side, chunks and the seven scores)."""
+        import numpy as np
+        o = PileupOpts()
+        self.L.mkt_pileup_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in PILEUP_OPTS:
+                raise TypeError(f"pileup: unknown option {k}")
+            if k == "kind" and isinstance(v, str):
+                if v not in VALUE_KINDS:
+                    raise ValueError(f"pileup: kind {v!r} (one of {', '.join(VALUE_KINDS)})")
+                v = VALUE_KINDS[v]
+            setattr(o, k, int(v))
+        a, b = np.ascontiguousarray(bin1, dtype=np.uint32).ravel(), np.ascontiguousarray(bin2, dtype=np.uint32).ravel()
+        if a.shape != b.shape:
+            raise ValueError(f"pileup: {a.size} first bins and {b.size} second bins")
+        info = _PileupInfoC()
+        self._chk(self.L.mkt_matrix_pileup(self.h, res, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), a.size, C.byref(o), C.byref(info)), "mkt_matrix_pileup")
+        self._pile_shape = getattr(self, "_pile_shape", {})
+        self._pile_shape[res] = (info.side, info.features)
+        return PileupInfo(*[getattr(info, k) for k in PileupInfo._fields])
+
+    def pileup_result(self, res):
+        """the arrays of the last pileup(res): Pileup(n, csum uint64 [side, side]; vsum, mean float64 [side, side], row p + flank, column
+        q + flank; status uint8 [features], the PILE_* of every feature)"""
+        import numpy as np
+        cap = 65 * 65
+        cols = [np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.float64), np.zeros(cap, np.float64)]
+        self._chk(self.L.mkt_matrix_fetch_pileup(self.h, res, *[a.ctypes.data_as(C.c_void_p) for a in cols]), "mkt_matrix_fetch_pileup")
+        side, nf = getattr(self, "_pile_shape", {}).get(res, (0, 0))
+        if not side:
+            raise MktError("pileup_result: the pileup of this resolution was not made through pileup()")
+        st = np.zeros(nf, np.uint8)
+        self._chk(self.L.mkt_matrix_fetch_pileup_status(self.h, res, 0, nf, st.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_pileup_status")
+        return Pileup(*[a[:side * side].reshape(side, side).copy() for a in cols], st)
+
+    def pileup_timing_ms(self, res):
+        """(setup ms, sweep ms) of the last pileup(res): device time, HIP events"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_pileup_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_pileup_timing")
+        return a.value, b.value
+
+    def pileup_loops(self, res, **opts):
+        """APA: pileup(res) around the peak cells of the last loops(res), in loop order"""
+        self._chk(self.L.mkt_matrix_fetch_loops(self.h, res, 0, 0, None), "mkt_matrix_fetch_loops")      # "loops first" when there are none
+        n = getattr(self, "_n_loops", {}).get(res, 0)
+        rows = (_LoopC * max(n, 1))()
+        self._chk(self.L.mkt_matrix_fetch_loops(self.h, res, 0, n, rows), "mkt_matrix_fetch_loops")
+        b1, b2 = [x.bin1 for x in rows[:n]], [x.bin2 for x in rows[:n]]
+        return self.pileup(res, b1, b2, **opts)
+
+    def pileup_boundaries(self, res, k, **opts):
+        """on-diagonal pileup(res) around (i, i) for the boundary bins of window k of the last insulation(res), ascending"""
+        import numpy as np
+        i = np.flatnonzero(self.insulation_track(res, k).boundary).astype(np.uint32)
+        return self.pileup(res, i, i, **opts)
 
     def close(self):
         if self.h:

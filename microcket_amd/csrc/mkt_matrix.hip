@@ -29,6 +29,7 @@
 #include "mkt_loops.h"
 #include "mkt_eigs.h"
 #include "mkt_insulation.h"
+#include "mkt_pileup.h"
 #include "mkt_launch.h"
 #include "mkt_layout.h"
 #include "mkt_segred.h"
@@ -295,6 +296,8 @@ struct MxRes {
     EigsState egs;
     // insulation scores and boundaries (mkt_matrix_insulation): the results live until the next balance or run
     InsState ins;
+    // pileup (mkt_matrix_pileup): the results live until the next expected, balance or run
+    PileState pile;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -371,6 +374,7 @@ static void mx_free_results(mkt_matrix* m) {
         r.exp_setup_ms = r.exp_sums_ms = 0;
         r.lps = LoopsState(); r.egs = EigsState();
         r.ins = InsState();
+        r.pile = PileState();
     }
     m->ran = false;
 }
@@ -418,7 +422,7 @@ static int mx_process_text(mkt_matrix* m, size_t n) {
 }
 
 // what an entry point needs of a resolution before it may go on; each has its message
-enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16, MX_INS = 32 };
+enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16, MX_INS = 32, MX_PILE = 64 };
 static int mx_need(mkt_matrix* m, uint32_t res_index, const MxRes& r, int need, const char* what = nullptr) {
     if ((need & MX_RAN) && !m->ran) return mfail(m, MKT_E_STATE, "%s before run", what);
     if ((need & MX_WEIGHTS) && !(m->ran && r.balanced)) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
@@ -426,6 +430,7 @@ static int mx_need(mkt_matrix* m, uint32_t res_index, const MxRes& r, int need, 
     if ((need & MX_LOOPS) && !(m->ran && r.lps.built)) return mfail(m, MKT_E_STATE, "no loops for resolution index %u: loops first", res_index);
     if ((need & MX_EIGS) && !(m->ran && r.egs.built)) return mfail(m, MKT_E_STATE, "no eigenvectors for resolution index %u: eigs first", res_index);
     if ((need & MX_INS) && !(m->ran && r.ins.built)) return mfail(m, MKT_E_STATE, "no insulation scores for resolution index %u: insulation first", res_index);
+    if ((need & MX_PILE) && !(m->ran && r.pile.built)) return mfail(m, MKT_E_STATE, "no pileup for resolution index %u: pileup first", res_index);
     return MKT_OK;
 }
 // the resolution of an entry point, or the error: the object, the index, then what it needs
@@ -758,6 +763,7 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     r.ext = ExpTables();                                                // tables of other weights
     r.lps = LoopsState(); r.egs = EigsState();
     r.ins = InsState();                                                 // scores of other weights
+    r.pile = PileState();
     DevBuf<double> d_bias, d_m, d_part, d_w;                            // d_w becomes r.d_w at the end: a failure leaves no weights
     DevBuf<BalState> d_state;
 #define BRUN(call) MX(m, "balance: ", call)
@@ -879,6 +885,7 @@ int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_op
     hipStream_t st = m->stream;
     r.ext = ExpTables();
     r.lps = LoopsState(); r.egs = EigsState();                          // loops and eigenvectors of other tables
+    r.pile = PileState();                                               // ... and a pileup of other divisors
     r.exp_sums_ms = r.exp_setup_ms = 0;
 #define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { r.ext = ExpTables(); return mx_hip(m, "expected: ", e_, true); } } while (0)
     if (!r.exs.built) {                                                 // with the chromosome of a bin when nothing has built it yet
@@ -1241,6 +1248,81 @@ int mkt_matrix_fetch_insulation(mkt_matrix* m, uint32_t res_index, uint32_t k, u
 int mkt_matrix_insulation_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
     if (!m || res_index >= m->res.size()) return MKT_E_ARG;
     const InsState& s = m->res[res_index].ins;
+    const bool have = m->ran && s.built;
+    if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
+    if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;
+    return MKT_OK;
+}
+
+}  // extern "C"
+
+// ---- pileups: the entry points; the sweep, the statuses and the scores are mkt_pileup.hip, the definition is in include/mkt.h
+extern "C" {
+
+void mkt_pileup_opts_default(mkt_pileup_opts* o) {
+    if (!o) return;
+    o->flank = 10; o->corner = 6; o->kind = MKT_VALUE_OE_SMOOTH; o->ignore_diags = 2; o->edges = 0; o->min_dist = 0; o->max_dist = 0; o->reserved = 0;
+}
+
+int mkt_matrix_pileup(mkt_matrix* m, uint32_t res_index, const uint32_t* bin1, const uint32_t* bin2, uint64_t n, const mkt_pileup_opts* opts, mkt_pileup_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    mkt_pileup_opts o;
+    mkt_pileup_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.flank < 1 || o.flank > kPileFlankMax) return mfail(m, MKT_E_ARG, "pileup: flank %d is outside 1 .. %d", o.flank, kPileFlankMax);
+    if (o.corner < 1 || o.corner > o.flank) return mfail(m, MKT_E_ARG, "pileup: corner %d is outside 1 .. flank %d", o.corner, o.flank);
+    if (o.kind != MKT_VALUE_BALANCED && o.kind != MKT_VALUE_OE && o.kind != MKT_VALUE_OE_SMOOTH) return mfail(m, MKT_E_ARG, "pileup: kind %d (0 balanced, 1 oe, 2 oe_smooth)", o.kind);
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "pileup: ignore_diags %d is negative", o.ignore_diags);
+    if (o.edges != 0 && o.edges != 1) return mfail(m, MKT_E_ARG, "pileup: edges %d (0 or 1)", o.edges);
+    if (o.min_dist < 0 || o.max_dist < 0) return mfail(m, MKT_E_ARG, "pileup: min_dist %d / max_dist %d is negative", o.min_dist, o.max_dist);
+    if (o.max_dist && o.max_dist < o.min_dist) return mfail(m, MKT_E_ARG, "pileup: max_dist %d is below min_dist %d", o.max_dist, o.min_dist);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "pileup: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "pileup")) return rc;
+    if (n && (!bin1 || !bin2)) return mfail(m, MKT_E_ARG, "pileup: %llu features without their bins (bin1 or bin2 is NULL)", (unsigned long long)n);
+    if (n >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "pileup: %llu features: fewer than 2^32 are needed", (unsigned long long)n);
+    if (r.nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "pileup: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)r.nnz);
+    PileState ps;                                                       // a refused or failed call leaves the previous results alone
+    std::string why;
+    if (!pileup_status(bin1, bin2, n, r.off, r.nbins, o, ps.status, why)) return mfail(m, MKT_E_ARG, "%s", why.c_str());
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    MX(m, "pileup: ", layout_rows(r.lay, mx_cells(r), st));             // the row pointers and the chromosome of a bin are all the sweep needs
+    PileIn in;
+    in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = r.lay.rowptr; in.off = r.d_off; in.chr = r.lay.chr;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr;
+    in.E = o.kind == MKT_VALUE_OE ? r.ext.d_cis_e.get() : o.kind == MKT_VALUE_OE_SMOOTH ? r.ext.d_cis_sm.get() : nullptr;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    MX(m, "pileup: ", pileup_run(ps, in, bin1, bin2, n, o, st));
+    r.pile = std::move(ps);
+    if (info) *info = r.pile.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_pileup(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* csum, double* vsum, double* mean) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_PILE);
+    const PileState* s = &rp->pile;
+    const uint64_t rows = s->n.size();
+    mx_copy_rows(n, s->n, 0, rows); mx_copy_rows(csum, s->csum, 0, rows); mx_copy_rows(vsum, s->vsum, 0, rows); mx_copy_rows(mean, s->mean, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_pileup_status(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_PILE);
+    const PileState* s = &rp->pile;
+    const uint64_t rows = s->status.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "pileup features [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    mx_copy_rows(status, s->status, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_pileup_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const PileState& s = m->res[res_index].pile;
     const bool have = m->ran && s.built;
     if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
     if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;

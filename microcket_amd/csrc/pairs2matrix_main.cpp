@@ -10,6 +10,7 @@
 //                [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]
 //                        [--eigs-track FILE]]
 //                [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]
+//                [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -45,6 +46,17 @@
 // NaN) and is_boundary_<bp> (0 / 1); and <prefix>.insulation.stat, one row per resolution and window: r, window_bp, bins, defined,
 // minima, boundaries.  Without --insulation neither appears and every other byte is the same.  A sub-option without --insulation is a
 // usage error, a malformed value exit 12.
+// With --apa (mkt_matrix_pileup of include/mkt.h around the peak cells of the loops, in loop order: aggregate peak analysis; it implies
+// --loops and with it --expected) also per resolution <prefix>.<r>.apa.tsv: a header line, then side^2 rows p, q, n, csum, vsum, mean in
+// ascending (p, q), doubles as %.17g and nan for NaN; and <prefix>.apa.stat, one row per resolution: r, features, used, trans, edge, dist,
+// peak, p2ll, p2ul, p2ur, p2lr, p2m, z_ll.  With --pileup FILE.bedpe (it implies --expected) the same around the pairs of anchors of the
+// file as <prefix>.<r>.pileup.tsv and <prefix>.pileup.stat: six tab-separated columns or more (chrom1, start1, end1, chrom2, start2,
+// end2), '#' lines and empty lines skipped; an anchor's bin is that of its midpoint (start + end) / 2, a pair whose first bin is the
+// larger is swapped; an unknown chromosome, a midpoint at or past the chromosome's length or a malformed line is exit 12 before anything
+// is read.  --pile-flank (1 .. 32, default 10), --pile-corner (1 .. flank, default 6, or the flank when that is smaller), --pile-kind
+// (default oe-smooth) and --pile-edges (clip the windows of features near a chromosome's end instead of leaving those features out) hold
+// for both; one of them without --apa or --pileup is a usage error, a bad value exit 12.  Without the two flags none of these files
+// appears and every other byte is the same.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -61,7 +73,8 @@ static int usage(const char* me) {
                     "                [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]\n"
                     "       [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]\n"
                     "               [--eigs-track FILE]]\n"
-                    "       [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]\n", me);
+                    "       [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]\n"
+                    "       [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -151,6 +164,77 @@ static void put_num(std::string& out, double x) {
     out += num;
 }
 
+// a start or an end of a BEDPE line: a whole non-negative decimal number
+static bool parse_coord(const std::string& f, uint64_t& out) {
+    if (f.empty() || f.size() > 18) return false;
+    uint64_t v = 0;
+    for (char ch : f) { if (ch < '0' || ch > '9') return false; v = v * 10 + (uint64_t)(ch - '0'); }
+    out = v;
+    return true;
+}
+// chrom1, start1, end1, chrom2, start2, end2 [, ...] per line -> (chromosome index, midpoint) twice per feature
+struct Anchor { size_t c1, c2; uint64_t m1, m2; };
+static bool parse_bedpe(const std::string& txt, const std::vector<Chrom>& chroms, std::vector<Anchor>& out, std::string& why) {
+    size_t p = 0, line = 0;
+    while (p < txt.size()) {
+        size_t q = txt.find('\n', p);
+        if (q == std::string::npos) q = txt.size();
+        size_t e = q;
+        ++line;
+        if (e > p && txt[e - 1] == '\r') --e;
+        if (e > p && txt[p] != '#') {
+            std::string f[6];
+            size_t at = p;
+            int k = 0;
+            for (; k < 6; ++k) {
+                size_t t = at;
+                while (t < e && txt[t] != '\t') ++t;
+                f[k] = txt.substr(at, t - at);
+                if (t >= e) { ++k; break; }
+                at = t + 1;
+            }
+            if (k < 6) { why = "line " + std::to_string(line) + ": six tab-separated columns are needed (chrom1, start1, end1, chrom2, start2, end2)"; return false; }
+            Anchor a;
+            uint64_t v[4];
+            for (int j = 0; j < 4; ++j)
+                if (!parse_coord(f[j < 2 ? 1 + j : 2 + j], v[j])) { why = "line " + std::to_string(line) + ": '" + f[j < 2 ? 1 + j : 2 + j] + "' is not a position"; return false; }
+            if (v[1] < v[0] || v[3] < v[2]) { why = "line " + std::to_string(line) + ": an end before its start"; return false; }
+            for (int side = 0; side < 2; ++side) {
+                const std::string& nm = f[side ? 3 : 0];
+                size_t c = 0;
+                while (c < chroms.size() && chroms[c].name != nm) ++c;
+                if (c == chroms.size()) { why = "line " + std::to_string(line) + ": unknown chromosome " + nm; return false; }
+                const uint64_t mid = (v[2 * side] + v[2 * side + 1]) / 2;
+                if (mid >= chroms[c].len) { why = "line " + std::to_string(line) + ": midpoint " + std::to_string(mid) + " is past the end of " + nm + " (" + std::to_string(chroms[c].len) + ")"; return false; }
+                (side ? a.c2 : a.c1) = c; (side ? a.m2 : a.m1) = mid;
+            }
+            out.push_back(a);
+        }
+        p = q + 1;
+    }
+    return true;
+}
+// the arrays and the info of the last mkt_matrix_pileup of resolution index k as <fn> and one more row of `stat`
+static int write_pileup(mkt_matrix* m, uint32_t k, uint32_t r, const mkt_pileup_info& pi, const std::string& fn, std::string& stat) {
+    const size_t S = pi.side, S2 = S * S;
+    std::vector<uint64_t> n(S2), cs(S2);
+    std::vector<double> vs(S2), mean(S2);
+    const int rc = mkt_matrix_fetch_pileup(m, k, n.data(), cs.data(), vs.data(), mean.data());
+    if (rc != MKT_OK) return rc;
+    std::string t = "p\tq\tn\tcsum\tvsum\tmean\n";
+    const int flank = (int)(S / 2);
+    for (size_t x = 0; x < S2; ++x) {
+        t += std::to_string((int)(x / S) - flank); t += '\t'; t += std::to_string((int)(x % S) - flank); t += '\t'; t += std::to_string(n[x]); t += '\t'; t += std::to_string(cs[x]); t += '\t';
+        put_num(t, vs[x]); t += '\t'; put_num(t, mean[x]); t += '\n';
+    }
+    if (!write_file(fn, t.data(), t.size())) return -1;
+    stat += std::to_string(r);
+    for (uint64_t v : {pi.features, pi.used, pi.trans, pi.edge, pi.dist}) { stat += '\t'; stat += std::to_string(v); }
+    for (double v : {pi.peak, pi.p2ll, pi.p2ul, pi.p2ur, pi.p2lr, pi.p2m, pi.z_ll}) { stat += '\t'; put_num(stat, v); }
+    stat += '\n';
+    return MKT_OK;
+}
+
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
@@ -162,6 +246,10 @@ int main(int argc, char* argv[]) {
     const char* ilist = nullptr;
     const char* iopt[3] = {nullptr, nullptr, nullptr};
     static const char* const iname[3] = {"--ins-ignore-diags", "--ins-min-frac-valid", "--ins-min-strength"};
+    bool apa = false;
+    const char* pfile = nullptr;
+    const char* popt[4] = {nullptr, nullptr, nullptr, nullptr};              // --pile-edges takes no value: its slot holds the flag itself
+    static const char* const pname[4] = {"--pile-flank", "--pile-corner", "--pile-kind", "--pile-edges"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -173,7 +261,13 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], gname[k])) g = k;
         int s = -1;
         for (int k = 0; k < 3; ++k) if (!strcmp(argv[i], iname[k])) s = k;
-        if (g >= 0) { if (i + 1 >= argc) return usage(argv[0]); gopt[g] = argv[++i]; }
+        int pl = -1;
+        for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], pname[k])) pl = k;
+        if (pl == 3) popt[3] = argv[i];
+        else if (pl >= 0) { if (i + 1 >= argc) return usage(argv[0]); popt[pl] = argv[++i]; }
+        else if (!strcmp(argv[i], "--apa")) apa = loops = expected = true;
+        else if (!strcmp(argv[i], "--pileup")) { if (i + 1 >= argc) return usage(argv[0]); pfile = argv[++i]; expected = true; }
+        else if (g >= 0) { if (i + 1 >= argc) return usage(argv[0]); gopt[g] = argv[++i]; }
         else if (s >= 0) { if (i + 1 >= argc) return usage(argv[0]); iopt[s] = argv[++i]; }
         else if (!strcmp(argv[i], "--insulation")) { if (i + 1 >= argc) return usage(argv[0]); ilist = argv[++i]; }
         else if (!strcmp(argv[i], "--eigs")) eigs = expected = true;
@@ -230,6 +324,22 @@ int main(int argc, char* argv[]) {
         const bool ok = k == 0 ? parse_int(iopt[k], io.ignore_diags) : k == 1 ? (parse_num(iopt[k], io.min_frac_valid) && io.min_frac_valid <= 1.0) : parse_num(iopt[k], io.min_strength);
         if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", iopt[k], iname[k], k == 0 ? "a whole number, 0 or more" : k == 1 ? "a number inside [0, 1]" : "a number, 0 or more"); return 12; }
     }
+    mkt_pileup_opts po;
+    mkt_pileup_opts_default(&po);
+    for (int k = 0; k < 4; ++k) {
+        if (!popt[k]) continue;
+        if (!apa && !pfile) { fprintf(stderr, "Error: %s needs --apa or --pileup\n", pname[k]); return usage(argv[0]); }
+        bool ok = true;
+        if (k == 0) ok = parse_int(popt[k], po.flank) && po.flank >= 1 && po.flank <= 32;
+        else if (k == 1) ok = parse_int(popt[k], po.corner) && po.corner >= 1;
+        else if (k == 2) {
+            if (!strcmp(popt[k], "balanced")) po.kind = MKT_VALUE_BALANCED; else if (!strcmp(popt[k], "oe")) po.kind = MKT_VALUE_OE;
+            else if (!strcmp(popt[k], "oe-smooth")) po.kind = MKT_VALUE_OE_SMOOTH; else ok = false;
+        } else po.edges = 1;
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", popt[k], pname[k], k == 0 ? "a whole number, 1 .. 32" : k == 1 ? "a whole number, at least 1" : "balanced, oe or oe-smooth"); return 12; }
+    }
+    if (!popt[1] && po.corner > po.flank) po.corner = po.flank;               // the default corner inside a small window
+    if ((apa || pfile) && po.corner > po.flank) { fprintf(stderr, "Error: --pile-corner %d is larger than --pile-flank %d\n", po.corner, po.flank); return 12; }
     std::vector<uint32_t> ibp;                                                // the windows in base pairs
     if (ilist && (!parse_res(ilist, ibp) || ibp.size() > 4)) { fprintf(stderr, "Error: bad window list '%s' for --insulation (1 .. 4 different positive numbers, comma separated)\n", ilist); return 12; }
     for (size_t k = 1; k < ibp.size(); ++k)
@@ -272,6 +382,12 @@ int main(int argc, char* argv[]) {
         for (const Chrom& c : chroms) nb += (c.len + r - 1) / r;
         if (nb >= (1ull << 32)) { fprintf(stderr, "Error: resolution %u gives 2^32 bins or more\n", r); return 12; }
     }
+    std::vector<Anchor> anchors;                                              // the features of --pileup
+    if (pfile) {
+        std::string txt;
+        if (!read_file(pfile, txt)) { fprintf(stderr, "Error: read pileup file failed!\n"); return 10; }
+        if (!parse_bedpe(txt, chroms, anchors, why)) { fprintf(stderr, "Error: bad pileup file: %s\n", why.c_str()); return 12; }
+    }
     std::vector<FILE*> in;
     for (const char* fn : files) {
         FILE* f = strcmp(fn, "-") ? fopen(fn, "rb") : stdin;
@@ -303,7 +419,7 @@ int main(int argc, char* argv[]) {
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
 
     const std::string pre = prefix;
-    std::string bstat, lstat, gstat, istat;
+    std::string bstat, lstat, gstat, istat, astat, pstat;
     const uint32_t ni = (uint32_t)ibp.size();
     std::vector<uint64_t> inv;                                                // [ni][nbins] of the resolution at hand
     std::vector<double> isc, ilg, ist;
@@ -414,6 +530,30 @@ int main(int argc, char* argv[]) {
                 span(t, c, L.box[0], L.box[1]); t += '\t'; span(t, c, L.box[2], L.box[3]); t += '\n';
             }
             if (!write_file(pre + "." + std::to_string(res[k]) + ".loops.bedpe", t.data(), t.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+            if (apa) {                                                            // the peak cells in loop order
+                std::vector<uint32_t> pa, pb;
+                for (const mkt_loop& L : rows) { pa.push_back(L.bin1); pb.push_back(L.bin2); }
+                mkt_pileup_info pi;
+                if ((rc = mkt_matrix_pileup(m, k, pa.data(), pb.data(), pa.size(), &po, &pi)) != MKT_OK) return lib_fail("GPU matrix pileup");
+                rc = write_pileup(m, k, res[k], pi, pre + "." + std::to_string(res[k]) + ".apa.tsv", astat);
+                if (rc < 0) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+                if (rc != MKT_OK) return lib_fail("GPU matrix pileup");
+            }
+        }
+        if (pfile) {
+            std::vector<uint64_t> first;
+            uint64_t nb = 0;
+            for (const Chrom& c : chroms) { first.push_back(nb); nb += (c.len + res[k] - 1) / res[k]; }
+            std::vector<uint32_t> pa, pb;
+            for (const Anchor& a : anchors) {
+                const uint32_t x = (uint32_t)(first[a.c1] + a.m1 / res[k]), y = (uint32_t)(first[a.c2] + a.m2 / res[k]);
+                pa.push_back(x < y ? x : y); pb.push_back(x < y ? y : x);
+            }
+            mkt_pileup_info pi;
+            if ((rc = mkt_matrix_pileup(m, k, pa.data(), pb.data(), pa.size(), &po, &pi)) != MKT_OK) return lib_fail("GPU matrix pileup");
+            rc = write_pileup(m, k, res[k], pi, pre + "." + std::to_string(res[k]) + ".pileup.tsv", pstat);
+            if (rc < 0) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+            if (rc != MKT_OK) return lib_fail("GPU matrix pileup");
         }
         if (eigs) {
             mkt_eigs_info gi;
@@ -507,6 +647,8 @@ int main(int argc, char* argv[]) {
         if (eigs && !write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (ni && !write_file(pre + "." + std::to_string(res[k]) + ".insulation.tsv", ibed.data(), ibed.size(), imode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
+    if (apa && !write_file(pre + ".apa.stat", astat.data(), astat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+    if (pfile && !write_file(pre + ".pileup.stat", pstat.data(), pstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (ni && !write_file(pre + ".insulation.stat", istat.data(), istat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (eigs && !write_file(pre + ".eigs.stat", gstat.data(), gstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (balance && !write_file(pre + ".balance.stat", bstat.data(), bstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
