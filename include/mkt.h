@@ -586,7 +586,7 @@ int mkt_matrix_loops_timing(const mkt_matrix* m, uint32_t res_index, double* pas
  * An absent cell counts as -1: where the cis matrix is mostly empty the leading vector is the all-ones direction with
  * lambda ~ -n_good.  Compartments are meant for resolutions where cis is dense (100 kb .. 1 Mb).
  * Out of scope: percentile clipping (it needs a selection), per-arm views, trans eigenvectors, Pearson-correlation (juicer-style)
- * vectors, Lanczos, a saddle plot.
+ * vectors, Lanczos.  (The saddle tables that judge the vectors are mkt_matrix_saddle below.)
  *
  * Determinism: no floating-point atomics; a row's sum is formed by a fixed number of lanes with a fixed stride and a fixed shuffle
  * tree (rows of more than 1024 cells: one workgroup, the four wave sums added in wave order); the per-chromosome dot products use
@@ -763,6 +763,79 @@ int mkt_matrix_pileup(mkt_matrix* m, uint32_t res_index, const uint32_t* bin1, c
 int mkt_matrix_fetch_pileup(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* csum, double* vsum, double* mean);
 int mkt_matrix_fetch_pileup_status(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status);
 int mkt_matrix_pileup_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms);
+
+/* ---- saddle tables and compartment strength: what judges the compartment eigenvectors -------------------------------------------------
+ * Bins are ranked by a track (an eigenvector of mkt_matrix_eigs, or any caller's values) and cut into Q groups; the mean observed /
+ * expected of every pair of groups is tabulated and reduced to one number, the compartment strength (AA + BB over AB).  The definition
+ * is this project's own, modelled on cooltools `saddle`; parity with cooltools is UNPINNED (it is not run anywhere here).
+ * tests/saddledef.py restates the definition in numpy.  All floating point is float64.
+ *
+ * Inputs, for one resolution: the cells (bin1 <= bin2, count) in the order of mkt_matrix_fetch, the chromosome ranges
+ * [off_c, off_c + n_c) and the state of the last mkt_matrix_expected: its use_weights, w[k] and valid(k), the genome-wide expected[d] and
+ * expected_smooth[d] and the trans expected of a block; v = ((double)count * w[bin1]) * w[bin2].  A track t[nbins] of doubles: NaN means
+ * no value, +-inf are ordinary values.  Options (mkt_saddle_opts): n_groups Q (2 .. 64), trim_lo, trim_hi (basis points, >= 0,
+ * trim_lo + trim_hi < 10000), contact (0 cis, 1 trans), kind (MKT_VALUE_OE or MKT_VALUE_OE_SMOOTH; only the cis divisor differs),
+ * min_diag, max_diag (cis; 0 = no upper limit), corner (0 = max(1, Q / 5), else 1 .. Q / 2).
+ *  1. GROUPS, on the host, integers only.  The candidates are the bins with valid(k) and a non-NaN t[k], ordered by t ascending; ties go
+ *     to the lower bin, and -0.0 == 0.0 is a tie.  With T candidates, lo = T * trim_lo / 10000 and hi = T * trim_hi / 10000 (integer
+ *     division); the candidates of rank r in [lo, T - hi) are kept, K = T - hi - lo of them, and get g = (r - lo) * Q / K.  Every other
+ *     bin gets g = 255 (none).  K < Q leaves some groups empty; K == 0 is not an error (every table entry is zero, the means and scores
+ *     are NaN).  Per group: the number of its bins and the track values of its lowest and of its highest rank (NaN for an empty group).
+ *  2. A stored cell (i, j, count), i <= j, is USED when both bins have a group and, cis: both lie in one chromosome, min_diag <= j - i,
+ *     and j - i <= max_diag when that is set; trans: they lie in different chromosomes.  Its value x = v / expected[j - i] (or
+ *     expected_smooth[j - i]) for cis, v / expected(block) for trans: one IEEE division, never fused, no reciprocal approximation.  Its
+ *     entry is the unordered pair (min(g_i, g_j), max(g_i, g_j)).
+ *  3. SUMMATION ORDER, which is part of the definition: chunk c is the stored cells [4096 c, 4096 c + 4096) (cells that are not used
+ *     keep their slots); T_c[entry] starts from +0.0 and takes the values of the chunk's used cells of that entry in ascending cell
+ *     index; vsum[entry] starts from +0.0 and takes T_0, T_1, .. in ascending c.  nnz (the used cells) and csum (the sum of their
+ *     counts) are exact uint64.  No floating-point atomics.  The order depends on the cells alone: the same bits from call to call,
+ *     process to process and by every route (add, add_device, add_keys), and the same bits as tests/saddledef.py.
+ *  4. POSITIONS: n[entry] (uint64, exact) = the pairs of bins (i <= j) that would be used if stored (an absent cell is a zero of the map
+ *     and counts in the mean): cis, in one chromosome with the diagonal in range and both bins grouped; trans, in different chromosomes
+ *     and both grouped.
+ *  5. TABLES, each [Q][Q] and symmetric (S[a][b] = S[b][a] = the unordered entry): n, nnz, csum, vsum and mean = vsum / (double)n, the
+ *     quiet NaN when n == 0.
+ *  6. SCORES, on the host, never fused, for k = 1 .. Q / 2: the vsum (in doubles) and the n (in uint64) of each block are added over
+ *     the unordered entries a <= b in ascending (a, b), row-major: BB(k) the entries with b < k, AA(k) those with a >= Q - k, AB(k)
+ *     those with a < k and b >= Q - k.  strength[k] = ((BBs + AAs) / (double)(BBn + AAn)) / (ABs / (double)ABn),
+ *     aa_ab[k] = (AAs / AAn) / (ABs / ABn), bb_ab[k] likewise.  A division by zero gives the quiet NaN, and every NaN is the one quiet
+ *     NaN.  The info carries the three at k = corner.
+ * Out of scope: per-chromosome or per-arm views, group edges given as values or quantiles of the genome-wide distribution (`vrange`,
+ * `qrange` of cooltools), the saddle plot itself, saddles of several tracks at once.
+ *
+ *   mkt_saddle_opts_default           n_groups 50, trim 250 / 250, contact 0, kind OE, min_diag 2, max_diag 0, corner 0
+ *   mkt_matrix_saddle                 valid after mkt_matrix_expected of that resolution (MKT_E_STATE "expected first" without tables,
+ *                                     "saddle before run" before mkt_matrix_run); opts NULL = the defaults.  MKT_E_ARG with a message for
+ *                                     a bad index, n_groups outside 2 .. 64, a negative trim or trim_lo + trim_hi >= 10000, a bad contact,
+ *                                     kind or corner, a negative diagonal, max_diag set and below min_diag, a non-zero reserved or a NULL
+ *                                     track.  info may be NULL.  A refused call leaves the previous results alone.  A later
+ *                                     mkt_matrix_run, add, balance or expected of that resolution discards the results; loops,
+ *                                     eigenvectors, insulation, pileup and saddle of one resolution do not disturb each other.  The partial
+ *                                     tables of all chunks are resident at once (chunks * Q (Q + 1) / 2 * 8 bytes): MKT_E_NOMEM otherwise.
+ *   mkt_matrix_fetch_saddle           n, nnz, csum, vsum, mean as [Q][Q]; any may be NULL
+ *   mkt_matrix_fetch_saddle_groups    the group byte of bins [first, first + n); MKT_E_ARG with a message for a bad range
+ *   mkt_matrix_fetch_saddle_edges     per group [Q]: its bins, the track value of its lowest and highest rank; any may be NULL
+ *   mkt_matrix_fetch_saddle_profile   strength, aa_ab, bb_ab as [Q / 2], index k - 1; any may be NULL
+ *   mkt_matrix_saddle_timing          of the last mkt_matrix_saddle of res_index (ms): the setup (on the host: the groups, the positions,
+ *                                     the copy of the weights and the upload of the groups; wall time) and the sweep (the chunk kernel
+ *                                     and the fold; HIP events).  A bad index is MKT_E_ARG without a message; 0, 0 without results. */
+#define MKT_SADDLE_NONE 255
+typedef struct mkt_saddle_opts {
+    int32_t n_groups, trim_lo, trim_hi, contact, kind, min_diag, max_diag, corner;
+    uint32_t reserved;       /* 0 */
+} mkt_saddle_opts;
+typedef struct mkt_saddle_info {
+    uint64_t candidates, kept, cells_used;
+    uint32_t n_groups, chunks, corner, reserved;
+    double strength, aa_ab, bb_ab;
+} mkt_saddle_info;
+void mkt_saddle_opts_default(mkt_saddle_opts* o);
+int mkt_matrix_saddle(mkt_matrix* m, uint32_t res_index, const mkt_saddle_opts* opts, const double* track, mkt_saddle_info* info);
+int mkt_matrix_fetch_saddle(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* nnz, uint64_t* csum, double* vsum, double* mean);
+int mkt_matrix_fetch_saddle_groups(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* group);
+int mkt_matrix_fetch_saddle_edges(mkt_matrix* m, uint32_t res_index, uint64_t* bins, double* lo, double* hi);
+int mkt_matrix_fetch_saddle_profile(mkt_matrix* m, uint32_t res_index, double* strength, double* aa_ab, double* bb_ab);
+int mkt_matrix_saddle_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,8 @@ EXPORTS = [
     "mkt_eigs_opts_default", "mkt_matrix_eigs", "mkt_matrix_fetch_eigvecs", "mkt_matrix_fetch_eigvals", "mkt_matrix_eigs_apply", "mkt_matrix_eigs_timing",
     "mkt_insulation_opts_default", "mkt_matrix_insulation", "mkt_matrix_fetch_insulation", "mkt_matrix_insulation_timing",
     "mkt_pileup_opts_default", "mkt_matrix_pileup", "mkt_matrix_fetch_pileup", "mkt_matrix_fetch_pileup_status", "mkt_matrix_pileup_timing",
+    "mkt_saddle_opts_default", "mkt_matrix_saddle", "mkt_matrix_fetch_saddle", "mkt_matrix_fetch_saddle_groups", "mkt_matrix_fetch_saddle_edges",
+    "mkt_matrix_fetch_saddle_profile", "mkt_matrix_saddle_timing",
 ]
 
 
@@ -154,6 +156,23 @@ PileupInfo = collections.namedtuple("PileupInfo", "features used trans edge dist
 Pileup = collections.namedtuple("Pileup", "n csum vsum mean status")
 PILEUP_OPTS = ("flank", "corner", "kind", "ignore_diags", "edges", "min_dist", "max_dist")
 PILE_USED, PILE_TRANS, PILE_EDGE, PILE_DIST = 1, 2, 3, 4
+
+
+class SaddleOpts(C.Structure):
+    """mkt_saddle_opts of include/mkt.h"""
+    _fields_ = [(k, C.c_int32) for k in ("n_groups", "trim_lo", "trim_hi", "contact", "kind", "min_diag", "max_diag", "corner")] + [("reserved", C.c_uint32)]
+
+
+class _SaddleInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("candidates", "kept", "cells_used")] + [(k, C.c_uint32) for k in ("n_groups", "chunks", "corner", "reserved")] + \
+               [(k, C.c_double) for k in ("strength", "aa_ab", "bb_ab")]
+
+
+SaddleInfo = collections.namedtuple("SaddleInfo", "n_groups candidates kept cells_used chunks corner strength aa_ab bb_ab")
+Saddle = collections.namedtuple("Saddle", "n nnz csum vsum mean groups group_bins group_lo group_hi strength aa_ab bb_ab")
+SADDLE_OPTS = ("n_groups", "trim_lo", "trim_hi", "contact", "kind", "min_diag", "max_diag", "corner")
+SADDLE_CONTACTS = {"cis": 0, "trans": 1}
+SADDLE_NONE = 255
 
 
 class Timing(C.Structure):
@@ -346,6 +365,14 @@ def load_library():
     L.mkt_matrix_fetch_pileup.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
     L.mkt_matrix_fetch_pileup_status.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mkt_matrix_pileup_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_saddle_opts_default.argtypes = [C.POINTER(SaddleOpts)]
+    L.mkt_saddle_opts_default.restype = None
+    L.mkt_matrix_saddle.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SaddleOpts), C.c_void_p, C.POINTER(_SaddleInfoC)]
+    L.mkt_matrix_fetch_saddle.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+    L.mkt_matrix_fetch_saddle_groups.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_fetch_saddle_edges.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+    L.mkt_matrix_fetch_saddle_profile.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+    L.mkt_matrix_saddle_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -998,6 +1025,66 @@ class Matrix:
         import numpy as np
         i = np.flatnonzero(self.insulation_track(res, k).boundary).astype(np.uint32)
         return self.pileup(res, i, i, **opts)
+
+    def saddle(self, res, track, **opts):
+        """Saddle tables of resolution index res after expected(res) for the track (nbins values, NaN = none): the definition is
+        mkt_matrix_saddle in include/mkt.h.  opts: n_groups, trim_lo, trim_hi (basis points), contact ("cis", "trans" or its number), kind
+        ("oe", "oe_smooth" or its number), min_diag, max_diag, corner.  Returns SaddleInfo (the counts, the corner and the three scores)."""
+        import numpy as np
+        o = SaddleOpts()
+        self.L.mkt_saddle_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in SADDLE_OPTS:
+                raise TypeError(f"saddle: unknown option {k}")
+            if k == "kind" and isinstance(v, str):
+                if v not in VALUE_KINDS:
+                    raise ValueError(f"saddle: kind {v!r} (one of {', '.join(VALUE_KINDS)})")
+                v = VALUE_KINDS[v]
+            if k == "contact" and isinstance(v, str):
+                if v not in SADDLE_CONTACTS:
+                    raise ValueError(f"saddle: contact {v!r} (cis or trans)")
+                v = SADDLE_CONTACTS[v]
+            setattr(o, k, int(v))
+        t = np.ascontiguousarray(track, dtype=np.float64)
+        nb = self.info(res)[0]
+        if t.shape != (nb,):
+            raise ValueError(f"saddle: the track has shape {t.shape}, ({nb},) is needed")
+        info = _SaddleInfoC()
+        self._chk(self.L.mkt_matrix_saddle(self.h, res, C.byref(o), t.ctypes.data_as(C.c_void_p), C.byref(info)), "mkt_matrix_saddle")
+        self._saddle_q = getattr(self, "_saddle_q", {})
+        self._saddle_q[res] = info.n_groups
+        return SaddleInfo(*[getattr(info, k) for k in SaddleInfo._fields])
+
+    def saddle_result(self, res):
+        """the arrays of the last saddle(res): Saddle(n, nnz, csum uint64 [Q, Q]; vsum, mean float64 [Q, Q]; groups uint8 [nbins], 255 = none;
+        group_bins uint64, group_lo, group_hi float64 [Q]; strength, aa_ab, bb_ab float64 [Q // 2], index k - 1)"""
+        import numpy as np
+        cap = 64 * 64
+        tabs = [np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.uint64), np.zeros(cap, np.float64), np.zeros(cap, np.float64)]
+        self._chk(self.L.mkt_matrix_fetch_saddle(self.h, res, *[a.ctypes.data_as(C.c_void_p) for a in tabs]), "mkt_matrix_fetch_saddle")
+        q = getattr(self, "_saddle_q", {}).get(res, 0)
+        if not q:
+            raise MktError("saddle_result: the saddle tables of this resolution were not made through saddle()")
+        g = np.zeros(self.info(res)[0], np.uint8)
+        self._chk(self.L.mkt_matrix_fetch_saddle_groups(self.h, res, 0, g.size, g.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_saddle_groups")
+        edges = [np.zeros(q, np.uint64), np.zeros(q, np.float64), np.zeros(q, np.float64)]
+        self._chk(self.L.mkt_matrix_fetch_saddle_edges(self.h, res, *[a.ctypes.data_as(C.c_void_p) for a in edges]), "mkt_matrix_fetch_saddle_edges")
+        prof = [np.zeros(q // 2, np.float64) for _ in range(3)]
+        self._chk(self.L.mkt_matrix_fetch_saddle_profile(self.h, res, *[a.ctypes.data_as(C.c_void_p) for a in prof]), "mkt_matrix_fetch_saddle_profile")
+        return Saddle(*[a[:q * q].reshape(q, q).copy() for a in tabs], g, *edges, *prof)
+
+    def saddle_timing_ms(self, res):
+        """(setup ms on the host, sweep + fold ms on the device) of the last saddle(res)"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_saddle_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_saddle_timing")
+        return a.value, b.value
+
+    def saddle_eigs(self, res, k=0, **opts):
+        """saddle(res) with eigenvector k of the last eigs(res) as the track"""
+        import numpy as np
+        v = np.zeros(self.info(res)[0], dtype=np.float64)
+        self._chk(self.L.mkt_matrix_fetch_eigvecs(self.h, res, k, 0, v.size, v.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_eigvecs")
+        return self.saddle(res, v, **opts)
 
     def close(self):
         if self.h:

@@ -30,6 +30,7 @@
 #include "mkt_eigs.h"
 #include "mkt_insulation.h"
 #include "mkt_pileup.h"
+#include "mkt_saddle.h"
 #include "mkt_launch.h"
 #include "mkt_layout.h"
 #include "mkt_segred.h"
@@ -298,6 +299,8 @@ struct MxRes {
     InsState ins;
     // pileup (mkt_matrix_pileup): the results live until the next expected, balance or run
     PileState pile;
+    // saddle tables (mkt_matrix_saddle): the results live until the next expected, balance or run
+    SaddleState sad;
 };
 thread_local std::string g_mx_create_err;
 }  // namespace
@@ -375,6 +378,7 @@ static void mx_free_results(mkt_matrix* m) {
         r.lps = LoopsState(); r.egs = EigsState();
         r.ins = InsState();
         r.pile = PileState();
+        r.sad = SaddleState();
     }
     m->ran = false;
 }
@@ -422,7 +426,7 @@ static int mx_process_text(mkt_matrix* m, size_t n) {
 }
 
 // what an entry point needs of a resolution before it may go on; each has its message
-enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16, MX_INS = 32, MX_PILE = 64 };
+enum { MX_RAN = 1, MX_WEIGHTS = 2, MX_TABLES = 4, MX_LOOPS = 8, MX_EIGS = 16, MX_INS = 32, MX_PILE = 64, MX_SADDLE = 128 };
 static int mx_need(mkt_matrix* m, uint32_t res_index, const MxRes& r, int need, const char* what = nullptr) {
     if ((need & MX_RAN) && !m->ran) return mfail(m, MKT_E_STATE, "%s before run", what);
     if ((need & MX_WEIGHTS) && !(m->ran && r.balanced)) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_index);
@@ -431,6 +435,7 @@ static int mx_need(mkt_matrix* m, uint32_t res_index, const MxRes& r, int need, 
     if ((need & MX_EIGS) && !(m->ran && r.egs.built)) return mfail(m, MKT_E_STATE, "no eigenvectors for resolution index %u: eigs first", res_index);
     if ((need & MX_INS) && !(m->ran && r.ins.built)) return mfail(m, MKT_E_STATE, "no insulation scores for resolution index %u: insulation first", res_index);
     if ((need & MX_PILE) && !(m->ran && r.pile.built)) return mfail(m, MKT_E_STATE, "no pileup for resolution index %u: pileup first", res_index);
+    if ((need & MX_SADDLE) && !(m->ran && r.sad.built)) return mfail(m, MKT_E_STATE, "no saddle tables for resolution index %u: saddle first", res_index);
     return MKT_OK;
 }
 // the resolution of an entry point, or the error: the object, the index, then what it needs
@@ -764,6 +769,7 @@ int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts
     r.lps = LoopsState(); r.egs = EigsState();
     r.ins = InsState();                                                 // scores of other weights
     r.pile = PileState();
+    r.sad = SaddleState();
     DevBuf<double> d_bias, d_m, d_part, d_w;                            // d_w becomes r.d_w at the end: a failure leaves no weights
     DevBuf<BalState> d_state;
 #define BRUN(call) MX(m, "balance: ", call)
@@ -886,6 +892,7 @@ int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_op
     r.ext = ExpTables();
     r.lps = LoopsState(); r.egs = EigsState();                          // loops and eigenvectors of other tables
     r.pile = PileState();                                               // ... and a pileup of other divisors
+    r.sad = SaddleState();                                              // ... and saddle tables of them
     r.exp_sums_ms = r.exp_setup_ms = 0;
 #define ERUN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { r.ext = ExpTables(); return mx_hip(m, "expected: ", e_, true); } } while (0)
     if (!r.exs.built) {                                                 // with the chromosome of a bin when nothing has built it yet
@@ -1323,6 +1330,99 @@ int mkt_matrix_fetch_pileup_status(mkt_matrix* m, uint32_t res_index, uint64_t f
 int mkt_matrix_pileup_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
     if (!m || res_index >= m->res.size()) return MKT_E_ARG;
     const PileState& s = m->res[res_index].pile;
+    const bool have = m->ran && s.built;
+    if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
+    if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;
+    return MKT_OK;
+}
+
+}  // extern "C"
+
+// ---- saddle tables: the entry points; the sweep, the groups, the positions and the scores are mkt_saddle.hip, the definition is in
+// include/mkt.h
+extern "C" {
+
+void mkt_saddle_opts_default(mkt_saddle_opts* o) {
+    if (!o) return;
+    o->n_groups = 50; o->trim_lo = 250; o->trim_hi = 250; o->contact = 0; o->kind = MKT_VALUE_OE; o->min_diag = 2; o->max_diag = 0; o->corner = 0; o->reserved = 0;
+}
+
+int mkt_matrix_saddle(mkt_matrix* m, uint32_t res_index, const mkt_saddle_opts* opts, const double* track, mkt_saddle_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    mkt_saddle_opts o;
+    mkt_saddle_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.n_groups < 2 || o.n_groups > kSaddleGroupsMax) return mfail(m, MKT_E_ARG, "saddle: n_groups %d is outside 2 .. %d", o.n_groups, kSaddleGroupsMax);
+    if (o.trim_lo < 0 || o.trim_hi < 0) return mfail(m, MKT_E_ARG, "saddle: trim_lo %d / trim_hi %d is negative", o.trim_lo, o.trim_hi);
+    if ((int64_t)o.trim_lo + o.trim_hi >= 10000) return mfail(m, MKT_E_ARG, "saddle: trim_lo %d + trim_hi %d leaves nothing (basis points: below 10000 together)", o.trim_lo, o.trim_hi);
+    if (o.contact != 0 && o.contact != 1) return mfail(m, MKT_E_ARG, "saddle: contact %d (0 cis, 1 trans)", o.contact);
+    if (o.kind != MKT_VALUE_OE && o.kind != MKT_VALUE_OE_SMOOTH) return mfail(m, MKT_E_ARG, "saddle: kind %d (1 oe, 2 oe_smooth)", o.kind);
+    if (o.min_diag < 0 || o.max_diag < 0) return mfail(m, MKT_E_ARG, "saddle: min_diag %d / max_diag %d is negative", o.min_diag, o.max_diag);
+    if (o.max_diag && o.max_diag < o.min_diag) return mfail(m, MKT_E_ARG, "saddle: max_diag %d is below min_diag %d", o.max_diag, o.min_diag);
+    if (o.corner < 0 || o.corner > o.n_groups / 2) return mfail(m, MKT_E_ARG, "saddle: corner %d is outside 1 .. n_groups / 2 = %d (0: the default)", o.corner, o.n_groups / 2);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "saddle: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "saddle")) return rc;
+    if (!track) return mfail(m, MKT_E_ARG, "saddle: no track (track is NULL)");
+    if (r.nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "saddle: %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)r.nnz);
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    MX(m, "saddle: ", layout_chr(r.lay, mx_cells(r), st));              // the chromosome of a bin is all the sweep needs of the layout
+    SaddleIn in;
+    in.b1 = r.d_b1; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.chr = r.lay.chr;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr;
+    in.cis_div = o.kind == MKT_VALUE_OE ? r.ext.d_cis_e.get() : r.ext.d_cis_sm.get(); in.tr_div = r.ext.d_tr_e;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    SaddleState ss;                                                     // a refused or failed call leaves the previous results alone
+    MX(m, "saddle: ", saddle_run(ss, in, r.off, track, o, st));
+    r.sad = std::move(ss);
+    if (info) *info = r.sad.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* nnz, uint64_t* csum, double* vsum, double* mean) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->n.size();
+    mx_copy_rows(n, s->n, 0, rows); mx_copy_rows(nnz, s->nnz, 0, rows); mx_copy_rows(csum, s->csum, 0, rows); mx_copy_rows(vsum, s->vsum, 0, rows);
+    mx_copy_rows(mean, s->mean, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle_groups(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* group) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->group.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "saddle groups of bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    mx_copy_rows(group, s->group, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle_edges(mkt_matrix* m, uint32_t res_index, uint64_t* bins, double* lo, double* hi) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->g_bins.size();
+    mx_copy_rows(bins, s->g_bins, 0, rows); mx_copy_rows(lo, s->g_lo, 0, rows); mx_copy_rows(hi, s->g_hi, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle_profile(mkt_matrix* m, uint32_t res_index, double* strength, double* aa_ab, double* bb_ab) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->strength.size();
+    mx_copy_rows(strength, s->strength, 0, rows); mx_copy_rows(aa_ab, s->aa_ab, 0, rows); mx_copy_rows(bb_ab, s->bb_ab, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_saddle_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const SaddleState& s = m->res[res_index].sad;
     const bool have = m->ran && s.built;
     if (setup_ms) *setup_ms = have ? s.setup_ms : 0.0;
     if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;

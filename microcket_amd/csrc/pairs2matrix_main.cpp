@@ -11,6 +11,8 @@
 //                        [--eigs-track FILE]]
 //                [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]
 //                [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]
+//                [--saddle [--saddle-groups N] [--saddle-trim LO,HI] [--saddle-contact cis|trans] [--saddle-kind oe|oe-smooth]
+//                          [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -57,6 +59,15 @@
 // (default oe-smooth) and --pile-edges (clip the windows of features near a chromosome's end instead of leaving those features out) hold
 // for both; one of them without --apa or --pileup is a usage error, a bad value exit 12.  Without the two flags none of these files
 // appears and every other byte is the same.
+// With --saddle (mkt_matrix_saddle of include/mkt.h with eigenvector 1 as the track, oriented by --eigs-track when that is given; it
+// implies --eigs) also per resolution <prefix>.<r>.saddle.tsv: a header line, then one row per pair of groups a <= b: a, b, n, nnz, csum,
+// vsum, mean, doubles as %.17g and nan for NaN; and <prefix>.saddle.stat, per resolution one "info" row (r, info, n_groups, candidates,
+// kept, cells_used, chunks, corner, strength, aa_ab, bb_ab), one "group" row per group (r, group, g, bins, lo, hi) and one "profile" row
+// per k = 1 .. n_groups / 2 (r, profile, k, strength, aa_ab, bb_ab).  --saddle-groups (2 .. 64, default 50), --saddle-trim LO,HI (basis
+// points, default 250,250), --saddle-contact (default cis), --saddle-kind (default oe), --saddle-min-dist / --saddle-max-dist (base pairs,
+// each a multiple of every -r; defaults: diagonals 2 and up, no upper limit), --saddle-corner (1 .. groups / 2; default max(1, groups / 5)).
+// One of them without --saddle is a usage error, a bad value exit 12.  Without --saddle neither file appears and every other byte is the
+// same.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -74,7 +85,9 @@ static int usage(const char* me) {
                     "       [--eigs [--eigs-n N] [--eigs-ignore-diags N] [--eigs-clip X] [--eigs-min-good N] [--eigs-tol X] [--eigs-max-iters N]\n"
                     "               [--eigs-track FILE]]\n"
                     "       [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]\n"
-                    "       [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]\n", me);
+                    "       [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]\n"
+                    "       [--saddle [--saddle-groups N] [--saddle-trim LO,HI] [--saddle-contact cis|trans] [--saddle-kind oe|oe-smooth]\n"
+                    "                 [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -235,6 +248,37 @@ static int write_pileup(mkt_matrix* m, uint32_t k, uint32_t r, const mkt_pileup_
     return MKT_OK;
 }
 
+// the tables, the group edges and the profile of the last mkt_matrix_saddle of resolution index k as <fn> and more rows of `stat`
+static int write_saddle(mkt_matrix* m, uint32_t k, uint32_t r, const mkt_saddle_info& si, const std::string& fn, std::string& stat) {
+    const size_t Q = si.n_groups, Q2 = Q * Q;
+    std::vector<uint64_t> n(Q2), nz(Q2), cs(Q2), gb(Q);
+    std::vector<double> vs(Q2), mean(Q2), lo(Q), hi(Q), st(Q / 2), aa(Q / 2), bb(Q / 2);
+    int rc = mkt_matrix_fetch_saddle(m, k, n.data(), nz.data(), cs.data(), vs.data(), mean.data());
+    if (rc == MKT_OK) rc = mkt_matrix_fetch_saddle_edges(m, k, gb.data(), lo.data(), hi.data());
+    if (rc == MKT_OK) rc = mkt_matrix_fetch_saddle_profile(m, k, st.data(), aa.data(), bb.data());
+    if (rc != MKT_OK) return rc;
+    std::string t = "a\tb\tn\tnnz\tcsum\tvsum\tmean\n";
+    for (size_t a = 0; a < Q; ++a)
+        for (size_t b = a; b < Q; ++b) {
+            const size_t x = a * Q + b;
+            t += std::to_string(a); t += '\t'; t += std::to_string(b); t += '\t'; t += std::to_string(n[x]); t += '\t'; t += std::to_string(nz[x]); t += '\t';
+            t += std::to_string(cs[x]); t += '\t'; put_num(t, vs[x]); t += '\t'; put_num(t, mean[x]); t += '\n';
+        }
+    if (!write_file(fn, t.data(), t.size())) return -1;
+    const std::string rs = std::to_string(r);
+    stat += rs; stat += "\tinfo";
+    for (uint64_t v : {(uint64_t)si.n_groups, si.candidates, si.kept, si.cells_used, (uint64_t)si.chunks, (uint64_t)si.corner}) { stat += '\t'; stat += std::to_string(v); }
+    for (double v : {si.strength, si.aa_ab, si.bb_ab}) { stat += '\t'; put_num(stat, v); }
+    stat += '\n';
+    for (size_t g = 0; g < Q; ++g) {
+        stat += rs; stat += "\tgroup\t"; stat += std::to_string(g); stat += '\t'; stat += std::to_string(gb[g]); stat += '\t'; put_num(stat, lo[g]); stat += '\t'; put_num(stat, hi[g]); stat += '\n';
+    }
+    for (size_t j = 0; j < Q / 2; ++j) {
+        stat += rs; stat += "\tprofile\t"; stat += std::to_string(j + 1); stat += '\t'; put_num(stat, st[j]); stat += '\t'; put_num(stat, aa[j]); stat += '\t'; put_num(stat, bb[j]); stat += '\n';
+    }
+    return MKT_OK;
+}
+
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
@@ -250,6 +294,9 @@ int main(int argc, char* argv[]) {
     const char* pfile = nullptr;
     const char* popt[4] = {nullptr, nullptr, nullptr, nullptr};              // --pile-edges takes no value: its slot holds the flag itself
     static const char* const pname[4] = {"--pile-flank", "--pile-corner", "--pile-kind", "--pile-edges"};
+    bool saddle = false;
+    const char* sopt[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    static const char* const sname[7] = {"--saddle-groups", "--saddle-trim", "--saddle-contact", "--saddle-kind", "--saddle-min-dist", "--saddle-max-dist", "--saddle-corner"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -263,7 +310,11 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 3; ++k) if (!strcmp(argv[i], iname[k])) s = k;
         int pl = -1;
         for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], pname[k])) pl = k;
-        if (pl == 3) popt[3] = argv[i];
+        int sd = -1;
+        for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], sname[k])) sd = k;
+        if (sd >= 0) { if (i + 1 >= argc) return usage(argv[0]); sopt[sd] = argv[++i]; }
+        else if (!strcmp(argv[i], "--saddle")) saddle = eigs = expected = true;
+        else if (pl == 3) popt[3] = argv[i];
         else if (pl >= 0) { if (i + 1 >= argc) return usage(argv[0]); popt[pl] = argv[++i]; }
         else if (!strcmp(argv[i], "--apa")) apa = loops = expected = true;
         else if (!strcmp(argv[i], "--pileup")) { if (i + 1 >= argc) return usage(argv[0]); pfile = argv[++i]; expected = true; }
@@ -340,6 +391,31 @@ int main(int argc, char* argv[]) {
     }
     if (!popt[1] && po.corner > po.flank) po.corner = po.flank;               // the default corner inside a small window
     if ((apa || pfile) && po.corner > po.flank) { fprintf(stderr, "Error: --pile-corner %d is larger than --pile-flank %d\n", po.corner, po.flank); return 12; }
+    mkt_saddle_opts so;
+    mkt_saddle_opts_default(&so);
+    int32_t sbp[2] = {-1, -1};                                                // --saddle-min-dist, --saddle-max-dist in base pairs
+    for (int k = 0; k < 7; ++k) {
+        if (!sopt[k]) continue;
+        if (!saddle) { fprintf(stderr, "Error: %s needs --saddle\n", sname[k]); return usage(argv[0]); }
+        bool ok = true;
+        if (k == 0) ok = parse_int(sopt[k], so.n_groups) && so.n_groups >= 2 && so.n_groups <= 64;
+        else if (k == 1) {
+            const char* comma = strchr(sopt[k], ',');
+            ok = comma && parse_int(std::string(sopt[k], comma).c_str(), so.trim_lo) && parse_int(comma + 1, so.trim_hi) && (int64_t)so.trim_lo + so.trim_hi < 10000;
+        } else if (k == 2) {
+            if (!strcmp(sopt[k], "cis")) so.contact = 0; else if (!strcmp(sopt[k], "trans")) so.contact = 1; else ok = false;
+        } else if (k == 3) {
+            if (!strcmp(sopt[k], "oe")) so.kind = MKT_VALUE_OE; else if (!strcmp(sopt[k], "oe-smooth")) so.kind = MKT_VALUE_OE_SMOOTH; else ok = false;
+        } else if (k < 6) ok = parse_int(sopt[k], sbp[k - 4]);
+        else ok = parse_int(sopt[k], so.corner) && so.corner >= 1;
+        if (!ok) {
+            fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", sopt[k], sname[k], k == 0 ? "a whole number, 2 .. 64" : k == 1 ? "two whole numbers LO,HI, 0 or more, below 10000 together"
+                    : k == 2 ? "cis or trans" : k == 3 ? "oe or oe-smooth" : k < 6 ? "a whole number of base pairs, 0 or more" : "a whole number, at least 1");
+            return 12;
+        }
+    }
+    if (saddle && so.corner > so.n_groups / 2) { fprintf(stderr, "Error: --saddle-corner %d is larger than half of --saddle-groups %d\n", so.corner, so.n_groups); return 12; }
+    if (saddle && sbp[1] > 0 && sbp[1] < sbp[0]) { fprintf(stderr, "Error: --saddle-max-dist %d is below --saddle-min-dist %d\n", sbp[1], sbp[0]); return 12; }
     std::vector<uint32_t> ibp;                                                // the windows in base pairs
     if (ilist && (!parse_res(ilist, ibp) || ibp.size() > 4)) { fprintf(stderr, "Error: bad window list '%s' for --insulation (1 .. 4 different positive numbers, comma separated)\n", ilist); return 12; }
     for (size_t k = 1; k < ibp.size(); ++k)
@@ -353,6 +429,9 @@ int main(int argc, char* argv[]) {
     for (uint32_t r : res)
         for (uint32_t bp : ibp)
             if (bp % r != 0 || bp / r > 1024) { fprintf(stderr, "Error: --insulation window %u is not a multiple of resolution %u of at most 1024 bins\n", bp, r); return 12; }
+    for (uint32_t r : res)
+        for (int k = 0; k < 2; ++k)
+            if (sbp[k] > 0 && (uint32_t)sbp[k] % r != 0) { fprintf(stderr, "Error: %s %d is not a multiple of resolution %u\n", sname[4 + k], sbp[k], r); return 12; }
     if (gopt[6] && res.size() != 1) { fprintf(stderr, "Error: --eigs-track needs a single resolution\n"); return usage(argv[0]); }
     std::vector<double> track;
     if (gopt[6]) {                                                            // the bins of .bins.bed in order, with a value each
@@ -419,7 +498,7 @@ int main(int argc, char* argv[]) {
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
 
     const std::string pre = prefix;
-    std::string bstat, lstat, gstat, istat, astat, pstat;
+    std::string bstat, lstat, gstat, istat, astat, pstat, sstat;
     const uint32_t ni = (uint32_t)ibp.size();
     std::vector<uint64_t> inv;                                                // [ni][nbins] of the resolution at hand
     std::vector<double> isc, ilg, ist;
@@ -573,6 +652,15 @@ int main(int argc, char* argv[]) {
                 gstat += '\n';
                 if (it[c] && !cv[c]) fprintf(stderr, "WARN: eigenvectors of %s at resolution %u did not converge in %u iterations.\n", chroms[c].name.c_str(), res[k], it[c]);
             }
+            if (saddle) {                                                         // the first vector as the track
+                if (sbp[0] >= 0) so.min_diag = sbp[0] / (int32_t)res[k];
+                if (sbp[1] >= 0) so.max_diag = sbp[1] / (int32_t)res[k];
+                mkt_saddle_info si;
+                if ((rc = mkt_matrix_saddle(m, k, &so, evec.data(), &si)) != MKT_OK) return lib_fail("GPU matrix saddle");
+                rc = write_saddle(m, k, res[k], si, pre + "." + std::to_string(res[k]) + ".saddle.tsv", sstat);
+                if (rc < 0) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+                if (rc != MKT_OK) return lib_fail("GPU matrix saddle");
+            }
         }
         if (ni) {
             io.n_windows = (int32_t)ni;
@@ -647,6 +735,7 @@ int main(int argc, char* argv[]) {
         if (eigs && !write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (ni && !write_file(pre + "." + std::to_string(res[k]) + ".insulation.tsv", ibed.data(), ibed.size(), imode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
+    if (saddle && !write_file(pre + ".saddle.stat", sstat.data(), sstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (apa && !write_file(pre + ".apa.stat", astat.data(), astat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (pfile && !write_file(pre + ".pileup.stat", pstat.data(), pstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (ni && !write_file(pre + ".insulation.stat", istat.data(), istat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
