@@ -837,6 +837,85 @@ int mkt_matrix_fetch_saddle_edges(mkt_matrix* m, uint32_t res_index, uint64_t* b
 int mkt_matrix_fetch_saddle_profile(mkt_matrix* m, uint32_t res_index, double* strength, double* aa_ab, double* bb_ab);
 int mkt_matrix_saddle_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms);
 
+/* ---- replicate comparison: the stratum-adjusted correlation coefficient (SCC) of two matrices ---------------------------------------------
+ * Do two contact maps agree?  Both are smoothed with a box filter and correlated diagonal by diagonal (stratum by stratum); the
+ * correlations are combined with weights into one number per chromosome and one for the genome.  The definition is this project's own,
+ * modelled on HiCRep (Yang et al. 2017); parity with HiCRep and hicreppy is UNPINNED (neither is run anywhere here).  Out of scope:
+ * HiCRep's rank-based variance weights (they need a sort per stratum; MKT_SCC_WEIGHT_VAR below uses the plain variances) and the
+ * down-sampling of both maps to equal depth, which is a separate step (count_a and count_b of the info show a depth imbalance).
+ * tests/sccdef.py restates the definition in numpy.  All floating point is float64; nothing is fused.
+ *
+ * Inputs: two matrix objects A and B on one device with equal chromosome tables (names and lengths, in order), a resolution index in
+ * each naming the same resolution r, both run.  A and B may be the same object.  Options (mkt_scc_opts): h (0 .. 16: the half width of
+ * the filter), min_diag, max_diag (0 <= min_diag <= max_diag; max_diag 0 = every diagonal of the longest chromosome), use_weights (0,
+ * 1), weighting (MKT_SCC_WEIGHT_N, MKT_SCC_WEIGHT_VAR), min_n (>= 2), slab_rows (0 = the library chooses, else a positive multiple of
+ * 256: how many rows of a chromosome are resident as a dense band at a time; the results do not depend on it), reserved (0).
+ *  1. JOINT VALIDITY.  use_weights 0: every bin is jointly valid and the value of a cell is (double)count.  use_weights 1 (both
+ *     resolutions balanced, MKT_E_STATE otherwise): bin k is jointly valid when its weight is NaN neither in A nor in B; the value in A
+ *     is ((double)count * wA[bin1]) * wA[bin2], in B the same with wB.
+ *  2. FULL MATRICES, per chromosome c of n_c bins, indices relative to the chromosome: F_A[i][j] = F_A[j][i] = the value of A's stored
+ *     cell (min, max), 0.0 when the cell is absent or one of the bins is not jointly valid; F_B likewise.  Cells of other chromosomes
+ *     and trans cells never enter.
+ *  3. SMOOTHING.  nv(a, b) = the jointly valid bins with relative index in [max(a, 0), min(b, n_c - 1)].
+ *     R[i'][j] = F[i'][j - h] + F[i'][j - h + 1] + .. + F[i'][j + h], added left to right, terms outside [0, n_c) being 0.0;
+ *     W[i][j] = R[i - h][j] + .. + R[i + h][j] in ascending i', rows outside the chromosome being 0.0;
+ *     x(i, j) = W_A[i][j] / (double)(nv(i - h, i + h) * nv(j - h, j + h)), y(i, j) the same from B.
+ *  4. STRATA.  For d in [min_diag, max_diag] and i in [0, n_c - d) the position (i, i + d) is a CANDIDATE when both bins are jointly
+ *     valid, and USED when it is a candidate and x != 0 || y != 0 (as in HiCRep, a position that is zero in both maps is left out).
+ *  5. SUMS per stratum (c, d): n_cand and n (the candidates and the used positions, exact uint64) and Sx, Sy, Sxx, Syy, Sxy, the sums of
+ *     x, y, x * x, y * y, x * y over the used positions, every product rounded on its own.  SUMMATION ORDER, which is part of the
+ *     definition: chunk q holds the positions with i in [256 q, 256 q + 256), an unused slot or a slot past the end holding 0.0;
+ *     inside a chunk, for half = 128, 64, .., 1: s[k] = s[k] + s[k + half] for k < half; then the chunks are added in ascending q.
+ *     No floating-point atomics: the same bits from call to call, by every route and for every slab_rows, and the same bits as
+ *     tests/sccdef.py.
+ *  6. SCORES per stratum, on the host, in this order of operations: mx = Sx / n, my = Sy / n, vx = Sxx / n - mx * mx,
+ *     vy = Syy / n - my * my, cv = Sxy / n - mx * my.  The stratum is SCORED when n >= min_n, vx > 0x1p-40 * (Sxx / n) and
+ *     vy > 0x1p-40 * (Syy / n).  Then rho = cv / sqrt(vx * vy) and the weight w = (double)n (WEIGHT_N) or n * sqrt(vx * vy)
+ *     (WEIGHT_VAR).  A stratum that is not scored has rho = NaN and w = 0.
+ *  7. PER CHROMOSOME: num_c = the sum of w * rho and den_c = the sum of w over the scored strata in ascending d;
+ *     scc_c = num_c / den_c, NaN when no stratum is scored.
+ *  8. GENOME-WIDE: scc = (the sum of num_c) / (the sum of den_c) over the chromosomes in table order, NaN when nothing is scored.
+ *     Every NaN is the one quiet NaN.
+ *  9. The strata table has n_chrom * (max_diag - min_diag + 1) rows, chromosome-major; a stratum with d >= n_c has n = 0 and is not
+ *     scored.
+ * 10. Exchanging A and B exchanges x and y (Sx with Sy, Sxx with Syy, count_a with count_b) and changes nothing else, bit for bit.
+ *
+ *   mkt_scc_opts_default           h 5, min_diag 0, max_diag 0, use_weights 0, weighting MKT_SCC_WEIGHT_N, min_n 3, slab_rows 0
+ *   mkt_matrix_scc                 opts NULL = the defaults; info may be NULL.  MKT_E_ARG with a message (on a) for a bad index, unequal
+ *                                  resolutions or chromosome tables, different devices, an option out of range, a non-zero reserved
+ *                                  word, b NULL; MKT_E_STATE "scc before run" when either object has not been run, and with use_weights
+ *                                  when either resolution has no weights; MKT_E_NOMEM with a message when the two bands do not fit at
+ *                                  the smallest slab (or at the slab_rows given), or when the partial sums of a chromosome (its chunks
+ *                                  * strata * 56 bytes) do not.  Everything is checked before anything is changed and the results
+ *                                  are built aside: a refused or failed call leaves the previous results alone.  The results live on
+ *                                  a at res_a and are a snapshot: a later change of b leaves them alone; a later mkt_matrix_run, add
+ *                                  or balance of a discards them.  The info: n_chrom, strata (per chromosome), the totals of candidates
+ *                                  and of used positions, the scored strata, count_a and count_b (the sum of the counts of the stored
+ *                                  cis cells with both bins jointly valid and min_diag <= bin2 - bin1 <= max_diag, of A and of B) and scc.
+ *   mkt_matrix_fetch_scc_strata    rows [first, first + n) of the strata table; any pointer may be NULL; MKT_E_ARG with a message for a
+ *                                  bad range
+ *   mkt_matrix_fetch_scc_chrom     per chromosome [first, first + n): scc_c, num_c, den_c and the scored strata; any may be NULL
+ *   mkt_matrix_scc_timing          of the last mkt_matrix_scc of res_index (ms, HIP events, added over the slabs): the fill (zeroing and
+ *                                  scattering the bands) and the sweep (with the fold).  A bad index is MKT_E_ARG without a message;
+ *                                  0, 0 without results. */
+#define MKT_SCC_WEIGHT_N 0
+#define MKT_SCC_WEIGHT_VAR 1
+typedef struct mkt_scc_opts {
+    int32_t h, min_diag, max_diag, use_weights, weighting, min_n, slab_rows;
+    uint32_t reserved[3];    /* 0 */
+} mkt_scc_opts;
+typedef struct mkt_scc_info {
+    uint32_t n_chrom, strata;
+    uint64_t candidates, used, scored, count_a, count_b;
+    double scc;
+} mkt_scc_info;
+void mkt_scc_opts_default(mkt_scc_opts* o);
+int mkt_matrix_scc(mkt_matrix* a, uint32_t res_a, mkt_matrix* b, uint32_t res_b, const mkt_scc_opts* opts, mkt_scc_info* info);
+int mkt_matrix_fetch_scc_strata(mkt_matrix* a, uint32_t res_a, uint64_t first, uint64_t n, uint64_t* n_cand, uint64_t* n_used, double* sx, double* sy, double* sxx,
+                                double* syy, double* sxy, double* rho, double* w);
+int mkt_matrix_fetch_scc_chrom(mkt_matrix* a, uint32_t res_a, uint64_t first, uint64_t n, double* scc, double* num, double* den, uint64_t* n_scored);
+int mkt_matrix_scc_timing(const mkt_matrix* a, uint32_t res_a, double* fill_ms, double* sweep_ms);
+
 #ifdef __cplusplus
 }
 #endif

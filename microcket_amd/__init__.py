@@ -35,6 +35,9 @@ from .capi import (  # noqa: F401
     Saddle,
     SaddleInfo,
     SaddleOpts,
+    Scc,
+    SccInfo,
+    SccOpts,
     TILES_AUTO,
     TILES_FAST,
     TILES_SMALL,
@@ -49,6 +52,6 @@ from .capi import (  # noqa: F401
 )
 
 __all__ = [
-    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Eigs", "EigsInfo", "EigsOpts", "Expected", "ExpectedOpts", "InsulationInfo", "InsulationOpts", "InsulationTrack", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "Pileup", "PileupInfo", "PileupOpts", "Saddle", "SaddleInfo", "SaddleOpts", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
+    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Eigs", "EigsInfo", "EigsOpts", "Expected", "ExpectedOpts", "InsulationInfo", "InsulationOpts", "InsulationTrack", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "Pileup", "PileupInfo", "PileupOpts", "Saddle", "SaddleInfo", "SaddleOpts", "Scc", "SccInfo", "SccOpts", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats",
     "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam",
 ]

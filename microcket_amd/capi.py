@@ -34,6 +34,7 @@ EXPORTS = [
     "mkt_pileup_opts_default", "mkt_matrix_pileup", "mkt_matrix_fetch_pileup", "mkt_matrix_fetch_pileup_status", "mkt_matrix_pileup_timing",
     "mkt_saddle_opts_default", "mkt_matrix_saddle", "mkt_matrix_fetch_saddle", "mkt_matrix_fetch_saddle_groups", "mkt_matrix_fetch_saddle_edges",
     "mkt_matrix_fetch_saddle_profile", "mkt_matrix_saddle_timing",
+    "mkt_scc_opts_default", "mkt_matrix_scc", "mkt_matrix_fetch_scc_strata", "mkt_matrix_fetch_scc_chrom", "mkt_matrix_scc_timing",
 ]
 
 
@@ -173,6 +174,21 @@ Saddle = collections.namedtuple("Saddle", "n nnz csum vsum mean groups group_bin
 SADDLE_OPTS = ("n_groups", "trim_lo", "trim_hi", "contact", "kind", "min_diag", "max_diag", "corner")
 SADDLE_CONTACTS = {"cis": 0, "trans": 1}
 SADDLE_NONE = 255
+
+
+class SccOpts(C.Structure):
+    """mkt_scc_opts of include/mkt.h"""
+    _fields_ = [(k, C.c_int32) for k in ("h", "min_diag", "max_diag", "use_weights", "weighting", "min_n", "slab_rows")] + [("reserved", C.c_uint32 * 3)]
+
+
+class _SccInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("n_chrom", "strata")] + [(k, C.c_uint64) for k in ("candidates", "used", "scored", "count_a", "count_b")] + [("scc", C.c_double)]
+
+
+SccInfo = collections.namedtuple("SccInfo", "n_chrom strata candidates used scored count_a count_b scc")
+Scc = collections.namedtuple("Scc", "n_cand n sx sy sxx syy sxy rho w scc num den n_scored")
+SCC_OPTS = ("h", "min_diag", "max_diag", "use_weights", "weighting", "min_n", "slab_rows")
+SCC_WEIGHTINGS = {"n": 0, "var": 1}
 
 
 class Timing(C.Structure):
@@ -373,6 +389,12 @@ def load_library():
     L.mkt_matrix_fetch_saddle_edges.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
     L.mkt_matrix_fetch_saddle_profile.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
     L.mkt_matrix_saddle_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_scc_opts_default.argtypes = [C.POINTER(SccOpts)]
+    L.mkt_scc_opts_default.restype = None
+    L.mkt_matrix_scc.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(SccOpts), C.POINTER(_SccInfoC)]
+    L.mkt_matrix_fetch_scc_strata.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 9
+    L.mkt_matrix_fetch_scc_chrom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 4
+    L.mkt_matrix_scc_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -1085,6 +1107,51 @@ class Matrix:
         v = np.zeros(self.info(res)[0], dtype=np.float64)
         self._chk(self.L.mkt_matrix_fetch_eigvecs(self.h, res, k, 0, v.size, v.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_eigvecs")
         return self.saddle(res, v, **opts)
+
+    def scc(self, other, res, **opts):
+        """Replicate comparison: the stratum-adjusted correlation of resolution index res of this matrix (A) and the same resolution of
+        `other` (B, found there by its value); the definition is mkt_matrix_scc in include/mkt.h.  opts: h, min_diag, max_diag,
+        use_weights, weighting ("n", "var" or its number), min_n, slab_rows.  The results live on this matrix.  Returns SccInfo."""
+        o = SccOpts()
+        self.L.mkt_scc_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in SCC_OPTS:
+                raise TypeError(f"scc: unknown option {k}")
+            if k == "weighting" and isinstance(v, str):
+                if v not in SCC_WEIGHTINGS:
+                    raise ValueError(f"scc: weighting {v!r} (n or var)")
+                v = SCC_WEIGHTINGS[v]
+            setattr(o, k, int(v))
+        if not 0 <= res < len(self.resolutions):
+            raise MktError(f"scc: resolution index {res} of {len(self.resolutions)}")
+        if self.resolutions[res] not in other.resolutions:
+            raise MktError(f"scc: the other matrix has no resolution {self.resolutions[res]}")
+        info = _SccInfoC()
+        self._chk(self.L.mkt_matrix_scc(self.h, res, other.h, other.resolutions.index(self.resolutions[res]), C.byref(o), C.byref(info)), "mkt_matrix_scc")
+        self._scc_shape = getattr(self, "_scc_shape", {})
+        self._scc_shape[res] = (info.n_chrom, info.strata)
+        return SccInfo(*[getattr(info, k) for k in SccInfo._fields])
+
+    def scc_result(self, res):
+        """the arrays of the last scc(.., res): Scc(n_cand, n uint64; sx, sy, sxx, syy, sxy, rho, w float64: the strata table
+        [n_chrom * strata], chromosome-major; scc, num, den float64 and n_scored uint64 per chromosome)"""
+        import numpy as np
+        self._chk(self.L.mkt_matrix_fetch_scc_chrom(self.h, res, 0, 0, None, None, None, None), "mkt_matrix_fetch_scc_chrom")
+        shape = getattr(self, "_scc_shape", {}).get(res)
+        if not shape:
+            raise MktError("scc_result: the comparison of this resolution was not made through scc()")
+        rows = shape[0] * shape[1]
+        tab = [np.zeros(rows, np.uint64), np.zeros(rows, np.uint64)] + [np.zeros(rows, np.float64) for _ in range(7)]
+        self._chk(self.L.mkt_matrix_fetch_scc_strata(self.h, res, 0, rows, *[a.ctypes.data_as(C.c_void_p) for a in tab]), "mkt_matrix_fetch_scc_strata")
+        ch = [np.zeros(shape[0], np.float64) for _ in range(3)] + [np.zeros(shape[0], np.uint64)]
+        self._chk(self.L.mkt_matrix_fetch_scc_chrom(self.h, res, 0, shape[0], *[a.ctypes.data_as(C.c_void_p) for a in ch]), "mkt_matrix_fetch_scc_chrom")
+        return Scc(*tab, *ch)
+
+    def scc_timing_ms(self, res):
+        """(fill ms, sweep + fold ms) on the device of the last scc(.., res)"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_scc_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_scc_timing")
+        return a.value, b.value
 
     def close(self):
         if self.h:

@@ -13,6 +13,7 @@
 //                [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]
 //                [--saddle [--saddle-groups N] [--saddle-trim LO,HI] [--saddle-contact cis|trans] [--saddle-kind oe|oe-smooth]
 //                          [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]
+//                [--compare OTHER.pairs [--scc-h N] [--scc-min-dist BP] [--scc-max-dist BP] [--scc-weighting n|var]]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -68,6 +69,15 @@
 // each a multiple of every -r; defaults: diagonals 2 and up, no upper limit), --saddle-corner (1 .. groups / 2; default max(1, groups / 5)).
 // One of them without --saddle is a usage error, a bad value exit 12.  Without --saddle neither file appears and every other byte is the
 // same.
+// With --compare OTHER.pairs (mkt_matrix_scc of include/mkt.h: the stratum-adjusted correlation of the input and a replicate) the second
+// file is binned with the same table and resolutions; with --balance both matrices are balanced with the same options and the weights
+// are used, without it raw counts.  Also per resolution <prefix>.<r>.scc.tsv: a header line, then the strata table, one row per
+// chromosome and diagonal: chrom, diag, dist_bp, n_cand, n, sx, sy, sxx, syy, sxy, rho, w, doubles as %.17g and nan for NaN; and
+// <prefix>.scc.stat, per resolution one "chrom" row per chromosome (r, chrom, name, scored strata, num, den, scc) and one "genome" row
+// (r, genome, n_chrom, strata, candidates, used, scored, count_a, count_b, scc).  --scc-h (0 .. 16, default 5), --scc-min-dist (default
+// 0) and --scc-max-dist (default 5000000, rounded down to whole bins and at least one bin; 0 = every diagonal) in base pairs, each given
+// value a multiple of every -r, --scc-weighting (default n).  One of them without --compare is a usage error, a bad value exit 12.
+// Without --compare neither file appears and every other byte is the same.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -87,7 +97,8 @@ static int usage(const char* me) {
                     "       [--insulation BP1[,BP2,..] [--ins-ignore-diags N] [--ins-min-frac-valid X] [--ins-min-strength X]]\n"
                     "       [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]\n"
                     "       [--saddle [--saddle-groups N] [--saddle-trim LO,HI] [--saddle-contact cis|trans] [--saddle-kind oe|oe-smooth]\n"
-                    "                 [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]\n", me);
+                    "                 [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]\n"
+                    "       [--compare OTHER.pairs [--scc-h N] [--scc-min-dist BP] [--scc-max-dist BP] [--scc-weighting n|var]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -279,6 +290,38 @@ static int write_saddle(mkt_matrix* m, uint32_t k, uint32_t r, const mkt_saddle_
     return MKT_OK;
 }
 
+// the strata table and the per-chromosome scores of the last mkt_matrix_scc of resolution index k as <fn> and more rows of `stat`
+static int write_scc(mkt_matrix* m, uint32_t k, uint32_t r, const mkt_scc_info& ci, int32_t min_diag, const std::vector<Chrom>& chroms, const std::string& fn, std::string& stat) {
+    const size_t D = ci.strata, rows = (size_t)ci.n_chrom * D;
+    std::vector<uint64_t> nc(rows), nu(rows), sc(ci.n_chrom);
+    std::vector<double> v[7], cs(ci.n_chrom), cn(ci.n_chrom), cd(ci.n_chrom);
+    for (auto& x : v) x.resize(rows);
+    int rc = mkt_matrix_fetch_scc_strata(m, k, 0, rows, nc.data(), nu.data(), v[0].data(), v[1].data(), v[2].data(), v[3].data(), v[4].data(), v[5].data(), v[6].data());
+    if (rc == MKT_OK) rc = mkt_matrix_fetch_scc_chrom(m, k, 0, ci.n_chrom, cs.data(), cn.data(), cd.data(), sc.data());
+    if (rc != MKT_OK) return rc;
+    std::string t = "chrom\tdiag\tdist_bp\tn_cand\tn\tsx\tsy\tsxx\tsyy\tsxy\trho\tw\n";
+    const char* md = "wb";
+    for (size_t c = 0; c < ci.n_chrom; ++c)
+        for (size_t j = 0; j < D; ++j) {
+            const size_t at = c * D + j;
+            const uint64_t d = (uint64_t)min_diag + j;
+            t += chroms[c].name; t += '\t'; t += std::to_string(d); t += '\t'; t += std::to_string(d * r); t += '\t'; t += std::to_string(nc[at]); t += '\t'; t += std::to_string(nu[at]);
+            for (auto& x : v) { t += '\t'; put_num(t, x[at]); }
+            t += '\n';
+            if (t.size() > ((size_t)32 << 20)) { if (!write_file(fn, t.data(), t.size(), md)) return -1; t.clear(); md = "ab"; }
+        }
+    if (!write_file(fn, t.data(), t.size(), md)) return -1;
+    const std::string rs = std::to_string(r);
+    for (size_t c = 0; c < ci.n_chrom; ++c) {
+        stat += rs; stat += "\tchrom\t"; stat += chroms[c].name; stat += '\t'; stat += std::to_string(sc[c]); stat += '\t'; put_num(stat, cn[c]); stat += '\t'; put_num(stat, cd[c]);
+        stat += '\t'; put_num(stat, cs[c]); stat += '\n';
+    }
+    stat += rs; stat += "\tgenome";
+    for (uint64_t x : {(uint64_t)ci.n_chrom, (uint64_t)ci.strata, ci.candidates, ci.used, ci.scored, ci.count_a, ci.count_b}) { stat += '\t'; stat += std::to_string(x); }
+    stat += '\t'; put_num(stat, ci.scc); stat += '\n';
+    return MKT_OK;
+}
+
 int main(int argc, char* argv[]) {
     const char *table = nullptr, *rlist = nullptr, *prefix = nullptr;
     std::vector<const char*> files;
@@ -297,6 +340,9 @@ int main(int argc, char* argv[]) {
     bool saddle = false;
     const char* sopt[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const sname[7] = {"--saddle-groups", "--saddle-trim", "--saddle-contact", "--saddle-kind", "--saddle-min-dist", "--saddle-max-dist", "--saddle-corner"};
+    const char* cfile = nullptr;                                              // --compare
+    const char* copt[4] = {nullptr, nullptr, nullptr, nullptr};
+    static const char* const cname[4] = {"--scc-h", "--scc-min-dist", "--scc-max-dist", "--scc-weighting"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -312,7 +358,11 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], pname[k])) pl = k;
         int sd = -1;
         for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], sname[k])) sd = k;
-        if (sd >= 0) { if (i + 1 >= argc) return usage(argv[0]); sopt[sd] = argv[++i]; }
+        int cm = -1;
+        for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], cname[k])) cm = k;
+        if (cm >= 0) { if (i + 1 >= argc) return usage(argv[0]); copt[cm] = argv[++i]; }
+        else if (!strcmp(argv[i], "--compare")) { if (i + 1 >= argc) return usage(argv[0]); cfile = argv[++i]; }
+        else if (sd >= 0) { if (i + 1 >= argc) return usage(argv[0]); sopt[sd] = argv[++i]; }
         else if (!strcmp(argv[i], "--saddle")) saddle = eigs = expected = true;
         else if (pl == 3) popt[3] = argv[i];
         else if (pl >= 0) { if (i + 1 >= argc) return usage(argv[0]); popt[pl] = argv[++i]; }
@@ -416,6 +466,20 @@ int main(int argc, char* argv[]) {
     }
     if (saddle && so.corner > so.n_groups / 2) { fprintf(stderr, "Error: --saddle-corner %d is larger than half of --saddle-groups %d\n", so.corner, so.n_groups); return 12; }
     if (saddle && sbp[1] > 0 && sbp[1] < sbp[0]) { fprintf(stderr, "Error: --saddle-max-dist %d is below --saddle-min-dist %d\n", sbp[1], sbp[0]); return 12; }
+    mkt_scc_opts co;
+    mkt_scc_opts_default(&co);
+    co.use_weights = balance ? 1 : 0;
+    int32_t cbp[2] = {-1, -1};                                                // --scc-min-dist, --scc-max-dist in base pairs
+    for (int k = 0; k < 4; ++k) {
+        if (!copt[k]) continue;
+        if (!cfile) { fprintf(stderr, "Error: %s needs --compare\n", cname[k]); return usage(argv[0]); }
+        bool ok = true;
+        if (k == 0) ok = parse_int(copt[k], co.h) && co.h <= 16;
+        else if (k < 3) ok = parse_int(copt[k], cbp[k - 1]);
+        else { if (!strcmp(copt[k], "n")) co.weighting = MKT_SCC_WEIGHT_N; else if (!strcmp(copt[k], "var")) co.weighting = MKT_SCC_WEIGHT_VAR; else ok = false; }
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", copt[k], cname[k], k == 0 ? "a whole number, 0 .. 16" : k < 3 ? "a whole number of base pairs, 0 or more" : "n or var"); return 12; }
+    }
+    if (cfile && cbp[1] > 0 && cbp[1] < cbp[0]) { fprintf(stderr, "Error: --scc-max-dist %d is below --scc-min-dist %d\n", cbp[1], cbp[0]); return 12; }
     std::vector<uint32_t> ibp;                                                // the windows in base pairs
     if (ilist && (!parse_res(ilist, ibp) || ibp.size() > 4)) { fprintf(stderr, "Error: bad window list '%s' for --insulation (1 .. 4 different positive numbers, comma separated)\n", ilist); return 12; }
     for (size_t k = 1; k < ibp.size(); ++k)
@@ -432,6 +496,9 @@ int main(int argc, char* argv[]) {
     for (uint32_t r : res)
         for (int k = 0; k < 2; ++k)
             if (sbp[k] > 0 && (uint32_t)sbp[k] % r != 0) { fprintf(stderr, "Error: %s %d is not a multiple of resolution %u\n", sname[4 + k], sbp[k], r); return 12; }
+    for (uint32_t r : res)
+        for (int k = 0; k < 2; ++k)
+            if (cbp[k] > 0 && (uint32_t)cbp[k] % r != 0) { fprintf(stderr, "Error: %s %d is not a multiple of resolution %u\n", cname[1 + k], cbp[k], r); return 12; }
     if (gopt[6] && res.size() != 1) { fprintf(stderr, "Error: --eigs-track needs a single resolution\n"); return usage(argv[0]); }
     std::vector<double> track;
     if (gopt[6]) {                                                            // the bins of .bins.bed in order, with a value each
@@ -474,6 +541,8 @@ int main(int argc, char* argv[]) {
         in.push_back(f);
     }
     if (in.empty()) in.push_back(stdin);
+    FILE* cin2 = nullptr;
+    if (cfile && !(cin2 = fopen(cfile, "rb"))) { fprintf(stderr, "Error: read input file failed!\n"); return 10; }
 
     const char* e = getenv("MKT_DEVICE");
     mkt_matrix* m = nullptr;
@@ -496,9 +565,24 @@ int main(int argc, char* argv[]) {
     }
     uint64_t pairs = 0, skipped = 0;
     if ((rc = mkt_matrix_run(m, &pairs, &skipped)) != MKT_OK) return lib_fail("GPU matrix");
+    mkt_matrix* m2 = nullptr;                                                 // the replicate of --compare: the same table and resolutions
+    struct Drop { mkt_matrix*& p; ~Drop() { if (p) mkt_matrix_destroy(p); } } drop2{m2};
+    auto lib_fail2 = [&](const char* what) { fprintf(stderr, "Error: %s: %s: %s\n", what, mkt_strerror(rc), mkt_matrix_error(m2)); mkt_matrix_destroy(m); return 21; };
+    if (cfile) {
+        rc = mkt_matrix_create(e ? atoi(e) : 0, ttxt.data(), ttxt.size(), res.data(), (uint32_t)res.size(), &m2);
+        if (rc != MKT_OK) { fprintf(stderr, "Error: GPU matrix: %s: %s\n", mkt_strerror(rc), mkt_matrix_error(nullptr)); mkt_matrix_destroy(m); return 21; }
+        for (;;) {
+            const size_t k = fread(buf.data(), 1, buf.size(), cin2);
+            if (k == 0) break;
+            if ((rc = mkt_matrix_add(m2, buf.data(), k)) != MKT_OK) return lib_fail2("GPU matrix (--compare)");
+        }
+        if (ferror(cin2)) { fprintf(stderr, "Error: read input file failed!\n"); mkt_matrix_destroy(m); return 10; }
+        fclose(cin2);
+        if ((rc = mkt_matrix_run(m2, nullptr, nullptr)) != MKT_OK) return lib_fail2("GPU matrix (--compare)");
+    }
 
     const std::string pre = prefix;
-    std::string bstat, lstat, gstat, istat, astat, pstat, sstat;
+    std::string bstat, lstat, gstat, istat, astat, pstat, sstat, cstat;
     const uint32_t ni = (uint32_t)ibp.size();
     std::vector<uint64_t> inv;                                                // [ni][nbins] of the resolution at hand
     std::vector<double> isc, ilg, ist;
@@ -529,6 +613,17 @@ int main(int argc, char* argv[]) {
             snprintf(line, sizeof line, "%u\t%u\t%d\t%.17g\t%.17g\t%llu\n", res[k], bs.iterations, bs.converged, bs.var, bs.scale, (unsigned long long)bs.masked);
             bstat += line;
             if (!bs.converged) fprintf(stderr, "WARN: balancing at resolution %u did not converge in %u iterations (var %g).\n", res[k], bs.iterations, bs.var);
+        }
+        if (cfile) {
+            if (balance && (rc = mkt_matrix_balance(m2, k, &bo, nullptr)) != MKT_OK) return lib_fail2("GPU matrix balance (--compare)");
+            co.min_diag = cbp[0] > 0 ? cbp[0] / (int32_t)res[k] : 0;
+            if (cbp[1] >= 0) co.max_diag = cbp[1] / (int32_t)res[k];
+            else { co.max_diag = (int32_t)(5000000u / res[k]); if (co.max_diag < 1) co.max_diag = 1; if (co.max_diag < co.min_diag) co.max_diag = co.min_diag; }
+            mkt_scc_info ci;
+            if ((rc = mkt_matrix_scc(m, k, m2, k, &co, &ci)) != MKT_OK) return lib_fail("GPU matrix scc");
+            rc = write_scc(m, k, res[k], ci, co.min_diag, chroms, pre + "." + std::to_string(res[k]) + ".scc.tsv", cstat);
+            if (rc < 0) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+            if (rc != MKT_OK) return lib_fail("GPU matrix scc");
         }
         if (expected) {
             mkt_expected_opts eo;
@@ -735,6 +830,7 @@ int main(int argc, char* argv[]) {
         if (eigs && !write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (ni && !write_file(pre + "." + std::to_string(res[k]) + ".insulation.tsv", ibed.data(), ibed.size(), imode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
+    if (cfile && !write_file(pre + ".scc.stat", cstat.data(), cstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (saddle && !write_file(pre + ".saddle.stat", sstat.data(), sstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (apa && !write_file(pre + ".apa.stat", astat.data(), astat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (pfile && !write_file(pre + ".pileup.stat", pstat.data(), pstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
