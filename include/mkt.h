@@ -916,6 +916,77 @@ int mkt_matrix_fetch_scc_strata(mkt_matrix* a, uint32_t res_a, uint64_t first, u
 int mkt_matrix_fetch_scc_chrom(mkt_matrix* a, uint32_t res_a, uint64_t first, uint64_t n, double* scc, double* num, double* den, uint64_t* n_scored);
 int mkt_matrix_scc_timing(const mkt_matrix* a, uint32_t res_a, double* fill_ms, double* sweep_ms);
 
+/* ---- viewpoint contact profiles (a virtual 4C): one chromosome against the rest of the genome -----------------------------------------------
+ * The contacts between one chromosome (the VIEWPOINT, e.g. a viral episome such as chrEBV) and a set of PARTNER chromosomes, the two sides
+ * binned at two different sizes, which the square matrices cannot express.  This is the reference's util/analyze.EBV (its two Perl
+ * scripts): with origin 0 and second_side_only 1 the three texts made from these results are theirs byte for byte (tests/golden/
+ * viewpoint_golden.json holds their output; tests/viewpointdef.py restates the definition).  Integers only on the device.
+ *
+ * Input: the resident pair records of a matrix object that has been run: table index and 1-based position of the two sides of every
+ * pair, in the order the sides were added (.pairs columns 2, 3 and 4, 5).  The resolutions of the object play no part.
+ * Options (mkt_viewpoint_opts):
+ *   viewpoint          table index of the viewpoint chromosome
+ *   partner_mask       one byte per chromosome of the table, non-zero = partner; NULL = every chromosome but the viewpoint.  The byte of
+ *                      the viewpoint itself must be 0 (cis profiles from a sub-range of a chromosome are out of scope).
+ *   vbin, pbin         bin sizes in bp of the viewpoint side and of the partner side, each at least 1
+ *   origin             0: bin = pos / size, the reference's int(pos / bin) on the 1-based position; 1: bin = (pos - 1) / size, the
+ *                      convention of the matrices
+ *   second_side_only   0: a pair matches when one side is on the viewpoint and the other on a partner, whichever is which;
+ *                      1: the reference's rule, the viewpoint must be the second side as stored and the partner the first
+ *   min_count          at least 1: the smallest count of a cell of the partner track
+ *   hotspot_ratio      in [0, 1)
+ *   reserved           0
+ * A record the matrix stage skipped (unknown chromosome, position 0 or past the length) or that is no pair never matches.  DEVIATION:
+ * the Perl scripts have no table and count such pairs.
+ * Results (counts exact uint32, totals uint64); they depend on the multiset of records only, with second_side_only 0 not on which side of
+ * a pair was written first either; input order, chunking and the route (add, add_device, add_keys) never change a byte:
+ *   total              the matching pairs
+ *   LINK TABLE         the non-empty cells (viewpoint bin, partner chromosome, partner bin, count), strictly ascending in that order
+ *   VIEWPOINT TRACK    dense counts of the viewpoint bins 0 .. the largest occupied one; length 0 when nothing matched.  DEVIATION: the
+ *                      Perl prints one line of zeros and warnings then.
+ *   PARTNER TRACK      the cells (partner chromosome, partner bin, count) with count >= min_count, ascending by (chromosome NAME bytewise,
+ *                      bin): the order of `LC_ALL=C sort -k1,1 -k2,2n`
+ * HOTSPOT CUT, on the host: over the distinct counts v of the link table in descending order, accum += v * (links with count v); at the
+ * first v where accum > (uint64)((double)total * hotspot_ratio) (">", not ">=") min_loop = v + 1; a min_loop above the largest count becomes
+ * the largest count.  0 without links.
+ * LINKS TEXT (csrc/mkt_viewpoint.h, vp_links_text): the links with count >= min_loop in the bytewise order of the text
+ * "<viewpoint bin>\t<hs name>\t<partner bin>" in decimal (so 10 sorts before 2), hs name = the chromosome name with its first "chr",
+ * wherever it stands, replaced by "hs"; each as  hs0 \t i * vbin * 5000 \t i * vbin * 5000 + vbin * 5000 \t <hs name> \t j * pbin \t
+ * j * pbin + pbin \t thickness=<t>p  with t = (int)(log((double)count) / log(2.0)) in doubles through the C library (not a bit length).
+ * A viewpoint chromosome whose last bin end, bins * vbin * 5000, does not stay below 2^63 is refused (MKT_E_ARG).
+ *
+ *   mkt_viewpoint_opts_default        vbin 200, pbin 1000000, origin 0, second_side_only 0, min_count 1, hotspot_ratio 0.01, mask NULL
+ *   mkt_matrix_viewpoint              opts NULL = the defaults (viewpoint 0); info may be NULL.  MKT_E_STATE "viewpoint before run" before
+ *                                     mkt_matrix_run.  MKT_E_ARG with a message for a viewpoint outside the table or inside its own mask, a
+ *                                     bin size of 0, an origin or second_side_only that is not 0 or 1, min_count 0, a ratio outside [0, 1),
+ *                                     a non-zero reserved word; MKT_E_CAPACITY for 2^32 bins or more on either side; MKT_E_NOMEM when the
+ *                                     dense tracks (4 bytes per bin of either side) do not fit half of the free memory.  Everything is
+ *                                     checked before anything changes and the results are built aside: a refused or failed call leaves the
+ *                                     previous results alone.  A later mkt_matrix_add or run discards them; the analyses of the resolutions
+ *                                     and this one do not disturb each other.
+ *   mkt_matrix_fetch_viewpoint_links     links [first, first + n); any pointer may be NULL; MKT_E_ARG with a message for a bad range
+ *   mkt_matrix_fetch_viewpoint_track     bins [first, first + n) of the viewpoint track
+ *   mkt_matrix_fetch_viewpoint_partners  cells [first, first + n) of the partner track (those with count >= min_count)
+ *   mkt_matrix_viewpoint_timing       of the last mkt_matrix_viewpoint (ms, HIP events): the two scans of the records, and the sort with the
+ *                                     run-length passes.  0, 0 without results. */
+typedef struct mkt_viewpoint_opts {
+    const uint8_t* partner_mask;
+    double hotspot_ratio;
+    uint32_t viewpoint, vbin, pbin, min_count;
+    int32_t origin, second_side_only;
+    uint32_t reserved[2];    /* 0 */
+} mkt_viewpoint_opts;
+typedef struct mkt_viewpoint_info {
+    uint64_t total, links, links_kept, partner_cells, partner_cells_kept;
+    uint32_t min_loop, viewpoint_bins;
+} mkt_viewpoint_info;
+void mkt_viewpoint_opts_default(mkt_viewpoint_opts* o);
+int mkt_matrix_viewpoint(mkt_matrix* m, const mkt_viewpoint_opts* opts, mkt_viewpoint_info* info);
+int mkt_matrix_fetch_viewpoint_links(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* vbin, uint32_t* chrom, uint32_t* pbin, uint32_t* count);
+int mkt_matrix_fetch_viewpoint_track(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* count);
+int mkt_matrix_fetch_viewpoint_partners(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* chrom, uint32_t* pbin, uint32_t* count);
+int mkt_matrix_viewpoint_timing(const mkt_matrix* m, double* scan_ms, double* sort_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -200,6 +200,13 @@ def build_test_tools():
     bsrc = os.path.join(ROOT, "tests", "host", "devbuf_check.cpp")
     if os.path.exists(bsrc) and _newer(dbc, [bsrc, os.path.join(CSRC, "mkt_devbuf.h")]):
         _run([hipcc(), f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-Wall", "-Wl,-rpath,/opt/rocm/lib", "-o", dbc, bsrc])
+    # host driver of the viewpoint profiles' host half (mkt_viewpoint.h), plain and with the address and undefined-behaviour sanitizers
+    # (a stand-alone program: nothing of it is loaded into python); a tree that carries an older tests/ has no such source
+    vsrc = os.path.join(ROOT, "tests", "host", "viewpoint_host.cpp")
+    for name, extra in (("viewpoint_host", ()), ("viewpoint_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        vph = os.path.join(out, name)
+        if os.path.exists(vsrc) and _newer(vph, [vsrc, os.path.join(CSRC, "mkt_viewpoint.h"), os.path.join(ROOT, "include", "mkt.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", vph, vsrc])
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
     synth = os.path.join(tout, "synth_sam")

@@ -35,6 +35,8 @@ EXPORTS = [
     "mkt_saddle_opts_default", "mkt_matrix_saddle", "mkt_matrix_fetch_saddle", "mkt_matrix_fetch_saddle_groups", "mkt_matrix_fetch_saddle_edges",
     "mkt_matrix_fetch_saddle_profile", "mkt_matrix_saddle_timing",
     "mkt_scc_opts_default", "mkt_matrix_scc", "mkt_matrix_fetch_scc_strata", "mkt_matrix_fetch_scc_chrom", "mkt_matrix_scc_timing",
+    "mkt_viewpoint_opts_default", "mkt_matrix_viewpoint", "mkt_matrix_fetch_viewpoint_links", "mkt_matrix_fetch_viewpoint_track",
+    "mkt_matrix_fetch_viewpoint_partners", "mkt_matrix_viewpoint_timing",
 ]
 
 
@@ -189,6 +191,21 @@ SccInfo = collections.namedtuple("SccInfo", "n_chrom strata candidates used scor
 Scc = collections.namedtuple("Scc", "n_cand n sx sy sxx syy sxy rho w scc num den n_scored")
 SCC_OPTS = ("h", "min_diag", "max_diag", "use_weights", "weighting", "min_n", "slab_rows")
 SCC_WEIGHTINGS = {"n": 0, "var": 1}
+
+
+class ViewpointOpts(C.Structure):
+    """mkt_viewpoint_opts of include/mkt.h"""
+    _fields_ = [("partner_mask", C.c_void_p), ("hotspot_ratio", C.c_double)] + [(k, C.c_uint32) for k in ("viewpoint", "vbin", "pbin", "min_count")] + \
+               [("origin", C.c_int32), ("second_side_only", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class _ViewpointInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("total", "links", "links_kept", "partner_cells", "partner_cells_kept")] + [(k, C.c_uint32) for k in ("min_loop", "viewpoint_bins")]
+
+
+ViewpointInfo = collections.namedtuple("ViewpointInfo", "total links links_kept partner_cells partner_cells_kept min_loop viewpoint_bins")
+Viewpoint = collections.namedtuple("Viewpoint", "link_vbin link_chrom link_pbin link_count track partner_chrom partner_pbin partner_count info")
+VIEWPOINT_OPTS = ("vbin", "pbin", "origin", "second_side_only", "min_count", "hotspot_ratio", "reserved")
 
 
 class Timing(C.Structure):
@@ -395,6 +412,13 @@ def load_library():
     L.mkt_matrix_fetch_scc_strata.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 9
     L.mkt_matrix_fetch_scc_chrom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 4
     L.mkt_matrix_scc_timing.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_viewpoint_opts_default.argtypes = [C.POINTER(ViewpointOpts)]
+    L.mkt_viewpoint_opts_default.restype = None
+    L.mkt_matrix_viewpoint.argtypes = [C.c_void_p, C.POINTER(ViewpointOpts), C.POINTER(_ViewpointInfoC)]
+    L.mkt_matrix_fetch_viewpoint_links.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 4
+    L.mkt_matrix_fetch_viewpoint_track.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_matrix_fetch_viewpoint_partners.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3
+    L.mkt_matrix_viewpoint_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -739,6 +763,8 @@ class Matrix:
     def __init__(self, chromsizes: bytes, resolutions, device=0):
         self.L = load_library()
         self.resolutions = [int(r) for r in resolutions]
+        # the names of the table in order, as the library reads them ('#' lines and empty lines are no chromosomes)
+        self.names = [ln.split(b"\t")[0].decode("latin-1") for ln in (x.rstrip(b"\r") for x in bytes(chromsizes).split(b"\n")) if ln and not ln.startswith(b"#")]
         arr = (C.c_uint32 * max(len(self.resolutions), 1))(*self.resolutions)
         self.h = C.c_void_p()
         rc = self.L.mkt_matrix_create(device, chromsizes, len(chromsizes), arr, len(self.resolutions), C.byref(self.h))
@@ -1151,6 +1177,64 @@ class Matrix:
         """(fill ms, sweep + fold ms) on the device of the last scc(.., res)"""
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_scc_timing(self.h, res, C.byref(a), C.byref(b)), "mkt_matrix_scc_timing")
+        return a.value, b.value
+
+    def viewpoint(self, name, partners=None, **opts):
+        """Viewpoint contact profile (a virtual 4C) of chromosome `name` over the resident pairs: mkt_matrix_viewpoint in include/mkt.h.
+        partners: None = every other chromosome, a string = a regular expression applied to the names with re.search (the viewpoint
+        itself is never a partner), else a list of names.  opts: vbin, pbin, origin, second_side_only, min_count, hotspot_ratio.
+        Returns ViewpointInfo."""
+        import re
+        if name not in self.names:
+            raise MktError(f"viewpoint: no chromosome {name!r} in the table")
+        v = self.names.index(name)
+        if partners is None:
+            mask = [i != v for i in range(len(self.names))]
+        elif isinstance(partners, str):
+            mask = [i != v and re.search(partners, n) is not None for i, n in enumerate(self.names)]
+        else:
+            partners = list(partners)
+            for n in partners:
+                if n not in self.names:
+                    raise MktError(f"viewpoint: no chromosome {n!r} in the table")
+            mask = [n in partners for n in self.names]                            # (the viewpoint among them: the library refuses)
+        o = ViewpointOpts()
+        self.L.mkt_viewpoint_opts_default(C.byref(o))
+        for k, x in opts.items():
+            if k not in VIEWPOINT_OPTS:
+                raise TypeError(f"viewpoint: unknown option {k}")
+            if k == "reserved":
+                o.reserved[0] = int(x)
+            else:
+                setattr(o, k, float(x) if k == "hotspot_ratio" else int(x))
+        mb = (C.c_uint8 * len(mask))(*[1 if x else 0 for x in mask])
+        o.partner_mask = C.cast(mb, C.c_void_p)
+        o.viewpoint = v
+        info = _ViewpointInfoC()
+        self._chk(self.L.mkt_matrix_viewpoint(self.h, C.byref(o), C.byref(info)), "mkt_matrix_viewpoint")
+        self._vp_info = ViewpointInfo(*[getattr(info, k) for k in ViewpointInfo._fields])
+        return self._vp_info
+
+    def viewpoint_result(self):
+        """the arrays of the last viewpoint(): Viewpoint(link_vbin, link_chrom, link_pbin, link_count: the link table, ascending; track: the
+        dense viewpoint track; partner_chrom, partner_pbin, partner_count: the partner track, by (name, bin); info), all uint32"""
+        import numpy as np
+        self._chk(self.L.mkt_matrix_fetch_viewpoint_track(self.h, 0, 0, None), "mkt_matrix_fetch_viewpoint_track")
+        info = getattr(self, "_vp_info", None)
+        if info is None:
+            raise MktError("viewpoint_result: the profile was not made through viewpoint()")
+        links = [np.zeros(info.links, np.uint32) for _ in range(4)]
+        track = np.zeros(info.viewpoint_bins, np.uint32)
+        part = [np.zeros(info.partner_cells_kept, np.uint32) for _ in range(3)]
+        self._chk(self.L.mkt_matrix_fetch_viewpoint_links(self.h, 0, info.links, *[a.ctypes.data_as(C.c_void_p) for a in links]), "mkt_matrix_fetch_viewpoint_links")
+        self._chk(self.L.mkt_matrix_fetch_viewpoint_track(self.h, 0, track.size, track.ctypes.data_as(C.c_void_p)), "mkt_matrix_fetch_viewpoint_track")
+        self._chk(self.L.mkt_matrix_fetch_viewpoint_partners(self.h, 0, info.partner_cells_kept, *[a.ctypes.data_as(C.c_void_p) for a in part]), "mkt_matrix_fetch_viewpoint_partners")
+        return Viewpoint(*links, track, *part, info)
+
+    def viewpoint_timing_ms(self):
+        """(scan ms, sort + run-length ms) on the device of the last viewpoint()"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(self.L.mkt_matrix_viewpoint_timing(self.h, C.byref(a), C.byref(b)), "mkt_matrix_viewpoint_timing")
         return a.value, b.value
 
     def close(self):

@@ -32,6 +32,8 @@
 #include "mkt_pileup.h"
 #include "mkt_saddle.h"
 #include "mkt_scc.h"
+#include "mkt_viewpoint.h"
+#include "mkt_rle.h"
 #include "mkt_launch.h"
 #include "mkt_layout.h"
 #include "mkt_segred.h"
@@ -323,6 +325,7 @@ struct mkt_matrix {
     bool ran = false;
     uint64_t pairs = 0, skipped = 0;
     std::vector<MxRes> res;
+    VpState vp;                                     // viewpoint profiles (mkt_matrix_viewpoint): the results live until the next add or run
     std::string err;
 };
 
@@ -384,6 +387,7 @@ static void mx_free_results(mkt_matrix* m) {
         r.sad = SaddleState();
         r.scc = SccState();
     }
+    m->vp = VpState();
     m->ran = false;
 }
 static int mx_reserve_rec(mkt_matrix* m, uint64_t need) {
@@ -479,33 +483,45 @@ struct MxScratch {
         MKT_TRY(a.alloc(n, 64));
         MKT_TRY(b.alloc(n, 64));
         MKT_TRY(radix.alloc(0, radix64_count_bytes(n)));
-        return sums.alloc((nv + MX_CPW - 1) / MX_CPW + 2);               // (at most nv cells: room for the text passes' sums, which are more than the head passes')
+        return sums.alloc(rle_sums_words(nv));
     }
 };
-// one resolution's cells and COO text from the n records (nv of them binned).  A cell count that cannot be (0, or above nv) is left
-// in r.nnz for the caller and nothing more is done.
-static hipError_t mx_bin(mkt_matrix* m, MxRes& r, MxScratch& sc, uint64_t n, uint64_t nv) {
-    hipStream_t st = m->stream;
+namespace mkt {
+size_t rle_sums_words(uint64_t nv) { return (size_t)((nv + MX_CPW - 1) / MX_CPW + 2); }        // (at most nv runs: room for the text passes' sums, which are more than the head passes')
+hipError_t rle_reduce(const uint64_t* key, uint64_t nv, int B, uint64_t* sums, DevBuf<uint32_t>& hi, DevBuf<uint32_t>& lo, DevBuf<uint32_t>& cnt, DevBuf<uint32_t>& pos,
+                      uint64_t* runs, uint64_t* text_bytes, hipStream_t st) {
     const uint64_t hblocks = (nv + MX_TILE - 1) / MX_TILE;
-    uint64_t *kA = sc.a, *kB = sc.b, *sums = sc.sums;                    // the passes swap the two as needed
-    hipLaunchKernelGGL(k_mx_keys, dim3(grid_for(n, MXWG)), dim3(MXWG), 0, st, (const MxRec*)m->d_rec, n, (const uint32_t*)r.d_off, r.r, r.B, r.nbins, kA);
-    MKT_TRY(launch_radix64(kA, kB, n, 0, 2 * r.B, sc.radix, st));
-    hipLaunchKernelGGL(k_mx_head_count, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, sums);
+    hipLaunchKernelGGL(k_mx_head_count, dim3((unsigned)hblocks), dim3(MXWG), 0, st, key, nv, sums);
     MKT_TRY(launch_exscan(sums, hblocks, sums + hblocks, st));
     uint64_t nnz = 0, tb = 0;
     MKT_TRY(hipMemcpyAsync(&nnz, sums + hblocks, 8, hipMemcpyDeviceToHost, st));
     MKT_TRY(hipStreamSynchronize(st));
-    r.nnz = nnz;
+    *runs = nnz; *text_bytes = 0;
     if (nnz == 0 || nnz > nv) return hipSuccess;
-    DevBuf<uint32_t>& pos = sc.pos;
-    MKT_TRY(r.d_b1.alloc(nnz)); MKT_TRY(r.d_b2.alloc(nnz)); MKT_TRY(r.d_cnt.alloc(nnz));
+    MKT_TRY(hi.alloc(nnz)); MKT_TRY(lo.alloc(nnz)); MKT_TRY(cnt.alloc(nnz));
     MKT_TRY(pos.alloc(nnz));
-    hipLaunchKernelGGL(k_mx_cells, dim3((unsigned)hblocks), dim3(MXWG), 0, st, (const uint64_t*)kA, nv, (const uint64_t*)sums, r.B, r.d_b1.get(), r.d_b2.get(), pos.get());
+    hipLaunchKernelGGL(k_mx_cells, dim3((unsigned)hblocks), dim3(MXWG), 0, st, key, nv, (const uint64_t*)sums, B, hi.get(), lo.get(), pos.get());
     const uint64_t tblocks = (nnz + MX_CPW - 1) / MX_CPW;
-    hipLaunchKernelGGL(k_mx_counts, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)pos, nnz, nv, r.d_cnt.get(), sums);
+    hipLaunchKernelGGL(k_mx_counts, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)hi, (const uint32_t*)lo, (const uint32_t*)pos, nnz, nv, cnt.get(), sums);
     MKT_TRY(launch_exscan(sums, tblocks, sums + tblocks, st));
     MKT_TRY(hipMemcpyAsync(&tb, sums + tblocks, 8, hipMemcpyDeviceToHost, st));
     MKT_TRY(hipStreamSynchronize(st));
+    *text_bytes = tb;
+    return hipGetLastError();
+}
+}  // namespace mkt
+// one resolution's cells and COO text from the n records (nv of them binned).  A cell count that cannot be (0, or above nv) is left
+// in r.nnz for the caller and nothing more is done.
+static hipError_t mx_bin(mkt_matrix* m, MxRes& r, MxScratch& sc, uint64_t n, uint64_t nv) {
+    hipStream_t st = m->stream;
+    uint64_t *kA = sc.a, *kB = sc.b, *sums = sc.sums;                    // the passes swap the two as needed
+    hipLaunchKernelGGL(k_mx_keys, dim3(grid_for(n, MXWG)), dim3(MXWG), 0, st, (const MxRec*)m->d_rec, n, (const uint32_t*)r.d_off, r.r, r.B, r.nbins, kA);
+    MKT_TRY(launch_radix64(kA, kB, n, 0, 2 * r.B, sc.radix, st));
+    uint64_t nnz = 0, tb = 0;
+    MKT_TRY(rle_reduce(kA, nv, r.B, sums, r.d_b1, r.d_b2, r.d_cnt, sc.pos, &nnz, &tb, st));
+    r.nnz = nnz;
+    if (nnz == 0 || nnz > nv) return hipSuccess;
+    const uint64_t tblocks = (nnz + MX_CPW - 1) / MX_CPW;
     MKT_TRY(r.d_text.alloc(tb, 64));
     hipLaunchKernelGGL(k_mx_text, dim3((unsigned)tblocks), dim3(MXWG), 0, st, (const uint32_t*)r.d_b1, (const uint32_t*)r.d_b2, (const uint32_t*)r.d_cnt, nnz, (const uint64_t*)sums, r.d_text.get());
     MKT_TRY(hipGetLastError());
@@ -1527,6 +1543,87 @@ int mkt_matrix_scc_timing(const mkt_matrix* m, uint32_t res_index, double* fill_
     const bool have = m->ran && s.built;
     if (fill_ms) *fill_ms = have ? s.fill_ms : 0.0;
     if (sweep_ms) *sweep_ms = have ? s.sweep_ms : 0.0;
+    return MKT_OK;
+}
+
+// ---- viewpoint contact profiles: the entry points; the scans are mkt_viewpoint.hip, the host half mkt_viewpoint.h, the definition is
+// in include/mkt.h -------------------------------------------------------------------------------------------------------------------
+void mkt_viewpoint_opts_default(mkt_viewpoint_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->vbin = 200; o->pbin = 1000000; o->min_count = 1; o->hotspot_ratio = 0.01;
+}
+
+int mkt_matrix_viewpoint(mkt_matrix* m, const mkt_viewpoint_opts* opts, mkt_viewpoint_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    mkt_viewpoint_opts o;
+    mkt_viewpoint_opts_default(&o);
+    if (opts) o = *opts;
+    const uint32_t nc = (uint32_t)m->names.size();
+    if (o.viewpoint >= nc) return mfail(m, MKT_E_ARG, "viewpoint: chromosome index %u of %u", o.viewpoint, nc);
+    if (o.partner_mask && o.partner_mask[o.viewpoint]) return mfail(m, MKT_E_ARG, "viewpoint: %s is in its own partner mask", m->names[o.viewpoint].c_str());
+    if (o.vbin == 0 || o.pbin == 0) return mfail(m, MKT_E_ARG, "viewpoint: a bin size of 0 (vbin %u, pbin %u)", o.vbin, o.pbin);
+    if (o.origin != 0 && o.origin != 1) return mfail(m, MKT_E_ARG, "viewpoint: origin %d (0 or 1)", o.origin);
+    if (o.second_side_only != 0 && o.second_side_only != 1) return mfail(m, MKT_E_ARG, "viewpoint: second_side_only %d (0 or 1)", o.second_side_only);
+    if (o.min_count == 0) return mfail(m, MKT_E_ARG, "viewpoint: min_count 0 (at least 1 is needed)");
+    if (!(o.hotspot_ratio >= 0.0 && o.hotspot_ratio < 1.0)) return mfail(m, MKT_E_ARG, "viewpoint: hotspot_ratio %g is outside [0, 1)", o.hotspot_ratio);
+    if (o.reserved[0] != 0 || o.reserved[1] != 0) return mfail(m, MKT_E_ARG, "viewpoint: a reserved word is not 0");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "viewpoint before run");
+    std::vector<uint8_t> role(nc, 0);
+    for (uint32_t c = 0; c < nc; ++c) role[c] = c == o.viewpoint ? 1 : (!o.partner_mask || o.partner_mask[c]) ? 2 : 0;
+    MCHK(m, hipSetDevice(m->device));
+    VpState vs;                                                         // a refused or failed call leaves the previous results alone
+    std::string why;
+    const int rc = vp_run(vs, reinterpret_cast<const uint4*>(m->d_rec.get()), m->n, m->names, m->lens, role, o, m->stream, &why);
+    if (rc != MKT_OK) return mfail(m, rc, "viewpoint: %s", why.c_str());
+    m->vp = std::move(vs);
+    if (info) *info = m->vp.info;
+    return MKT_OK;
+}
+
+static int vp_have(mkt_matrix* m) {
+    if (!m) return MKT_E_ARG;
+    if (!(m->ran && m->vp.built)) return mfail(m, MKT_E_STATE, "no viewpoint profile: viewpoint first");
+    return MKT_OK;
+}
+int mkt_matrix_fetch_viewpoint_links(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* vbin, uint32_t* chrom, uint32_t* pbin, uint32_t* count) {
+    if (const int rc = vp_have(m)) return rc;
+    const std::vector<VpLink>& v = m->vp.links;
+    if (first > v.size() || n > v.size() - first) return mfail(m, MKT_E_ARG, "viewpoint links [%llu, +%llu) of %zu", (unsigned long long)first, (unsigned long long)n, v.size());
+    for (uint64_t k = 0; k < n; ++k) {
+        const VpLink& l = v[first + k];
+        if (vbin) vbin[k] = l.vbin;
+        if (chrom) chrom[k] = l.chrom;
+        if (pbin) pbin[k] = l.pbin;
+        if (count) count[k] = l.count;
+    }
+    return MKT_OK;
+}
+int mkt_matrix_fetch_viewpoint_track(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* count) {
+    if (const int rc = vp_have(m)) return rc;
+    const std::vector<uint32_t>& v = m->vp.track;
+    if (first > v.size() || n > v.size() - first) return mfail(m, MKT_E_ARG, "viewpoint track bins [%llu, +%llu) of %zu", (unsigned long long)first, (unsigned long long)n, v.size());
+    if (count && n) memcpy(count, v.data() + first, n * 4);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_viewpoint_partners(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* chrom, uint32_t* pbin, uint32_t* count) {
+    if (const int rc = vp_have(m)) return rc;
+    const std::vector<VpCell>& v = m->vp.partners;
+    if (first > v.size() || n > v.size() - first) return mfail(m, MKT_E_ARG, "viewpoint partner cells [%llu, +%llu) of %zu", (unsigned long long)first, (unsigned long long)n, v.size());
+    for (uint64_t k = 0; k < n; ++k) {
+        const VpCell& c = v[first + k];
+        if (chrom) chrom[k] = c.chrom;
+        if (pbin) pbin[k] = c.pbin;
+        if (count) count[k] = c.count;
+    }
+    return MKT_OK;
+}
+int mkt_matrix_viewpoint_timing(const mkt_matrix* m, double* scan_ms, double* sort_ms) {
+    if (!m) return MKT_E_ARG;
+    const bool have = m->ran && m->vp.built;
+    if (scan_ms) *scan_ms = have ? m->vp.scan_ms : 0.0;
+    if (sort_ms) *sort_ms = have ? m->vp.sort_ms : 0.0;
     return MKT_OK;
 }
 

@@ -14,6 +14,8 @@
 //                [--saddle [--saddle-groups N] [--saddle-trim LO,HI] [--saddle-contact cis|trans] [--saddle-kind oe|oe-smooth]
 //                          [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]
 //                [--compare OTHER.pairs [--scc-h N] [--scc-min-dist BP] [--scc-max-dist BP] [--scc-weighting n|var]]
+//                [--viewpoint NAME | --ebv] [--vp-bin BP] [--vp-partner-bin BP] [--vp-track-bin BP] [--vp-min-count N] [--vp-hotspot R]
+//                                           [--vp-partners REGEX] [--vp-second-side]
 //
 // Writes per resolution <prefix>.<r>.coo (lines bin1 \t bin2 \t count, made on the device; empty for an empty matrix) and
 // <prefix>.<r>.bins.bed (chrom \t start \t end per bin, end clipped to the chromosome length), and <prefix>.matrix.stat
@@ -78,14 +80,30 @@
 // 0) and --scc-max-dist (default 5000000, rounded down to whole bins and at least one bin; 0 = every diagonal) in base pairs, each given
 // value a multiple of every -r, --scc-weighting (default n).  One of them without --compare is a usage error, a bad value exit 12.
 // Without --compare neither file appears and every other byte is the same.
+// With --viewpoint NAME (mkt_matrix_viewpoint of include/mkt.h: the contacts of one chromosome with the rest of the genome, the
+// reference's util/analyze.EBV) also <prefix>.viewpoint.bedgraph (NAME, start, end, count for the viewpoint bins 0 .. the last occupied
+// one, bins of --vp-bin, default 200), <prefix>.viewpoint.links (Circos links of the cells above the hotspot cut of --vp-hotspot, default
+// 0.01, partner bins of --vp-partner-bin, default 1000000), <prefix>.partners.bedgraph (a second profile with partner bins of
+// --vp-track-bin, default 1000: the cells with at least --vp-min-count pairs, default 1, by name and start) and <prefix>.viewpoint.stat.
+// --vp-partners REGEX keeps the chromosomes whose name the expression finds (ECMAScript, unanchored; default: every other chromosome);
+// --vp-second-side counts only pairs whose second side is on the viewpoint.  --ebv is the preset of the reference's analyze.EBV.sh:
+// --viewpoint chrEBV --vp-partners 'chr\d+$' --vp-second-side --vp-min-count 5, the other defaults as above, each --vp-* still
+// overriding; for a pairs file the matrix stage accepts in full the first three files are then byte for byte what the reference's
+// calc.inter.EBV.matrix.and.circos.pl (stdout, stderr) and calc.loop2EBV.pl | LC_ALL=C sort -k1,1 -k2,2n write.  DEVIATIONS: pairs the
+// matrix stage skips (unknown chromosome, position outside the length; "Skipped" of the .stat) are absent here where the Perl counts
+// them; without a matching pair the bedgraph is empty where the Perl prints a line of zeros; juicer_tools pre of analyze.EBV.sh is out
+// of scope.  One of --vp-* without --viewpoint or --ebv is a usage error, a bad value, an unknown NAME or an expression that keeps
+// nothing exit 12.  Without the two flags none of these files appears and every other byte is the same.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <regex>
 #include <string>
 #include <vector>
 #include "../../include/mkt.h"
+#include "mkt_viewpoint.h"
 
 static int usage(const char* me) {
     fprintf(stderr, "Usage: %s -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]\n"
@@ -98,7 +116,9 @@ static int usage(const char* me) {
                     "       [--apa] [--pileup FILE.bedpe] [--pile-flank N] [--pile-corner N] [--pile-kind balanced|oe|oe-smooth] [--pile-edges]\n"
                     "       [--saddle [--saddle-groups N] [--saddle-trim LO,HI] [--saddle-contact cis|trans] [--saddle-kind oe|oe-smooth]\n"
                     "                 [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]\n"
-                    "       [--compare OTHER.pairs [--scc-h N] [--scc-min-dist BP] [--scc-max-dist BP] [--scc-weighting n|var]]\n", me);
+                    "       [--compare OTHER.pairs [--scc-h N] [--scc-min-dist BP] [--scc-max-dist BP] [--scc-weighting n|var]]\n"
+                    "       [--viewpoint NAME | --ebv] [--vp-bin BP] [--vp-partner-bin BP] [--vp-track-bin BP] [--vp-min-count N] [--vp-hotspot R]\n"
+                    "                                  [--vp-partners REGEX] [--vp-second-side]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -343,6 +363,10 @@ int main(int argc, char* argv[]) {
     const char* cfile = nullptr;                                              // --compare
     const char* copt[4] = {nullptr, nullptr, nullptr, nullptr};
     static const char* const cname[4] = {"--scc-h", "--scc-min-dist", "--scc-max-dist", "--scc-weighting"};
+    const char* vname = nullptr;                                              // --viewpoint
+    bool ebv = false;
+    const char* vopt[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // --vp-second-side takes no value: its slot holds the flag itself
+    static const char* const vpname[7] = {"--vp-bin", "--vp-partner-bin", "--vp-track-bin", "--vp-min-count", "--vp-hotspot", "--vp-partners", "--vp-second-side"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -360,7 +384,13 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], sname[k])) sd = k;
         int cm = -1;
         for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], cname[k])) cm = k;
-        if (cm >= 0) { if (i + 1 >= argc) return usage(argv[0]); copt[cm] = argv[++i]; }
+        int vp = -1;
+        for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], vpname[k])) vp = k;
+        if (vp == 6) vopt[6] = argv[i];
+        else if (vp >= 0) { if (i + 1 >= argc) return usage(argv[0]); vopt[vp] = argv[++i]; }
+        else if (!strcmp(argv[i], "--viewpoint")) { if (i + 1 >= argc) return usage(argv[0]); vname = argv[++i]; }
+        else if (!strcmp(argv[i], "--ebv")) ebv = true;
+        else if (cm >= 0) { if (i + 1 >= argc) return usage(argv[0]); copt[cm] = argv[++i]; }
         else if (!strcmp(argv[i], "--compare")) { if (i + 1 >= argc) return usage(argv[0]); cfile = argv[++i]; }
         else if (sd >= 0) { if (i + 1 >= argc) return usage(argv[0]); sopt[sd] = argv[++i]; }
         else if (!strcmp(argv[i], "--saddle")) saddle = eigs = expected = true;
@@ -480,6 +510,22 @@ int main(int argc, char* argv[]) {
         if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", copt[k], cname[k], k == 0 ? "a whole number, 0 .. 16" : k < 3 ? "a whole number of base pairs, 0 or more" : "n or var"); return 12; }
     }
     if (cfile && cbp[1] > 0 && cbp[1] < cbp[0]) { fprintf(stderr, "Error: --scc-max-dist %d is below --scc-min-dist %d\n", cbp[1], cbp[0]); return 12; }
+    mkt_viewpoint_opts vo;
+    mkt_viewpoint_opts_default(&vo);
+    int32_t vtrack_bin = 1000;
+    std::string vre;                                                          // the partners' expression; empty: every other chromosome
+    if (ebv) { if (!vname) vname = "chrEBV"; vre = "chr\\d+$"; vo.second_side_only = 1; vo.min_count = 5; }
+    for (int k = 0; k < 7; ++k) {
+        if (!vopt[k]) continue;
+        if (!vname) { fprintf(stderr, "Error: %s needs --viewpoint or --ebv\n", vpname[k]); return usage(argv[0]); }
+        bool ok = true;
+        int32_t v = 0;
+        if (k < 4) { ok = parse_int(vopt[k], v) && v >= 1; if (ok) { if (k == 0) vo.vbin = (uint32_t)v; else if (k == 1) vo.pbin = (uint32_t)v; else if (k == 2) vtrack_bin = v; else vo.min_count = (uint32_t)v; } }
+        else if (k == 4) ok = parse_num(vopt[k], vo.hotspot_ratio) && vo.hotspot_ratio < 1.0;
+        else if (k == 5) { vre = vopt[k]; ok = !vre.empty(); }
+        else vo.second_side_only = 1;
+        if (!ok) { fprintf(stderr, "Error: bad value '%s' for %s (%s)\n", vopt[k], vpname[k], k < 4 ? "a whole number, at least 1" : k == 4 ? "a number inside [0, 1)" : "a regular expression"); return 12; }
+    }
     std::vector<uint32_t> ibp;                                                // the windows in base pairs
     if (ilist && (!parse_res(ilist, ibp) || ibp.size() > 4)) { fprintf(stderr, "Error: bad window list '%s' for --insulation (1 .. 4 different positive numbers, comma separated)\n", ilist); return 12; }
     for (size_t k = 1; k < ibp.size(); ++k)
@@ -488,6 +534,25 @@ int main(int argc, char* argv[]) {
     if (!read_file(table, ttxt)) { fprintf(stderr, "Error: read chromosome table failed!\n"); return 10; }
     std::vector<Chrom> chroms;
     if (!parse_table(ttxt, chroms, why)) { fprintf(stderr, "Error: bad chromosome table: %s\n", why.c_str()); return 12; }
+    std::vector<uint8_t> vmask;                                               // the partners of --viewpoint
+    if (vname) {
+        size_t v = 0;
+        while (v < chroms.size() && chroms[v].name != vname) ++v;
+        if (v == chroms.size()) { fprintf(stderr, "Error: --viewpoint %s is not in the chromosome table\n", vname); return 12; }
+        vo.viewpoint = (uint32_t)v;
+        vmask.assign(chroms.size(), 1);
+        if (!vre.empty()) {
+            try {
+                const std::regex re(vre, std::regex::ECMAScript);
+                for (size_t c = 0; c < chroms.size(); ++c) vmask[c] = std::regex_search(chroms[c].name, re) ? 1 : 0;
+            } catch (const std::regex_error&) { fprintf(stderr, "Error: bad value '%s' for --vp-partners (a regular expression)\n", vre.c_str()); return 12; }
+        }
+        vmask[v] = 0;
+        size_t np = 0;
+        for (uint8_t x : vmask) np += x;
+        if (np == 0) { fprintf(stderr, "Error: --vp-partners '%s' keeps no chromosome\n", vre.c_str()); return 12; }
+        vo.partner_mask = vmask.data();
+    }
     std::vector<uint32_t> res;
     if (!parse_res(rlist, res)) { fprintf(stderr, "Error: bad resolution list '%s' (1 .. 16 different positive numbers, comma separated)\n", rlist); return 12; }
     for (uint32_t r : res)
@@ -582,6 +647,38 @@ int main(int argc, char* argv[]) {
     }
 
     const std::string pre = prefix;
+    if (vname) {                                                              // two profiles: the links at --vp-partner-bin, the partner track at --vp-track-bin
+        std::vector<std::string> names;
+        for (const Chrom& c : chroms) names.push_back(c.name);
+        mkt_viewpoint_info vi, ti;
+        mkt_viewpoint_opts lo2 = vo;
+        lo2.min_count = 1;
+        if ((rc = mkt_matrix_viewpoint(m, &lo2, &vi)) != MKT_OK) return lib_fail("GPU viewpoint profile");
+        std::vector<mkt::VpLink> links(vi.links);
+        std::vector<uint32_t> a(vi.links), b(vi.links), c(vi.links), d(vi.links), track(vi.viewpoint_bins);
+        if ((rc = mkt_matrix_fetch_viewpoint_links(m, 0, vi.links, a.data(), b.data(), c.data(), d.data())) != MKT_OK) return lib_fail("GPU viewpoint profile");
+        if ((rc = mkt_matrix_fetch_viewpoint_track(m, 0, vi.viewpoint_bins, track.data())) != MKT_OK) return lib_fail("GPU viewpoint profile");
+        for (size_t k = 0; k < links.size(); ++k) links[k] = {a[k], b[k], c[k], d[k]};
+        const std::string bg = mkt::vp_track_text(track, vname, vo.vbin), lk = mkt::vp_links_text(links, names, vi.min_loop, vo.vbin, vo.pbin);
+        mkt_viewpoint_opts to = vo;
+        to.pbin = (uint32_t)vtrack_bin;
+        if ((rc = mkt_matrix_viewpoint(m, &to, &ti)) != MKT_OK) return lib_fail("GPU viewpoint profile");
+        std::vector<mkt::VpCell> cells(ti.partner_cells_kept);
+        a.resize(cells.size()); b.resize(cells.size()); c.resize(cells.size());
+        if ((rc = mkt_matrix_fetch_viewpoint_partners(m, 0, cells.size(), a.data(), b.data(), c.data())) != MKT_OK) return lib_fail("GPU viewpoint profile");
+        for (size_t k = 0; k < cells.size(); ++k) cells[k] = {a[k], b[k], c[k]};
+        const std::string pt = mkt::vp_partners_text(cells, names, (uint64_t)vtrack_bin);
+        size_t np = 0;
+        for (uint8_t x : vmask) np += x;
+        std::string vs = std::string("Viewpoint\t") + vname + "\nPartners\t" + std::to_string(np) + "\nSecondSideOnly\t" + std::to_string(vo.second_side_only) + "\nViewpointBin\t" + std::to_string(vo.vbin) +
+                         "\nPartnerBin\t" + std::to_string(vo.pbin) + "\nTrackBin\t" + std::to_string(vtrack_bin) + "\nMinCount\t" + std::to_string(vo.min_count) + "\nHotspotRatio\t";
+        put_num(vs, vo.hotspot_ratio);
+        vs += "\nTotal\t" + std::to_string(vi.total) + "\nLinks\t" + std::to_string(vi.links) + "\nMinLoop\t" + std::to_string(vi.min_loop) + "\nLinksKept\t" + std::to_string(vi.links_kept) +
+              "\nViewpointBins\t" + std::to_string(vi.viewpoint_bins) + "\nPartnerCells\t" + std::to_string(ti.partner_cells) + "\nPartnerCellsKept\t" + std::to_string(ti.partner_cells_kept) +
+              "\nSkipped\t" + std::to_string(skipped) + "\n";                  // pairs the matrix stage left out: they are absent from the profile
+        if (!write_file(pre + ".viewpoint.bedgraph", bg.data(), bg.size()) || !write_file(pre + ".viewpoint.links", lk.data(), lk.size()) || !write_file(pre + ".partners.bedgraph", pt.data(), pt.size()) ||
+            !write_file(pre + ".viewpoint.stat", vs.data(), vs.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+    }
     std::string bstat, lstat, gstat, istat, astat, pstat, sstat, cstat;
     const uint32_t ni = (uint32_t)ibp.size();
     std::vector<uint64_t> inv;                                                // [ni][nbins] of the resolution at hand
