@@ -13,7 +13,8 @@
 // third-party binary (bin/samtools), which is never run here: parity with it is UNPINNED.  What is checked instead
 // (tests/test_gpu_bam.py): every block inflates with Python's zlib (which verifies CRC-32 and ISIZE), an independent reader
 // written from the specification (tests/bamio.py) gets the input lines back in coordinate order, and every region query
-// through the .bai returns exactly the records a brute-force scan finds.  Conventions that the specification leaves open follow
+// through the .bai returns exactly the records a brute-force scan finds; the records themselves are byte for byte those of an
+// encoder written from the specification (tests/bamdef.py; DESIGN.md "The records, exactly").  Conventions that the specification leaves open follow
 // htslib's documented behaviour: integer tags in the smallest type that holds them (unsigned types for values >= 0), `bin`
 // from [pos, end) with a length of 1 for unmapped reads or empty CIGARs, a mapped read without CIGAR marked unmapped, ties
 // of the sort key (reference, position, strand) in input order, @HD SO:coordinate set in the header of a sorted file.
@@ -117,9 +118,13 @@ __device__ inline int64_t dec_s(const uint8_t* t, uint64_t a, uint64_t b, bool* 
     if (v > (1ull << 62)) { *ok = false; return 0; }
     return neg ? -(int64_t)v : (int64_t)v;
 }
-// decimal floating point text -> float (tags of type f and B:f).  Mantissa of up to 19 digits, power of ten applied in double:
-// exact for every value samtools itself prints with %g (<= 9 significant digits, |exponent| <= 22); beyond that the result can
-// differ from strtof in the last bit.
+// decimal floating point text -> float (tags of type f and B:f).  Mantissa M of up to 19 digits, power of ten E applied in double.
+// Where M < 2^53 and |E| <= 22 (which holds whatever samtools prints with %g up to %.15g at those exponents) both are exact
+// doubles and one multiplication or division gives M * 10^E; that one result is rounded TO ODD (the fma gives the side the exact
+// value lies on), so the rounding to float that follows is the correct rounding of the decimal, ties to even: a double rounded to
+// nearest can land exactly on a float midpoint the decimal only comes close to (967498269e-19 does), and then goes the wrong way.
+// The %.9g print of ANY finite float also comes back as that float (it lies within 5e-10 of it, the nearest midpoint 6e-8 away;
+// the few double roundings cannot bridge that).  Everything else -- more digits, |E| > 22 -- can differ from strtof in the last bit.
 __device__ inline float dec_f(const uint8_t* t, uint64_t a, uint64_t b, bool* ok) {
     bool neg = false;
     if (a < b && (t[a] == '-' || t[a] == '+')) { neg = t[a] == '-'; ++a; }
@@ -147,9 +152,18 @@ __device__ inline float dec_f(const uint8_t* t, uint64_t a, uint64_t b, bool* ok
     double d = (double)m;
     const double p10[] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
     int e = e10;
-    while (e > 22) { d *= 1e22; e -= 22; }
-    while (e < -22) { d /= 1e22; e += 22; }
-    d = e >= 0 ? d * p10[e] : d / p10[-e];
+    if (m < (1ull << 53) && e >= -22 && e <= 22) {
+        const double pw = p10[e >= 0 ? e : -e];
+        double left;                                   // exact value minus d, in sign (exactly zero when d is exact)
+        if (e >= 0) { const double x = d * pw; left = fma(d, pw, -x); d = x; }
+        else { const double q = d / pw; left = fma(-q, pw, d); d = q; }
+        long long bits = __double_as_longlong(d);      // d > 0 here (or m == 0 and left == 0): neighbours are bits +- 1
+        if (left != 0.0 && !(bits & 1ll)) d = __longlong_as_double(bits + (left > 0.0 ? 1ll : -1ll));
+    } else {
+        while (e > 22) { d *= 1e22; e -= 22; }
+        while (e < -22) { d /= 1e22; e += 22; }
+        d = e >= 0 ? d * p10[e] : d / p10[-e];
+    }
     const float f = (float)d;
     return neg ? -f : f;
 }

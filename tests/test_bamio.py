@@ -14,7 +14,11 @@ def bgzf(raw: bytes, level=6) -> bytes:
     return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(d) + 25) + d + struct.pack("<II", zlib.crc32(raw), len(raw)))
 
 
-def test_reader_on_a_hand_made_bam():
+HAND_MADE_SAM = "r001\t99\tref\t7\t30\t8M2I4M1D3M\t=\t37\t39\tTTAGATAAAGGATACTG\t*\tNM:i:1\tXS:i:-300\tRG:Z:grp\tXB:B:S,7,9"
+
+
+def hand_made_raw():
+    """-> (header text, the uncompressed BAM assembled by hand, the length of its one record's body); the record is HAND_MADE_SAM"""
     text = "@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:ref\tLN:45\n"
     raw = b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", 1) + struct.pack("<i", 4) + b"ref\0" + struct.pack("<i", 45)
     # the specification's example read r001 (SAMv1 1.1): 99 ref 7 30 8M2I4M1D3M = 37 39 TTAGATAAAGGATACTG *
@@ -29,15 +33,20 @@ def test_reader_on_a_hand_made_bam():
     body += b"".join(struct.pack("<I", l << 4 | o) for l, o in cigar) + bytes(packed) + b"\xff" * len(seq)
     body += b"NMC\x01" + b"XSs" + struct.pack("<h", -300) + b"RGZgrp\0" + b"XBBS" + struct.pack("<iHH", 2, 7, 9)
     raw += struct.pack("<i", len(body)) + body
+    return text, raw, len(body)
+
+
+def test_reader_on_a_hand_made_bam():
+    text, raw, l_body = hand_made_raw()
     data = bgzf(raw[:50]) + bgzf(raw[50:]) + bamio.EOF_BLOCK
     bam = bamio.Bam(data)
     assert bam.refs == [("ref", 45)] and bam.text == text and len(bam.records) == 1
     v0, v1, r = bam.records[0]
-    assert bam.sam_line(r) == "r001\t99\tref\t7\t30\t8M2I4M1D3M\t=\t37\t39\tTTAGATAAAGGATACTG\t*\tNM:i:1\tXS:i:-300\tRG:Z:grp\tXB:B:S,7,9"
+    assert bam.sam_line(r) == HAND_MADE_SAM
     assert bamio.ref_span(r) == (6, 22)
     # the record starts in the second block
     first_len = len(bgzf(raw[:50]))
-    assert v0 >> 16 == first_len and v0 & 0xFFFF == len(raw) - 50 - 4 - len(body)
+    assert v0 >> 16 == first_len and v0 & 0xFFFF == len(raw) - 50 - 4 - l_body
     with pytest.raises(zlib.error):                                     # a flipped payload bit: zlib's CRC check
         bad = bytearray(data)
         bad[first_len + 30] ^= 1

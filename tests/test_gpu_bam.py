@@ -5,7 +5,8 @@ block and verifies its CRC-32 / ISIZE).  samtools ships with the reference only 
 parity with samtools' exact bytes is UNPINNED; what is pinned: the decoded records equal the input lines, the order is
 (reference id, position, strand) with ties in input order, the header carries the @SQ dictionary and SO:coordinate, integer
 tags use the smallest type, `bin` is reg2bin of the alignment, every query through the .bai finds the records a scan finds,
-and the .bai is byte for byte the index that DESIGN.md defines ("The index, exactly"; built independently by tests/baidef.py)."""
+the .bai is byte for byte the index that DESIGN.md defines ("The index, exactly"; built independently by tests/baidef.py), and the
+inflated stream -- header and every record -- is byte for byte what tests/bamdef.py encodes from the same text ("The records, exactly")."""
 import os
 import random
 import subprocess
@@ -13,6 +14,7 @@ import subprocess
 import pytest
 
 import baidef
+import bamdef
 import bamio
 import util
 
@@ -78,8 +80,34 @@ def check_index_loose(bam, bai_bytes):
                 assert w < len(lin) and lin[w] <= v0
 
 
+def check_records_exact(sam_header: bytes, body: bytes, bam_bytes: bytes, sorted_=True, ignore=()):
+    """the inflated blocks, joined, are exactly the definition's stream (tests/bamdef.py); on a difference: which record, which field"""
+    got = b"".join(raw for _, _, raw in bamio.bgzf_blocks(bam_bytes))
+    header, lines = bamdef.split_sam(sam_header + body)
+    assert header == sam_header
+    if ignore or got != bamdef.stream_bytes(header, lines, sorted_):
+        msg = bamdef.explain(got, header, lines, sorted_, ignore)
+        assert msg == "", msg
+
+
 def check_bam(sam_header: bytes, body: bytes, bam_bytes: bytes, bai_bytes: bytes, nrec, sorted_=True, order=None, lens=None):
     """lens: the references' LN where they are not the 250 Mb of header_for"""
+    bam = check_records_decoded(sam_header, body, bam_bytes, nrec, sorted_, order, lens)
+    # ... and the records are exactly the ones DESIGN.md defines ("The records, exactly"), byte for byte
+    check_records_exact(sam_header, body, bam_bytes, sorted_)
+    if not sorted_:
+        assert bai_bytes == b""
+        return bam
+    check_index_loose(bam, bai_bytes)
+    # ... and the index is exactly the one DESIGN.md defines ("The index, exactly"), byte for byte
+    want = baidef.bai_definition(bam)
+    assert baidef.bai_bytes(want) == bai_bytes, baidef.explain(bai_bytes, want)
+    return bam
+
+
+def check_records_decoded(sam_header: bytes, body: bytes, bam_bytes: bytes, nrec, sorted_=True, order=None, lens=None):
+    """What the independent reader gets back, compared as SAM text (floats in %g form, SEQ in upper case).  Many wrong record streams
+    pass this: see tests/test_bamdef_host.py; check_bam adds the exact comparison."""
     bam = bamio.Bam(bam_bytes)
     lines = [ln for ln in body.decode().split("\n") if ln]
     assert nrec == len(lines) == len(bam.records)
@@ -101,13 +129,6 @@ def check_bam(sam_header: bytes, body: bytes, bam_bytes: bytes, bai_bytes: bytes
         for tag, ty, v in r["tags"]:
             if ty in "cCsSiI":
                 assert ty == bamio.expected_int_type(v), (tag, ty, v)
-    if not sorted_:
-        assert bai_bytes == b""
-        return bam
-    check_index_loose(bam, bai_bytes)
-    # ... and the index is exactly the one DESIGN.md defines ("The index, exactly"), byte for byte
-    want = baidef.bai_definition(bam)
-    assert baidef.bai_bytes(want) == bai_bytes, baidef.explain(bai_bytes, want)
     return bam
 
 
