@@ -308,8 +308,9 @@ int mkt_bam_stats(const mkt_bam* b, uint64_t stats[5] /* runs, temporary bytes w
 int mkt_group_count(mkt_ctx* ctx, uint64_t* groups);
 
 /* ---- pairs -> binned contact matrix at several resolutions (the driver's last stage, microcket:520-554) -------------------
- * What `juicer_tools pre -r ...` and `cooler cload pairix` spend their time on: the sparse binned matrix.  The containers they
- * write (.hic, .cool) and zoomify are out of scope; parity with those tools is unpinned.  Bin drop-in: bin/pairs2matrix.
+ * What `juicer_tools pre -r ...` and `cooler cload pairix` spend their time on: the sparse binned matrix.  The .hic container is
+ * defined at the end of this file, behind mkt_matrix_hic; the .cool container and zoomify are out of scope; parity with those tools
+ * is unpinned.  Bin drop-in: bin/pairs2matrix.
  * Balancing (iterative correction) of each resolution's matrix is defined below, behind mkt_matrix_balance, and the expected
  * (distance decay) tables and observed / expected values behind mkt_matrix_expected.
  *
@@ -370,7 +371,7 @@ int mkt_matrix_timing(const mkt_matrix* m, uint32_t res_index, double* ms);
  *     m /= mean; m[m == 0] = 1; bias /= m; var < tol: converged, stop.
  *  5. weight = bias / sqrt(mean) with the last mean; bins with bias == 0 get NaN.  iterations = the last it, scale = the last mean,
  *     masked = the number of NaN weights.  The balanced value of a cell is count * weight[bin1] * weight[bin2].
- * Out of scope: cis_only / trans_only (per-chromosome loops), KR / VC vectors, the .cool / .hic containers.  What follows the
+ * Out of scope: cis_only / trans_only (per-chromosome loops), KR / VC vectors, the .cool container.  What follows the
  * weights (expected tables, balanced and observed / expected values of the cells) is defined below, behind mkt_matrix_expected; a
  * per-cell TEXT dump of those values stays out of scope.
  *
@@ -457,7 +458,7 @@ int mkt_matrix_balance_timing(const mkt_matrix* m, uint32_t res_index, double* s
  *   mkt_matrix_expected_timing        device time (ms, HIP events) of the last mkt_matrix_expected of res_index: the one-time grouping of
  *                                     the cells by segment (12 bytes per cell, kept until the next run; 0 when it was reused) and the
  *                                     sums (validity bits, n_valid, the segment sums).  A bad index is MKT_E_ARG without a message.
- * Out of scope: a per-cell text dump, per-chromosome smoothing, the .hic / .cool containers.
+ * Out of scope: a per-cell text dump, per-chromosome smoothing, the .cool container.
  * Limit: bits of (nbins + trans rows) + bits of the cell count <= 64 (MKT_E_CAPACITY with a message). */
 typedef struct mkt_expected_opts { int32_t use_weights; uint32_t reserved; /* 0 */ } mkt_expected_opts;
 typedef struct mkt_expected_info { uint64_t cis_rows, trans_rows, genome_rows; uint32_t n_chrom, smooth_groups; } mkt_expected_info;
@@ -986,6 +987,67 @@ int mkt_matrix_fetch_viewpoint_links(mkt_matrix* m, uint64_t first, uint64_t n, 
 int mkt_matrix_fetch_viewpoint_track(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* count);
 int mkt_matrix_fetch_viewpoint_partners(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* chrom, uint32_t* pbin, uint32_t* count);
 int mkt_matrix_viewpoint_timing(const mkt_matrix* m, double* scan_ms, double* sort_ms);
+
+/* ---- the .hic container: every resolution of the object in one file (the driver's `juicer_tools pre ... $sid.hic`, microcket:529) ----------
+ * The file definition is this project's own, modelled on hic format version 8; tests/hicdef.py restates it in pure Python (struct and
+ * zlib only: a builder and a parser that accounts for every byte).  PARITY with juicer_tools, straw and Juicebox is UNPINNED: none of them
+ * is run.  All integers are little-endian; "string" is bytes followed by a NUL.
+ *
+ * HEADER   "HIC\0" | int32 version = 8 | int64 footerPosition | string genomeId | int32 nAttributes = 1: string "software", string
+ *          "microcket-mi355x" | int32 nChrs, per chromosome of the table in file order: string name, int32 length | int32 nBpRes, the
+ *          object's bin sizes in DESCENDING order (zoom index = position in this list; the same bin size twice is MKT_E_ARG) |
+ *          int32 nFragRes = 0.  DEVIATION: the ALL pseudo-chromosome and its whole-genome matrix are NOT written, so chromosome index k is
+ *          table index k.
+ * BODY     for every chromosome pair c1 <= c2 (table index) with at least one cell at ANY resolution, ascending in (c1, c2), a matrix
+ *          record: int32 c1, int32 c2, int32 nRes (every resolution, also one without cells), per resolution in header order:
+ *          string "BP" | int32 zoomIndex | float32 sumCounts (the exact integer sum of the pair's counts at this resolution, converted
+ *          once, round to nearest even) | float32 0, 0, 0 (occupied cells, stddev, percent95: not computed) | int32 binSize | int32
+ *          blockBinCount bb | int32 blockColumnCount = max(L_c1, L_c2) / binSize / bb + 1 (integer divisions) | int32 blockCount | per
+ *          non-empty block, ascending blockNumber: int32 blockNumber, int64 position, int32 sizeBytes.
+ *          The blocks of the matrix follow its record immediately, in the order of the index (resolution by resolution).
+ * BLOCK    a cell (bin1, bin2) of the genome-wide matrix has x = bin1 - off_c1, y = bin2 - off_c2 (cis: x <= y);
+ *          blockNumber = (y / bb) * blockColumnCount + x / bb.  Payload: int32 nRecords | int32 xOff = (x / bb) * bb | int32 yOff =
+ *          (y / bb) * bb | uint8 useShort (1 if and only if every count of the block is <= 32767) | uint8 matrixType = 1 (list of rows; the
+ *          dense type 2 is never written) | int16 rowCount | per distinct y, ascending: int16 y - yOff, int16 recordCount, and per record
+ *          of the row, ascending x: int16 x - xOff, then int16 count (useShort) or float32 count (round to nearest even).
+ *          On disk a block is one zlib stream (RFC 1950) of the payload: 78 9C, the payload cut into pieces of at most 65280 bytes, each
+ *          piece deflate block(s) with BFINAL = 0 that end on a byte (a coded piece is closed by an empty stored block 000, padding,
+ *          00 00 FF FF; a piece that does not shrink is one stored block), then 03 00 and the Adler-32, big-endian.  level: 0 stored
+ *          pieces, 1 fixed codes, 2 codes built per piece (the LZ77 + Huffman stage of mkt_bam, the same greedy one-pass parse).
+ * FOOTER   at footerPosition: int32 nBytes (the bytes of the footer behind this field: everything up to the end of the vector index, the
+ *          vectors themselves not counted) | int32 nEntries, per matrix record: string "c1_c2" (decimal), int64 position, int32 size
+ *          (record plus its blocks) | int32 nExpectedValueVectors = 0 | int32 nNormExpectedValueVectors = 0 | int32 nNormVectors, per
+ *          vector: string type (norm_label) | int32 chrIdx | string "BP" | int32 binSize | int64 position | int32 nBytes.
+ * VECTORS  behind the index, in its order: int32 nValues = n_i, float64 values.  With norm = 1 every resolution that holds balancing weights
+ *          when mkt_matrix_hic is called gets one vector per chromosome (resolutions in header order, chromosomes in table order).  .hic
+ *          vectors DIVIDE: v = 1 / w, one IEEE division; the NaN 0x7FF8000000000000 where the weight is NaN (a masked bin).  Expected-value
+ *          vectors are not written.
+ * Nothing lies between these parts and the file ends with the last vector (or the index).  The bytes depend on the multiset of pairs,
+ * the weights and the options only.
+ * Limits: block_bins 1 .. 32767 (MKT_E_ARG); chromosome lengths below 2^31, block numbers below 2^31, a deflated block, a matrix record
+ * with its blocks and a vector below 2^31 bytes (MKT_E_CAPACITY); always with a message, never a truncated file.
+ *
+ *   mkt_hic_opts_default    block_bins 1000, level 2, norm 1, genome_id NULL (""), norm_label NULL ("ICE")
+ *   mkt_matrix_hic          opts NULL = the defaults; info may be NULL.  MKT_E_STATE "hic before run" before mkt_matrix_run.  The file stays
+ *                           in device memory until the next add or run; a later balance does not change it.
+ *   mkt_matrix_fetch_hic    bytes [off, off + n) of the file; MKT_E_ARG with a message for a range past its end
+ *   mkt_matrix_hic_timing   of the last mkt_matrix_hic, per resolution index of the object (ms, HIP events): the sort with the head flags
+ *                           and their scan; tables, sizes and serialisation; deflate; placing the streams in the file */
+typedef struct mkt_hic_opts {
+    const char* genome_id;
+    const char* norm_label;
+    uint32_t block_bins;
+    int32_t level, norm;
+    uint32_t reserved;                    /* 0 */
+} mkt_hic_opts;
+typedef struct mkt_hic_info {
+    uint64_t file_bytes, matrices, blocks, float_blocks, pieces;
+    uint64_t raw_bytes, deflated_bytes;   /* the payloads; their zlib streams */
+} mkt_hic_info;
+void mkt_hic_opts_default(mkt_hic_opts* o);
+int mkt_matrix_hic(mkt_matrix* m, const mkt_hic_opts* opts, mkt_hic_info* info);
+int mkt_matrix_fetch_hic(mkt_matrix* m, uint64_t off, char* out, size_t n);
+int mkt_matrix_hic_timing(const mkt_matrix* m, uint32_t res_index, double* sort_ms, double* serialise_ms, double* deflate_ms, double* pack_ms);
 
 #ifdef __cplusplus
 }

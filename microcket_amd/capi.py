@@ -37,6 +37,7 @@ EXPORTS = [
     "mkt_scc_opts_default", "mkt_matrix_scc", "mkt_matrix_fetch_scc_strata", "mkt_matrix_fetch_scc_chrom", "mkt_matrix_scc_timing",
     "mkt_viewpoint_opts_default", "mkt_matrix_viewpoint", "mkt_matrix_fetch_viewpoint_links", "mkt_matrix_fetch_viewpoint_track",
     "mkt_matrix_fetch_viewpoint_partners", "mkt_matrix_viewpoint_timing",
+    "mkt_hic_opts_default", "mkt_matrix_hic", "mkt_matrix_fetch_hic", "mkt_matrix_hic_timing",
 ]
 
 
@@ -197,6 +198,15 @@ class ViewpointOpts(C.Structure):
     """mkt_viewpoint_opts of include/mkt.h"""
     _fields_ = [("partner_mask", C.c_void_p), ("hotspot_ratio", C.c_double)] + [(k, C.c_uint32) for k in ("viewpoint", "vbin", "pbin", "min_count")] + \
                [("origin", C.c_int32), ("second_side_only", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class HicOpts(C.Structure):
+    """mkt_hic_opts of include/mkt.h"""
+    _fields_ = [("genome_id", C.c_char_p), ("norm_label", C.c_char_p), ("block_bins", C.c_uint32), ("level", C.c_int32), ("norm", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class _HicInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("file_bytes", "matrices", "blocks", "float_blocks", "pieces", "raw_bytes", "deflated_bytes")]
 
 
 class _ViewpointInfoC(C.Structure):
@@ -419,6 +429,11 @@ def load_library():
     L.mkt_matrix_fetch_viewpoint_track.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
     L.mkt_matrix_fetch_viewpoint_partners.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3
     L.mkt_matrix_viewpoint_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_hic_opts_default.argtypes = [C.POINTER(HicOpts)]
+    L.mkt_hic_opts_default.restype = None
+    L.mkt_matrix_hic.argtypes = [C.c_void_p, C.POINTER(HicOpts), C.POINTER(_HicInfoC)]
+    L.mkt_matrix_fetch_hic.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_matrix_hic_timing.argtypes = [C.c_void_p, C.c_uint32] + [C.POINTER(C.c_double)] * 4
     _lib = L
     return L
 
@@ -1236,6 +1251,52 @@ class Matrix:
         a, b = C.c_double(), C.c_double()
         self._chk(self.L.mkt_matrix_viewpoint_timing(self.h, C.byref(a), C.byref(b)), "mkt_matrix_viewpoint_timing")
         return a.value, b.value
+
+    def hic(self, **opts):
+        """The .hic container of every resolution (and, with norm, of the weights the balanced ones hold): mkt_matrix_hic in
+        include/mkt.h.  opts: block_bins, level, norm, genome_id, norm_label (str or bytes).  Returns the info as a dict."""
+        o = HicOpts()
+        self.L.mkt_hic_opts_default(C.byref(o))
+        for k, v in opts.items():
+            if k not in ("block_bins", "level", "norm", "genome_id", "norm_label"):
+                raise TypeError(f"hic: unknown option {k}")
+            if k in ("genome_id", "norm_label"):
+                v = v.encode() if isinstance(v, str) else v
+            elif k == "norm":
+                v = 1 if v is True else 0 if v is False else v
+            setattr(o, k, v)
+        info = _HicInfoC()
+        self._chk(self.L.mkt_matrix_hic(self.h, C.byref(o), C.byref(info)), "mkt_matrix_hic")
+        self._hic_bytes = info.file_bytes
+        return {k: getattr(info, k) for k, _ in _HicInfoC._fields_}
+
+    def hic_bytes(self):
+        """the file of the last hic(), as made on the device"""
+        self._chk(self.L.mkt_matrix_fetch_hic(self.h, 0, None, 0), "mkt_matrix_fetch_hic")
+        n = getattr(self, "_hic_bytes", None)
+        if n is None:
+            raise MktError("hic_bytes: the file was not made through hic()")
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_matrix_fetch_hic(self.h, 0, buf, n), "mkt_matrix_fetch_hic")
+        return buf.raw[:n]
+
+    def write_hic(self, path, **opts):
+        """hic(**opts), then the file to `path` in pieces of 64 MiB; returns the info"""
+        info = self.hic(**opts)
+        n, step = info["file_bytes"], 64 << 20
+        buf = C.create_string_buffer(min(step, max(n, 1)))
+        with open(path, "wb") as f:
+            for off in range(0, n, step):
+                k = min(step, n - off)
+                self._chk(self.L.mkt_matrix_fetch_hic(self.h, off, buf, k), "mkt_matrix_fetch_hic")
+                f.write(buf.raw[:k])
+        return info
+
+    def hic_timing_ms(self, res):
+        """(sort, serialise, deflate, pack) ms on the device of resolution index res in the last hic()"""
+        t = [C.c_double() for _ in range(4)]
+        self._chk(self.L.mkt_matrix_hic_timing(self.h, res, *[C.byref(x) for x in t]), "mkt_matrix_hic_timing")
+        return tuple(x.value for x in t)
 
     def close(self):
         if self.h:

@@ -36,6 +36,7 @@
 #include "mkt_deflate_codes.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
+#include "mkt_zstream.h"
 
 using namespace mkt;
 
@@ -419,6 +420,33 @@ __device__ inline uint32_t block_crc(const uint8_t* src, uint32_t n, const uint3
     __syncthreads();
     return r;
 }
+// block-wide Adler-32 (RFC 1950) of n <= 65 280 bytes at src, from the state (1, 0): slices of ceil(n / NTH) bytes; a slice [s, e) gives
+// a = sum d_i and b = sum (e - i) d_i, and the whole is A = 1 + sum a, B = n + sum (b + (n - e) a), both mod 65521.  Integer sums in a
+// fixed tree: the value does not depend on the order anything ran in.
+template <int NTH>
+__device__ inline uint32_t block_adler(const uint8_t* src, uint32_t n, uint32_t* sh /* [NTH / 64] */) {
+    const uint32_t per = (n + NTH - 1) / NTH;                 // <= 256 bytes for NTH >= 256: a < 2^16, b < 2^24
+    const uint32_t s = threadIdx.x * per < n ? threadIdx.x * per : n, e = s + per < n ? s + per : n;
+    uint32_t a = 0, b = 0;
+    for (uint32_t i = s; i < e; ++i) { a += src[i]; b += a; }
+    uint32_t tb = (uint32_t)(((uint64_t)b + (uint64_t)(n - e) * a) % 65521u);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { a += (uint32_t)__shfl_xor((int)a, d, 64); tb += (uint32_t)__shfl_xor((int)tb, d, 64); }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+    __syncthreads();
+    uint32_t A = 1;
+#pragma unroll
+    for (int w = 0; w < NTH / 64; ++w) A += sh[w];
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = tb;
+    __syncthreads();
+    uint32_t Bs = n;
+#pragma unroll
+    for (int w = 0; w < NTH / 64; ++w) Bs += sh[w];
+    __syncthreads();
+    return ((Bs % 65521u) << 16) | (A % 65521u);
+}
 __device__ inline void bgzf_header(uint8_t* o, uint32_t bsize_minus1) {     // SAMv1 4.1
     const uint8_t h[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0};
     for (int i = 0; i < 16; ++i) o[i] = h[i];
@@ -491,9 +519,13 @@ struct BitSink {                                         // one lane appends bit
     }
 };
 
-template <bool DYN>
+// Two framings of the same parse and coder.  ZS = false: a self-contained BGZF member per block of BGZF_RAW bytes (BFINAL = 1, gzip
+// header, CRC-32 and size behind it).  ZS = true: a PIECE of a zlib stream (mkt_zstream.h): block `blk` is the piece zp.off[blk],
+// zp.len[blk] of raw; its deflate block has BFINAL = 0 and is followed by an empty stored block (000, padding, 00 00 FF FF), so that the
+// piece ends on a byte and pieces can be joined by copying; no header, the piece's Adler-32 goes to zp.adler[blk].
+template <bool DYN, bool ZS>
 __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw, uint64_t nraw, uint64_t first_block, const CrcTabs* ct, uint8_t* comp, uint64_t* csize,
-                                                             uint32_t* scratch /* per block of the launch: DZ_WAVES * DZ_WAVE_SCRATCH words */) {
+                                                             uint32_t* scratch /* per block of the launch: DZ_WAVES * DZ_WAVE_SCRATCH words */, ZsPieces zp) {
     __shared__ __attribute__((aligned(16))) uint32_t in32[(BGZF_RAW + 288) / 4];      // + what a length measurement reads past the end
     __shared__ uint32_t htab[DZ_WAVES][1u << DZ_HBITS];
     __shared__ uint32_t stage_[DZ_WAVES][DZ_STAGE];
@@ -512,13 +544,13 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
         return __builtin_amdgcn_alignbyte(in32[i + 1], in32[i], off & 3u);
     };
     volatile uint32_t (*stage)[DZ_STAGE] = stage_;       // lanes of a wave hand bits to each other through it
-    if (tid < 256) tabl[tid] = ct->t[tid];
-    if (tid < 32) { x2n[tid] = ct->x2n[tid]; d_hist[tid] = 0; }
+    if (!ZS && tid < 256) tabl[tid] = ct->t[tid];
+    if (tid < 32) { if (!ZS) x2n[tid] = ct->x2n[tid]; d_hist[tid] = 0; }
     if (tid < 288) ll_hist[tid] = 0;
     for (int i = tid; i < DZ_HDRW; i += DZ_THREADS) hdrw[i] = 0;
     const uint64_t blk = first_block + blockIdx.x;
-    const uint64_t b0 = blk * BGZF_RAW;
-    const uint32_t n = (uint32_t)(nraw - b0 < BGZF_RAW ? nraw - b0 : BGZF_RAW);
+    const uint64_t b0 = ZS ? zp.off[blk] : blk * BGZF_RAW;
+    const uint32_t n = ZS ? zp.len[blk] : (uint32_t)(nraw - b0 < BGZF_RAW ? nraw - b0 : BGZF_RAW);
     {   // the block into LDS, 16 bytes per load (blocks start on multiples of 16; the raw buffer is readable 64 bytes past its end,
         // and what lies behind byte n is never looked at)
         const uint4* src = reinterpret_cast<const uint4*>(raw + b0);
@@ -527,7 +559,7 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
     }
     for (uint32_t i = lane; i < (1u << DZ_HBITS); i += 64) htab[wv][i] = 0;          // 0 = empty (positions are stored + 1)
     __syncthreads();
-    const uint32_t crc = block_crc<DZ_THREADS>(in, n, tabl, x2n, sh);
+    const uint32_t crc = ZS ? block_adler<DZ_THREADS>(in, n, sh) : block_crc<DZ_THREADS>(in, n, tabl, x2n, sh);       // (ZS: the piece's Adler-32)
     // ---- pass 1: this wave's share -> tokens (a literal byte, or 1 << 31 | length - 3 << 16 | distance - 1)
     const uint32_t q0 = wv * DZ_Q < n ? wv * DZ_Q : n, q1 = q0 + DZ_Q < n ? q0 + DZ_Q : n;
     uint32_t* wtok = scratch + ((uint64_t)blockIdx.x * DZ_WAVES + wv) * DZ_WAVE_SCRATCH;
@@ -620,7 +652,7 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
             ll_tab[s] = code | (nb << 16);
         }
         if (tid < 32) d_tab[tid] = bitrev((uint32_t)tid, 5) | (5u << 16);
-        if (tid == 0) hdrw[0] = 3u;                          // BFINAL = 1, BTYPE = 01
+        if (tid == 0) hdrw[0] = ZS ? 2u : 3u;                // BFINAL = 1 (ZS: 0), BTYPE = 01
         __syncthreads();
     } else {
         if (tid == 0) {
@@ -694,7 +726,7 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
             int nclc = 19;
             while (nclc > 4 && !(ctab[order[nclc - 1]] >> 16)) --nclc;
             BitSink B{hdrw, 0};
-            B.put(5u, 3);                                    // BFINAL = 1, BTYPE = 10
+            B.put(ZS ? 4u : 5u, 3);                          // BFINAL = 1 (ZS: 0), BTYPE = 10
             B.put((uint32_t)(nll - 257), 5); B.put((uint32_t)(nd - 1), 5); B.put((uint32_t)(nclc - 4), 4);
             for (int i = 0; i < nclc; ++i) B.put(ctab[order[i]] >> 16, 3);
             for (int i = 0; i < ncl; ++i) {
@@ -758,7 +790,7 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
         __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0) { ws[wpos] = stage[wv][0]; wbits[1 + wv] = wpos * 32u + carry_bits; }
-    if (tid == 0) { wbits[0] = hdr_bits; wbits[DZ_WAVES + 1] = ll_tab[256] >> 16; }
+    if (tid == 0) { wbits[0] = hdr_bits; wbits[DZ_WAVES + 1] = (ll_tab[256] >> 16) + (ZS ? 3u : 0u); }       // (ZS: + the 000 of the empty stored block)
     __threadfence_block();
     __syncthreads();
     // ---- join: header, the waves' streams in order, the end-of-block code
@@ -767,7 +799,16 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
     const uint32_t total_bits = woff[DZ_WAVES + 2];
     const uint32_t cbytes = (total_bits + 7u) >> 3;
     uint8_t* o = comp + blk * BGZF_STRIDE;
-    if (cbytes >= n + 5u) {                               // did not shrink: stored
+    constexpr uint32_t HDR = ZS ? 0u : 18u;              // bytes in front of the deflate data
+    if (ZS && cbytes + 4u >= n + 5u) {                    // did not shrink: one stored block, BFINAL = 0
+        if (tid == 0) {
+            o[0] = 0; o[1] = (uint8_t)n; o[2] = (uint8_t)(n >> 8); o[3] = (uint8_t)~n; o[4] = (uint8_t)(~n >> 8);
+            csize[blk] = n + 5u; zp.adler[blk] = crc;
+        }
+        for (uint32_t i = tid; i < n; i += DZ_THREADS) o[5 + i] = in[i];
+        return;
+    }
+    if (!ZS && cbytes >= n + 5u) {                        // did not shrink: stored
         const uint32_t total = 18 + 5 + n + 8;
         if (tid == 0) {
             bgzf_header(o, total - 1);
@@ -810,12 +851,20 @@ __global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw,
             }
             word |= v;
         }
-        uint8_t* d = o + 18 + 4u * k;
+        uint8_t* d = o + HDR + 4u * k;
         const uint32_t left = cbytes - 4u * k;
         d[0] = (uint8_t)word;
         if (left > 1) d[1] = (uint8_t)(word >> 8);
         if (left > 2) d[2] = (uint8_t)(word >> 16);
         if (left > 3) d[3] = (uint8_t)(word >> 24);
+    }
+    if (ZS) {
+        if (tid == 0) {
+            uint8_t* e = o + cbytes;
+            e[0] = 0; e[1] = 0; e[2] = 0xFF; e[3] = 0xFF;       // LEN = 0, NLEN of the empty stored block
+            csize[blk] = cbytes + 4u; zp.adler[blk] = crc;
+        }
+        return;
     }
     if (tid == 0) {
         const uint32_t total = 18 + cbytes + 8;
@@ -1341,13 +1390,46 @@ static void bgzf_launch(const uint8_t* raw, uint64_t nraw, uint64_t nblocks, int
     if (level > 0) {
         for (uint64_t fb = 0; fb < nblocks; fb += batch) {
             const unsigned g = (unsigned)(nblocks - fb < batch ? nblocks - fb : batch);
-            if (level >= 2) hipLaunchKernelGGL(k_bgzf_deflate<true>, dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch);
-            else hipLaunchKernelGGL(k_bgzf_deflate<false>, dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch);
+            if (level >= 2) hipLaunchKernelGGL((k_bgzf_deflate<true, false>), dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch, ZsPieces{});
+            else hipLaunchKernelGGL((k_bgzf_deflate<false, false>), dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch, ZsPieces{});
         }
     } else {
         hipLaunchKernelGGL(k_bgzf_stored, dim3((unsigned)nblocks), dim3(BWG), 0, st, raw, nraw, ct, comp, csize);
     }
 }
+
+// ---- the stream framing (mkt_zstream.h): the same kernels over a piece table
+namespace mkt {
+// level 0: one stored deflate block (BFINAL = 0) per piece
+__global__ __launch_bounds__(BWG) void k_zs_stored(const uint8_t* raw, ZsPieces zp, uint8_t* comp, uint64_t* csize) {
+    __shared__ uint32_t sh[BWG / 64];
+    const uint64_t p = blockIdx.x;
+    const uint8_t* src = raw + zp.off[p];
+    const uint32_t n = zp.len[p];
+    uint8_t* o = comp + p * kZsStride;
+    const uint32_t ad = block_adler<BWG>(src, n, sh);
+    if (threadIdx.x == 0) {
+        o[0] = 0; o[1] = (uint8_t)n; o[2] = (uint8_t)(n >> 8); o[3] = (uint8_t)~n; o[4] = (uint8_t)(~n >> 8);
+        csize[p] = n + 5u; zp.adler[p] = ad;
+    }
+    for (uint32_t i = threadIdx.x; i < n; i += BWG) o[5 + i] = src[i];
+}
+static_assert(kZsPiece == BGZF_RAW && kZsStride == BGZF_STRIDE, "a piece is what the deflate kernel takes as a block");
+size_t zs_scratch_bytes(uint64_t batch) { return (size_t)(batch * kDzPerBlock); }
+hipError_t zs_deflate(const uint8_t* raw, ZsPieces zp, uint64_t npieces, int level, uint8_t* comp, uint64_t* csize, uint32_t* scratch, uint64_t batch, hipStream_t st) {
+    if (npieces == 0) return hipSuccess;
+    if (level <= 0) hipLaunchKernelGGL(k_zs_stored, dim3((unsigned)npieces), dim3(BWG), 0, st, raw, zp, comp, csize);
+    else {
+        if (!scratch || batch == 0) return hipErrorInvalidValue;
+        for (uint64_t fb = 0; fb < npieces; fb += batch) {
+            const unsigned g = (unsigned)(npieces - fb < batch ? npieces - fb : batch);
+            if (level >= 2) hipLaunchKernelGGL((k_bgzf_deflate<true, true>), dim3(g), dim3(DZ_THREADS), 0, st, raw, (uint64_t)0, fb, (const CrcTabs*)nullptr, comp, csize, scratch, zp);
+            else hipLaunchKernelGGL((k_bgzf_deflate<false, true>), dim3(g), dim3(DZ_THREADS), 0, st, raw, (uint64_t)0, fb, (const CrcTabs*)nullptr, comp, csize, scratch, zp);
+        }
+    }
+    return hipGetLastError();
+}
+}  // namespace mkt
 
 // ---- the steps of a conversion: the single pass and the out-of-core mode both go through these -------------------------------
 // compress nblocks blocks of raw; csize becomes the blocks' compressed offsets, csize[nblocks] and (after a synchronisation)

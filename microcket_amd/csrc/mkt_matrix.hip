@@ -1,5 +1,5 @@
 // mkt_matrix.hip -- the last stage of the driver (microcket:520-554): reported pairs -> a binned contact matrix at several
-// resolutions, on the GPU.  The containers the driver's tools write (.hic, .cool) are out of scope; what is computed here is what
+// resolutions, on the GPU.  The .hic container is written by mkt_hic.hip from the cells made here; .cool is out of scope; what is computed here is what
 // they spend their time on, the sparse upper-triangle matrix, handed back as arrays and as the COO text `cooler load -f coo` reads.
 //
 // Definition (include/mkt.h has it in full): chromosome i of length L_i owns ceil(L_i / r) bins in table order; a pair
@@ -33,6 +33,7 @@
 #include "mkt_saddle.h"
 #include "mkt_scc.h"
 #include "mkt_viewpoint.h"
+#include "mkt_hic.h"
 #include "mkt_rle.h"
 #include "mkt_launch.h"
 #include "mkt_layout.h"
@@ -326,6 +327,7 @@ struct mkt_matrix {
     uint64_t pairs = 0, skipped = 0;
     std::vector<MxRes> res;
     VpState vp;                                     // viewpoint profiles (mkt_matrix_viewpoint): the results live until the next add or run
+    HicState hic;                                   // the .hic file (mkt_matrix_hic): the image lives until the next add or run
     std::string err;
 };
 
@@ -388,6 +390,7 @@ static void mx_free_results(mkt_matrix* m) {
         r.scc = SccState();
     }
     m->vp = VpState();
+    m->hic = HicState();
     m->ran = false;
 }
 static int mx_reserve_rec(mkt_matrix* m, uint64_t need) {
@@ -594,6 +597,7 @@ void mkt_matrix_destroy(mkt_matrix* m) {
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     m->res.clear();                                                     // every device buffer goes with its owner, before the stream
+    m->hic = HicState();
     m->d_tab.reset(); m->d_counters.reset(); m->d_rec.reset(); m->d_text.reset();
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
@@ -1624,6 +1628,66 @@ int mkt_matrix_viewpoint_timing(const mkt_matrix* m, double* scan_ms, double* so
     const bool have = m->ran && m->vp.built;
     if (scan_ms) *scan_ms = have ? m->vp.scan_ms : 0.0;
     if (sort_ms) *sort_ms = have ? m->vp.sort_ms : 0.0;
+    return MKT_OK;
+}
+
+// ---- the .hic container: the entry points; the device side and the file layout are mkt_hic.hip, the definition is in include/mkt.h --------
+void mkt_hic_opts_default(mkt_hic_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->block_bins = 1000; o->level = 2; o->norm = 1;
+}
+
+int mkt_matrix_hic(mkt_matrix* m, const mkt_hic_opts* opts, mkt_hic_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    mkt_hic_opts o;
+    mkt_hic_opts_default(&o);
+    if (opts) o = *opts;
+    if (o.block_bins < 1 || o.block_bins > kHicBlockBinsMax) return mfail(m, MKT_E_ARG, "hic: block_bins %u (1 .. %u: block coordinates are int16)", o.block_bins, kHicBlockBinsMax);
+    if (o.level < 0 || o.level > 2) return mfail(m, MKT_E_ARG, "hic: level %d (0 stored, 1 fixed codes, 2 dynamic codes)", o.level);
+    if (o.norm != 0 && o.norm != 1) return mfail(m, MKT_E_ARG, "hic: norm %d (0 or 1)", o.norm);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "hic: the reserved field is not 0");
+    if (o.norm_label && !*o.norm_label) return mfail(m, MKT_E_ARG, "hic: an empty norm_label");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "hic before run");
+    MCHK(m, hipSetDevice(m->device));
+    std::vector<HicResIn> in(m->res.size());
+    for (size_t k = 0; k < m->res.size(); ++k) {
+        MxRes& r = m->res[k];
+        if (r.nnz) MX(m, "hic: ", layout_chr(r.lay, mx_cells(r), m->stream));
+        in[k].cells = mx_cells(r);
+        in[k].chr = r.nnz ? r.lay.chr.get() : nullptr;
+        in[k].off = &r.off;
+        in[k].bin_size = r.r;
+        in[k].d_w = r.balanced ? r.d_w.get() : nullptr;
+    }
+    HicState hs;                                                        // a refused or failed call leaves the previous file alone
+    std::string why;
+    const int rc = hic_build(hs, in, m->names, m->lens, o, m->stream, &why);
+    if (rc != MKT_OK) return mfail(m, rc, "%s", why.c_str());
+    m->hic = std::move(hs);
+    if (info) *info = m->hic.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_hic(mkt_matrix* m, uint64_t off, char* out, size_t n) {
+    if (!m || (n && !out)) return MKT_E_ARG;
+    if (!(m->ran && m->hic.built)) return mfail(m, MKT_E_STATE, "no .hic file: hic first");
+    const uint64_t fb = m->hic.info.file_bytes;
+    if (off > fb || n > fb - off) return mfail(m, MKT_E_ARG, "range past the end of the .hic file");
+    MCHK(m, hipSetDevice(m->device));
+    if (n) MCHK(m, hipMemcpy(out, m->hic.image.get() + off, n, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+
+int mkt_matrix_hic_timing(const mkt_matrix* m, uint32_t res_index, double* sort_ms, double* serialise_ms, double* deflate_ms, double* pack_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const bool have = m->ran && m->hic.built && res_index < m->hic.timing.size();
+    const HicTiming t = have ? m->hic.timing[res_index] : HicTiming();
+    if (sort_ms) *sort_ms = t.sort_ms;
+    if (serialise_ms) *serialise_ms = t.serialise_ms;
+    if (deflate_ms) *deflate_ms = t.deflate_ms;
+    if (pack_ms) *pack_ms = t.pack_ms;
     return MKT_OK;
 }
 

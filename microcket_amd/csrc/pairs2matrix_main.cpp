@@ -94,6 +94,11 @@
 // them; without a matching pair the bedgraph is empty where the Perl prints a line of zeros; juicer_tools pre of analyze.EBV.sh is out
 // of scope.  One of --vp-* without --viewpoint or --ebv is a usage error, a bad value, an unknown NAME or an expression that keeps
 // nothing exit 12.  Without the two flags none of these files appears and every other byte is the same.
+// With --hic (mkt_matrix_hic of include/mkt.h) also <prefix>.hic, every resolution in one container (with --balance the weights as
+// normalisation vectors of the label --hic-norm-label, default ICE), and <prefix>.hic.stat (file bytes, matrices, blocks, float blocks,
+// pieces, raw and deflated bytes, level, block bins).  --hic-level 0 .. 2 (default 2), --hic-block-bins 1 .. 32767 (default 1000),
+// --hic-genome ID (default empty).  One of them without --hic is a usage error, a value that is no number exit 12.  Without --hic
+// neither file appears and every other byte is the same.
 // Exit codes: 0 ok, 2 usage, 10 unreadable input or table, 12 bad table / resolution list, 20 no GPU, 21 library error, 22 write failure.
 #include <cerrno>
 #include <cstdio>
@@ -118,7 +123,8 @@ static int usage(const char* me) {
                     "                 [--saddle-min-dist BP] [--saddle-max-dist BP] [--saddle-corner N]]\n"
                     "       [--compare OTHER.pairs [--scc-h N] [--scc-min-dist BP] [--scc-max-dist BP] [--scc-weighting n|var]]\n"
                     "       [--viewpoint NAME | --ebv] [--vp-bin BP] [--vp-partner-bin BP] [--vp-track-bin BP] [--vp-min-count N] [--vp-hotspot R]\n"
-                    "                                  [--vp-partners REGEX] [--vp-second-side]\n", me);
+                    "                                  [--vp-partners REGEX] [--vp-second-side]\n"
+                    "       [--hic [--hic-level N] [--hic-block-bins N] [--hic-genome ID] [--hic-norm-label S]]\n", me);
     return 2;
 }
 static bool read_file(const char* fn, std::string& out) {
@@ -367,6 +373,9 @@ int main(int argc, char* argv[]) {
     bool ebv = false;
     const char* vopt[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // --vp-second-side takes no value: its slot holds the flag itself
     static const char* const vpname[7] = {"--vp-bin", "--vp-partner-bin", "--vp-track-bin", "--vp-min-count", "--vp-hotspot", "--vp-partners", "--vp-second-side"};
+    bool hic = false;                                                         // --hic
+    const char* hopt[4] = {nullptr, nullptr, nullptr, nullptr};
+    static const char* const hname[4] = {"--hic-level", "--hic-block-bins", "--hic-genome", "--hic-norm-label"};
     const char* bopt[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static const char* const bname[6] = {"--ignore-diags", "--min-nnz", "--min-count", "--mad-max", "--tol", "--max-iters"};
     for (int i = 1; i < argc; ++i) {
@@ -386,7 +395,11 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], cname[k])) cm = k;
         int vp = -1;
         for (int k = 0; k < 7; ++k) if (!strcmp(argv[i], vpname[k])) vp = k;
-        if (vp == 6) vopt[6] = argv[i];
+        int hc = -1;
+        for (int k = 0; k < 4; ++k) if (!strcmp(argv[i], hname[k])) hc = k;
+        if (hc >= 0) { if (i + 1 >= argc) return usage(argv[0]); hopt[hc] = argv[++i]; }
+        else if (!strcmp(argv[i], "--hic")) hic = true;
+        else if (vp == 6) vopt[6] = argv[i];
         else if (vp >= 0) { if (i + 1 >= argc) return usage(argv[0]); vopt[vp] = argv[++i]; }
         else if (!strcmp(argv[i], "--viewpoint")) { if (i + 1 >= argc) return usage(argv[0]); vname = argv[++i]; }
         else if (!strcmp(argv[i], "--ebv")) ebv = true;
@@ -414,6 +427,17 @@ int main(int argc, char* argv[]) {
         else files.push_back(argv[i]);
     }
     if (!table || !rlist || !prefix) return usage(argv[0]);
+    mkt_hic_opts ho;
+    mkt_hic_opts_default(&ho);
+    for (int k = 0; k < 4; ++k) {
+        if (!hopt[k]) continue;
+        if (!hic) { fprintf(stderr, "Error: %s needs --hic\n", hname[k]); return usage(argv[0]); }
+        if (k >= 2) { (k == 2 ? ho.genome_id : ho.norm_label) = hopt[k]; continue; }
+        char* end = nullptr;
+        const long v = strtol(hopt[k], &end, 10);
+        if (!*hopt[k] || *end || v < 0 || v > 0x7FFFFFFFl) { fprintf(stderr, "Error: %s %s is not a number\n", hname[k], hopt[k]); return 12; }
+        if (k == 0) ho.level = (int32_t)v; else ho.block_bins = (uint32_t)v;
+    }
     mkt_balance_opts bo;
     mkt_balance_opts_default(&bo);
     for (int k = 0; k < 6; ++k) {
@@ -926,6 +950,22 @@ int main(int argc, char* argv[]) {
         if (balance && !write_file(pre + "." + std::to_string(res[k]) + ".weights.bed", wbed.data(), wbed.size(), wmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (eigs && !write_file(pre + "." + std::to_string(res[k]) + ".eigs.tsv", gbed.data(), gbed.size(), gmode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
         if (ni && !write_file(pre + "." + std::to_string(res[k]) + ".insulation.tsv", ibed.data(), ibed.size(), imode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+    }
+    if (hic) {                                                                // every resolution in one container, with the weights of --balance
+        mkt_hic_info hi;
+        if ((rc = mkt_matrix_hic(m, &ho, &hi)) != MKT_OK) return lib_fail("GPU .hic container");
+        std::vector<char> buf((size_t)std::min<uint64_t>(hi.file_bytes, (uint64_t)64 << 20));
+        const char* mode = "wb";
+        for (uint64_t off = 0; off < hi.file_bytes; off += buf.size()) {
+            const size_t n = (size_t)std::min<uint64_t>(buf.size(), hi.file_bytes - off);
+            if ((rc = mkt_matrix_fetch_hic(m, off, buf.data(), n)) != MKT_OK) return lib_fail("GPU .hic container");
+            if (!write_file(pre + ".hic", buf.data(), n, mode)) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
+            mode = "ab";
+        }
+        const std::string hs = "FileBytes\t" + std::to_string(hi.file_bytes) + "\nMatrices\t" + std::to_string(hi.matrices) + "\nBlocks\t" + std::to_string(hi.blocks) +
+                               "\nFloatBlocks\t" + std::to_string(hi.float_blocks) + "\nPieces\t" + std::to_string(hi.pieces) + "\nRawBytes\t" + std::to_string(hi.raw_bytes) +
+                               "\nDeflatedBytes\t" + std::to_string(hi.deflated_bytes) + "\nLevel\t" + std::to_string(ho.level) + "\nBlockBins\t" + std::to_string(ho.block_bins) + "\n";
+        if (!write_file(pre + ".hic.stat", hs.data(), hs.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     }
     if (cfile && !write_file(pre + ".scc.stat", cstat.data(), cstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
     if (saddle && !write_file(pre + ".saddle.stat", sstat.data(), sstat.size())) { fprintf(stderr, "Error: write output failed!\n"); mkt_matrix_destroy(m); return 22; }
