@@ -28,24 +28,20 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <unistd.h>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/mkt.h"
-#include "mkt_deflate_codes.h"
+#include "mkt_deflate.h"
+#include "mkt_devbuf.h"
 #include "mkt_launch.h"
 #include "mkt_sortlib.h"
-#include "mkt_zstream.h"
 
 using namespace mkt;
 
 namespace mkt {
 
 enum { BE_FIELDS = 1, BE_REF = 2, BE_NUM = 4, BE_CIGAR = 8, BE_TAG = 16, BE_SEQ = 32, BE_NAME = 64 };
-constexpr uint32_t BGZF_RAW = 0xff00;                 // uncompressed bytes per BGZF block (htslib's BGZF_BLOCK_SIZE)
-constexpr uint32_t BGZF_STRIDE = 0x10000;             // room for one compressed block in the work buffer (a block is <= 64 KiB)
-constexpr int BWG = 256;
 
 struct RefTab {                                       // reference names -> ids (built on the host from the @SQ lines)
     const unsigned long long* hash;                   // FNV-1a of the name, 0 = empty
@@ -87,7 +83,6 @@ __device__ inline uint32_t reg2bin(int64_t beg, int64_t end) {        // SAMv1 5
 }
 __device__ inline void put8(uint8_t*& o, uint32_t v) { *o++ = (uint8_t)v; }
 __device__ inline void put16(uint8_t*& o, uint32_t v) { o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o += 2; }
-__device__ inline void put32(uint8_t*& o, uint32_t v) { o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16); o[3] = (uint8_t)(v >> 24); o += 4; }
 // A record's bytes go out through this: single bytes up to the first 8-byte boundary, then whole aligned 8-byte words, single
 // bytes for the rest (the neighbours on both sides belong to other threads' records).
 struct Sink {
@@ -379,502 +374,6 @@ __global__ void k_bam_write(const uint8_t* text, const uint64_t* starts, uint64_
     idx[r] = ix;
 }
 
-// ---- CRC-32 (RFC 1952) of a block: every thread takes a slice, the slices are combined as polynomials ------------------------
-__device__ inline uint32_t crc_mulmod(uint32_t a, uint32_t b) {       // a(x) * b(x) mod P(x), reflected representation (zlib's multmodp)
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) { p ^= b; if ((a & (m - 1u)) == 0u) break; }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
-}
-__device__ inline uint32_t crc_x8n(uint32_t nbytes, const uint32_t* x2n /* x^(2^k) mod P, k = 0..31 */) {        // x^(8 * nbytes) mod P
-    uint32_t p = 1u << 31;                                            // the polynomial 1
-    uint32_t n = nbytes;
-    int k = 3;                                                        // bits -> bytes
-    while (n) { if (n & 1u) p = crc_mulmod(x2n[k & 31], p); n >>= 1; ++k; }
-    return p;
-}
-__device__ inline uint32_t crc_bytes(const uint8_t* d, uint32_t n, const uint32_t* tabl) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < n; ++i) c = tabl[(c ^ d[i]) & 0xFFu] ^ (c >> 8);
-    return c ^ 0xFFFFFFFFu;
-}
-struct CrcTabs { uint32_t t[256]; uint32_t x2n[32]; };
-
-// block-wide CRC of n bytes at src (global or LDS): slices of ceil(n / NTH) bytes
-template <int NTH>
-__device__ inline uint32_t block_crc(const uint8_t* src, uint32_t n, const uint32_t* tabl, const uint32_t* x2n, uint32_t* sh /* [NTH / 64] */) {
-    const uint32_t per = (n + NTH - 1) / NTH;
-    const uint32_t a = threadIdx.x * per < n ? threadIdx.x * per : n, b = a + per < n ? a + per : n;
-    uint32_t c = 0;
-    if (b > a) { c = crc_bytes(src + a, b - a, tabl); if (n - b) c = crc_mulmod(crc_x8n(n - b, x2n), c); }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c ^= (uint32_t)__shfl_xor((int)c, d, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-    __syncthreads();
-    uint32_t r = 0;
-#pragma unroll
-    for (int w = 0; w < NTH / 64; ++w) r ^= sh[w];
-    __syncthreads();
-    return r;
-}
-// block-wide Adler-32 (RFC 1950) of n <= 65 280 bytes at src, from the state (1, 0): slices of ceil(n / NTH) bytes; a slice [s, e) gives
-// a = sum d_i and b = sum (e - i) d_i, and the whole is A = 1 + sum a, B = n + sum (b + (n - e) a), both mod 65521.  Integer sums in a
-// fixed tree: the value does not depend on the order anything ran in.
-template <int NTH>
-__device__ inline uint32_t block_adler(const uint8_t* src, uint32_t n, uint32_t* sh /* [NTH / 64] */) {
-    const uint32_t per = (n + NTH - 1) / NTH;                 // <= 256 bytes for NTH >= 256: a < 2^16, b < 2^24
-    const uint32_t s = threadIdx.x * per < n ? threadIdx.x * per : n, e = s + per < n ? s + per : n;
-    uint32_t a = 0, b = 0;
-    for (uint32_t i = s; i < e; ++i) { a += src[i]; b += a; }
-    uint32_t tb = (uint32_t)(((uint64_t)b + (uint64_t)(n - e) * a) % 65521u);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a += (uint32_t)__shfl_xor((int)a, d, 64); tb += (uint32_t)__shfl_xor((int)tb, d, 64); }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-    __syncthreads();
-    uint32_t A = 1;
-#pragma unroll
-    for (int w = 0; w < NTH / 64; ++w) A += sh[w];
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = tb;
-    __syncthreads();
-    uint32_t Bs = n;
-#pragma unroll
-    for (int w = 0; w < NTH / 64; ++w) Bs += sh[w];
-    __syncthreads();
-    return ((Bs % 65521u) << 16) | (A % 65521u);
-}
-__device__ inline void bgzf_header(uint8_t* o, uint32_t bsize_minus1) {     // SAMv1 4.1
-    const uint8_t h[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0};
-    for (int i = 0; i < 16; ++i) o[i] = h[i];
-    o[16] = (uint8_t)bsize_minus1; o[17] = (uint8_t)(bsize_minus1 >> 8);
-}
-
-// level 0: one stored deflate block per BGZF block
-__global__ __launch_bounds__(BWG) void k_bgzf_stored(const uint8_t* raw, uint64_t nraw, const CrcTabs* ct, uint8_t* comp, uint64_t* csize) {
-    __shared__ uint32_t tabl[256], x2n[32], sh[BWG / 64];
-    tabl[threadIdx.x] = ct->t[threadIdx.x];
-    if (threadIdx.x < 32) x2n[threadIdx.x] = ct->x2n[threadIdx.x];
-    __syncthreads();
-    const uint64_t b0 = (uint64_t)blockIdx.x * BGZF_RAW;
-    const uint32_t n = (uint32_t)(nraw - b0 < BGZF_RAW ? nraw - b0 : BGZF_RAW);
-    const uint8_t* src = raw + b0;
-    uint8_t* o = comp + (uint64_t)blockIdx.x * BGZF_STRIDE;
-    const uint32_t crc = block_crc<BWG>(src, n, tabl, x2n, sh);
-    const uint32_t total = 18 + 5 + n + 8;
-    if (threadIdx.x == 0) {
-        bgzf_header(o, total - 1);
-        o[18] = 1;                                         // BFINAL = 1, BTYPE = 00
-        o[19] = (uint8_t)n; o[20] = (uint8_t)(n >> 8); o[21] = (uint8_t)~n; o[22] = (uint8_t)(~n >> 8);
-        uint8_t* e = o + 23 + n;
-        put32(e, crc); put32(e, n);
-        csize[blockIdx.x] = total;
-    }
-    for (uint32_t i = threadIdx.x; i < n; i += BWG) o[23 + i] = src[i];
-}
-// the compressed blocks, packed
-__global__ __launch_bounds__(BWG) void k_bgzf_pack(const uint8_t* comp, const uint64_t* coff, uint64_t nblocks, uint8_t* out) {
-    const uint64_t b = blockIdx.x;
-    const uint64_t o = coff[b], n = coff[b + 1] - o;
-    const uint8_t* s = comp + b * BGZF_STRIDE;
-    for (uint32_t i = threadIdx.x; i < n; i += BWG) out[o + i] = s[i];
-}
-
-// ---- levels 1 and 2: LZ77 + Huffman codes (RFC 1951), one workgroup per BGZF block ------------------------------------------
-// Every wave parses its share of the block (an eighth by default) with its own hash table (matches stay inside the share), 64
-// positions per step: a hash of four bytes names a candidate from earlier steps (distance 1 first, for runs), checked on four
-// bytes in parallel; then the greedy parse of the step token by token -- literals skipped in bulk, a match's length measured
-// by the whole wave at once -- and the tokens go to a list.  Level 1 codes them with the fixed tables of RFC 1951 3.2.6, level 2
-// with tables built for the block (3.2.7): symbol counts gathered while parsing, code lengths by the in-place minimum-redundancy
-// algorithm of Moffat and Katajainen on the sorted counts, limited to 15 (7) bits by moving codes down the Kraft sum, canonical
-// codes, the code lengths themselves run-length coded as the format prescribes.  Second pass: 64 tokens per step to bits, bit
-// offsets by a wave scan, ORed into the wave's stream; header, the waves' streams and the end-of-block code are then joined
-// bit-exactly.  A block that does not shrink is stored.
-#ifndef MKT_DZ_WAVES
-#define MKT_DZ_WAVES 8
-#endif
-constexpr int DZ_WAVES = MKT_DZ_WAVES;                  // waves per BGZF block (4, 8 or 16); 64 KiB of hash tables in all
-constexpr int DZ_THREADS = 64 * DZ_WAVES;
-constexpr uint32_t DZ_Q = BGZF_RAW / DZ_WAVES;           // bytes per wave (BGZF_RAW = 2^8 * 255 divides evenly)
-constexpr uint32_t DZ_HBITS = DZ_WAVES == 4 ? 12 : (DZ_WAVES == 8 ? 11 : 10);
-static_assert(DZ_Q * DZ_WAVES == BGZF_RAW, "even split");
-constexpr uint32_t DZ_MAXLEN = 258, DZ_MINLEN = 4;
-constexpr uint32_t DZ_QWORDS = (DZ_Q * 15 / 8 + 64) / 4 + 2;      // a wave's bit stream: at most 15 bits per byte
-constexpr uint32_t DZ_WAVE_SCRATCH = DZ_Q + DZ_QWORDS;            // words per wave: token list + bit stream
-constexpr int DZ_STAGE = 104;                            // one step's bits of a wave: 64 tokens of <= 48 bits + the carry
-constexpr int DZ_HDRW = 176;                             // dynamic block header: <= 3 + 14 + 57 + 316 * 14 bits
-
-// len_code, dist_code, mk_lengths, huff_codes, bitrev: mkt_deflate_codes.h (shared with the host test driver)
-struct BitSink {                                         // one lane appends bits to words in LDS
-    uint32_t* w; uint32_t n;
-    __device__ inline void put(uint32_t v, uint32_t nb) {
-        if (!nb) return;
-        const uint32_t i = n >> 5, s = n & 31u;
-        w[i] |= v << s;
-        if (s + nb > 32u) w[i + 1] |= v >> (32u - s);
-        n += nb;
-    }
-};
-
-// Two framings of the same parse and coder.  ZS = false: a self-contained BGZF member per block of BGZF_RAW bytes (BFINAL = 1, gzip
-// header, CRC-32 and size behind it).  ZS = true: a PIECE of a zlib stream (mkt_zstream.h): block `blk` is the piece zp.off[blk],
-// zp.len[blk] of raw; its deflate block has BFINAL = 0 and is followed by an empty stored block (000, padding, 00 00 FF FF), so that the
-// piece ends on a byte and pieces can be joined by copying; no header, the piece's Adler-32 goes to zp.adler[blk].
-template <bool DYN, bool ZS>
-__global__ __launch_bounds__(DZ_THREADS) void k_bgzf_deflate(const uint8_t* raw, uint64_t nraw, uint64_t first_block, const CrcTabs* ct, uint8_t* comp, uint64_t* csize,
-                                                             uint32_t* scratch /* per block of the launch: DZ_WAVES * DZ_WAVE_SCRATCH words */, ZsPieces zp) {
-    __shared__ __attribute__((aligned(16))) uint32_t in32[(BGZF_RAW + 288) / 4];      // + what a length measurement reads past the end
-    __shared__ uint32_t htab[DZ_WAVES][1u << DZ_HBITS];
-    __shared__ uint32_t stage_[DZ_WAVES][DZ_STAGE];
-    __shared__ uint32_t tabl[256], x2n[32], sh[DZ_THREADS / 64];
-    __shared__ uint32_t wbits[DZ_WAVES + 2], woff[DZ_WAVES + 3], wntok[DZ_WAVES];
-    __shared__ uint32_t ll_tab[288], d_tab[32];          // symbol -> reversed code | length << 16
-    __shared__ uint32_t ll_hist[288], d_hist[32];
-    __shared__ uint32_t skey[288], dkey[32];
-    __shared__ uint16_t ssym[288], dsym[32];
-    __shared__ uint32_t hdrw[DZ_HDRW];
-    __shared__ uint32_t nused[2];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    uint8_t* in = reinterpret_cast<uint8_t*>(in32);
-    auto word_at = [&](uint32_t off) {                   // the four bytes at any offset (two aligned reads)
-        const uint32_t i = off >> 2;
-        return __builtin_amdgcn_alignbyte(in32[i + 1], in32[i], off & 3u);
-    };
-    volatile uint32_t (*stage)[DZ_STAGE] = stage_;       // lanes of a wave hand bits to each other through it
-    if (!ZS && tid < 256) tabl[tid] = ct->t[tid];
-    if (tid < 32) { if (!ZS) x2n[tid] = ct->x2n[tid]; d_hist[tid] = 0; }
-    if (tid < 288) ll_hist[tid] = 0;
-    for (int i = tid; i < DZ_HDRW; i += DZ_THREADS) hdrw[i] = 0;
-    const uint64_t blk = first_block + blockIdx.x;
-    const uint64_t b0 = ZS ? zp.off[blk] : blk * BGZF_RAW;
-    const uint32_t n = ZS ? zp.len[blk] : (uint32_t)(nraw - b0 < BGZF_RAW ? nraw - b0 : BGZF_RAW);
-    {   // the block into LDS, 16 bytes per load (blocks start on multiples of 16; the raw buffer is readable 64 bytes past its end,
-        // and what lies behind byte n is never looked at)
-        const uint4* src = reinterpret_cast<const uint4*>(raw + b0);
-        uint4* dst = reinterpret_cast<uint4*>(in32);
-        for (uint32_t i = tid; i < (BGZF_RAW + 288) / 16; i += DZ_THREADS) dst[i] = (i << 4) < n ? src[i] : make_uint4(0, 0, 0, 0);
-    }
-    for (uint32_t i = lane; i < (1u << DZ_HBITS); i += 64) htab[wv][i] = 0;          // 0 = empty (positions are stored + 1)
-    __syncthreads();
-    const uint32_t crc = ZS ? block_adler<DZ_THREADS>(in, n, sh) : block_crc<DZ_THREADS>(in, n, tabl, x2n, sh);       // (ZS: the piece's Adler-32)
-    // ---- pass 1: this wave's share -> tokens (a literal byte, or 1 << 31 | length - 3 << 16 | distance - 1)
-    const uint32_t q0 = wv * DZ_Q < n ? wv * DZ_Q : n, q1 = q0 + DZ_Q < n ? q0 + DZ_Q : n;
-    uint32_t* wtok = scratch + ((uint64_t)blockIdx.x * DZ_WAVES + wv) * DZ_WAVE_SCRATCH;
-    uint32_t* ws = wtok + DZ_Q;
-    uint32_t ntok = 0;
-    uint32_t cur = q0;                                   // first position not yet covered by a token
-    for (uint32_t base = q0; base < q1; base += 64) {
-        const uint32_t p = base + lane;
-        const bool live = p < q1;
-        uint32_t mlen = 0, mdist = 0;
-        uint32_t h = 0;
-        const bool hashable = live && p + DZ_MINLEN <= q1;
-        const bool open_step = cur < base + 64u && cur < q1;      // (uniform) false: an earlier token covers all 64 positions
-        // every position's candidate, checked on its first four bytes only: distance 1 (runs) before the table's
-        uint32_t cand = 0xFFFFFFFFu;
-        if (hashable) {
-            const uint32_t v = word_at(p);
-            h = (v * 2654435761u) >> (32 - DZ_HBITS);
-            const uint32_t c1 = htab[wv][h];
-            if (open_step) {
-                if (p > q0 && word_at(p - 1u) == v) cand = p - 1u;
-                else if (c1 && word_at(c1 - 1u) == v) cand = c1 - 1u;          // < base: only earlier steps have written
-            }
-        }
-        // (all lanes have read the table before any lane of this wave writes: one wave, program order)
-        if (hashable) atomicMax(&htab[wv][h], p + 1);
-        if (!open_step) continue;
-        // greedy parse of the step, token by token; literals are skipped in bulk, a match's length is measured by the whole
-        // wave at once (lane i compares bytes 4 i .. 4 i + 3), so the cost does not grow with the length
-        uint64_t sel = 0;
-        {
-            const uint64_t hasm = __ballot(cand != 0xFFFFFFFFu);
-            const uint32_t nlive = q1 - base < 64u ? q1 - base : 64u;
-            uint32_t pos = cur - base;
-            while (pos < nlive) {
-                const uint64_t rem = hasm >> pos;
-                const uint32_t lit = rem ? (uint32_t)__builtin_ctzll(rem) : 64u;       // literals up to the next candidate
-                if (lit) {
-                    const uint32_t e = pos + lit < nlive ? pos + lit : nlive;
-                    sel |= (e >= 64u ? ~0ull : ((1ull << e) - 1ull)) & ~((1ull << pos) - 1ull);
-                    pos = e;
-                    continue;
-                }
-                const uint32_t c = (uint32_t)__shfl((int)cand, (int)pos, 64), pp = base + pos;
-                const uint32_t lim = q1 - pp < DZ_MAXLEN ? q1 - pp : DZ_MAXLEN;
-                const uint32_t x = word_at(c + 4u * (uint32_t)lane) ^ word_at(pp + 4u * (uint32_t)lane);
-                const uint64_t ne = __ballot(x != 0u);
-                uint32_t len;
-                if (ne) {
-                    const int j = (int)__builtin_ctzll(ne);
-                    const uint32_t xj = (uint32_t)__shfl((int)x, j, 64);
-                    len = 4u * (uint32_t)j + ((uint32_t)__builtin_ctz(xj) >> 3);
-                } else {                                         // 256 equal bytes: two more decide between 256, 257, 258
-                    const uint32_t y = word_at(c + 256u) ^ word_at(pp + 256u);
-                    len = 256u + ((y & 0xFFu) ? 0u : ((y & 0xFF00u) ? 1u : 2u));
-                }
-                if (len > lim) len = lim;
-                if ((uint32_t)lane == pos) { mlen = len; mdist = pp - c; }
-                sel |= 1ull << pos;
-                pos += len;
-            }
-            cur = base + pos;
-        }
-        if ((sel >> lane) & 1ull) {
-            const uint32_t rank = (uint32_t)__popcll(sel & ((1ull << lane) - 1ull));
-            wtok[ntok + rank] = mlen ? (0x80000000u | ((mlen - 3u) << 16) | (mdist - 1u)) : (uint32_t)in[p];
-            if (DYN) {
-                if (mlen) {
-                    uint32_t sy, eb, ev;
-                    len_code(mlen, sy, eb, ev);
-                    atomicAdd(&ll_hist[sy], 1u);
-                    dist_code(mdist, sy, eb, ev);
-                    atomicAdd(&d_hist[sy], 1u);
-                } else atomicAdd(&ll_hist[in[p]], 1u);
-            }
-        }
-        ntok += (uint32_t)__popcll(sel);
-    }
-    if (lane == 0) wntok[wv] = ntok;
-    __syncthreads();
-    // ---- the code tables and the block header
-    uint32_t hdr_bits = 3;
-    if (!DYN) {
-        for (int s = tid; s < 288; s += DZ_THREADS) {        // RFC 1951 3.2.6
-            uint32_t code, nb;
-            if (s < 144) { code = bitrev(0x30 + s, 8); nb = 8; }
-            else if (s < 256) { code = bitrev(0x190 + (s - 144), 9); nb = 9; }
-            else if (s < 280) { code = bitrev(s - 256, 7); nb = 7; }
-            else { code = bitrev(0xC0 + (s - 280), 8); nb = 8; }
-            ll_tab[s] = code | (nb << 16);
-        }
-        if (tid < 32) d_tab[tid] = bitrev((uint32_t)tid, 5) | (5u << 16);
-        if (tid == 0) hdrw[0] = ZS ? 2u : 3u;                // BFINAL = 1 (ZS: 0), BTYPE = 01
-        __syncthreads();
-    } else {
-        if (tid == 0) {
-            ll_hist[256] = 1;                                // end of block
-            int nz = 0;
-            for (int s = 0; s < 30; ++s) nz += d_hist[s] != 0u;
-            if (nz == 0) { d_hist[0] = 1; d_hist[1] = 1; }       // (as zlib: never fewer than two distance codes)
-            else if (nz == 1) { if (d_hist[0]) d_hist[1] = 1; else d_hist[0] = 1; }
-            int nl = 0;
-            for (int s = 0; s < 286; ++s) nl += ll_hist[s] != 0u;
-            if (nl < 2) { if (!ll_hist[0]) ll_hist[0] = 1; else ll_hist[1] = 1; }
-        }
-        __syncthreads();
-        // used symbols in ascending order of their counts (rank by counting; ties by symbol)
-        for (int t = tid; t < 286; t += DZ_THREADS) {
-            const uint32_t f = ll_hist[t];
-            if (f) {
-                uint32_t r = 0;
-                for (int j = 0; j < 286; ++j) { const uint32_t g = ll_hist[j]; r += (g != 0u) && (g < f || (g == f && j < t)); }
-                skey[r] = f; ssym[r] = (uint16_t)t;
-            }
-        }
-        for (int t = DZ_THREADS - 1 - tid; t < 30; t += DZ_THREADS) {           // (the last threads: they have no literal symbol to rank)
-            const uint32_t f = d_hist[t];
-            if (f) {
-                uint32_t r = 0;
-                for (int j = 0; j < 30; ++j) { const uint32_t g = d_hist[j]; r += (g != 0u) && (g < f || (g == f && j < t)); }
-                dkey[r] = f; dsym[r] = (uint16_t)t;
-            }
-        }
-        if (tid == 0) { int a = 0; for (int s = 0; s < 286; ++s) a += ll_hist[s] != 0u; nused[0] = (uint32_t)a; }
-        if (tid == 64) { int a = 0; for (int s = 0; s < 30; ++s) a += d_hist[s] != 0u; nused[1] = (uint32_t)a; }
-        __syncthreads();
-        if (tid == 0) huff_codes(skey, ssym, (int)nused[0], 15, ll_tab, 288);
-        if (tid == 64) huff_codes(dkey, dsym, (int)nused[1], 15, d_tab, 32);
-        __syncthreads();
-        if (tid == 0) {                                      // RFC 1951 3.2.7
-            int nll = 286, nd = 30;
-            while (nll > 257 && !(ll_tab[nll - 1] >> 16)) --nll;
-            while (nd > 1 && !(d_tab[nd - 1] >> 16)) --nd;
-            // the code lengths, run-length coded: symbols 0..15 literal lengths, 16 repeat previous 3..6, 17 zeros 3..10, 18 zeros 11..138
-            uint16_t* cl = reinterpret_cast<uint16_t*>(skey);         // (the sort arrays are free again) symbol | extra value << 8
-            int ncl = 0;
-            uint32_t clh[19];
-            for (int i = 0; i < 19; ++i) clh[i] = 0;
-            const int tot = nll + nd;
-            auto L = [&](int i) { return i < nll ? ll_tab[i] >> 16 : d_tab[i - nll] >> 16; };
-            for (int i = 0; i < tot;) {
-                const uint32_t v = L(i);
-                int run = 1;
-                while (i + run < tot && L(i + run) == v) ++run;
-                i += run;
-                if (v == 0) {
-                    while (run >= 11) { const int r = run < 138 ? run : 138; cl[ncl++] = (uint16_t)(18 | ((r - 11) << 8)); clh[18]++; run -= r; }
-                    if (run >= 3) { cl[ncl++] = (uint16_t)(17 | ((run - 3) << 8)); clh[17]++; run = 0; }
-                    while (run-- > 0) { cl[ncl++] = 0; clh[0]++; }
-                } else {
-                    cl[ncl++] = (uint16_t)v; clh[v]++; --run;
-                    while (run >= 3) { const int r = run < 6 ? run : 6; cl[ncl++] = (uint16_t)(16 | ((r - 3) << 8)); clh[16]++; run -= r; }
-                    while (run-- > 0) { cl[ncl++] = (uint16_t)v; clh[v]++; }
-                }
-            }
-            // the code for those 19 symbols (<= 7 bits; never fewer than two of them)
-            { int nzc = 0, only = 0; for (int s2 = 0; s2 < 19; ++s2) if (clh[s2]) { ++nzc; only = s2; } if (nzc == 1) clh[only ? 0 : 1] = 1; }
-            uint32_t ck[19], ctab[19];
-            uint16_t cs[19];
-            int nc = 0;
-            for (int s = 0; s < 19; ++s) if (clh[s]) { int k = nc++; while (k > 0 && (ck[k - 1] > clh[s])) { ck[k] = ck[k - 1]; cs[k] = cs[k - 1]; --k; } ck[k] = clh[s]; cs[k] = (uint16_t)s; }
-            huff_codes(ck, cs, nc, 7, ctab, 19);
-            const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-            int nclc = 19;
-            while (nclc > 4 && !(ctab[order[nclc - 1]] >> 16)) --nclc;
-            BitSink B{hdrw, 0};
-            B.put(ZS ? 4u : 5u, 3);                          // BFINAL = 1 (ZS: 0), BTYPE = 10
-            B.put((uint32_t)(nll - 257), 5); B.put((uint32_t)(nd - 1), 5); B.put((uint32_t)(nclc - 4), 4);
-            for (int i = 0; i < nclc; ++i) B.put(ctab[order[i]] >> 16, 3);
-            for (int i = 0; i < ncl; ++i) {
-                const uint32_t sy = cl[i] & 0xFFu, ev = cl[i] >> 8;
-                B.put(ctab[sy] & 0xFFFFu, ctab[sy] >> 16);
-                if (sy == 16) B.put(ev, 2); else if (sy == 17) B.put(ev, 3); else if (sy == 18) B.put(ev, 7);
-            }
-            nused[0] = B.n;
-        }
-        __syncthreads();
-        hdr_bits = nused[0];
-    }
-    // ---- pass 2: tokens -> bits
-    ntok = wntok[wv];
-    uint32_t wpos = 0;                                   // whole words already flushed to ws
-    uint32_t carry_bits = 0;                             // bits waiting in stage[wv][0]
-    if (lane == 0) stage[wv][0] = 0;
-    for (uint32_t t0 = 0; t0 < ntok; t0 += 64) {
-        uint32_t a = 0, na = 0, b = 0, nbb = 0;          // literal / length part, distance part
-        if (t0 + lane < ntok) {
-            const uint32_t tok = wtok[t0 + lane];
-            if (tok >> 31) {
-                uint32_t sy, eb, ev;
-                len_code(((tok >> 16) & 0xFFu) + 3u, sy, eb, ev);
-                const uint32_t e = ll_tab[sy];
-                a = (e & 0xFFFFu) | (ev << (e >> 16)); na = (e >> 16) + eb;
-                dist_code((tok & 0xFFFFu) + 1u, sy, eb, ev);
-                const uint32_t d = d_tab[sy];
-                b = (d & 0xFFFFu) | (ev << (d >> 16)); nbb = (d >> 16) + eb;
-            } else { const uint32_t e = ll_tab[tok]; a = e & 0xFFFFu; na = e >> 16; }
-        }
-        const uint32_t nb = na + nbb;
-        uint32_t inc = nb;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, d, 64); if (lane >= d) inc += y; }
-        const uint32_t tot = (uint32_t)__shfl((int)inc, 63, 64);
-        const uint32_t bo = carry_bits + inc - nb;
-        // stage[1..] cleared for this step (word 0 holds the carry)
-        for (uint32_t i = 1 + lane; i < (uint32_t)DZ_STAGE; i += 64) stage[wv][i] = 0;
-        __builtin_amdgcn_wave_barrier();
-        if (na) {
-            const uint32_t w = bo >> 5, s = bo & 31u;
-            const uint64_t lo = (uint64_t)a << s;
-            atomicOr(&stage_[wv][w], (uint32_t)lo);
-            if ((uint32_t)(lo >> 32)) atomicOr(&stage_[wv][w + 1], (uint32_t)(lo >> 32));
-        }
-        if (nbb) {
-            const uint32_t w = (bo + na) >> 5, s = (bo + na) & 31u;
-            const uint64_t lo = (uint64_t)b << s;
-            atomicOr(&stage_[wv][w], (uint32_t)lo);
-            if ((uint32_t)(lo >> 32)) atomicOr(&stage_[wv][w + 1], (uint32_t)(lo >> 32));
-        }
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t endb = carry_bits + tot, full = endb >> 5;
-        for (uint32_t i = lane; i < full; i += 64) ws[wpos + i] = stage[wv][i];
-        const uint32_t rest = stage[wv][full];
-        __builtin_amdgcn_wave_barrier();
-        wpos += full;
-        carry_bits = endb & 31u;
-        if (lane == 0) stage[wv][0] = carry_bits ? rest : 0u;
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (lane == 0) { ws[wpos] = stage[wv][0]; wbits[1 + wv] = wpos * 32u + carry_bits; }
-    if (tid == 0) { wbits[0] = hdr_bits; wbits[DZ_WAVES + 1] = (ll_tab[256] >> 16) + (ZS ? 3u : 0u); }       // (ZS: + the 000 of the empty stored block)
-    __threadfence_block();
-    __syncthreads();
-    // ---- join: header, the waves' streams in order, the end-of-block code
-    if (tid == 0) { uint32_t a = 0; for (int w = 0; w < DZ_WAVES + 2; ++w) { woff[w] = a; a += wbits[w]; } woff[DZ_WAVES + 2] = a; }
-    __syncthreads();
-    const uint32_t total_bits = woff[DZ_WAVES + 2];
-    const uint32_t cbytes = (total_bits + 7u) >> 3;
-    uint8_t* o = comp + blk * BGZF_STRIDE;
-    constexpr uint32_t HDR = ZS ? 0u : 18u;              // bytes in front of the deflate data
-    if (ZS && cbytes + 4u >= n + 5u) {                    // did not shrink: one stored block, BFINAL = 0
-        if (tid == 0) {
-            o[0] = 0; o[1] = (uint8_t)n; o[2] = (uint8_t)(n >> 8); o[3] = (uint8_t)~n; o[4] = (uint8_t)(~n >> 8);
-            csize[blk] = n + 5u; zp.adler[blk] = crc;
-        }
-        for (uint32_t i = tid; i < n; i += DZ_THREADS) o[5 + i] = in[i];
-        return;
-    }
-    if (!ZS && cbytes >= n + 5u) {                        // did not shrink: stored
-        const uint32_t total = 18 + 5 + n + 8;
-        if (tid == 0) {
-            bgzf_header(o, total - 1);
-            o[18] = 1; o[19] = (uint8_t)n; o[20] = (uint8_t)(n >> 8); o[21] = (uint8_t)~n; o[22] = (uint8_t)(~n >> 8);
-            uint8_t* e = o + 23 + n;
-            put32(e, crc); put32(e, n);
-            csize[blk] = total;
-        }
-        for (uint32_t i = tid; i < n; i += DZ_THREADS) o[23 + i] = in[i];
-        return;
-    }
-    const uint32_t eobw = ll_tab[256] & 0xFFFFu;
-    const uint32_t* s0 = scratch + ((uint64_t)blockIdx.x * DZ_WAVES) * DZ_WAVE_SCRATCH + DZ_Q;
-    // output word k holds bits [32 k, 32 k + 32) of the joined stream
-    const uint32_t nwords = (total_bits + 31u) >> 5;
-    for (uint32_t k = tid; k < nwords; k += DZ_THREADS) {
-        uint32_t word = 0;
-        const uint32_t lo = k << 5, hi = lo + 32u;
-        for (int s = 0; s < DZ_WAVES + 2; ++s) {
-            const uint32_t so = woff[s], sn = wbits[s];
-            if (sn == 0u || so >= hi || so + sn <= lo) continue;
-            auto sword = [&](uint32_t w) -> uint32_t {
-                if (s == 0) return hdrw[w];
-                if (s == DZ_WAVES + 1) return w ? 0u : eobw;
-                return s0[(uint64_t)(s - 1) * DZ_WAVE_SCRATCH + w];
-            };
-            // bits of stream s that land in this word: stream bit j -> joined bit so + j
-            const int64_t j0 = (int64_t)lo - (int64_t)so;            // stream bit at the word's bit 0 (may be negative)
-            uint32_t v;
-            if (j0 >= 0) {
-                const uint32_t w = (uint32_t)j0 >> 5, sft = (uint32_t)j0 & 31u;
-                const uint64_t two = (uint64_t)sword(w) | ((uint64_t)(((w + 1u) << 5) < sn ? sword(w + 1) : 0u) << 32);
-                v = (uint32_t)(two >> sft);
-                const uint32_t avail = sn - (uint32_t)j0;             // stream bits from j0 on
-                if (avail < 32u) v &= (1u << avail) - 1u;
-            } else {
-                const uint32_t sft = (uint32_t)(-j0);                 // 1..31
-                v = sword(0) << sft;
-                if (sn + sft < 32u) v &= (1u << (sn + sft)) - 1u;
-            }
-            word |= v;
-        }
-        uint8_t* d = o + HDR + 4u * k;
-        const uint32_t left = cbytes - 4u * k;
-        d[0] = (uint8_t)word;
-        if (left > 1) d[1] = (uint8_t)(word >> 8);
-        if (left > 2) d[2] = (uint8_t)(word >> 16);
-        if (left > 3) d[3] = (uint8_t)(word >> 24);
-    }
-    if (ZS) {
-        if (tid == 0) {
-            uint8_t* e = o + cbytes;
-            e[0] = 0; e[1] = 0; e[2] = 0xFF; e[3] = 0xFF;       // LEN = 0, NLEN of the empty stored block
-            csize[blk] = cbytes + 4u; zp.adler[blk] = crc;
-        }
-        return;
-    }
-    if (tid == 0) {
-        const uint32_t total = 18 + cbytes + 8;
-        bgzf_header(o, total - 1);
-        uint8_t* e = o + 18 + cbytes;
-        put32(e, crc); put32(e, n);
-        csize[blk] = total;
-    }
-}
-
 // ---- BAI reductions -------------------------------------------------------------------------------------------------------
 struct BaiHead { uint32_t r; int32_t tid; uint32_t bin; uint32_t pad; uint64_t voff; };
 struct BaiRef { unsigned long long n_mapped, n_unmapped, beg, end; };          // beg: min start voffset, end: max end voffset
@@ -1031,55 +530,58 @@ struct SpillCur {                                      // a run's window during 
     std::string bytes;
 };
 struct BgzfStream {                                    // BGZF output of a stream: d_win = the partial last block (carry bytes), then the current window
-    uint8_t* d_win = nullptr; size_t cap = 0;
+    LedgerBuf<uint8_t> d_win;
     uint64_t carry = 0, blk0 = 0, cbase = 0;           // blk0: file block at d_win[0]; cbase: compressed bytes before it
-    uint8_t* d_comp = nullptr; size_t comp_cap = 0;
-    uint64_t* d_csize = nullptr; size_t csize_cap = 0;
-    uint32_t* d_scratch = nullptr; size_t scratch_cap = 0;
-    uint8_t* d_pack = nullptr; size_t pack_cap = 0;
+    LedgerBuf<uint8_t> d_comp, d_pack;                 // (these four: grow-only)
+    LedgerBuf<uint64_t> d_csize;
+    LedgerBuf<uint32_t> d_scratch;
 };
 struct BaiAcc {                                        // the index across the windows of a file (the single pass: one window): small arrays that stay resident
     bool on = false, has_prev = false;
     std::vector<uint64_t> lin_off;
-    uint64_t* d_lin_off = nullptr;
-    unsigned long long *d_lin = nullptr, *d_nocoor = nullptr;
-    BaiRef* d_refs = nullptr;
-    BamIdx* d_prev = nullptr;
-    uint64_t* d_hflag = nullptr; size_t hflag_cap = 0; // per window (grow-only)
-    BaiHead* d_heads = nullptr; size_t heads_cap = 0;
+    LedgerBuf<uint64_t> d_lin_off;
+    LedgerBuf<unsigned long long> d_lin, d_nocoor;
+    LedgerBuf<BaiRef> d_refs;
+    LedgerBuf<BamIdx> d_prev;
+    LedgerBuf<uint64_t> d_hflag;                       // per window (grow-only)
+    LedgerBuf<BaiHead> d_heads;
     std::vector<BaiHead> heads;
     uint64_t end_voff = 0;
 };
 struct MergeBufs {                                     // one merge round on the device (grow-only)
-    SpillRec* rec = nullptr; size_t rec_cap = 0;
-    uint64_t* src = nullptr; size_t src_cap = 0;
-    uint8_t* bytes = nullptr; size_t bytes_cap = 0;
-    SortRec *rA = nullptr, *rB = nullptr; size_t rA_cap = 0, rB_cap = 0;
-    uint32_t* hist = nullptr; size_t hist_cap = 0;
-    uint64_t* off = nullptr; size_t off_cap = 0;
-    BamIdx* idx = nullptr; size_t idx_cap = 0;
+    LedgerBuf<SpillRec> rec;
+    LedgerBuf<uint64_t> src, off;
+    LedgerBuf<uint8_t> bytes;
+    LedgerBuf<SortRec> rA, rB;
+    LedgerBuf<uint32_t> hist;
+    LedgerBuf<BamIdx> idx;
+};
+struct BamTabs {                                       // what bam_setup puts on the device: the name table, the CRC tables, the error word; find_nl's word
+    LedgerBuf<uint8_t> rt[4];
+    LedgerBuf<CrcTabs> ct;
+    LedgerBuf<uint32_t> err;
+    LedgerBuf<unsigned long long> nl;
 };
 
 struct mkt_bam {
     int device = 0;
-    hipStream_t stream = nullptr;
-    uint8_t* d_text = nullptr; size_t cap = 0, len = 0;
+    DevStream stream;                                   // (first: it goes last)
+    // device bytes held by this object: every device buffer below is a LedgerBuf charged to it.  limit = $MKT_BAM_DEVICE_LIMIT: the
+    // device bytes this object may hold (as if HBM ended there)
+    DevLedger led;
+    LedgerBuf<uint8_t> d_text; size_t cap = 0, len = 0;
     uint64_t tstart = 0;                                // text before this offset has gone into runs (out-of-core mode)
     bool header_done = false, ran = false;
     std::string header, pending;
-    uint8_t* d_bam = nullptr; uint64_t bam_len = 0;
+    LedgerBuf<uint8_t> d_bam; uint64_t bam_len = 0;
     std::string bai;
     uint64_t records = 0;
     // pinned staging for callers that move files (mkt_bam_window / _commit / _read / _pull): two slots, used alternately
-    char* h_io[2] = {nullptr, nullptr};
-    hipEvent_t ev_io[2] = {nullptr, nullptr};
+    PinBuf<char> h_io[2];
+    DevEvents<2> ev_io;
     bool io_busy[2] = {false, false};
     int io_slot = 0;
     std::string err, note;
-    // device bytes held by this object (every allocation goes through dalloc / dfree)
-    std::map<void*, size_t> dmem;
-    size_t dev_now = 0, dev_peak = 0;
-    size_t dev_limit = 0;                               // $MKT_BAM_DEVICE_LIMIT: device bytes this object may hold (as if HBM ended there)
     // out-of-core mode (mkt_bam_spill)
     bool spill_set = false, autob = false, spilled = false;
     uint64_t budget = 0;                                // text bytes per run; 0 = single pass
@@ -1087,17 +589,14 @@ struct mkt_bam {
     std::string tmp_path[2];                            // records, keys
     int tmp_fd[2] = {-1, -1};
     bool tmp_made[2] = {false, false};                  // created by this object (only those are removed)
-    char* h_stage = nullptr;                            // pinned staging of run data on its way to the temporary files
+    PinBuf<char> h_stage;                               // pinned staging of run data on its way to the temporary files
     uint64_t tmp_bytes = 0, nruns = 0, rounds = 0;
     std::vector<SpillRun> runs;
     std::vector<SpillCur> cur;
     bool hdr_ready = false;
     BamHeader H;
     RefTab rt{};
-    void* d_rt[4] = {nullptr, nullptr, nullptr, nullptr};
-    CrcTabs* d_ct = nullptr;
-    uint32_t* d_err = nullptr;
-    unsigned long long* d_nl = nullptr;
+    BamTabs tb;
     BgzfStream bs;
     BaiAcc bx;
     MergeBufs mb;
@@ -1118,59 +617,23 @@ static int bfail(mkt_bam* s, int code, const char* fmt, ...) {
 }
 #define BCHK(s, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bfail((s), MKT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); } while (0)
 
-static void dtrack(mkt_bam* s, void* p, size_t n) {
-    s->dmem[p] = n;
-    s->dev_now += n;
-    if (s->dev_now > s->dev_peak) s->dev_peak = s->dev_now;
+// `bytes` for a device buffer of this object: a new allocation / only if they do not fit yet (grow-only, contents not kept)
+template <typename T>
+static int dev_alloc(mkt_bam* s, LedgerBuf<T>& b, size_t bytes, bool grow = false) {
+    const hipError_t e = grow ? b.grow(s->led, bytes) : b.alloc(s->led, bytes);
+    if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+    return MKT_OK;
 }
-static hipError_t dalloc(mkt_bam* s, void** p, size_t n) {
-    *p = nullptr;
-    if (s->dev_limit && s->dev_now + n > s->dev_limit) return hipErrorOutOfMemory;
-    const hipError_t e = hipMalloc(p, n);
-    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return e; }
-    dtrack(s, *p, n);
-    return hipSuccess;
-}
+template <typename T>
+static int dev_grow(mkt_bam* s, LedgerBuf<T>& b, size_t bytes) { return dev_alloc(s, b, bytes, true); }
 static uint64_t device_free(mkt_bam* s) {                           // what this object may still allocate
     size_t fr = 0, tot = 0;
     (void)hipMemGetInfo(&fr, &tot);
-    if (s->dev_limit) { const uint64_t l = s->dev_limit > s->dev_now ? s->dev_limit - s->dev_now : 0; if (l < fr) fr = (size_t)l; }
+    if (s->led.limit) { const uint64_t l = s->led.limit > s->led.now ? s->led.limit - s->led.now : 0; if (l < fr) fr = (size_t)l; }
     return fr;
 }
-static void dfree(mkt_bam* s, void* p) {
-    if (!p) return;
-    auto it = s->dmem.find(p);
-    if (it != s->dmem.end()) { s->dev_now -= it->second; s->dmem.erase(it); }
-    (void)hipFree(p);
-}
-// a device buffer that only grows (its contents are not kept)
-template <typename T>
-static int dgrow(mkt_bam* s, T*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap && p) return MKT_OK;
-    dfree(s, p); p = nullptr; cap = 0;
-    const hipError_t e = dalloc(s, (void**)&p, bytes);
-    if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-    cap = bytes;
-    return MKT_OK;
-}
-// the device buffers of one function: freed when it returns, on every path, unless dropped before
-struct DevScope {
-    mkt_bam* s;
-    std::vector<void*> own;
-    explicit DevScope(mkt_bam* s_) : s(s_) {}
-    DevScope(const DevScope&) = delete;
-    DevScope& operator=(const DevScope&) = delete;
-    ~DevScope() { for (void* p : own) dfree(s, p); }
-    template <typename T>
-    int alloc(T*& p, size_t bytes) {
-        const hipError_t e = dalloc(s, (void**)&p, bytes);
-        if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-        own.push_back(p);
-        return MKT_OK;
-    }
-    void adopt(void* p, size_t bytes) { dtrack(s, p, bytes); own.push_back(p); }      // (a buffer that sort_line_index allocated)
-    void drop(void* p) { dfree(s, p); own.erase(std::remove(own.begin(), own.end(), p), own.end()); }
-};
+// the end of a conversion: what the object holds on the device besides the text and the BAM goes
+static void bam_release_work(mkt_bam* s) { s->bs = BgzfStream(); s->mb = MergeBufs(); s->bx = BaiAcc(); s->tb = BamTabs(); }
 struct PhaseMarks {                                    // MKT_VERBOSE: the time since the previous mark (call sites follow a stream synchronisation)
     bool on;
     std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
@@ -1188,12 +651,12 @@ static int bam_reserve(mkt_bam* s, size_t need) {
     size_t ncap = s->cap ? s->cap : ((size_t)64 << 20);
     if (!s->cap && s->budget && ncap > 2 * s->budget + ((size_t)1 << 20)) ncap = 2 * s->budget + ((size_t)1 << 20);     // runs: sized by the budget
     while (ncap < need) ncap *= 2;
-    uint8_t* nb = nullptr;
+    LedgerBuf<uint8_t> nb;
     // (doubling keeps old and new side by side during the copy; when that does not fit: just enough; when that does not either, the
     //  input is larger than one GPU takes -- text + records + compressed blocks are resident together, ~2.2 x the .sam: INTEGRATION.md)
-    hipError_t e = dalloc(s, (void**)&nb, ncap + 64);
-    if (e != hipSuccess) { ncap = need + ((size_t)64 << 20); e = dalloc(s, (void**)&nb, ncap + 64); }
-    if (e != hipSuccess) { ncap = need; e = dalloc(s, (void**)&nb, ncap + 64); }
+    hipError_t e = nb.alloc(s->led, ncap + 64);
+    if (e != hipSuccess) { ncap = need + ((size_t)64 << 20); e = nb.alloc(s->led, ncap + 64); }
+    if (e != hipSuccess) { ncap = need; e = nb.alloc(s->led, ncap + 64); }
     if (e != hipSuccess) {
         size_t fr = 0, tot = 0;
         (void)hipMemGetInfo(&fr, &tot);
@@ -1203,30 +666,10 @@ static int bam_reserve(mkt_bam* s, size_t need) {
     if (s->d_text) {
         BCHK(s, hipStreamSynchronize(s->stream));
         if (s->len > s->tstart) BCHK(s, hipMemcpy(nb, s->d_text + s->tstart, s->len - s->tstart, hipMemcpyDeviceToDevice));
-        dfree(s, s->d_text);
     }
     s->len -= s->tstart; s->tstart = 0;
-    s->d_text = nb; s->cap = ncap;
+    s->d_text = std::move(nb); s->cap = ncap;                   // (the old text goes here, after the copy)
     return MKT_OK;
-}
-static void crc_tables(CrcTabs* ct) {
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-        ct->t[i] = c;
-    }
-    auto mul = [](uint32_t a, uint32_t b) {
-        uint32_t m = 1u << 31, p = 0;
-        for (;;) {
-            if (a & m) { p ^= b; if ((a & (m - 1u)) == 0u) break; }
-            m >>= 1;
-            b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-        }
-        return p;
-    };
-    uint32_t p = 1u << 30;                              // x^1
-    ct->x2n[0] = p;
-    for (int k = 1; k < 32; ++k) { p = mul(p, p); ct->x2n[k] = p; }
 }
 static void put_le32(std::string& s, uint32_t v) { char b[4] = {(char)v, (char)(v >> 8), (char)(v >> 16), (char)(v >> 24)}; s.append(b, 4); }
 static void put_le64(std::string& s, uint64_t v) { put_le32(s, (uint32_t)v); put_le32(s, (uint32_t)(v >> 32)); }
@@ -1382,82 +825,16 @@ static void bai_assemble(mkt_bam* s, uint32_t nref, const std::vector<uint64_t>&
     }
 }
 static const char kNoIndexLongRef[] = "no index written: a reference is longer than the 2^29 bases a BAI index can address (samtools index would need -c)";
-static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static constexpr uint64_t kDzPerBlock = (uint64_t)DZ_WAVES * DZ_WAVE_SCRATCH * sizeof(uint32_t);     // deflate scratch per block of a launch
-// nblocks BGZF blocks of raw[0, nraw) -> comp (BGZF_STRIDE apart), their sizes -> csize; `batch` blocks per deflate launch
-static void bgzf_launch(const uint8_t* raw, uint64_t nraw, uint64_t nblocks, int level, const CrcTabs* ct, uint8_t* comp, uint64_t* csize, uint32_t* scratch,
-                        uint64_t batch, hipStream_t st) {
-    if (level > 0) {
-        for (uint64_t fb = 0; fb < nblocks; fb += batch) {
-            const unsigned g = (unsigned)(nblocks - fb < batch ? nblocks - fb : batch);
-            if (level >= 2) hipLaunchKernelGGL((k_bgzf_deflate<true, false>), dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch, ZsPieces{});
-            else hipLaunchKernelGGL((k_bgzf_deflate<false, false>), dim3(g), dim3(DZ_THREADS), 0, st, raw, nraw, fb, ct, comp, csize, scratch, ZsPieces{});
-        }
-    } else {
-        hipLaunchKernelGGL(k_bgzf_stored, dim3((unsigned)nblocks), dim3(BWG), 0, st, raw, nraw, ct, comp, csize);
-    }
-}
-
-// ---- the stream framing (mkt_zstream.h): the same kernels over a piece table
-namespace mkt {
-// level 0: one stored deflate block (BFINAL = 0) per piece
-__global__ __launch_bounds__(BWG) void k_zs_stored(const uint8_t* raw, ZsPieces zp, uint8_t* comp, uint64_t* csize) {
-    __shared__ uint32_t sh[BWG / 64];
-    const uint64_t p = blockIdx.x;
-    const uint8_t* src = raw + zp.off[p];
-    const uint32_t n = zp.len[p];
-    uint8_t* o = comp + p * kZsStride;
-    const uint32_t ad = block_adler<BWG>(src, n, sh);
-    if (threadIdx.x == 0) {
-        o[0] = 0; o[1] = (uint8_t)n; o[2] = (uint8_t)(n >> 8); o[3] = (uint8_t)~n; o[4] = (uint8_t)(~n >> 8);
-        csize[p] = n + 5u; zp.adler[p] = ad;
-    }
-    for (uint32_t i = threadIdx.x; i < n; i += BWG) o[5 + i] = src[i];
-}
-static_assert(kZsPiece == BGZF_RAW && kZsStride == BGZF_STRIDE, "a piece is what the deflate kernel takes as a block");
-size_t zs_scratch_bytes(uint64_t batch) { return (size_t)(batch * kDzPerBlock); }
-hipError_t zs_deflate(const uint8_t* raw, ZsPieces zp, uint64_t npieces, int level, uint8_t* comp, uint64_t* csize, uint32_t* scratch, uint64_t batch, hipStream_t st) {
-    if (npieces == 0) return hipSuccess;
-    if (level <= 0) hipLaunchKernelGGL(k_zs_stored, dim3((unsigned)npieces), dim3(BWG), 0, st, raw, zp, comp, csize);
-    else {
-        if (!scratch || batch == 0) return hipErrorInvalidValue;
-        for (uint64_t fb = 0; fb < npieces; fb += batch) {
-            const unsigned g = (unsigned)(npieces - fb < batch ? npieces - fb : batch);
-            if (level >= 2) hipLaunchKernelGGL((k_bgzf_deflate<true, true>), dim3(g), dim3(DZ_THREADS), 0, st, raw, (uint64_t)0, fb, (const CrcTabs*)nullptr, comp, csize, scratch, zp);
-            else hipLaunchKernelGGL((k_bgzf_deflate<false, true>), dim3(g), dim3(DZ_THREADS), 0, st, raw, (uint64_t)0, fb, (const CrcTabs*)nullptr, comp, csize, scratch, zp);
-        }
-    }
-    return hipGetLastError();
-}
-}  // namespace mkt
-
 // ---- the steps of a conversion: the single pass and the out-of-core mode both go through these -------------------------------
 // compress nblocks blocks of raw; csize becomes the blocks' compressed offsets, csize[nblocks] and (after a synchronisation)
 // *ctot their total.  The buffers and the launch batch are the caller's.
 static int bgzf_compress(mkt_bam* s, const uint8_t* raw, uint64_t nraw, uint64_t nblocks, int level, uint8_t* comp, uint64_t* csize, uint32_t* scratch,
                          uint64_t batch, uint64_t* ctot) {
     hipStream_t st = s->stream;
-    bgzf_launch(raw, nraw, nblocks, level, s->d_ct, comp, csize, scratch, batch, st);
-    BCHK(s, hipGetLastError());
+    BCHK(s, bgzf_launch(raw, nraw, nblocks, level, s->tb.ct, comp, csize, scratch, batch, st));
     BCHK(s, launch_exscan(csize, nblocks, csize + nblocks, st));
     BCHK(s, hipMemcpyAsync(ctot, csize + nblocks, sizeof *ctot, hipMemcpyDeviceToHost, st));
     return MKT_OK;
-}
-// the end of a conversion: what the object holds on the device besides the text and the BAM
-static void bam_free_device(mkt_bam* s) {
-    BgzfStream& b = s->bs;
-    for (void* p : {(void*)b.d_win, (void*)b.d_comp, (void*)b.d_csize, (void*)b.d_scratch, (void*)b.d_pack}) dfree(s, p);
-    b = BgzfStream();
-    MergeBufs& m = s->mb;
-    for (void* p : {(void*)m.rec, (void*)m.src, (void*)m.bytes, (void*)m.rA, (void*)m.rB, (void*)m.hist, (void*)m.off, (void*)m.idx}) dfree(s, p);
-    m = MergeBufs();
-    BaiAcc& x = s->bx;
-    for (void* p : {(void*)x.d_lin_off, (void*)x.d_lin, (void*)x.d_nocoor, (void*)x.d_refs, (void*)x.d_prev, (void*)x.d_hflag, (void*)x.d_heads}) dfree(s, p);
-    x = BaiAcc();
-    for (int k = 0; k < 4; ++k) { dfree(s, s->d_rt[k]); s->d_rt[k] = nullptr; }
-    dfree(s, s->d_ct); s->d_ct = nullptr;
-    dfree(s, s->d_err); s->d_err = nullptr;
-    dfree(s, s->d_nl); s->d_nl = nullptr;
 }
 // the header is known (the first alignment line has arrived, or the input has ended): parse it once, put the name table, the
 // CRC tables and the error word on the device
@@ -1471,18 +848,18 @@ static int bam_setup(mkt_bam* s, bool sorted) {
     const size_t sz[4] = {H.tcap * sizeof(unsigned long long), H.tcap * sizeof(int32_t), (nref + 1) * sizeof(uint32_t), H.blob.size() + 16};
     const void* src[4] = {H.th.data(), H.tidv.data(), H.noff.data(), H.blob.data()};
     for (int k = 0; k < 4; ++k) {
-        BCHK(s, dalloc(s, &s->d_rt[k], sz[k]));
-        if (k < 3 || !H.blob.empty()) BCHK(s, hipMemcpyAsync(s->d_rt[k], src[k], k < 3 ? sz[k] : H.blob.size(), hipMemcpyHostToDevice, st));
+        BCHK(s, s->tb.rt[k].alloc(s->led, sz[k]));
+        if (k < 3 || !H.blob.empty()) BCHK(s, hipMemcpyAsync(s->tb.rt[k], src[k], k < 3 ? sz[k] : H.blob.size(), hipMemcpyHostToDevice, st));
     }
     CrcTabs ct;
     crc_tables(&ct);
-    BCHK(s, dalloc(s, (void**)&s->d_ct, sizeof(CrcTabs)));
-    BCHK(s, dalloc(s, (void**)&s->d_err, 256));
-    BCHK(s, hipMemcpyAsync(s->d_ct, &ct, sizeof ct, hipMemcpyHostToDevice, st));
-    BCHK(s, hipMemsetAsync(s->d_err, 0, 256, st));
+    BCHK(s, s->tb.ct.alloc(s->led, sizeof(CrcTabs)));
+    BCHK(s, s->tb.err.alloc(s->led, 256));
+    BCHK(s, hipMemcpyAsync(s->tb.ct, &ct, sizeof ct, hipMemcpyHostToDevice, st));
+    BCHK(s, hipMemsetAsync(s->tb.err, 0, 256, st));
     BCHK(s, hipStreamSynchronize(st));
-    s->rt.hash = (const unsigned long long*)s->d_rt[0]; s->rt.id = (const int32_t*)s->d_rt[1]; s->rt.name_off = (const uint32_t*)s->d_rt[2];
-    s->rt.names = (const uint8_t*)s->d_rt[3]; s->rt.mask = H.tcap - 1; s->rt.nref = nref;
+    s->rt.hash = (const unsigned long long*)s->tb.rt[0].get(); s->rt.id = (const int32_t*)s->tb.rt[1].get(); s->rt.name_off = (const uint32_t*)s->tb.rt[2].get();
+    s->rt.names = (const uint8_t*)s->tb.rt[3].get(); s->rt.mask = H.tcap - 1; s->rt.nref = nref;
     s->hdr_ready = true;
     return MKT_OK;
 }
@@ -1494,38 +871,39 @@ static int bam_key_bits(const mkt_bam* s) {
     return 33 + tbits;
 }
 // resident text (whole lines) as records: the line starts, the keys in output order, the records' sizes and their offsets in
-// the output (off[nl] = total).  The buffers belong to the caller's scope.
+// the output (off[nl] = total).  The buffers go with the struct, or earlier where the caller resets them.
 struct BamRecs {
-    uint64_t* d_starts = nullptr;
-    SortRec *rA = nullptr, *rB = nullptr;             // (rB: the sort's other buffer)
-    uint32_t* d_size = nullptr;
-    uint64_t* d_off = nullptr;
+    LedgerBuf<uint64_t> d_starts, d_off;
+    LedgerBuf<SortRec> rA, rB;                        // (rB and d_hist: the sort's other buffer and its histograms)
+    LedgerBuf<uint32_t> d_size, d_hist;
     uint64_t nl = 0, total = 0;
     unsigned grid() const { return (unsigned)((nl + 255) / 256); }
 };
-static int bam_records(mkt_bam* s, DevScope& own, const uint8_t* text, uint64_t len, bool sorted, PhaseMarks& mark, BamRecs* out) {
+static int bam_records(mkt_bam* s, const uint8_t* text, uint64_t len, bool sorted, PhaseMarks& mark, BamRecs* out) {
     hipStream_t st = s->stream;
     BamRecs& R = *out;
     int rc;
     if (len) {
-        const hipError_t e = sort_line_index(text, len, st, &R.d_starts, &R.nl);
+        uint64_t* starts = nullptr;
+        const hipError_t e = sort_line_index(text, len, st, &starts, &R.nl);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return bfail(s, MKT_E_NOMEM, "the line index does not fit beside the text"); }
         if (e != hipSuccess) return bfail(s, MKT_E_HIP, "sort_line_index failed: %s", hipGetErrorString(e));
-        own.adopt(R.d_starts, (R.nl + 2) * sizeof(uint64_t));
+        R.d_starts.adopt(s->led, starts, (R.nl + 2) * sizeof(uint64_t));
     }
     mark("header + line index");
     const uint64_t nl = R.nl;
     if (nl >= (1ull << 32) - 1) return bfail(s, MKT_E_ARG, "%llu lines: records are indexed with 32 bits", (unsigned long long)nl);
     if (!nl) return MKT_OK;
-    if ((rc = own.alloc(R.rA, (nl + 1) * sizeof(SortRec))) || (rc = own.alloc(R.d_size, (nl + 1) * sizeof(uint32_t))) || (rc = own.alloc(R.d_off, (nl + 2) * sizeof(uint64_t)))) return rc;
-    hipLaunchKernelGGL(k_bam_keys, dim3(R.grid()), dim3(256), 0, st, text, (const uint64_t*)R.d_starts, nl, s->rt, R.rA, R.d_size, s->d_err);
+    if ((rc = dev_alloc(s, R.rA, (nl + 1) * sizeof(SortRec))) || (rc = dev_alloc(s, R.d_size, (nl + 1) * sizeof(uint32_t))) || (rc = dev_alloc(s, R.d_off, (nl + 2) * sizeof(uint64_t)))) return rc;
+    hipLaunchKernelGGL(k_bam_keys, dim3(R.grid()), dim3(256), 0, st, text, (const uint64_t*)R.d_starts, nl, s->rt, R.rA, R.d_size, s->tb.err);
     if (sorted) {
-        uint32_t* d_hist = nullptr;
-        if ((rc = own.alloc(R.rB, (nl + 1) * sizeof(SortRec))) || (rc = own.alloc(d_hist, kSortHistBytes))) return rc;
-        sort_radix_passes(R.rA, R.rB, nl, d_hist, 1, 0, bam_key_bits(s), st);
+        if ((rc = dev_alloc(s, R.rB, (nl + 1) * sizeof(SortRec))) || (rc = dev_alloc(s, R.d_hist, kSortHistBytes))) return rc;
+        SortRec *a = R.rA, *b = R.rB;
+        sort_radix_passes(a, b, nl, R.d_hist, 1, 0, bam_key_bits(s), st);
+        if (a != R.rA.get()) std::swap(R.rA, R.rB);                 // (the passes leave the result in `a`: rA holds it, as before)
     }
     uint32_t herr = 0;
-    BCHK(s, hipMemcpyAsync(&herr, s->d_err, sizeof herr, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipMemcpyAsync(&herr, s->tb.err, sizeof herr, hipMemcpyDeviceToHost, st));
     BCHK(s, hipStreamSynchronize(st));
     if (herr) return bfail(s, MKT_E_ARG, "not SAM alignment text (error bits 0x%x: 1 fewer than 11 fields, 2 reference name not in the header, 4 number, 8 CIGAR, 16 optional field, 32 SEQ / QUAL lengths, 64 QNAME length)", herr);
     mark(sorted ? "keys + radix sort" : "keys");
@@ -1537,7 +915,7 @@ static int bam_records(mkt_bam* s, DevScope& own, const uint8_t* text, uint64_t 
 }
 // the records' bytes -> dst (at their offsets), their index fields -> d_idx
 static void bam_write(mkt_bam* s, const uint8_t* text, const BamRecs& R, uint8_t* dst, BamIdx* d_idx) {
-    hipLaunchKernelGGL(k_bam_write, dim3(R.grid()), dim3(256), 0, s->stream, text, (const uint64_t*)R.d_starts, R.nl, s->rt, (const SortRec*)R.rA, (const uint64_t*)R.d_off, dst, d_idx, s->d_err);
+    hipLaunchKernelGGL(k_bam_write, dim3(R.grid()), dim3(256), 0, s->stream, text, (const uint64_t*)R.d_starts, R.nl, s->rt, (const SortRec*)R.rA, (const uint64_t*)R.d_off, dst, d_idx, s->tb.err);
 }
 
 // ---- the index (coordinate order only; the format ends at 2^29 bases per reference -- longer ones would need a CSI index: none
@@ -1555,11 +933,11 @@ static int bai_begin(mkt_bam* s) {
     const uint64_t nlin = x.lin_off[nref];
     std::vector<BaiRef> init(nref);
     for (auto& r : init) { r.n_mapped = 0; r.n_unmapped = 0; r.beg = ~0ull; r.end = 0; }
-    BCHK(s, dalloc(s, (void**)&x.d_lin_off, (nref + 1) * sizeof(uint64_t)));
-    BCHK(s, dalloc(s, (void**)&x.d_lin, (nlin + 1) * sizeof(unsigned long long)));
-    BCHK(s, dalloc(s, (void**)&x.d_refs, (nref + 1) * sizeof(BaiRef)));
-    BCHK(s, dalloc(s, (void**)&x.d_nocoor, 256));
-    BCHK(s, dalloc(s, (void**)&x.d_prev, sizeof(BamIdx) + 64));
+    BCHK(s, x.d_lin_off.alloc(s->led, (nref + 1) * sizeof(uint64_t)));
+    BCHK(s, x.d_lin.alloc(s->led, (nlin + 1) * sizeof(unsigned long long)));
+    BCHK(s, x.d_refs.alloc(s->led, (nref + 1) * sizeof(BaiRef)));
+    BCHK(s, x.d_nocoor.alloc(s->led, 256));
+    BCHK(s, x.d_prev.alloc(s->led, sizeof(BamIdx) + 64));
     BCHK(s, hipMemcpyAsync(x.d_lin_off, x.lin_off.data(), (nref + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     BCHK(s, hipMemsetAsync(x.d_lin, 0xFF, (nlin + 1) * sizeof(unsigned long long), st));
     if (nref) BCHK(s, hipMemcpyAsync(x.d_refs, init.data(), nref * sizeof(BaiRef), hipMemcpyHostToDevice, st));
@@ -1574,8 +952,8 @@ static int bai_window(mkt_bam* s, const BaiWin& w, const VoffMap& vm, const uint
     hipStream_t st = s->stream;
     const uint64_t n = w.n;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    const BamIdx* prev = x.has_prev ? x.d_prev : nullptr;
-    int rc = dgrow(s, x.d_hflag, x.hflag_cap, (n + 2) * sizeof(uint64_t));
+    const BamIdx* prev = x.has_prev ? x.d_prev.get() : nullptr;
+    int rc = dev_grow(s, x.d_hflag, (n + 2) * sizeof(uint64_t));
     if (rc) return rc;
     hipLaunchKernelGGL(k_bai, dim3(grid), dim3(256), 0, st, w.idx, w.off, n, vm, coff, (const uint64_t*)x.d_lin_off, s->rt.nref, x.d_lin, x.d_refs, x.d_hflag, x.d_nocoor, prev);
     BCHK(s, hipGetLastError());
@@ -1584,7 +962,7 @@ static int bai_window(mkt_bam* s, const BaiWin& w, const VoffMap& vm, const uint
     BCHK(s, hipMemcpyAsync(&nheads, x.d_hflag + n, sizeof nheads, hipMemcpyDeviceToHost, st));
     BCHK(s, hipStreamSynchronize(st));
     if (nheads) {
-        if ((rc = dgrow(s, x.d_heads, x.heads_cap, (nheads + 1) * sizeof(BaiHead)))) return rc;
+        if ((rc = dev_grow(s, x.d_heads, (nheads + 1) * sizeof(BaiHead)))) return rc;
         hipLaunchKernelGGL(k_bai_heads, dim3(grid), dim3(256), 0, st, w.idx, w.off, n, vm, coff, (const uint64_t*)x.d_hflag, x.d_heads, prev);
         BCHK(s, hipGetLastError());
         const size_t h0 = x.heads.size();
@@ -1656,7 +1034,7 @@ static int write_all(mkt_bam* s, int k, const void* p, size_t n) {
 }
 // device bytes -> temporary file k, 64 MiB at a time through pinned memory
 static int write_dev(mkt_bam* s, int k, const void* d, uint64_t n) {
-    if (!s->h_stage) BCHK(s, hipHostMalloc((void**)&s->h_stage, kBamIoCap, hipHostMallocDefault));
+    if (!s->h_stage) BCHK(s, s->h_stage.alloc(kBamIoCap));
     for (uint64_t o = 0; o < n; o += kBamIoCap) {
         const size_t m = (size_t)(n - o < kBamIoCap ? n - o : kBamIoCap);
         BCHK(s, hipMemcpyAsync(s->h_stage, (const char*)d + o, m, hipMemcpyDeviceToHost, s->stream));
@@ -1693,16 +1071,15 @@ static int spill_begin(mkt_bam* s) {
 static int bs_reserve(mkt_bam* s, uint64_t n) {                  // room for n more bytes after the carry
     BgzfStream& b = s->bs;
     const size_t need = b.carry + n + 64;                          // (the deflate kernel reads up to 15 bytes past a block's end)
-    if (need <= b.cap) return MKT_OK;
-    size_t ncap = b.cap ? b.cap : ((size_t)1 << 20);
+    if (need <= b.d_win.bytes()) return MKT_OK;
+    size_t ncap = b.d_win.bytes() ? b.d_win.bytes() : ((size_t)1 << 20);
     while (ncap < need) ncap *= 2;
-    uint8_t* nb = nullptr;
-    const hipError_t e = dalloc(s, (void**)&nb, ncap);
-    if (e != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of %zu bytes failed: %s", ncap, hipGetErrorString(e));
+    LedgerBuf<uint8_t> nb;
+    const int rc = dev_alloc(s, nb, ncap);
+    if (rc) return rc;
     if (b.carry) BCHK(s, hipMemcpyAsync(nb, b.d_win, b.carry, hipMemcpyDeviceToDevice, s->stream));
     BCHK(s, hipStreamSynchronize(s->stream));
-    dfree(s, b.d_win);
-    b.d_win = nb; b.cap = ncap;
+    b.d_win = std::move(nb);                                       // (the old window goes here, after the synchronisation)
     return MKT_OK;
 }
 // n_new bytes have been put after the carry: compress the complete blocks (all of them when final), reduce the window's records
@@ -1714,25 +1091,24 @@ static int bs_commit(mkt_bam* s, uint64_t n_new, bool final, const BaiWin* w) {
     const uint64_t nfull = final ? (len + BGZF_RAW - 1) / BGZF_RAW : len / BGZF_RAW;
     const uint64_t nraw = final ? len : nfull * BGZF_RAW;
     const VoffMap vm{b.blk0 * BGZF_RAW + b.carry, b.blk0, b.cbase};
-    int rc = dgrow(s, b.d_csize, b.csize_cap, (nfull + 2) * sizeof(uint64_t));
+    int rc = dev_grow(s, b.d_csize, (nfull + 2) * sizeof(uint64_t));
     if (rc) return rc;
     uint64_t ctot = 0;
     if (nfull) {
-        rc = dgrow(s, b.d_comp, b.comp_cap, nfull * (uint64_t)BGZF_STRIDE + 64);
+        rc = dev_grow(s, b.d_comp, nfull * (uint64_t)BGZF_STRIDE + 64);
         if (rc) return rc;
         uint64_t cap_b = s->budget / (4 * (uint64_t)BGZF_RAW);       // blocks per deflate launch: the scratch follows the budget
         cap_b = cap_b < 16 ? 16 : (cap_b > 2048 ? 2048 : cap_b);
         const uint64_t batch = nfull < cap_b ? nfull : cap_b;
-        if (s->sp_level > 0 && (rc = dgrow(s, b.d_scratch, b.scratch_cap, batch * kDzPerBlock + 64))) return rc;
+        if (s->sp_level > 0 && (rc = dev_grow(s, b.d_scratch, deflate_scratch_bytes(batch) + 64))) return rc;
         if ((rc = bgzf_compress(s, b.d_win, nraw, nfull, s->sp_level, b.d_comp, b.d_csize, b.d_scratch, batch, &ctot))) return rc;
     } else BCHK(s, hipMemsetAsync(b.d_csize, 0, 2 * sizeof(uint64_t), st));
     if (w && (rc = bai_window(s, *w, vm, b.d_csize))) return rc;
     if (final && (rc = bai_data_end(s, b.blk0 * BGZF_RAW + len, vm, b.d_csize))) return rc;
     BCHK(s, hipStreamSynchronize(st));
     if (ctot) {
-        if ((rc = dgrow(s, b.d_pack, b.pack_cap, ctot + 64))) return rc;
-        hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)nfull), dim3(BWG), 0, st, (const uint8_t*)b.d_comp, (const uint64_t*)b.d_csize, nfull, b.d_pack);
-        BCHK(s, hipGetLastError());
+        if ((rc = dev_grow(s, b.d_pack, ctot + 64))) return rc;
+        BCHK(s, bgzf_pack(b.d_comp, b.d_csize, nfull, b.d_pack, st));
         if (s->outq_pos == s->outq.size()) { s->outq.clear(); s->outq_pos = 0; }
         const size_t q0 = s->outq.size();
         s->outq.resize(q0 + ctot);
@@ -1756,15 +1132,15 @@ static int bs_commit(mkt_bam* s, uint64_t n_new, bool final, const BaiWin* w) {
 static int find_nl(mkt_bam* s, uint64_t a, uint64_t b, bool first, uint64_t* pos /* position + 1; 0 = none */) {
     *pos = 0;
     if (a >= b) return MKT_OK;
-    if (!s->d_nl) BCHK(s, dalloc(s, (void**)&s->d_nl, 64));
+    if (!s->tb.nl) BCHK(s, s->tb.nl.alloc(s->led, 64));
     hipStream_t st = s->stream;
-    BCHK(s, hipMemsetAsync(s->d_nl, first ? 0xFF : 0, sizeof(unsigned long long), st));
+    BCHK(s, hipMemsetAsync(s->tb.nl, first ? 0xFF : 0, sizeof(unsigned long long), st));
     const uint64_t want = (b - a + 255) / 256;
     const unsigned grid = (unsigned)(want < 1024 ? want : 1024);
-    hipLaunchKernelGGL(k_find_nl, dim3(grid), dim3(256), 0, st, (const uint8_t*)s->d_text, a, b, first ? 1 : 0, s->d_nl);
+    hipLaunchKernelGGL(k_find_nl, dim3(grid), dim3(256), 0, st, (const uint8_t*)s->d_text, a, b, first ? 1 : 0, s->tb.nl);
     BCHK(s, hipGetLastError());
     unsigned long long v = 0;
-    BCHK(s, hipMemcpyAsync(&v, s->d_nl, sizeof v, hipMemcpyDeviceToHost, st));
+    BCHK(s, hipMemcpyAsync(&v, s->tb.nl, sizeof v, hipMemcpyDeviceToHost, st));
     BCHK(s, hipStreamSynchronize(st));
     *pos = (first && v == ~0ull) ? 0 : v;
     return MKT_OK;
@@ -1777,17 +1153,16 @@ static int spill_form(mkt_bam* s, uint64_t a, uint64_t b) {
     hipStream_t st = s->stream;
     const bool sorted = s->sp_sorted != 0;
     const uint8_t* text = s->d_text + a;
-    DevScope own(s);
     PhaseMarks quiet{false};
     BamRecs R;
-    if ((rc = bam_records(s, own, text, b - a, sorted, quiet, &R))) return rc;
+    if ((rc = bam_records(s, text, b - a, sorted, quiet, &R))) return rc;
     const uint64_t nl = R.nl, total = R.total;
-    BamIdx* d_idx = nullptr;
-    if ((rc = own.alloc(d_idx, (nl + 1) * sizeof(BamIdx)))) return rc;
+    LedgerBuf<BamIdx> d_idx;
+    LedgerBuf<uint8_t> d_raw;                                      // (these three go when the function returns)
+    LedgerBuf<SpillRec> d_rec;
+    if ((rc = dev_alloc(s, d_idx, (nl + 1) * sizeof(BamIdx)))) return rc;
     if (sorted) {
-        uint8_t* d_raw = nullptr;
-        SpillRec* d_rec = nullptr;
-        if ((rc = own.alloc(d_raw, total + 64)) || (rc = own.alloc(d_rec, (nl + 1) * sizeof(SpillRec)))) return rc;
+        if ((rc = dev_alloc(s, d_raw, total + 64)) || (rc = dev_alloc(s, d_rec, (nl + 1) * sizeof(SpillRec)))) return rc;
         bam_write(s, text, R, d_raw, d_idx);
         hipLaunchKernelGGL(k_spill_recs, dim3(R.grid()), dim3(256), 0, st, (const SortRec*)R.rA, (const uint32_t*)R.d_size, (const BamIdx*)d_idx, nl, d_rec);
         BCHK(s, hipGetLastError());
@@ -1886,7 +1261,7 @@ static int merge_finish(mkt_bam* s) {
     const int rc = bai_end(s);
     if (rc) return rc;
     spill_remove(s);
-    bam_free_device(s);
+    bam_release_work(s);
     s->merging = false;
     s->done = true;
     if (getenv("MKT_VERBOSE"))
@@ -1952,10 +1327,10 @@ static int merge_round(mkt_bam* s) {
     hipStream_t st = s->stream;
     MergeBufs& m = s->mb;
     if (n) {
-        if ((rc = dgrow(s, m.rec, m.rec_cap, (n + 1) * sizeof(SpillRec))) || (rc = dgrow(s, m.src, m.src_cap, (n + 1) * sizeof(uint64_t))) ||
-            (rc = dgrow(s, m.bytes, m.bytes_cap, nb + 64)) || (rc = dgrow(s, m.rA, m.rA_cap, (n + 1) * sizeof(SortRec))) ||
-            (rc = dgrow(s, m.rB, m.rB_cap, (n + 1) * sizeof(SortRec))) || (rc = dgrow(s, m.hist, m.hist_cap, kSortHistBytes)) ||
-            (rc = dgrow(s, m.off, m.off_cap, (n + 2) * sizeof(uint64_t))) || (rc = dgrow(s, m.idx, m.idx_cap, (n + 1) * sizeof(BamIdx))) ||
+        if ((rc = dev_grow(s, m.rec, (n + 1) * sizeof(SpillRec))) || (rc = dev_grow(s, m.src, (n + 1) * sizeof(uint64_t))) ||
+            (rc = dev_grow(s, m.bytes, nb + 64)) || (rc = dev_grow(s, m.rA, (n + 1) * sizeof(SortRec))) ||
+            (rc = dev_grow(s, m.rB, (n + 1) * sizeof(SortRec))) || (rc = dev_grow(s, m.hist, kSortHistBytes)) ||
+            (rc = dev_grow(s, m.off, (n + 2) * sizeof(uint64_t))) || (rc = dev_grow(s, m.idx, (n + 1) * sizeof(BamIdx))) ||
             (rc = bs_reserve(s, nb)))
             return rc;
         BCHK(s, hipMemcpyAsync(m.rec, hrec.data(), n * sizeof(SpillRec), hipMemcpyHostToDevice, st));
@@ -1999,8 +1374,8 @@ int mkt_bam_create(int device, mkt_bam** out) {
     if (device < 0 || device >= ndev) return MKT_E_ARG;
     mkt_bam* s = new mkt_bam();
     s->device = device;
-    if (const char* e = getenv("MKT_BAM_DEVICE_LIMIT")) s->dev_limit = (size_t)strtoull(e, nullptr, 10);
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { delete s; return MKT_E_HIP; }
+    if (const char* e = getenv("MKT_BAM_DEVICE_LIMIT")) s->led.limit = (size_t)strtoull(e, nullptr, 10);
+    if (hipSetDevice(device) != hipSuccess || s->stream.create(hipStreamNonBlocking) != hipSuccess) { delete s; return MKT_E_HIP; }
     *out = s;
     return MKT_OK;
 }
@@ -2009,13 +1384,7 @@ void mkt_bam_destroy(mkt_bam* s) {
     (void)hipSetDevice(s->device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     spill_remove(s);
-    bam_free_device(s);
-    if (s->d_text) dfree(s, s->d_text);
-    if (s->d_bam) dfree(s, s->d_bam);
-    for (int k = 0; k < 2; ++k) { if (s->h_io[k]) (void)hipHostFree(s->h_io[k]); if (s->ev_io[k]) (void)hipEventDestroy(s->ev_io[k]); }
-    if (s->h_stage) (void)hipHostFree(s->h_stage);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;                                                       // (the members release: device buffers, pinned memory, events, the stream last)
 }
 const char* mkt_bam_error(const mkt_bam* s) { return s ? s->err.c_str() : ""; }
 const char* mkt_bam_note(const mkt_bam* s) { return s ? s->note.c_str() : ""; }
@@ -2090,8 +1459,8 @@ int mkt_bam_reserve(mkt_bam* s, size_t bytes) {
 }
 static int bam_io_slot(mkt_bam* s, int k) {
     if (!s->h_io[k]) {
-        BCHK(s, hipHostMalloc((void**)&s->h_io[k], kBamIoCap, hipHostMallocDefault));
-        BCHK(s, hipEventCreateWithFlags(&s->ev_io[k], hipEventDisableTiming));
+        BCHK(s, s->h_io[k].alloc(kBamIoCap));
+        BCHK(s, s->ev_io.create(k, hipEventDisableTiming));
     }
     if (s->io_busy[k]) { BCHK(s, hipEventSynchronize(s->ev_io[k])); s->io_busy[k] = false; }
     return MKT_OK;
@@ -2138,12 +1507,12 @@ int mkt_bam_add_device(mkt_bam* s, const void* d_bytes, size_t n) {
 static int spill_run_end(mkt_bam* s) {
     int rc = spill_cut(s, true);
     if (rc) return rc;
-    dfree(s, s->d_text); s->d_text = nullptr; s->cap = s->len = 0; s->tstart = 0;
+    s->d_text.reset(); s->cap = s->len = 0; s->tstart = 0;
     if (getenv("MKT_VERBOSE"))
         fprintf(stderr, "[mkt_bam] %-28s %8.2f ms\n", (std::to_string(s->nruns) + (s->sp_sorted ? " runs formed" : " pieces converted")).c_str(), s->t_form);
     if (s->sp_sorted) return merge_begin(s);
     if ((rc = bs_commit(s, 0, true, nullptr))) return rc;
-    bam_free_device(s);
+    bam_release_work(s);
     s->done = true;
     return MKT_OK;
 }
@@ -2185,7 +1554,7 @@ static int bam_run(mkt_bam* s, int sorted, int level, uint64_t* records, uint64_
         rc = spill_cut(s, true);
         if (!rc && !s->spilled) rc = bfail(s, MKT_E_NOMEM, "no run could be formed");
     }
-    if (!s->spilled) bam_free_device(s);                           // the single pass has ended: only the BAM stays
+    if (!s->spilled) bam_release_work(s);                           // the single pass has ended: only the BAM stays
     if (rc) return rc;
     if (s->spilled) {
         if ((rc = spill_run_end(s))) return rc;
@@ -2205,64 +1574,62 @@ static int bam_single(mkt_bam* s, int sorted, int level, bool verbose) {
     int rc = bam_setup(s, sorted != 0);
     if (rc) return rc;
     const uint64_t hdr_len = s->H.hdr.size();
-    DevScope own(s);
     BamRecs R;
-    if ((rc = bam_records(s, own, s->d_text, s->len, sorted != 0, mark, &R))) return rc;
+    if ((rc = bam_records(s, s->d_text, s->len, sorted != 0, mark, &R))) return rc;
     const uint64_t nl = R.nl, nraw = hdr_len + R.total;
     if (s->autob) {
         // "auto": does the rest of the pass fit?  Next the records and their index fields beside the text and the sort records; then,
         // with those gone, the compressed blocks, the deflate scratch, the packed BAM and the index's head flags.
         const uint64_t nblk = (nraw + BGZF_RAW - 1) / BGZF_RAW;
-        uint64_t batch = ((uint64_t)8 << 30) / kDzPerBlock;
+        uint64_t batch = ((uint64_t)8 << 30) / deflate_scratch_bytes(1);
         if (batch > nblk) batch = nblk;
         const uint64_t next = nraw + 64 + (nl + 1) * sizeof(BamIdx);
         const uint64_t freed = s->cap + 64 + (nl + 2) * sizeof(uint64_t) + (nl + 1) * (2 * sizeof(SortRec) + sizeof(uint32_t)) + kSortHistBytes;
-        const uint64_t later = 2 * nblk * (uint64_t)BGZF_STRIDE + (nblk + 2) * sizeof(uint64_t) + (level > 0 ? batch * kDzPerBlock : 0) + (nl + 2) * sizeof(uint64_t);
+        const uint64_t later = 2 * nblk * (uint64_t)BGZF_STRIDE + (nblk + 2) * sizeof(uint64_t) + (level > 0 ? deflate_scratch_bytes(batch) : 0) + (nl + 2) * sizeof(uint64_t);
         const uint64_t fr = device_free(s), slack = ((uint64_t)1 << 20) + (next + later) / 20;
         if (next + slack > fr || next + later + slack > fr + freed)
             return bfail(s, MKT_E_NOMEM, "the single pass does not fit this GPU (%.2f GB free beside the text)", (double)fr / 1e9);
     }
-    uint8_t* d_raw = nullptr;
-    BamIdx* d_idx = nullptr;
-    if ((rc = own.alloc(d_raw, nraw + 64))) return rc;
+    LedgerBuf<uint8_t> d_raw;
+    LedgerBuf<BamIdx> d_idx;
+    if ((rc = dev_alloc(s, d_raw, nraw + 64))) return rc;
     BCHK(s, hipMemcpyAsync(d_raw, s->H.hdr.data(), hdr_len, hipMemcpyHostToDevice, st));
     if (nl) {
-        if ((rc = own.alloc(d_idx, (nl + 1) * sizeof(BamIdx)))) return rc;
+        if ((rc = dev_alloc(s, d_idx, (nl + 1) * sizeof(BamIdx)))) return rc;
         bam_write(s, s->d_text, R, d_raw + hdr_len, d_idx);
         BCHK(s, hipGetLastError());
         BCHK(s, hipStreamSynchronize(st));
         mark("records");
         // the text and the sort records are no longer needed
-        own.drop(R.rA); if (R.rB) own.drop(R.rB); own.drop(R.d_size); own.drop(R.d_starts);
+        R.rA.reset(); R.rB.reset(); R.d_size.reset(); R.d_starts.reset();
     }
-    dfree(s, s->d_text); s->d_text = nullptr; s->cap = s->len = 0;
+    s->d_text.reset(); s->cap = s->len = 0;
 
     // ---- BGZF: the whole file at once, the packed bytes stay on the device (mkt_bam_fetch / _read)
     const uint64_t nblocks = (nraw + BGZF_RAW - 1) / BGZF_RAW;
-    uint8_t* d_comp = nullptr;
-    uint64_t* d_csize = nullptr;
-    uint32_t* d_scratch = nullptr;
-    if ((rc = own.alloc(d_comp, nblocks * (uint64_t)BGZF_STRIDE + 64)) || (rc = own.alloc(d_csize, (nblocks + 2) * sizeof(uint64_t)))) return rc;
+    LedgerBuf<uint8_t> d_comp;
+    LedgerBuf<uint64_t> d_csize;
+    LedgerBuf<uint32_t> d_scratch;
+    if ((rc = dev_alloc(s, d_comp, nblocks * (uint64_t)BGZF_STRIDE + 64)) || (rc = dev_alloc(s, d_csize, (nblocks + 2) * sizeof(uint64_t)))) return rc;
     // the token lists and bit streams of the blocks of one launch (levels 1, 2): at most 8 GB of scratch
-    uint64_t batch = ((uint64_t)8 << 30) / kDzPerBlock;
+    uint64_t batch = ((uint64_t)8 << 30) / deflate_scratch_bytes(1);
     if (batch > nblocks) batch = nblocks;
     if (batch < 1) batch = 1;
-    if (level > 0 && (rc = own.alloc(d_scratch, batch * kDzPerBlock + 64))) return rc;
+    if (level > 0 && (rc = dev_alloc(s, d_scratch, deflate_scratch_bytes(batch) + 64))) return rc;
     uint64_t clen = 0;
     if ((rc = bgzf_compress(s, d_raw, nraw, nblocks, level, d_comp, d_csize, d_scratch, batch, &clen))) return rc;
     BCHK(s, hipStreamSynchronize(st));
     mark(level > 0 ? "BGZF deflate" : "BGZF stored");
-    own.drop(d_raw);
-    if (d_scratch) own.drop(d_scratch);
-    { hipError_t e_ = dalloc(s, (void**)&s->d_bam, clen + 28 + 64); if (e_ != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of the BAM failed: %s", hipGetErrorString(e_)); }
-    hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)nblocks), dim3(BWG), 0, st, (const uint8_t*)d_comp, (const uint64_t*)d_csize, nblocks, s->d_bam);
+    d_raw.reset();
+    d_scratch.reset();
+    { hipError_t e_ = s->d_bam.alloc(s->led, clen + 28 + 64); if (e_ != hipSuccess) return bfail(s, MKT_E_NOMEM, "hipMalloc of the BAM failed: %s", hipGetErrorString(e_)); }
+    BCHK(s, bgzf_pack(d_comp, d_csize, nblocks, s->d_bam, st));
     BCHK(s, hipMemcpyAsync(s->d_bam + clen, kBgzfEof, 28, hipMemcpyHostToDevice, st));
-    BCHK(s, hipGetLastError());
     BCHK(s, hipStreamSynchronize(st));
     s->bam_len = clen + 28;
     s->records = nl;
     s->nruns = nl ? 1 : 0;
-    own.drop(d_comp);
+    d_comp.reset();
     mark("pack");
 
     // ---- BAI: one window over the whole file (after the compression: the virtual offsets need d_csize)
@@ -2350,7 +1717,7 @@ int mkt_bam_stats(const mkt_bam* s, uint64_t stats[5]) {
     if (!s || !stats) return MKT_E_ARG;
     stats[0] = s->nruns;
     stats[1] = s->tmp_bytes;
-    stats[2] = s->dev_peak;
+    stats[2] = s->led.peak;
     stats[3] = s->spilled ? s->out_total : s->bam_len;
     stats[4] = s->bai.size();
     return MKT_OK;

@@ -1,4 +1,4 @@
-// mkt_deflate_codes.h -- the code construction of the BGZF deflate kernel (k_bgzf_deflate in mkt_bam.hip), written once for
+// mkt_deflate_codes.h -- the code construction of the deflate kernel (k_bgzf_deflate in mkt_deflate.hip), written once for
 // the gfx950 kernel and for the host driver of the CPU tests (tests/host/deflate_codes.cpp): RFC 1951 length / distance symbols,
 // minimum-redundancy code lengths, the length limiter and the canonical codes.  Nothing here is a product CPU path: the library
 // only ever runs this code inside HIP kernels.

@@ -1,6 +1,6 @@
 // mkt_devbuf.h -- who frees device memory, pinned host memory, events and streams: a move-only owner per allocation, and the one
 // early return on a HIP error.  A struct of owners is released by `s = S()` or with the struct; a function that fails half way
-// leaks nothing.  Used by the matrix analyses and by the contexts of the C ABI.
+// leaks nothing.  Used by the matrix analyses, the contexts of the C ABI and sam2bam.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -90,6 +90,46 @@ public:
     operator T*() const { return b_.get(); }
 };
 template <typename T> using PinGrowBuf = GrowBuf<T, PinMem>;
+
+// Device bytes that one object holds, where that sum decides something (sam2bam spills by it: DESIGN.md 6c).  limit 0: none.
+struct DevLedger { size_t now = 0, peak = 0, limit = 0; };
+// An owner whose bytes (the caller's formula, pads included) are charged to a ledger on allocation or adoption and credited on release.
+template <typename T>
+class LedgerBuf {
+    DevLedger* l_ = nullptr;
+    T* p_ = nullptr;
+    size_t bytes_ = 0;
+    void take(DevLedger& l, T* p, size_t bytes) { l_ = &l; p_ = p; bytes_ = bytes; l.now += bytes; if (l.now > l.peak) l.peak = l.now; }
+
+public:
+    LedgerBuf() = default;
+    LedgerBuf(const LedgerBuf&) = delete;
+    LedgerBuf& operator=(const LedgerBuf&) = delete;
+    LedgerBuf(LedgerBuf&& o) noexcept : l_(o.l_), p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    LedgerBuf& operator=(LedgerBuf&& o) noexcept {
+        if (this != &o) { reset(); l_ = o.l_; p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; }
+        return *this;
+    }
+    ~LedgerBuf() { reset(); }
+    // what was held is released first.  Refused with hipErrorOutOfMemory BEFORE any hipMalloc where the ledger's limit would be
+    // exceeded; a hipMalloc that fails leaves no pending error.  Either way the buffer is empty afterwards.
+    hipError_t alloc(DevLedger& l, size_t bytes) {
+        reset();
+        if (l.limit && l.now + bytes > l.limit) return hipErrorOutOfMemory;
+        T* p = nullptr;
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+        take(l, p, bytes);
+        return hipSuccess;
+    }
+    // a buffer that only grows, contents not kept: nothing when `bytes` fit, else alloc
+    hipError_t grow(DevLedger& l, size_t bytes) { return p_ && bytes <= bytes_ ? hipSuccess : alloc(l, bytes); }
+    void adopt(DevLedger& l, T* p, size_t bytes) { reset(); take(l, p, bytes); }      // memory that another module allocated for its caller
+    void reset() { if (p_) { l_->now -= bytes_; (void)hipFree(p_); } p_ = nullptr; bytes_ = 0; }
+    size_t bytes() const { return bytes_; }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
 
 // the same for the events a call times its phases with (flags 0: hipEventCreate)
 template <int N>

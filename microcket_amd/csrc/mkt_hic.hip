@@ -1,6 +1,6 @@
 // mkt_hic.hip -- the .hic container (include/mkt.h has the definition) from the resident cells of a matrix object: regroup the cells of
-// every resolution by chromosome pair and block, serialise the blocks, deflate them into zlib streams (mkt_zstream.h: the LZ77 + Huffman
-// stage of mkt_bam.hip under its second framing) and place them in the file image; the host writes the header, the matrix records, the
+// every resolution by chromosome pair and block, serialise the blocks, deflate them into zlib streams (mkt_deflate.h: the LZ77 + Huffman
+// stage of mkt_deflate.hip under its zlib framing) and place them in the file image; the host writes the header, the matrix records, the
 // footer and the normalisation vectors around them.  mkt_matrix.hip has the entry points (mkt_matrix_hic, mkt_matrix_fetch_hic).
 //
 // Per resolution, from cells that are strictly ascending in (bin1, bin2), that is in (pair, x, y):
@@ -28,7 +28,7 @@
 #include "mkt_hic.h"
 #include "mkt_launch.h"
 #include "mkt_segred.h"
-#include "mkt_zstream.h"
+#include "mkt_deflate.h"
 
 namespace mkt {
 
@@ -292,7 +292,7 @@ static int hic_resolution(const HicResIn& in, const std::vector<uint32_t>& lens,
     HIC_HIP(out.comp.alloc(npieces * (uint64_t)kZsStride, 64)); HIC_HIP(out.csize.alloc(npieces)); HIC_HIP(out.sadler.alloc(nblk));
     const uint64_t batch = std::min<uint64_t>(npieces, 1024);
     DevBuf<uint32_t> scratch;
-    if (o.level > 0) HIC_HIP(scratch.alloc(0, zs_scratch_bytes(batch)));
+    if (o.level > 0) HIC_HIP(scratch.alloc(0, deflate_scratch_bytes(batch)));
     HIC_HIP(hipMemsetAsync(raw, 0, raw_room + 64, st));                          // (the room between payloads: read by the 16-byte loads, never coded)
     hipLaunchKernelGGL(k_hic_pieces, dim3(grid_for(nblk, HWG)), dim3(HWG), 0, st, (const uint64_t*)psize, (const uint64_t*)poff, (const uint64_t*)out.pfirst, nblk, piece_off.get(), piece_len.get());
     hipLaunchKernelGGL(k_hic_serialise, dim3(grid), dim3(HWG), 0, st, g, (const uint64_t*)bk, (const uint32_t*)yx, (const uint32_t*)cc, (const uint64_t*)scan, (const uint32_t*)bstart,

@@ -4,7 +4,7 @@ such a string at a chosen offset of the BAM's uncompressed stream.  Seeded, plai
 import random
 
 BGZF_RAW = 0xff00
-DZ_WAVES = 8                       # follows MKT_DZ_WAVES in microcket_amd/csrc/mkt_bam.hip
+DZ_WAVES = 8                       # follows MKT_DZ_WAVES in microcket_amd/csrc/mkt_deflate.hip
 DZ_Q = BGZF_RAW // DZ_WAVES        # bytes of a block that one wave parses: matches never leave a share
 REC_HEAD = 46                      # block_size 4 + fixed fields 32 + "r\0" 2 + tag XB:B:C 4 + count 4
 FILL = bytes([1, 2, 3, 7])         # filler alphabet: compressible, and never a run byte of the tests

@@ -1,5 +1,5 @@
 // devbuf_check.cpp -- the owning buffer types of microcket_amd/csrc/mkt_devbuf.h on a real device: growth with and without the
-// contents kept, failed allocations, moves, and the pinned counterparts.  One line per check; the first failed check ends the
+// contents kept, failed allocations, moves, the pinned counterparts, and the ledger-charged owner.  One line per check; the first failed check ends the
 // program with status 1 (nothing further is started on the device).  tests/test_gpu_devbuf.py runs it.
 #include <stdint.h>
 #include <stdio.h>
@@ -135,6 +135,60 @@ int main() {
         uint64_t* sp = s.get();
         PinBuf<uint64_t> t(std::move(s));
         check(t.get() == sp && s.get() == nullptr, "PinBuf: move-construction transfers");
+    }
+    {   // LedgerBuf: every byte charged to the ledger and credited again, the limit refuses before hipMalloc, grow keeps what fits
+        DevLedger L;
+        {
+            LedgerBuf<uint64_t> a, b;
+            check(a.get() == nullptr && a.bytes() == 0 && L.now == 0 && L.peak == 0, "a new ledger buffer is empty, the ledger at 0");
+            hip_ok(a.alloc(L, 8000 + 64), "LedgerBuf::alloc(8064)");
+            check(a.get() != nullptr && a.bytes() == 8064 && L.now == 8064 && L.peak == 8064, "alloc charges its bytes, pad included");
+            hip_ok(hipMemcpy(a.get(), pat.data(), 8000, hipMemcpyHostToDevice), "upload");
+            uint64_t* before = a.get();
+            hip_ok(a.grow(L, 8064), "grow of what fits");
+            hip_ok(a.grow(L, 100), "grow of less");
+            check(a.get() == before && a.bytes() == 8064 && L.now == 8064 && holds(a.get(), pat), "grow of what fits keeps pointer, size, contents and ledger");
+            hip_ok(b.alloc(L, 1000), "second alloc");
+            check(L.now == 9064 && L.peak == 9064, "two buffers: the ledger holds their sum");
+            hip_ok(a.grow(L, 16000), "grow(16000)");
+            check(a.bytes() == 16000 && L.now == 17000 && L.peak == 17000, "grow frees first, then allocates: no moment with both sizes in the ledger");
+            b.reset();
+            check(b.get() == nullptr && b.bytes() == 0 && L.now == 16000 && L.peak == 17000, "reset credits; the peak stays");
+            b.reset();
+            check(L.now == 16000, "a second reset credits nothing");
+            // the limit: refused before any hipMalloc (a request the runtime could serve), nothing charged, what was held released first
+            L.limit = 20000;
+            hip_ok(b.alloc(L, 4000), "alloc up to the limit exactly");
+            check(L.now == 20000, "an allocation that reaches the limit exactly is allowed");
+            const hipError_t e = b.alloc(L, 4001);
+            check(e == hipErrorOutOfMemory && b.get() == nullptr && b.bytes() == 0 && L.now == 16000, "one byte past the limit: out of memory, the buffer empty, its old bytes credited");
+            check(hipGetLastError() == hipSuccess, "a refusal by the limit is not a HIP error");
+            const hipError_t e2 = a.grow(L, 16001 + 4000);
+            check(e2 == hipErrorOutOfMemory && a.get() == nullptr && L.now == 0, "grow past the limit: the contents are dropped first, as for any growth");
+            L.limit = 0;
+            const hipError_t e3 = a.alloc(L, (size_t)1 << 60);
+            check(e3 == hipErrorOutOfMemory && a.get() == nullptr && L.now == 0, "hipMalloc of 2^60 bytes: out of memory, nothing charged");
+            check(hipGetLastError() == hipSuccess, "after a failed hipMalloc no error is pending");
+            // adoption and moves
+            uint64_t* raw = nullptr;
+            hip_ok(hipMalloc((void**)&raw, 512), "hipMalloc(512)");
+            a.adopt(L, raw, 512);
+            check(a.get() == raw && a.bytes() == 512 && L.now == 512, "adopt charges the size it is given");
+            LedgerBuf<uint64_t> c(std::move(a));
+            check(c.get() == raw && c.bytes() == 512 && a.get() == nullptr && a.bytes() == 0 && L.now == 512, "move-construction transfers, the ledger unchanged");
+            hip_ok(b.alloc(L, 256), "alloc(256)");
+            b = std::move(c);
+            check(b.get() == raw && c.get() == nullptr && L.now == 512, "move-assignment releases what the target held and transfers");
+            LedgerBuf<uint64_t>& bself = b;
+            b = std::move(bself);
+            check(b.get() == raw && b.bytes() == 512 && L.now == 512, "self-move-assignment is harmless");
+            struct Two { LedgerBuf<uint64_t> x, y; } two;
+            hip_ok(two.x.alloc(L, 128), "alloc(128)"); hip_ok(two.y.alloc(L, 64), "alloc(64)");
+            check(L.now == 704, "a struct of owners: charged");
+            two = Two();
+            check(two.x.get() == nullptr && L.now == 512, "s = S() releases a struct of owners");
+        }
+        check(L.now == 0 && L.peak == 20000, "the destructors credit the rest; the peak is the largest sum ever held");
     }
     hip_ok(hipDeviceSynchronize(), "hipDeviceSynchronize");
     printf("devbuf_check: %d checks passed\n", g_checks);

@@ -1,4 +1,4 @@
-"""The GPU BGZF deflate (k_bgzf_deflate in microcket_amd/csrc/mkt_bam.hip) at its block, share and code-length edges.
+"""The GPU BGZF deflate (k_bgzf_deflate in microcket_amd/csrc/mkt_deflate.hip) at its block, share and code-length edges.
 
 Everything goes through microcket_amd.sam_to_bam in input order.  The uncompressed stream is shaped from the SAM side
 (tests/deflate_inputs.py): a header @CO line steers its length, one unmapped record carries arbitrary bytes in a B:C array.
@@ -8,7 +8,7 @@ verified), the bytes equal the level-0 block, tests/inflatedef.py (a plain infla
 test_inflatedef_host.py) agrees and shows the block type, the code lengths sent and the tokens; level 1 blocks are fixed or
 stored, level 2 blocks dynamic or stored; no block is larger than stored; a dynamic block sends at least two distance codes.
 
-A wave parses DZ_Q = 0xff00 // 8 bytes of a block (the 8 follows MKT_DZ_WAVES in mkt_bam.hip); matches never leave a share."""
+A wave parses DZ_Q = 0xff00 // 8 bytes of a block (the 8 follows MKT_DZ_WAVES in mkt_deflate.hip); matches never leave a share."""
 import pytest
 
 import bamio
