@@ -1,6 +1,6 @@
 // mkt_devbuf.h -- who frees device memory, pinned host memory, events and streams: a move-only owner per allocation, and the one
 // early return on a HIP error.  A struct of owners is released by `s = S()` or with the struct; a function that fails half way
-// leaks nothing.  Used by the matrix analyses, the contexts of the C ABI and sam2bam.
+// leaks nothing.  Used by the matrix analyses, the contexts of the C ABI, sam2bam, the sorter and rmdup.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -45,6 +45,7 @@ public:
         if (p_) M::free(p_);
         p_ = nullptr;
     }
+    T* release() { T* p = p_; p_ = nullptr; return p; }      // the caller frees
     T* get() const { return p_; }
     operator T*() const { return p_; }
     T* operator->() const { return p_; }

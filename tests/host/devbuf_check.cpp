@@ -1,5 +1,5 @@
 // devbuf_check.cpp -- the owning buffer types of microcket_amd/csrc/mkt_devbuf.h on a real device: growth with and without the
-// contents kept, failed allocations, moves, the pinned counterparts, and the ledger-charged owner.  One line per check; the first failed check ends the
+// contents kept, failed allocations, moves, release(), the pinned counterparts, and the ledger-charged owner.  One line per check; the first failed check ends the
 // program with status 1 (nothing further is started on the device).  tests/test_gpu_devbuf.py runs it.
 #include <stdint.h>
 #include <stdio.h>
@@ -107,6 +107,14 @@ int main() {
         DevBuf<uint64_t>& eself = e;
         e = std::move(eself);
         check(e.get() == q && d.get() == nullptr, "DevBuf: moves transfer, a self-move is harmless");
+        // release: the pointer is the caller's from then on
+        hip_ok(hipMemcpy(q, pat.data(), 8 * sizeof(uint64_t), hipMemcpyHostToDevice), "upload");
+        uint64_t* r = e.release();
+        check(r == q && e.get() == nullptr, "DevBuf::release hands the pointer over, the owner is empty");
+        e.reset();
+        e = DevBuf<uint64_t>();
+        check(holds(r, std::vector<uint64_t>(pat.begin(), pat.begin() + 8)), "after release, reset and reassignment of the owner the memory is still valid");
+        check(hipFree(r) == hipSuccess, "the caller frees what was released (the owner did not)");
     }
     {   // pinned host memory: allocate, use, grow, move (no failure request: a modest one that succeeds)
         PinGrowBuf<uint64_t> h;

@@ -25,5 +25,6 @@ def test_devbuf_check():
                  "regrow_keep with keep = the old capacity keeps all of it", "an ensure of what fits reallocates nothing",
                  "regrow of a larger size updates the capacity", "after it the buffer is empty with capacity 0",
                  "after it the old pointer, capacity and contents are intact", "self-move-assignment is harmless",
-                 "pinned move-assignment transfers, a self-move is harmless"):
+                 "pinned move-assignment transfers, a self-move is harmless", "DevBuf::release hands the pointer over, the owner is empty",
+                 "the caller frees what was released (the owner did not)"):
         assert "ok   " + what in lines, what

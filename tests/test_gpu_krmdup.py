@@ -67,6 +67,25 @@ def test_rmdup_streaming_segments_equal_the_oracle(monkeypatch):
     assert st3 == st2 and inter == b"".join(b"\n".join(l1[i:i + 4] + l2[i:i + 4]) + b"\n" for i in range(0, len(l1), 4))
 
 
+def test_rmdup_text_buffer_grows_with_its_contents_kept():
+    """The resident form of m.rmdup reserves nothing: every piece goes through mkt_rmdup_add, whose text buffer starts at 256 MiB and
+    doubles with what it holds carried over.  A block of about 1.1 MB of whole pairs, 258 times, crosses that size (this route, add
+    after add, is the one that grows).  Every pair after the first copy of the block is a duplicate, and all first occurrences lie
+    in the first 2^16-pair batch: the outputs are those of the block alone, in the block's order."""
+    if m.device_count() < 1:
+        pytest.fail("no HIP device")
+    block = util.synth_fastq(81, 6000, 36, dup_rate=0.3)
+    reps = 258
+    assert len(block) * reps > 256 << 20 > len(block) * 2                              # grows with many blocks held, more follow
+    assert block.count(b"\n") // 8 < 1 << 16
+    o1, o2, ol = util.krmdup_oracle(block)
+    total, uniq, dup, discard = (int(line.split(b"\t")[1]) for line in ol.splitlines())
+    assert total == uniq + dup + discard and uniq and dup and discard
+    r1, r2, st = m.rmdup(block * reps, piece=len(block))
+    assert util.krmdup_log(*st) == util.krmdup_log(total * reps, uniq, total * reps - uniq - discard * reps, discard * reps)
+    assert (r1, r2) == (o1, o2)
+
+
 def test_krmdup_executables_are_drop_ins():
     if m.device_count() < 1:
         pytest.fail("no HIP device")
