@@ -268,6 +268,61 @@ int mkt_rmdup_run(mkt_rmdup* r, uint32_t hskip1, uint32_t keylen1, uint32_t hski
                   uint64_t stats[4] /* total, uniq, dup, discard */, uint64_t out_bytes[2]);
 int mkt_rmdup_fetch(mkt_rmdup* r, int which /* 0: read 1 or the interleaved stream, 1: read 2 */, uint64_t off, char* out, size_t n);
 
+/* ---- read stitching: the driver's `flash ... -To -c - | perl deal.flash.pl - PREFIX` (microcket:405-408, 430-438) ----------------
+ * Interleaved paired-end FASTQ in (8 lines per pair, as bin/krmdup.pipe writes it); out, in INPUT order, four streams:
+ *   MKT_STITCH_TAB   FLASH's tab-delimited lines: "tag \t seq \t qual" for a combined pair, "tag \t seq1 \t qual1 \t seq2 \t qual2" else
+ *   MKT_STITCH_EXT   PREFIX.ext.fq: every combined pair as "@tag \n seq \n + \n qual \n"
+ *   MKT_STITCH_CUT1 / MKT_STITCH_CUT2   PREFIX.cut.read1.fq / .cut.read2.fq: every uncombined pair whose read 1 has at least
+ *                    min_size + cut_tail bases (only read 1 is tested), the last cut_tail characters cut from all four strings
+ * and the counters of PREFIX.stitch.stat.  The definition (restated in tests/stitchdef.py, pinned to FLASH v1.2.11 and deal.flash.pl
+ * by tests/golden/stitch_golden.json); qualities are Phred values, byte - phred_offset:
+ *   reading      letters are upper-cased, anything outside ACGT becomes N, and is written that way; the tag is read 1's header without
+ *                '@', cut at its LAST '/' if it has one ("a/1" -> "a", "d/1 x y" -> "d", "b 1:N:0:ACGT" and "e_1" stay whole)
+ *   orientation  read 2 is reverse-complemented, its qualities reversed
+ *   candidates   offsets i = max(0, n1 - n2) .. n1 - min_overlap into read 1, overlap length n1 - i, in this order
+ *   scoring      a position where either base is N is uncalled; eff = overlap - uncalled, mm = called positions that differ, mq = the
+ *                sum of min(q1, q2) over those; a candidate counts only if eff >= min_overlap
+ *   comparing    in float32: sl = min(eff, max_overlap), d = mm / sl, qs = mq / sl; the best starts at d = x + 1, qs = 0 and is replaced
+ *                when d <= best_d && (d < best_d || qs < best_qs); best_d > x after the scan: not combined.  So the first candidate
+ *                with the smallest (d, qs) wins.  Every d and qs is a fraction with a denominator <= max_overlap, and only d < 2 and
+ *                qs < 93 * 2 ever decide: two different ones differ by at least 1 / max_overlap^2, more than a float32 step (2^-16 below
+ *                256) for max_overlap <= MKT_STITCH_MAX_M = 255.  In that range the kernels' cross-multiplied integer comparison is the
+ *                same decision, and a larger max_overlap is refused; `d > x` is taken from a table of the float32 quotients themselves.
+ *   combining    read 1 before the offset | the overlap | the rest of the reverse-complemented read 2; in the overlap equal bases keep the
+ *                base with max(q1, q2), different bases get max(|q1 - q2|, 2) and the base of the higher quality, on a tie read 2's
+ *                unless that is N
+ *   cutting      a string shorter than cut_tail (only read 2 can be) keeps 2 * length - cut_tail characters or none: Perl's substr
+ *                with a negative length
+ * The program itself writes its tab lines in blocks of 35 per kind, so its stream alternates between runs of combined and uncombined
+ * lines even with one thread (and has no defined order with several); each kind by itself is in input order, which is all that
+ * deal.flash.pl's files show.  Out of scope: outie pairs (-O), the other output formats, histograms.
+ * Limits, each MKT_E_ARG with a message that names the pair, never a truncation: reads of 1 .. MKT_STITCH_MAX_READ bases, sequence
+ * and quality of equal length, quality bytes in phred_offset .. phred_offset + 93, whole pairs (a line count that is no multiple of 8
+ * at the end of the input is an error); 1 <= min_overlap <= max_overlap <= MKT_STITCH_MAX_M, 0 <= max_mismatch_density <= 1,
+ * phred_offset 0 .. 127, cut_tail and min_size below 2^16.
+ * The input is worked off in segments of whole pairs (mkt_stitch_segment_pairs, default 2^20; MKT_STITCH_SEGMENT_PAIRS), a record
+ * may be split anywhere between pushes; the outputs are the same bytes whatever the pieces and the segment size.
+ *   mkt_stitch_check   the argument check of mkt_stitch_begin without a device: MKT_OK, or MKT_E_ARG with the message in msg
+ *   mkt_stitch_push    the next bytes (may be none); final != 0 ends the input.  out_bytes = what this push left in the four streams
+ *                      (fetch before the next push), zeros when no segment was worked off
+ *   mkt_stitch_timing  ms (HIP events) of the segments so far: line index, scoring, sizes and their scans, writing */
+#define MKT_STITCH_MAX_READ 512
+#define MKT_STITCH_MAX_M 255
+enum { MKT_STITCH_TAB = 0, MKT_STITCH_EXT = 1, MKT_STITCH_CUT1 = 2, MKT_STITCH_CUT2 = 3 };
+typedef struct mkt_stitch mkt_stitch;
+int mkt_stitch_create(int device, mkt_stitch** out);
+void mkt_stitch_destroy(mkt_stitch* s);
+const char* mkt_stitch_error(const mkt_stitch* s);
+int mkt_stitch_check(uint32_t min_overlap, uint32_t max_overlap, double max_mismatch_density, uint32_t phred_offset, uint32_t cut_tail, uint32_t min_size,
+                     char* msg, size_t msg_cap);
+int mkt_stitch_segment_pairs(mkt_stitch* s, uint64_t pairs);        /* before begin; at least 1 */
+int mkt_stitch_begin(mkt_stitch* s, uint32_t min_overlap, uint32_t max_overlap, double max_mismatch_density, uint32_t phred_offset, uint32_t cut_tail,
+                     uint32_t min_size);
+int mkt_stitch_push(mkt_stitch* s, const char* bytes, size_t n, int final, uint64_t out_bytes[4]);
+int mkt_stitch_fetch(mkt_stitch* s, int which /* MKT_STITCH_* */, uint64_t off, char* out, size_t n);
+int mkt_stitch_stats(const mkt_stitch* s, uint64_t* total, uint64_t* combined, uint64_t* uncombined, uint64_t* pass);
+int mkt_stitch_timing(const mkt_stitch* s, double* index_ms, double* score_ms, double* scan_ms, double* write_ms);
+
 /* ---- the .sam -> BAM tail of the pipeline -----------------------------------------------------------
  * Replaces microcket:533-540: `cat header flash.sam unc.sam | samtools view -b | samtools sort -o valid.bam; samtools index`.
  * SAM text in (leading '@' lines = the header, then alignment lines), out a BGZF-compressed BAM -- records in input order

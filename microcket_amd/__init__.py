@@ -42,6 +42,8 @@ from .capi import (  # noqa: F401
     TILES_FAST,
     TILES_SMALL,
     Stats,
+    StitchStats,
+    Stitcher,
     Viewpoint,
     ViewpointInfo,
     ViewpointOpts,
@@ -52,9 +54,10 @@ from .capi import (  # noqa: F401
     rmdup,
     run_sam2pairs,
     sam_to_bam,
+    stitch_check,
 )
 
 __all__ = [
-    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Eigs", "EigsInfo", "EigsOpts", "Expected", "ExpectedOpts", "InsulationInfo", "InsulationOpts", "InsulationTrack", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "Pileup", "PileupInfo", "PileupOpts", "Saddle", "SaddleInfo", "SaddleOpts", "Scc", "SccInfo", "SccOpts", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats", "Viewpoint", "ViewpointInfo", "ViewpointOpts",
-    "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam",
+    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Eigs", "EigsInfo", "EigsOpts", "Expected", "ExpectedOpts", "InsulationInfo", "InsulationOpts", "InsulationTrack", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "Pileup", "PileupInfo", "PileupOpts", "Saddle", "SaddleInfo", "SaddleOpts", "Scc", "SccInfo", "SccOpts", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats", "StitchStats", "Stitcher", "Viewpoint", "ViewpointInfo", "ViewpointOpts",
+    "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam", "stitch_check",
 ]

@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -139,6 +139,19 @@ def build_krmdup(force=False):
     return KRMDUP
 
 
+STITCH = os.path.join(HERE, "bin", "stitch")
+
+
+def build_stitch(force=False):
+    """bin/stitch: the driver's `flash ... -To -c - | perl deal.flash.pl - PREFIX` step on the GPU (read stitching)."""
+    src = os.path.join(CSRC, "stitch_main.cpp")
+    if force or _newer(STITCH, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(STITCH), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", STITCH, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return STITCH
+
+
 SAM2BAM = os.path.join(HERE, "bin", "sam2bam")
 
 
@@ -220,6 +233,7 @@ def build_all(force=False, extras=True):
     build_exe(force)
     build_pairsort(force)
     build_krmdup(force)
+    build_stitch(force)
     build_sam2bam(force)
     build_pairs2matrix(force)
     build_makestat(force)

@@ -20,6 +20,8 @@ EXPORTS = [
     "mkt_sorter_create", "mkt_sorter_destroy", "mkt_sorter_error", "mkt_sorter_add", "mkt_sorter_add_device", "mkt_sorter_sort", "mkt_sorter_fetch",
     "mkt_rmdup_create", "mkt_rmdup_destroy", "mkt_rmdup_error", "mkt_rmdup_reserve", "mkt_rmdup_add", "mkt_rmdup_run", "mkt_rmdup_fetch",
     "mkt_rmdup_begin", "mkt_rmdup_push", "mkt_rmdup_stats",
+    "mkt_stitch_create", "mkt_stitch_destroy", "mkt_stitch_error", "mkt_stitch_check", "mkt_stitch_segment_pairs", "mkt_stitch_begin", "mkt_stitch_push",
+    "mkt_stitch_fetch", "mkt_stitch_stats", "mkt_stitch_timing",
     "mkt_bam_create", "mkt_bam_destroy", "mkt_bam_error", "mkt_bam_note", "mkt_bam_add", "mkt_bam_add_device", "mkt_bam_run", "mkt_bam_fetch",
     "mkt_bam_reserve", "mkt_bam_window", "mkt_bam_commit", "mkt_bam_read", "mkt_bam_spill", "mkt_bam_pull", "mkt_bam_stats",
     "mkt_matrix_create", "mkt_matrix_destroy", "mkt_matrix_error", "mkt_matrix_add", "mkt_matrix_add_device", "mkt_matrix_add_keys", "mkt_matrix_run",
@@ -338,6 +340,18 @@ def load_library():
     L.mkt_rmdup_begin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
     L.mkt_rmdup_push.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
     L.mkt_rmdup_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mkt_stitch_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mkt_stitch_destroy.argtypes = [C.c_void_p]
+    L.mkt_stitch_destroy.restype = None
+    L.mkt_stitch_error.argtypes = [C.c_void_p]
+    L.mkt_stitch_error.restype = C.c_char_p
+    L.mkt_stitch_check.argtypes = [C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.mkt_stitch_segment_pairs.argtypes = [C.c_void_p, C.c_uint64]
+    L.mkt_stitch_begin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.mkt_stitch_push.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
+    L.mkt_stitch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_stitch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mkt_stitch_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mkt_bam_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_bam_destroy.argtypes = [C.c_void_p]
     L.mkt_bam_destroy.restype = None
@@ -1357,6 +1371,93 @@ def rmdup(text: bytes, hskip1=5, keylen1=16, hskip2=5, keylen2=16, interleaved=F
         return b"".join(outs[0]), b"".join(outs[1]), tuple(int(x) for x in st)
     finally:
         L.mkt_rmdup_destroy(h)
+
+
+STITCH_MAX_READ, STITCH_MAX_M = 512, 255
+StitchStats = collections.namedtuple("StitchStats", "total combined uncombined passed")
+
+
+def stitch_check(min_overlap=10, max_overlap=150, max_mismatch_density=0.25, phred_offset=33, cut_tail=10, min_size=36):
+    """mkt_stitch_check: the argument check of Stitcher, which needs no device.  Returns None or the refusal's text."""
+    L = load_library()
+    msg = C.create_string_buffer(256)
+    rc = L.mkt_stitch_check(min_overlap, max_overlap, max_mismatch_density, phred_offset, cut_tail, min_size, msg, 256)
+    return None if rc == 0 else msg.value.decode()
+
+
+class Stitcher:
+    """Read stitching on the GPU (mkt_stitch_*, include/mkt.h): the driver's `flash | deal.flash.pl` step.  push() the interleaved
+    FASTQ in any pieces, finish() at its end; tab / ext / cut1 / cut2 collect the four streams (input order), stats() the counters.
+    segment_pairs: pairs per segment (default 2^20)."""
+
+    STREAMS = ("tab", "ext", "cut1", "cut2")
+
+    def __init__(self, min_overlap=10, max_overlap=150, max_mismatch_density=0.25, phred_offset=33, cut_tail=10, min_size=36, device=0, segment_pairs=None):
+        self._L = L = load_library()
+        self._h = C.c_void_p()
+        rc = L.mkt_stitch_create(device, C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise MktError(f"mkt_stitch_create: {L.mkt_strerror(rc).decode()} (no GPU, no CPU path)")
+        self._parts = ([], [], [], [])
+        try:
+            if segment_pairs is not None:
+                self._check(L.mkt_stitch_segment_pairs(self._h, segment_pairs), "mkt_stitch_segment_pairs")
+            self._check(L.mkt_stitch_begin(self._h, min_overlap, max_overlap, max_mismatch_density, phred_offset, cut_tail, min_size), "mkt_stitch_begin")
+        except MktError:
+            self.close()
+            raise
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise MktError(f"{what}: {self._L.mkt_strerror(rc).decode()}: {self._L.mkt_stitch_error(self._h).decode()}")
+
+    def push(self, data: bytes, final=False):
+        ob = (C.c_uint64 * 4)()
+        self._check(self._L.mkt_stitch_push(self._h, data, len(data), 1 if final else 0, ob), "mkt_stitch_push")
+        for which in range(4):
+            if ob[which]:
+                buf = C.create_string_buffer(ob[which])
+                self._check(self._L.mkt_stitch_fetch(self._h, which, 0, buf, ob[which]), "mkt_stitch_fetch")
+                self._parts[which].append(buf.raw[:ob[which]])
+
+    def finish(self):
+        self.push(b"", final=True)
+        return self
+
+    def stream(self, which):
+        return b"".join(self._parts[which])
+
+    tab = property(lambda self: self.stream(0))
+    ext = property(lambda self: self.stream(1))
+    cut1 = property(lambda self: self.stream(2))
+    cut2 = property(lambda self: self.stream(3))
+
+    def stats(self):
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self._L.mkt_stitch_stats(self._h, *[C.byref(x) for x in v]), "mkt_stitch_stats")
+        return StitchStats(*[int(x.value) for x in v])
+
+    def stat_line(self):
+        st = self.stats()
+        return b"Combined\t%d\tUncombined\t%d\tPass\t%d\n" % (st.combined, st.uncombined, st.passed)
+
+    def timing(self):
+        """ms so far: (line index, scoring, sizes and scans, writing)"""
+        v = [C.c_double() for _ in range(4)]
+        self._check(self._L.mkt_stitch_timing(self._h, *[C.byref(x) for x in v]), "mkt_stitch_timing")
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self._h:
+            self._L.mkt_stitch_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def run_sam2pairs(in_sam, mode, prefix, threads=4, ratio=0.5, mapq=10, sam="yes", env=None, exe=None):
