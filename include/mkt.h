@@ -277,7 +277,9 @@ int mkt_rmdup_fetch(mkt_rmdup* r, int which /* 0: read 1 or the interleaved stre
  * and the counters of PREFIX.stitch.stat.  The definition (restated in tests/stitchdef.py, pinned to FLASH v1.2.11 and deal.flash.pl
  * by tests/golden/stitch_golden.json); qualities are Phred values, byte - phred_offset:
  *   reading      letters are upper-cased, anything outside ACGT becomes N, and is written that way; the tag is read 1's header without
- *                '@', cut at its LAST '/' if it has one ("a/1" -> "a", "d/1 x y" -> "d", "b 1:N:0:ACGT" and "e_1" stay whole)
+ *                '@' and without white space at its end.  A combined pair's is cut at its LAST '/' if it has one ("a/1" -> "a",
+ *                "d/1 x y" -> "d", "b 1:N:0:ACGT" and "e_1" stay whole); an uncombined pair's only loses a "/1" or "/2" at its very end
+ *                ("a/1" -> "a", but "d/1 x y", "a/3" and "x/y" stay whole)
  *   orientation  read 2 is reverse-complemented, its qualities reversed
  *   candidates   offsets i = max(0, n1 - n2) .. n1 - min_overlap into read 1, overlap length n1 - i, in this order
  *   scoring      a position where either base is N is uncalled; eff = overlap - uncalled, mm = called positions that differ, mq = the

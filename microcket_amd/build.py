@@ -208,6 +208,11 @@ def build_test_tools():
     dsrc = os.path.join(ROOT, "tests", "host", "deflate_codes.cpp")
     if os.path.exists(dsrc) and _newer(dzc, [dsrc, os.path.join(CSRC, "mkt_deflate_codes.h")]):
         _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-o", dzc, dsrc])
+    # host driver of read stitching's threshold table (mkt_stitch.h); a tree that carries an older tests/ has no such source
+    sth = os.path.join(out, "stitch_thresholds")
+    tsrc = os.path.join(ROOT, "tests", "host", "stitch_thresholds.cpp")
+    if os.path.exists(tsrc) and _newer(sth, [tsrc, os.path.join(CSRC, "mkt_stitch.h"), os.path.join(ROOT, "include", "mkt.h")]):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-o", sth, tsrc])
     # device check of the owning buffer types (mkt_devbuf.h): HIP runtime only; a tree that carries an older tests/ has no such source
     dbc = os.path.join(out, "devbuf_check")
     bsrc = os.path.join(ROOT, "tests", "host", "devbuf_check.cpp")

@@ -42,6 +42,7 @@ __device__ inline uint8_t st_norm(uint8_t c) {
     if (c >= 'a' && c <= 'z') c = (uint8_t)(c - 32);
     return (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? c : (uint8_t)'N';
 }
+__device__ inline bool st_space(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r' && c != '\n'); }      // what the program drops at a line's end
 __device__ inline uint32_t st_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }      // (normalised)
 __device__ inline uint8_t st_comp(uint8_t c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : 'N'; }
 // the lines of pair r: 0 header 1, 1 seq 1, 3 qual 1, 4 header 2, 5 seq 2, 7 qual 2
@@ -188,14 +189,20 @@ __global__ __launch_bounds__(ST_WAVES * 64) void k_st_score(const uint8_t* text,
             best = st_wave_min(qb);
         }
     }
-    // ---- the tag: the header without '@', cut at its last '/'
+    // ---- the tag: the header without '@' and the white space at its end; a combined pair's is cut at its last '/', an uncombined
+    // pair's only loses a closing "/1" or "/2" (`combined` is the same in every lane)
     uint32_t t0 = 0, tlen = 0;
     if (have) {
         t0 = (hl && text[h0] == '@') ? 1u : 0u;
-        int last = -1;
-        for (uint32_t j = t0 + lane; j < hl; j += 64) if (text[h0 + j] == '/') last = (int)j;
-        last = st_wave_max(last);
-        tlen = last >= 0 ? (uint32_t)last - t0 : hl - t0;
+        uint32_t he = hl;
+        while (he > t0 && st_space(text[h0 + he - 1])) --he;
+        tlen = he - t0;
+        if (combined) {
+            int last = -1;
+            for (uint32_t j = t0 + lane; j < he; j += 64) if (text[h0 + j] == '/') last = (int)j;
+            last = st_wave_max(last);
+            if (last >= 0) tlen = (uint32_t)last - t0;
+        } else if (tlen >= 2u && text[h0 + he - 2] == '/' && (text[h0 + he - 1] == '1' || text[h0 + he - 1] == '2')) tlen -= 2u;
     }
     if (have && lane == 0) {
         uint64_t lt = 0, le = 0, l1 = 0, l2 = 0;

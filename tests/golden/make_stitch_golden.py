@@ -73,7 +73,12 @@ def edge_records():
     add("tag_space", s30, rc(s30), h1="b 1:N:0:ACGT", h2="b 2:N:0:ACGT")
     add("tag_underscore", s30, rc(s30), h1="e_1", h2="e_2")
     add("tag_two_slashes", s30, rc(s30), h1="x/y/1", h2="x/y/2")
-    # lower case and '.', combined and not
+    # the two kinds form the tag differently: a '/' inside the header cuts a combined pair's tag only; an uncombined pair's loses
+    # nothing but a closing "/1" or "/2"; white space at the header's end goes in both
+    for h in ("x/y z", "a/2", "a/3", "q/1/", "/1", "a/1 ", "a b \t", "x/y/1"):
+        k = len(E)
+        add(f"tag_kind_comb_{k}", s30, rc(s30), h1=h, h2=h)
+        add(f"tag_kind_unc_{k}", f[300:350], "T" * 30, h1=h, h2=h)
     add("lower_dot_combined", s30.lower(), rc(s30)[:10] + "." + rc(s30)[11:].lower())
     add("lower_dot_uncombined", f[40:70].lower(), "acgt.nACGTRYacgtac", q2="5" * 18)
     # the shortest reads

@@ -5,7 +5,8 @@ by tests/golden/stitch_golden.json (made by tests/golden/make_stitch_golden.py) 
 
 The rule (qualities are Phred values, byte - phred_offset):
   reading      letters are upper-cased, anything outside ACGT becomes N (shown that way in every output); the tag is read 1's header
-               without '@', cut at its LAST '/' if it has one
+               without '@' and without white space at its end; a combined pair's is cut at its LAST '/' if it has one, an
+               uncombined pair's only loses a "/1" or "/2" at its very end ("a/b x" -> "a" combined, whole uncombined)
   orientation  read 2 is reverse-complemented, its qualities reversed
   candidates   offsets i = max(0, n1 - n2) .. n1 - m into read 1, overlap length n1 - i, in this order
   scoring      a position where either base is N is uncalled; eff = overlap - uncalled, mm = called positions that differ,
@@ -33,14 +34,22 @@ def sha(b):
     return hashlib.sha256(b).hexdigest()
 
 
-def tag_of(header):
-    t = header[1:] if header.startswith(b"@") else header
-    k = t.rfind(b"/")
-    return t[:k] if k >= 0 else t
+def header_of(line):
+    """read 1's header line without '@' and the white space at its end"""
+    return (line[1:] if line.startswith(b"@") else line).rstrip(b" \t\r\v\f")
+
+
+def tag_of(header, combined=True):
+    """the tag of a pair from header_of(): a combined pair's is cut at the last '/', an uncombined pair's keeps everything but a
+    closing "/1" or "/2" """
+    if combined:
+        k = header.rfind(b"/")
+        return header[:k] if k >= 0 else header
+    return header[:-2] if header.endswith((b"/1", b"/2")) else header
 
 
 def parse(text, phred=33):
-    """-> [(tag, seq1, qual1, seq2, qual2)] with the sequences normalised.  A last line without its newline still counts."""
+    """-> [(header_of(read 1's header), seq1, qual1, seq2, qual2)] with the sequences normalised.  A last line without its newline still counts."""
     if not text:
         return []
     lines = text.split(b"\n")
@@ -59,7 +68,7 @@ def parse(text, phred=33):
             raise ValueError(f"pair {k // 8}: a read of {max(len(s1), len(s2))} bases (limit {MAX_READ})")
         if any(not phred <= c <= phred + 93 for c in q1 + q2):
             raise ValueError(f"pair {k // 8}: a quality byte outside {phred} .. {phred + 93}")
-        out.append((tag_of(lines[k]), s1.translate(_NORM), q1, s2.translate(_NORM), q2))
+        out.append((header_of(lines[k]), s1.translate(_NORM), q1, s2.translate(_NORM), q2))
     return out
 
 
@@ -108,6 +117,49 @@ def _best_offsets(pairs, m, M, x, phred):
     return off
 
 
+def candidates(pair, m, M, phred=33):
+    """[(offset, eff, mm, mq)] of one parsed pair, every candidate offset in scan order, by plain loops over the positions (those
+    with eff < m are listed too; they do not count).  The second, slow statement of the scoring: tests/stitch_edge_cases.py works out
+    from it which classes its inputs reach, and tests/test_stitch_edges_host.py holds it against _best_offsets.  (M and phred only
+    bound and shift: sl = min(eff, M) is left to choose().)"""
+    _t, s1, q1, s2, q2 = pair
+    n1, n2 = len(s1), len(s2)
+    r2, p2 = s2.translate(_COMP)[::-1], q2[::-1]
+    out = []
+    for i in range(max(0, n1 - n2), n1 - m + 1):
+        eff = mm = mq = 0
+        for c1, c2, a, b in zip(s1[i:], r2, q1[i:], p2):
+            if c1 != 78 and c2 != 78:
+                eff += 1
+                if c1 != c2:
+                    mm += 1
+                    mq += (a if a < b else b) - phred
+        out.append((i, eff, mm, mq))
+    return out
+
+
+def choose(cands, m, M, x):
+    """The comparing rule on candidates(): the chosen offset, or -1."""
+    one = np.float32(1)
+    best_d, best_q, best = np.float32(x) + one, np.float32(0), -1
+    for i, eff, mm, mq in cands:
+        if eff < m:
+            continue
+        sl = np.float32(min(eff, M))
+        d, qs = np.float32(mm) / sl, np.float32(mq) / sl
+        if d <= best_d and (d < best_d or qs < best_q):
+            best_d, best_q, best = d, qs, i
+    return best if best >= 0 and not best_d > np.float32(x) else -1
+
+
+def threshold(sl, x):
+    """The largest mm for which float32(mm) / float32(sl) > float32(x) is false, searched up to MAX_READ as mkt_stitch.h does."""
+    mm = 0
+    while mm < MAX_READ and not np.float32(mm + 1) / np.float32(sl) > np.float32(x):
+        mm += 1
+    return mm
+
+
 def _combine(s1, q1, s2, q2, i, phred):
     r2 = s2.translate(_COMP)[::-1]
     p2 = q2[::-1]
@@ -145,7 +197,8 @@ def stitch(text, m=10, M=150, x=0.25, phred=33, cut_tail=10, min_size=36):
     tab, ext, c1, c2 = [], [], [], []
     comb = unc = passed = 0
     off = _best_offsets(pairs, m, M, x, phred) if pairs else []
-    for (tag, s1, q1, s2, q2), i in zip(pairs, off):
+    for (head, s1, q1, s2, q2), i in zip(pairs, off):
+        tag = tag_of(head, i >= 0)
         if i >= 0:
             seq, qual = _combine(s1, q1, s2, q2, int(i), phred)
             comb += 1

@@ -110,7 +110,13 @@ def test_definition_refuses_what_the_abi_refuses():
             sd.stitch(bad)
     with pytest.raises(ValueError):
         sd.stitch(rec(30), M=sd.MAX_M + 1)
-    hdr = open(os.path.join(ROOT, "include", "mkt.h")).read()
+    recq = lambda c: b"@a/1\n%s\n+\n%s\n@a/2\n%s\n+\n%s\n" % (b"A" * 30, bytes([c]) * 30, b"C" * 30, bytes([c]) * 30)
+    for phred in (33, 64):                                        # a quality byte: phred_offset .. phred_offset + 93, for any offset
+        assert sd.stitch(recq(phred), phred=phred)["total"] == 1 and sd.stitch(recq(phred + 93), phred=phred)["total"] == 1
+        for c in (phred - 1, phred + 94):
+            with pytest.raises(ValueError):
+                sd.stitch(recq(c), phred=phred)
+    hdr =open(os.path.join(ROOT, "include", "mkt.h")).read()
     assert int(re.search(r"#define MKT_STITCH_MAX_READ (\d+)", hdr).group(1)) == sd.MAX_READ == m.capi.STITCH_MAX_READ >= 512
     assert int(re.search(r"#define MKT_STITCH_MAX_M (\d+)", hdr).group(1)) == sd.MAX_M == m.capi.STITCH_MAX_M
 

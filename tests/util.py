@@ -12,6 +12,7 @@ REF_EXE = os.path.join(ROOT, "oracle", "_ref", "sam2pairs.ref")
 EMUL_SO = os.path.join(ROOT, "tests", "host", "_build", "libmkt_emul.so")
 SYNTH_EXE = os.path.join(ROOT, "tools", "_build", "synth_sam")
 DEFLATE_CODES_EXE = os.path.join(ROOT, "tests", "host", "_build", "deflate_codes")
+STITCH_THRESHOLDS_EXE = os.path.join(ROOT, "tests", "host", "_build", "stitch_thresholds")
 DEVBUF_CHECK_EXE = os.path.join(ROOT, "tests", "host", "_build", "devbuf_check")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
