@@ -249,15 +249,16 @@ MKT_HD int parse_record_fast(const TextView& tv, uint32_t off, const Params& P, 
 
 // unsigned decimal token of `len` bytes at window offset rr (all bytes inside the window)
 MKT_HD uint32_t win_parse_uint(const TextView& tv, uint32_t rr, uint32_t len, bool& ok) {
-    if (len > 10u) { ok = false; return 0; }
+    // (no limit on the token's length: `00000000065` is 65 to `ss >> unsigned`, leading zeros do not count towards the ten
+    // digits a value can have; v stops growing once it is past 32 bits)
     uint64_t v = 0;
     for (uint32_t i = 0; i < len; i += 4u) {
         uint32_t w = win_load4(tv, rr + i);
         const uint32_t m = len - i < 4u ? len - i : 4u;
         for (uint32_t b = 0; b < m; ++b) {
             const uint32_t d = (w & 0xFFu) - (uint32_t)'0';
-            if (d > 9u) ok = false;
-            v = v * 10u + d;
+            if (d > 9u || v > 0xFFFFFFFFull) ok = false;
+            else v = v * 10u + d;
             w >>= 8;
         }
     }

@@ -353,15 +353,14 @@ MKT_HD int parse_record_lean(const TextView& tv, uint32_t off, const Params& P, 
     r.rn_off = p[1] + 1u; r.rn_len = p[2] - p[1] - 1u;
     const uint32_t fl_len = p[1] - p[0] - 1u, pos_len = p[3] - p[2] - 1u, mq_len = p[4] - p[3] - 1u;
     // (12 readable bytes in front of a long field's end: true for every line whose QNAME has five bytes or more)
-    if (pos_len > 10u) { ok = false; r.pos = 0; }                               // (as parse_record: more than ten digits never fit)
-    else if (p[3] < 12u) return LP_ODD;
-    else r.pos = lean_uint12(tv, off + p[3], pos_len, ok);
+    // (more than ten characters: zero padded, the value may still fit -- `00000000065` is 65 to the reference -- so the generic parser decides)
+    if (pos_len > 10u || p[3] < 12u) return LP_ODD;
+    r.pos = lean_uint12(tv, off + p[3], pos_len, ok);
     if (fl_len <= 4u) r.flag = lean_uint4(tv, off + p[0] + 1u, fl_len, ok);
-    else if (fl_len > 10u) { ok = false; r.flag = 0; }
-    else if (p[1] < 12u) return LP_ODD;
+    else if (fl_len > 10u || p[1] < 12u) return LP_ODD;
     else r.flag = lean_uint12(tv, off + p[1], fl_len, ok);
     if (mq_len <= 4u) r.mapq = lean_uint4(tv, off + p[3] + 1u, mq_len, ok);
-    else if (mq_len > 10u) { ok = false; r.mapq = 0; }
+    else if (mq_len > 10u) return LP_ODD;
     else r.mapq = lean_uint12(tv, off + p[4], mq_len, ok);                      // (p[4] > p[3] >= 12)
     // CIGAR, per OPERATION: bit i of `dig` <-> byte i of the token is a decimal digit; every other byte is an operation whose
     // count is the digit run in front of it (up to four digits: the four bytes in front of the operation as one dword; longer

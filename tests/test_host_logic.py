@@ -4,7 +4,7 @@ tests/host/tile_emul.cpp runs the SAME per-tile phase functions the HIP kernel r
 (microcket_amd/csrc/mkt_tile.h, mkt_core.h), serially, for several tile geometries -- including
 tiny tiles and halos that force every out-of-window path -- plus the block cutting and Q1/Q2
 bookkeeping of mkt_host.h.  It is a test tool, not a product path: the library has no CPU fallback
-(test_abi.py checks that)."""
+(test_abi.py checks that).  The lean path's own byte limits are in test_fast_edges_host.py (tests/fast_edge_cases.py)."""
 import os
 
 import pytest
