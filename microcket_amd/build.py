@@ -225,6 +225,12 @@ def build_test_tools():
         vph = os.path.join(out, name)
         if os.path.exists(vsrc) and _newer(vph, [vsrc, os.path.join(CSRC, "mkt_viewpoint.h"), os.path.join(ROOT, "include", "mkt.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", vph, vsrc])
+    # host driver of the chunked text writer (mkt_chunked_file.h), plain and sanitized like the one above
+    csrc = os.path.join(ROOT, "tests", "host", "chunked_file.cpp")
+    for name, extra in (("chunked_file", ()), ("chunked_file_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        chf = os.path.join(out, name)
+        if os.path.exists(csrc) and _newer(chf, [csrc, os.path.join(CSRC, "mkt_chunked_file.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", chf, csrc])
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
     synth = os.path.join(tout, "synth_sam")
