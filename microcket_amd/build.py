@@ -196,6 +196,21 @@ def build_oracle():
     _run(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
 
 
+def build_emit_parts():
+    """tests/host/emit_parts: host driver of the lean kernel's piecewise .pairs emitter (fast_emit_part in mkt_fast.h), plain and
+    with the address and undefined-behaviour sanitizers (a stand-alone program: nothing of it is loaded into python)."""
+    out = os.path.join(ROOT, "tests", "host", "_build")
+    os.makedirs(out, exist_ok=True)
+    src = os.path.join(ROOT, "tests", "host", "emit_parts.cpp")
+    made = []
+    for name, extra in (("emit_parts", ()), ("emit_parts_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        exe = os.path.join(out, name)
+        if os.path.exists(src) and _newer(exe, [src] + _headers()):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", exe, src])
+        made.append(exe)
+    return made
+
+
 def build_test_tools():
     out = os.path.join(ROOT, "tests", "host", "_build")
     os.makedirs(out, exist_ok=True)
@@ -231,6 +246,7 @@ def build_test_tools():
         chf = os.path.join(out, name)
         if os.path.exists(csrc) and _newer(chf, [csrc, os.path.join(CSRC, "mkt_chunked_file.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", chf, csrc])
+    build_emit_parts()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
     synth = os.path.join(tout, "synth_sam")

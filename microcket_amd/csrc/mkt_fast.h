@@ -696,11 +696,11 @@ template <class Cfg> MKT_HD uint8_t fast_pair_byte(const FastState<Cfg>& st, uin
     const uint32_t i = g.em_idx[fast_pair_find(st, k)];
     return fast_layout_byte(st, g.g_slot[i], k - g.x_pair[i]);
 }
-// ---- emit: ONE lane writes one whole .pairs line ------------------------------------------------------------
-// The line is five byte runs of this state object (see FastLayout).  The lane streams them through a 64-bit byte FIFO
-// and writes destination-aligned dwords; the bytes in front of the first aligned dword and behind the last one go out
-// as single bytes (neighbouring lines own the rest of those dwords).  ~20 instructions per output dword for the one
-// lane that runs them, instead of a layout lookup per byte on every lane of the workgroup.
+// ---- emit: a few lanes write one .pairs line, a piece each ---------------------------------------------------
+// The line is five byte runs of this state object (see FastLayout).  A lane streams its piece of them through a 64-bit byte
+// FIFO and writes destination-aligned dwords; the bytes in front of the line's first aligned dword and behind its last one
+// go out as single bytes (neighbouring lines own the rest of those dwords).  A few dozen instructions per output dword for
+// the lane that runs them, instead of a layout lookup per byte on every lane of the workgroup.
 MKT_HD uint32_t state_load4(const uint8_t* base, uint32_t off) {       // four bytes at any offset, from aligned dwords
     const uint32_t* w = reinterpret_cast<const uint32_t*>(base);
     const uint32_t i = off >> 2;
@@ -712,41 +712,55 @@ MKT_HD uint32_t state_load4(const uint8_t* base, uint32_t off) {       // four b
     return sh ? ((lo >> sh) | (hi << (32u - sh))) : lo;
 #endif
 }
-template <class Cfg> MKT_HD void fast_emit_line(const FastState<Cfg>& st, uint32_t slot, uint32_t plen, uint8_t* dst) {
-    const auto& g = st.u.g;
+//
+// fast_emit_part: the line cut into `parts` contiguous pieces on the destination's aligned dword grid, one caller (lane) per
+// piece.  With a = dst & 3 the line touches nd = ceil((a + plen) / 4) aligned dwords; piece p owns dwords [p q, min((p + 1) q, nd))
+// with q = ceil(nd / parts), i.e. the line's bytes [4 p q - a, 4 (p + 1) q - a) cut to [0, plen).  A piece with no dwords (nd <
+// parts) does nothing.  Interior piece boundaries are whole dwords; the line's first and last dword are shared with the lines
+// around it and go out as single bytes, from the pieces that own them.
+// ONE loop for all five runs: every step finds the run that holds line byte o as fast_layout_byte does (four compares against
+// e0 .. e3), takes up to four bytes of it and goes on behind them.  The lanes of a wave are then in step whichever run their
+// pieces start in (a loop per run would make the wave walk every run for as long as its slowest lane needs there).
+template <class Cfg> MKT_HD void fast_emit_part(const FastState<Cfg>& st, uint32_t slot, uint32_t plen, uint8_t* dst, uint32_t part, uint32_t parts) {
     const uint8_t* base = reinterpret_cast<const uint8_t*>(&st);
-    const uint32_t w = (uint32_t)(st.win - base);
-    const uint32_t e0 = g.l_e0[slot], e1 = g.l_e1[slot], e2 = g.l_e2[slot], e3 = g.l_e3[slot];
-    const uint32_t rs[5] = {w + g.l_qa[slot], w + g.l_ca[slot], (uint32_t)(reinterpret_cast<const uint8_t*>(&g.l_litA[slot][0]) - base),
-                            w + g.l_cb[slot], (uint32_t)(reinterpret_cast<const uint8_t*>(&g.l_litB[slot][0]) - base)};
-    const uint32_t rl[5] = {e0, e1 - e0, e2 - e1, e3 - e2, plen - e3};
     const uint32_t a = (uint32_t)((uintptr_t)dst & 3u);
-    uint32_t* d = reinterpret_cast<uint32_t*>(dst - a);            // the aligned dword that holds the line's first byte
+    const uint32_t nd = (a + plen + 3u) >> 2, q = (nd + parts - 1u) / parts;
+    const uint32_t d0 = part * q, d1 = d0 + q < nd ? d0 + q : nd;
+    if (d0 >= d1) return;
+    const FastLayout<Cfg> L = fast_layout(st, slot);
+    uint32_t o = d0 ? 4u * d0 - a : 0u;                            // the piece is the line's bytes [o, oe)
+    const uint32_t oe = 4u * d1 - a < plen ? 4u * d1 - a : plen;
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst - a) + d0;       // the piece's first aligned dword
     uint64_t acc = 0;
-    uint32_t cnt = a;                                              // its low `a` bytes belong to the line before
-    bool first = a != 0u;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int r = 0; r < 5; ++r) {
-        for (uint32_t k = 0; k < rl[r]; k += 4u) {
-            uint32_t x = state_load4(base, rs[r] + k);
-            const uint32_t take = rl[r] - k < 4u ? rl[r] - k : 4u;
-            if (take < 4u) x &= (1u << (8u * take)) - 1u;
-            acc |= (uint64_t)x << (8u * cnt);
-            cnt += take;
-            if (cnt >= 4u) {
-                const uint32_t v = (uint32_t)acc;
-                if (first) { uint8_t* b = reinterpret_cast<uint8_t*>(d); for (uint32_t q = a; q < 4u; ++q) *MKT_GLOBAL(uint8_t, b + q) = (uint8_t)(v >> (8u * q)); first = false; }
-                else *MKT_GLOBAL(uint32_t, d) = v;
-                ++d; acc >>= 32; cnt -= 4u;
-            }
+    uint32_t cnt = d0 ? 0u : a;                                    // the line's first dword: its low `a` bytes belong to the line before
+    bool first = d0 == 0u && a != 0u;
+    while (o < oe) {
+        uint32_t ad = L.a0, end = L.e0;                            // the run that holds byte o: where it lies, where it ends
+        if (o >= L.e0) { ad = L.a1; end = L.e1; }
+        if (o >= L.e1) { ad = L.a2; end = L.e2; }
+        if (o >= L.e2) { ad = L.a3; end = L.e3; }
+        if (o >= L.e3) { ad = L.a4; end = plen; }
+        end = end < oe ? end : oe;
+        uint32_t x = state_load4(base, ad + o);
+        const uint32_t take = end - o < 4u ? end - o : 4u;         // (>= 1: o is inside its run and in front of oe)
+        if (take < 4u) x &= (1u << (8u * take)) - 1u;
+        acc |= (uint64_t)x << (8u * cnt);
+        cnt += take; o += take;
+        if (cnt >= 4u) {
+            const uint32_t v = (uint32_t)acc;
+            if (first) { uint8_t* b = reinterpret_cast<uint8_t*>(d); for (uint32_t k = a; k < 4u; ++k) *MKT_GLOBAL(uint8_t, b + k) = (uint8_t)(v >> (8u * k)); first = false; }
+            else *MKT_GLOBAL(uint32_t, d) = v;
+            ++d; acc >>= 32; cnt -= 4u;
         }
     }
-    {   // what is left: cnt (< 4) bytes of the last, shared dword
+    {   // what is left: cnt (< 4) bytes of the line's last, shared dword (an interior piece ends on a whole dword: nothing)
         uint8_t* b = reinterpret_cast<uint8_t*>(d);
-        for (uint32_t q = first ? a : 0u; q < cnt; ++q) *MKT_GLOBAL(uint8_t, b + q) = (uint8_t)((uint32_t)acc >> (8u * q));
+        for (uint32_t k = first ? a : 0u; k < cnt; ++k) *MKT_GLOBAL(uint8_t, b + k) = (uint8_t)((uint32_t)acc >> (8u * k));
     }
+}
+// the whole line by one caller
+template <class Cfg> MKT_HD void fast_emit_line(const FastState<Cfg>& st, uint32_t slot, uint32_t plen, uint8_t* dst) {
+    fast_emit_part(st, slot, plen, dst, 0u, 1u);
 }
 
 }  // namespace mkt

@@ -50,15 +50,39 @@ struct ScanScratch { uint64_t a[NT / 64], b[NT / 64]; };
     } while (0)
 #define STAMP_FLUSH(t0_)                                                                \
     do {                                                                                \
-        if ((t0_) == 0 && a.stamps) for (int k_ = 1; k_ < 16; ++k_) if (stamp_acc_[k_]) atomicAdd(&a.stamps[k_], stamp_acc_[k_]); \
+        if ((t0_) == 0 && a.stamps) for (int k_ = 0; k_ < 16; ++k_) if (stamp_acc_[k_]) atomicAdd(&a.stamps[k_], stamp_acc_[k_]); \
     } while (0)
 #define STOP_AFTER(k) if (a.debug_stop == (k)) { __syncthreads(); continue; }
+// the "account + emit" interval (STAMP(7) .. STAMP(11)) taken apart: the first lane of every wave leaves its shader clock in
+// s_part_end[wave] when it is through with its share (the accounting on the first waves, the .pairs lines on the emitting ones;
+// one CU, one clock).  Behind the interval's barrier lane 0 adds up, in the two spare phase words: [0] the time from STAMP(7) to
+// the accounting waves' end, [15] how long the LAST emitting wave ran on after that (0 where the accounting was the longer).
+#define STAMP_PART_DECL() __shared__ unsigned long long s_part_end[NT / 64]
+#define STAMP_PART()                                                                    \
+    do {                                                                                \
+        if ((tid & 63) == 0 && a.stamps) s_part_end[tid >> 6] = __builtin_amdgcn_s_memtime(); \
+    } while (0)
+#define STAMP_PARTS(nacc, nwv)                                                          \
+    do {                                                                                \
+        if (tid == 0 && a.stamps) {                                                     \
+            unsigned long long acc_ = 0, em_ = 0;                                       \
+            for (int w_ = 0; w_ < (nwv); ++w_) {                                        \
+                const unsigned long long x_ = s_part_end[w_];                           \
+                if (w_ < (nacc)) acc_ = x_ > acc_ ? x_ : acc_; else em_ = x_ > em_ ? x_ : em_; \
+            }                                                                           \
+            if (acc_ > stamp_prev_) stamp_acc_[0] += acc_ - stamp_prev_;                \
+            if (em_ > acc_) stamp_acc_[15] += em_ - acc_;                               \
+        }                                                                               \
+    } while (0)
 #else
 #define STAMP_DECL() do { } while (0)
 #define STAMP(k) do { } while (0)
 #define STAMP_FLUSH(t0_) do { } while (0)
 #define STAMP_SPAN(t0_) do { } while (0)
 #define STOP_AFTER(k)
+#define STAMP_PART_DECL() do { } while (0)
+#define STAMP_PART() do { } while (0)
+#define STAMP_PARTS(nacc, nwv) do { } while (0)
 #endif
 
 __device__ inline uint64_t shfl_up64(uint64_t v, int d) { return (uint64_t)__shfl_up((long long)v, d, 64); }
@@ -550,6 +574,10 @@ __device__ inline void fast_scan(const KArgs& a, uint32_t tt, uint64_t* hit, uin
     }
 }
 
+// lanes per .pairs line in k_fast's emit phase: a power of two (the lanes of a line are neighbours in one wave)
+constexpr uint32_t kEmitLanes = 4;
+static_assert(kEmitLanes && (kEmitLanes & (kEmitLanes - 1u)) == 0u && kEmitLanes <= 64u, "a line's lanes share a wave");
+
 template <class Cfg, int NTW, int RR, int WPS>
 __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
     __shared__ FastState<Cfg> st;
@@ -562,6 +590,7 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
     __shared__ OutPtrs s_out;
     const uint32_t region = blockIdx.x & (uint32_t)(a.nregions - 1);
     STAMP_DECL();
+    STAMP_PART_DECL();
 
     __shared__ uint32_t wg_cnt[C_COUNT];                  // this workgroup's share of the block's counters
     // Newline bitmaps of two windows: while waves 0 and 1 parse and classify tile t, the waves that have nothing to do in those
@@ -851,15 +880,19 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
             fast_account(st, s_out, t, i);
             fast_last(st, G, &a.tile_last[t], i);
         }
-        // .pairs: one lane per reported pair writes its whole line (fast_emit_line), on the waves the accounting left idle
+        // .pairs: kEmitLanes adjacent lanes per reported pair write its line, a piece each (fast_emit_part: their stores fall
+        // into the same one or two cache lines), on the waves the accounting left idle; work item = pair * kEmitLanes + piece
         if (total && st.base.pair_bytes + total <= s_out.pairs_cap) {
             const auto& g = st.u.g;
-            for (uint32_t e = (ltid + (uint32_t)(NTW / 2)) & (uint32_t)(NTW - 1); e < st.sums.emitted; e += NTW) {
-                const uint32_t i = g.em_idx[e];
-                fast_emit_line(st, g.g_slot[i], g.g_plen[i], dst + g.x_pair[i]);
+            const uint32_t items = st.sums.emitted * kEmitLanes;          // <= GCAP * kEmitLanes
+            for (uint32_t w = (ltid + (uint32_t)(NTW / 2)) & (uint32_t)(NTW - 1); w < items; w += NTW) {
+                const uint32_t i = g.em_idx[w / kEmitLanes];
+                fast_emit_part(st, g.g_slot[i], g.g_plen[i], dst + g.x_pair[i], w % kEmitLanes, kEmitLanes);
             }
         }
+        STAMP_PART();
         __syncthreads();
+        STAMP_PARTS(NWV / 2, NWV);
         STAMP(11);
         // counters and error bits of the tile are final here; flushed once per workgroup (9 global atomics per TILE on one
         // cache line would queue up behind each other)

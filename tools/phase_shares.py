@@ -33,6 +33,11 @@ print(f"pairs {ds.total_groups} bytes {ds.total_bytes} kernel_ms(1 pass) {t.tile
 for k in ORDER:
     print(f"{LABEL[k]:24s} {out[k]:16d} {100.0 * out[k] / tot:6.2f} %")
 
+# "account + emit" taken apart (STAMP_PARTS): words 0 and 15 lie inside that interval, they are no phases of their own
+print(f"{'  accounting waves done':24s} {out[0]:16d} {100.0 * out[0] / tot:6.2f} %   (from the interval's start)")
+print(f"{'  emit waves run on':24s} {out[15]:16d} {100.0 * out[15] / tot:6.2f} %   (after the accounting waves are done: the ceiling of a faster emitter)")
+print(f"{'  rest: barrier':24s} {out[11] - out[0] - out[15]:16d} {100.0 * (out[11] - out[0] - out[15]) / tot:6.2f} %")
+
 names = "LCAP LONG TAB PREV_WS PREV_HEAD NO_PREV OPEN_GROUP LAST_LINE GCAP PAIR_BYTES SHORT_LINE".split()
 why = {names[4 * q + k]: (out[12 + q] >> (16 * k)) & 0xFFFF for q in range(3) for k in range(4) if 4 * q + k < len(names)}
 print("deferred tiles by reason (2 passes):", {k: v for k, v in why.items() if v}, " of", t.tiles, "tiles per pass; deferred per pass", t.deferred_tiles, [hex(out[k]) for k in (12, 13, 14)])
