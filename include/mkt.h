@@ -1106,6 +1106,72 @@ int mkt_matrix_hic(mkt_matrix* m, const mkt_hic_opts* opts, mkt_hic_info* info);
 int mkt_matrix_fetch_hic(mkt_matrix* m, uint64_t off, char* out, size_t n);
 int mkt_matrix_hic_timing(const mkt_matrix* m, uint32_t res_index, double* sort_ms, double* serialise_ms, double* deflate_ms, double* pack_ms);
 
+/* ---- pair-level concordance of two .pairs texts (the reference's benchmarking/check.consistency.pl) on the GPU --------------------
+ * Two texts A and B of tab-separated lines  id c1 p1 c2 p2 [more ...]  are joined on the exact bytes of id, and every line gets a
+ * class.  No chromosome table: chromosome names are compared as bytes.  Independent of mkt_matrix.
+ *
+ * LINES   a line that starts with '#' is skipped (class 0); a last line without a newline counts; p1 and p2 are decimal integers in
+ *         [0, 2^31).  A data line with fewer than five fields or a position that is not such an integer is refused: MKT_E_ARG, the
+ *         message names the file (A or B) and the 1-based line.  max_dist 0 means 200.
+ * DISTRIBUTION, per side, every data line counted (repeats of an id too): trans if c1 and c2 differ as bytes; else d = |p2 - p1|:
+ *         d > 10000 cis>10K, d < 1000 cis<1K, anything else cis 1-10K.
+ * JOIN    of several A lines with one id the LAST is the value, the earlier ones are superseded.  B lines are taken in file order: if
+ *         the id has an A value that no earlier B line has claimed, the B line claims it, and the two are CONSISTENT if, with D =
+ *         max_dist, either  a.c1 == b.c1, |a.p1 - b.p1| < D, a.c2 == b.c2, |a.p2 - b.p2| < D  (straight)  or  a.c1 == b.c2,
+ *         |a.p1 - b.p2| < D, a.c2 == b.c1, |a.p2 - b.p1| < D  (swapped) holds, both comparisons strict, else DISCORDANT.  Every other B
+ *         line is B-only (a second B line of a claimed id too, whatever it holds); unclaimed A values are A-only.
+ * CLASSES one byte per input line.  A side: 0 comment, 1 superseded, 2 A-only, 3 consistent, 4 discordant.  B side: 0 comment,
+ *         2 B-only, 3 consistent, 4 discordant.
+ * REPORT  the script's stdout: "Using Distance: D", "Loading file A: <name> ...", "Loading file B: <name> ..." and an empty line; then
+ *         A_only = a_only + discordant, B_only = b_only + discordant, Consistent, #Disconcordant and the two distributions, every count
+ *         divided by 1e6 and printed with %.15g (3 is 3e-06, 0 is 0, 1234567 is 1.234567).
+ * TEXT    (want_lines) in B's file order one line  I \t id \t A's c1 p1 c2 p2 \t vs \t B's c1 p1 c2 p2  per discordant B line and one
+ *         line  B \t id \t c1 p1 c2 p2  per B-only line; behind all of them one line  A \t id \t c1 p1 c2 p2  per A-only value, in
+ *         ascending line number (the script walks a hash there).  Fields are copied as text: 007 stays 007.
+ * The classes, counters and bytes depend on the two texts and max_dist only: not on the route (host or device bytes, any chunking of
+ * add), not on hash_bits, and they are the same on every call.  Integers only.
+ * Both texts stay on the device; together they hold at most 2^32 - 1 lines (MKT_E_CAPACITY with a message beyond; MKT_E_NOMEM with a
+ * message when device memory does not suffice).
+ *
+ *   mkt_paircmp_add / _add_device   side 0 = A, 1 = B; repeatable, a chunk need not end at a line end; host bytes are copied before the
+ *                                   call returns
+ *   mkt_paircmp_opts_default        max_dist 200, want_lines 1, hash_bits 0
+ *   mkt_paircmp_run                 opts NULL = the defaults; info may be NULL; repeatable with other options on the same texts.
+ *                                   hash_bits 0: ids are keyed by the full 95-bit hash; 1 .. 32: by that many bits only, a TEST KNOB that
+ *                                   forces different ids onto one key (such runs are resolved on the host by exact string grouping;
+ *                                   info.host_runs counts them; nothing else may change).  MKT_E_ARG for hash_bits > 32 or a non-zero
+ *                                   reserved word.
+ *   mkt_paircmp_fetch_classes       the class bytes of lines [first, first + n) of one side (MKT_E_STATE before run)
+ *   mkt_paircmp_fetch_lines         bytes [off, off + n) of the text of the last run
+ *   mkt_paircmp_report              host only, no handle: the report into out (cap bytes, NUL-terminated); returns its length without
+ *                                   the NUL, or -1 when cap is too small
+ *   mkt_paircmp_timing              of the last run, ms from HIP events: line index and parse; radix passes; join (the host's share
+ *                                   included) and the class counts; the text */
+typedef struct mkt_paircmp mkt_paircmp;
+typedef struct mkt_paircmp_opts {
+    uint32_t max_dist, want_lines, hash_bits;
+    uint32_t reserved[5];                 /* 0 */
+} mkt_paircmp_opts;
+typedef struct mkt_paircmp_info {
+    uint64_t lines[2], data_lines[2];     /* per side: all lines; those that are no comment */
+    uint64_t distinct_a;                  /* different ids in A = A-only + consistent + discordant */
+    uint64_t consistent, discordant, a_only, b_only;
+    uint64_t dist[2][4];                  /* per side: cis<1K, cis 1-10K, cis>10K, trans */
+    uint64_t host_runs;                   /* runs of one key with different ids, resolved on the host */
+    uint64_t lines_bytes;                 /* bytes of the text (0 without want_lines) */
+} mkt_paircmp_info;
+int mkt_paircmp_create(int device, mkt_paircmp** out);
+void mkt_paircmp_destroy(mkt_paircmp* p);
+const char* mkt_paircmp_error(const mkt_paircmp* p);
+int mkt_paircmp_add(mkt_paircmp* p, int side, const char* bytes, size_t n);
+int mkt_paircmp_add_device(mkt_paircmp* p, int side, const void* d_bytes, size_t n);
+void mkt_paircmp_opts_default(mkt_paircmp_opts* o);
+int mkt_paircmp_run(mkt_paircmp* p, const mkt_paircmp_opts* opts, mkt_paircmp_info* info);
+int mkt_paircmp_fetch_classes(mkt_paircmp* p, int side, uint64_t first, uint64_t n, uint8_t* out);
+int mkt_paircmp_fetch_lines(mkt_paircmp* p, uint64_t off, char* out, size_t n);
+long mkt_paircmp_report(const mkt_paircmp_info* info, uint32_t max_dist, const char* name_a, const char* name_b, char* out, size_t cap);
+int mkt_paircmp_timing(const mkt_paircmp* p, double* parse_ms, double* sort_ms, double* join_ms, double* emit_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ from .capi import (  # noqa: F401
     MktError,
     MODE_FLASH,
     MODE_UNC,
+    PairCompare,
     PairsSorter,
     Pileup,
     PileupInfo,
@@ -58,6 +59,6 @@ from .capi import (  # noqa: F401
 )
 
 __all__ = [
-    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Eigs", "EigsInfo", "EigsOpts", "Expected", "ExpectedOpts", "InsulationInfo", "InsulationOpts", "InsulationTrack", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairsSorter", "Pileup", "PileupInfo", "PileupOpts", "Saddle", "SaddleInfo", "SaddleOpts", "Scc", "SccInfo", "SccOpts", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats", "StitchStats", "Stitcher", "Viewpoint", "ViewpointInfo", "ViewpointOpts",
+    "BalanceOpts", "BalanceStats", "Context", "EXT_KEYS", "EXT_LANES", "Eigs", "EigsInfo", "EigsOpts", "Expected", "ExpectedOpts", "InsulationInfo", "InsulationOpts", "InsulationTrack", "Loop", "LoopCells", "Loops", "LoopsInfo", "LoopsOpts", "Matrix", "MktError", "MODE_FLASH", "MODE_UNC", "PairCompare", "PairsSorter", "Pileup", "PileupInfo", "PileupOpts", "Saddle", "SaddleInfo", "SaddleOpts", "Scc", "SccInfo", "SccOpts", "TILES_AUTO", "TILES_FAST", "TILES_SMALL", "Stats", "StitchStats", "Stitcher", "Viewpoint", "ViewpointInfo", "ViewpointOpts",
     "device_count", "exe_path", "lib_path", "load_library", "rmdup", "run_sam2pairs", "sam_to_bam", "stitch_check",
 ]

@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -179,6 +179,20 @@ def build_pairs2matrix(force=False):
     return PAIRS2MATRIX
 
 
+PAIRSCMP = os.path.join(HERE, "bin", "pairscmp")
+
+
+def build_pairscmp(force=False):
+    """bin/pairscmp: the reference's benchmarking/check.consistency.pl on the GPU (pair-level concordance of two .pairs files,
+    DESIGN.md 6e); same argv, same stdout."""
+    src = os.path.join(CSRC, "pairscmp_main.cpp")
+    if force or _newer(PAIRSCMP, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(PAIRSCMP), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", PAIRSCMP, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return PAIRSCMP
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -246,6 +260,13 @@ def build_test_tools():
         chf = os.path.join(out, name)
         if os.path.exists(csrc) and _newer(chf, [csrc, os.path.join(CSRC, "mkt_chunked_file.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", chf, csrc])
+    # host driver of the pair comparison's host half (mkt_paircmp.h: the report, the grouping by id string), plain and sanitized
+    # like the ones above; a tree that carries an older tests/ has no such source
+    psrc = os.path.join(ROOT, "tests", "host", "paircmp_host.cpp")
+    for name, extra in (("paircmp_host", ()), ("paircmp_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        pch = os.path.join(out, name)
+        if os.path.exists(psrc) and _newer(pch, [psrc, os.path.join(CSRC, "mkt_paircmp.h"), os.path.join(ROOT, "include", "mkt.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", pch, psrc])
     build_emit_parts()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
@@ -263,6 +284,7 @@ def build_all(force=False, extras=True):
     build_stitch(force)
     build_sam2bam(force)
     build_pairs2matrix(force)
+    build_pairscmp(force)
     build_makestat(force)
     if extras:
         build_oracle()

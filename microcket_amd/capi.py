@@ -40,6 +40,8 @@ EXPORTS = [
     "mkt_viewpoint_opts_default", "mkt_matrix_viewpoint", "mkt_matrix_fetch_viewpoint_links", "mkt_matrix_fetch_viewpoint_track",
     "mkt_matrix_fetch_viewpoint_partners", "mkt_matrix_viewpoint_timing",
     "mkt_hic_opts_default", "mkt_matrix_hic", "mkt_matrix_fetch_hic", "mkt_matrix_hic_timing",
+    "mkt_paircmp_create", "mkt_paircmp_destroy", "mkt_paircmp_error", "mkt_paircmp_add", "mkt_paircmp_add_device", "mkt_paircmp_opts_default", "mkt_paircmp_run",
+    "mkt_paircmp_fetch_classes", "mkt_paircmp_fetch_lines", "mkt_paircmp_report", "mkt_paircmp_timing",
 ]
 
 
@@ -220,6 +222,15 @@ Viewpoint = collections.namedtuple("Viewpoint", "link_vbin link_chrom link_pbin 
 VIEWPOINT_OPTS = ("vbin", "pbin", "origin", "second_side_only", "min_count", "hotspot_ratio", "reserved")
 
 
+class PairCompareOpts(C.Structure):
+    _fields_ = [("max_dist", C.c_uint32), ("want_lines", C.c_uint32), ("hash_bits", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class _PairCompareInfoC(C.Structure):
+    _fields_ = [("lines", C.c_uint64 * 2), ("data_lines", C.c_uint64 * 2), ("distinct_a", C.c_uint64), ("consistent", C.c_uint64), ("discordant", C.c_uint64),
+                ("a_only", C.c_uint64), ("b_only", C.c_uint64), ("dist", (C.c_uint64 * 4) * 2), ("host_runs", C.c_uint64), ("lines_bytes", C.c_uint64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("tile_kernel_ms", C.c_double), ("tile_launches", C.c_uint64), ("tile_bytes", C.c_uint64), ("other_ms", C.c_double),
                 ("tiles", C.c_uint64), ("deferred_tiles", C.c_uint64)]
@@ -329,6 +340,21 @@ def load_library():
     L.mkt_sorter_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.mkt_sorter_sort.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.mkt_sorter_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_paircmp_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mkt_paircmp_destroy.argtypes = [C.c_void_p]
+    L.mkt_paircmp_destroy.restype = None
+    L.mkt_paircmp_error.argtypes = [C.c_void_p]
+    L.mkt_paircmp_error.restype = C.c_char_p
+    L.mkt_paircmp_add.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.mkt_paircmp_add_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    L.mkt_paircmp_opts_default.argtypes = [C.POINTER(PairCompareOpts)]
+    L.mkt_paircmp_opts_default.restype = None
+    L.mkt_paircmp_run.argtypes = [C.c_void_p, C.POINTER(PairCompareOpts), C.POINTER(_PairCompareInfoC)]
+    L.mkt_paircmp_fetch_classes.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mkt_paircmp_fetch_lines.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_paircmp_report.argtypes = [C.POINTER(_PairCompareInfoC), C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
+    L.mkt_paircmp_report.restype = C.c_long
+    L.mkt_paircmp_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mkt_rmdup_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_rmdup_destroy.argtypes = [C.c_void_p]
     L.mkt_rmdup_destroy.restype = None
@@ -776,6 +802,96 @@ class PairsSorter:
     def close(self):
         if self.h:
             self.L.mkt_sorter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class PairCompare:
+    """Pair-level concordance of two .pairs texts (the reference's benchmarking/check.consistency.pl) on the GPU: see mkt_paircmp_* in
+    include/mkt.h, where the definition stands."""
+    DIST_KEYS = ("cis_lt_1k", "cis_1_10k", "cis_gt_10k", "trans")
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.h = C.c_void_p()
+        self._info = None
+        self._max_dist = 200
+        rc = self.L.mkt_paircmp_create(device, C.byref(self.h))
+        if rc != 0:
+            raise MktError(f"mkt_paircmp_create: {self.L.mkt_strerror(rc).decode()}")
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise MktError(f"{what}: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_paircmp_error(self.h).decode()}")
+
+    def add_a(self, data: bytes):
+        self._chk(self.L.mkt_paircmp_add(self.h, 0, data, len(data)), "mkt_paircmp_add")
+
+    def add_b(self, data: bytes):
+        self._chk(self.L.mkt_paircmp_add(self.h, 1, data, len(data)), "mkt_paircmp_add")
+
+    def add_device(self, side, d_ptr, n):
+        """n bytes of device memory at d_ptr to side "a" or "b" """
+        self._chk(self.L.mkt_paircmp_add_device(self.h, {"a": 0, "b": 1}[side], C.c_void_p(d_ptr), n), "mkt_paircmp_add_device")
+
+    def run(self, max_dist=200, want_lines=True, hash_bits=0):
+        """The join of what was added; returns the counters as a dict.  Repeatable with other options."""
+        o = PairCompareOpts()
+        self.L.mkt_paircmp_opts_default(C.byref(o))
+        o.max_dist, o.want_lines, o.hash_bits = max_dist, 1 if want_lines else 0, hash_bits
+        info = _PairCompareInfoC()
+        self._info = None
+        self._chk(self.L.mkt_paircmp_run(self.h, C.byref(o), C.byref(info)), "mkt_paircmp_run")
+        self._info, self._max_dist = info, max_dist
+        d = {k: int(getattr(info, k)) for k in ("distinct_a", "consistent", "discordant", "a_only", "b_only", "host_runs", "lines_bytes")}
+        d["lines"] = [int(x) for x in info.lines]
+        d["data_lines"] = [int(x) for x in info.data_lines]
+        d["dist"] = [dict(zip(self.DIST_KEYS, (int(x) for x in info.dist[s]))) for s in range(2)]
+        return d
+
+    def report(self, name_a, name_b):
+        """The report of the last run as the script prints it (bytes)."""
+        if self._info is None:
+            raise MktError("report before run")
+        na, nb = os.fsencode(name_a), os.fsencode(name_b)
+        buf = C.create_string_buffer(4096 + len(na) + len(nb))
+        n = self.L.mkt_paircmp_report(C.byref(self._info), self._max_dist, na, nb, buf, len(buf))
+        if n < 0:
+            raise MktError("mkt_paircmp_report: the buffer is too small")
+        return buf.raw[:n]
+
+    def classes(self, side):
+        """One class byte per input line of side "a" or "b" (numpy uint8)."""
+        import numpy as np
+        if self._info is None:
+            raise MktError("classes before run")
+        s = {"a": 0, "b": 1}[side]
+        out = np.zeros(int(self._info.lines[s]), dtype=np.uint8)
+        self._chk(self.L.mkt_paircmp_fetch_classes(self.h, s, 0, out.size, C.c_void_p(out.ctypes.data)), "mkt_paircmp_fetch_classes")
+        return out
+
+    def lines(self):
+        """The inconsistent text of the last run (b"" without want_lines)."""
+        if self._info is None:
+            raise MktError("lines before run")
+        n = int(self._info.lines_bytes)
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_paircmp_fetch_lines(self.h, 0, buf, n), "mkt_paircmp_fetch_lines")
+        return buf.raw[:n]
+
+    def timing_ms(self):
+        t = [C.c_double() for _ in range(4)]
+        self._chk(self.L.mkt_paircmp_timing(self.h, *[C.byref(x) for x in t]), "mkt_paircmp_timing")
+        return dict(zip(("parse", "sort", "join", "emit"), (x.value for x in t)))
+
+    def close(self):
+        if self.h:
+            self.L.mkt_paircmp_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):
