@@ -1,4 +1,4 @@
-// mkt_balance.h -- what mkt_matrix.hip needs of mkt_balance.hip: iterative correction over one resolution's resident cells.
+// mkt_balance.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_balance.hip: iterative correction over one resolution's resident cells.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

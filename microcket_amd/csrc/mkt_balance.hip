@@ -1,5 +1,5 @@
 // mkt_balance.hip -- iterative correction (ICE) of one resolution's binned contact matrix on the GPU; include/mkt.h has the
-// definition, mkt_matrix.hip the entry points (mkt_matrix_balance) and the host-side filters.
+// definition; the entry points (mkt_matrix_balance) and the host-side filters are at the end, on the object of mkt_matrix_obj.h.
 //
 // One sweep reads 8 bytes per cell from each half of the cell layout (mkt_layout.h: the rows of the cells and the transposed copy)
 // and gathers bias[] (nbins doubles, meant to stay in cache).
@@ -9,8 +9,11 @@
 // workgroup tree.  Mean and variance of the non-zero marginals are two-level reductions of fixed shape (tile partials, then one
 // workgroup), the variance as a second pass over (m - mean)^2 so that tol far below 1e-10 still decides the way the definition does.
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <cmath>
 
-#include "mkt_balance.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 namespace mkt {
@@ -177,3 +180,132 @@ hipError_t bal_weights(const double* bias, uint64_t nbins, const BalState* state
 }
 
 }  // namespace mkt
+
+// ---- the entry points -----------------------------------------------------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_balance_opts_default(mkt_balance_opts* o) {
+    if (!o) return;
+    o->ignore_diags = 2; o->min_nnz = 10; o->min_count = 0.0; o->mad_max = 5.0; o->tol = 1e-5; o->max_iters = 200; o->reserved = 0;
+}
+
+int mkt_matrix_balance(mkt_matrix* m, uint32_t res_index, const mkt_balance_opts* opts, mkt_balance_stats* stats) {
+    if (m && stats) memset(stats, 0, sizeof *stats);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    const mkt_balance_opts o = mx_opts(opts, mkt_balance_opts_default);
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "balance: ignore_diags %d is negative", o.ignore_diags);
+    if (o.min_nnz < 0) return mfail(m, MKT_E_ARG, "balance: min_nnz %d is negative", o.min_nnz);
+    if (!(o.min_count >= 0.0)) return mfail(m, MKT_E_ARG, "balance: min_count %g is negative or NaN", o.min_count);
+    if (!(o.mad_max >= 0.0)) return mfail(m, MKT_E_ARG, "balance: mad_max %g is negative or NaN", o.mad_max);
+    if (!(o.tol >= 0.0)) return mfail(m, MKT_E_ARG, "balance: tol %g is negative or NaN", o.tol);
+    if (o.max_iters <= 0) return mfail(m, MKT_E_ARG, "balance: max_iters %d (at least 1 is needed)", o.max_iters);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "balance: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN, "balance")) return rc;
+    if (const int rc = mx_cells32(m, "balance", r.nnz)) return rc;
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    const uint64_t nb = r.nbins;
+    mx_invalidate(r, MX_NEW_WEIGHTS);
+    r.bal_setup_ms = r.bal_iter_ms = 0;
+    DevBuf<double> d_bias, d_m, d_part, d_w;                            // d_w becomes r.d_w at the end: a failure leaves no weights
+    DevBuf<BalState> d_state;
+#define BRUN(call) MX(m, "balance: ", call)
+    if (!r.lay.has_full) BRUN(mx_timed(m, &r.bal_setup_ms, [&] { return layout_full(r.lay, mx_cells(r), st); }));
+    BRUN(d_bias.alloc(nb, 64));
+    BRUN(d_m.alloc(nb, 64));
+    BRUN(d_w.alloc(nb, 64));
+    BRUN(d_part.alloc(0, bal_partial_bytes(nb)));
+    BRUN(d_state.alloc(1));
+    BRUN(hipMemsetAsync(d_state, 0, sizeof(BalState), st));
+
+    // steps 2 and 3 on the host, from one nbins-sized copy of the exact (integer-valued) marginals
+    std::vector<double> bias(nb, 1.0), hm(nb);
+    const uint32_t ig = (uint32_t)o.ignore_diags;
+    if (o.min_nnz > 0) {
+        BRUN(bal_marginal(r.lay, r.d_b2, r.d_cnt, nb, ig, true, nullptr, d_m, st));
+        BRUN(hipMemcpyAsync(hm.data(), d_m, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+        BRUN(hipStreamSynchronize(st));
+        for (uint64_t k = 0; k < nb; ++k) if (hm[k] < (double)o.min_nnz) bias[k] = 0.0;
+    }
+    BRUN(hipMemcpyAsync(d_bias, bias.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+    BRUN(bal_marginal(r.lay, r.d_b2, r.d_cnt, nb, ig, false, d_bias, d_m, st));
+    BRUN(hipMemcpyAsync(hm.data(), d_m, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    BRUN(hipStreamSynchronize(st));
+    if (o.min_count > 0.0)
+        for (uint64_t k = 0; k < nb; ++k) if (hm[k] < o.min_count) bias[k] = 0.0;
+    if (o.mad_max > 0.0) {
+        auto median = [](std::vector<double>& v) { std::sort(v.begin(), v.end()); const size_t n = v.size(); return n & 1 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0; };
+        std::vector<double> tmp;
+        const size_t nc = r.off.size();
+        for (size_t i = 0; i < nc; ++i) {
+            const uint64_t lo = r.off[i], hi = i + 1 < nc ? r.off[i + 1] : nb;
+            tmp.clear();
+            for (uint64_t k = lo; k < hi; ++k) if (hm[k] > 0.0) tmp.push_back(hm[k]);
+            if (tmp.empty()) continue;
+            const double med = median(tmp);
+            for (uint64_t k = lo; k < hi; ++k) hm[k] /= med;
+        }
+        tmp.clear();
+        for (uint64_t k = 0; k < nb; ++k) if (hm[k] > 0.0) tmp.push_back(std::log(hm[k]));
+        if (!tmp.empty()) {
+            const double med = median(tmp);
+            for (double& x : tmp) x = std::fabs(x - med);
+            const double dev = median(tmp), cut = std::exp(med - o.mad_max * dev);
+            for (uint64_t k = 0; k < nb; ++k) if (hm[k] < cut) bias[k] = 0.0;
+        }
+    }
+    uint64_t masked = 0;
+    for (uint64_t k = 0; k < nb; ++k) masked += bias[k] == 0.0;
+    BRUN(hipMemcpyAsync(d_bias, bias.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+
+    // step 4 on the device: a few iterations per look at the state (an iteration behind `done` is a no-op: five empty launches).
+    // $MKT_BALANCE_BATCH (1 .. 64) is there to measure other batch sizes (tools/balance_bench.py); the result does not depend on it.
+    BalState hs;
+    memset(&hs, 0, sizeof hs);
+    uint32_t per_look = 4;
+    if (const char* e = getenv("MKT_BALANCE_BATCH")) { const int v = atoi(e); if (v >= 1 && v <= 64) per_look = (uint32_t)v; }
+    BRUN(mx_timed(m, &r.bal_iter_ms, [&]() -> hipError_t {
+        for (uint32_t left = (uint32_t)o.max_iters; left && !hs.done;) {
+            const uint32_t batch = left < per_look ? left : per_look;
+            MKT_TRY(bal_iterate(r.lay, r.d_b2, r.d_cnt, nb, ig, o.tol, batch, d_bias, d_m, d_part, d_state, st));
+            MKT_TRY(hipMemcpyAsync(&hs, d_state, sizeof hs, hipMemcpyDeviceToHost, st));
+            MKT_TRY(hipStreamSynchronize(st));
+            left -= batch;
+        }
+        return hipSuccess;
+    }));
+    BRUN(bal_weights(d_bias, nb, d_state, d_w, st));
+    BRUN(hipStreamSynchronize(st));
+#undef BRUN
+    r.d_w = std::move(d_w);
+    r.balanced = true;
+    if (stats) {
+        stats->iterations = hs.iters; stats->converged = hs.converged ? 1 : 0; stats->var = hs.var; stats->scale = hs.mean;
+        stats->masked = hs.empty ? nb : masked;
+    }
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_weights(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, double* out) {
+    if (n && !out) return MKT_E_ARG;
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_WEIGHTS);
+    const MxRes& r = *rp;
+    if (first > r.nbins || n > r.nbins - first) return mfail(m, MKT_E_ARG, "weights [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nbins);
+    MCHK(m, hipSetDevice(m->device));
+    if (n) MCHK(m, hipMemcpy(out, r.d_w.get() + first, n * 8, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+
+int mkt_matrix_balance_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* iter_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const MxRes& r = m->res[res_index];
+    const bool have = m->ran && r.balanced;
+    mx_ms(setup_ms, have, r.bal_setup_ms); mx_ms(iter_ms, have, r.bal_iter_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

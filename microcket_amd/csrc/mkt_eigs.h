@@ -1,4 +1,4 @@
-// mkt_eigs.h -- what mkt_matrix.hip needs of mkt_eigs.hip: the leading eigenvectors of every chromosome's cis observed / expected - 1
+// mkt_eigs.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_eigs.hip: the leading eigenvectors of every chromosome's cis observed / expected - 1
 // matrix (compartments) over one resolution's resident cells, by a block iteration whose product A X never forms the matrix.
 // include/mkt.h has the definition.
 #pragma once

@@ -1,5 +1,5 @@
 // mkt_eigs.hip -- compartment eigenvectors: the leading eigenpairs of every chromosome's cis observed / expected - 1 matrix on the
-// GPU; include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_eigs, mkt_matrix_eigs_apply, the fetches).
+// GPU; include/mkt.h has the definition; the entry points (mkt_matrix_eigs, .._eigs_apply, the fetches) are at the end (mkt_matrix_obj.h).
 //
 // The matrix A = S - (g g^T - B) is never formed.  One sweep Y = A X multiplies a block of 8 columns: bin k's lanes walk its row
 // segment of the cells and its column segment of the layout's transposed copy (as the balance sweep does), form oe from the
@@ -19,7 +19,7 @@
 #include <cstring>
 #include <limits>
 
-#include "mkt_eigs.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 namespace mkt {
@@ -529,3 +529,107 @@ hipError_t eigs_run(EigsState& s, const EigsIn& in, const std::vector<uint32_t>&
 }
 
 }  // namespace mkt
+
+// ---- the entry points -----------------------------------------------------------------------------------------------------------
+using namespace mkt;
+
+extern "C" void mkt_eigs_opts_default(mkt_eigs_opts* o) {
+    if (!o) return;
+    o->n_eigs = 3; o->ignore_diags = 2; o->min_good = 9; o->max_iters = 300; o->tol = 1e-8; o->clip = 0.0; o->reserved = 0;
+}
+
+// the options checked, the tables there and the full layout built: what eigs and apply share
+static int mx_eigs_ready(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, mkt_eigs_opts& o, EigsIn& in, double* setup_ms) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    o = mx_opts(opts, mkt_eigs_opts_default);
+    if (o.n_eigs < 1 || o.n_eigs > 4) return mfail(m, MKT_E_ARG, "eigs: n_eigs %d (1 .. 4)", o.n_eigs);
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "eigs: ignore_diags %d is negative", o.ignore_diags);
+    if (o.min_good < 0) return mfail(m, MKT_E_ARG, "eigs: min_good %d is negative", o.min_good);
+    if (o.max_iters < 0) return mfail(m, MKT_E_ARG, "eigs: max_iters %d is negative", o.max_iters);
+    if (!(o.tol > 0.0 && o.tol < 1.0)) return mfail(m, MKT_E_ARG, "eigs: tol %g is not inside (0, 1)", o.tol);
+    if (!(o.clip >= 0.0)) return mfail(m, MKT_E_ARG, "eigs: clip %g is negative or NaN", o.clip);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "eigs: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "eigs")) return rc;
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    if (setup_ms) *setup_ms = 0;
+    if (!r.lay.has_full) {                                              // raw counts: the transposed half without a balance
+        MX(m, "eigs: ", mx_timed(m, &r.bal_setup_ms, [&] { return layout_full(r.lay, mx_cells(r), st); }));
+        if (setup_ms) *setup_ms = r.bal_setup_ms;
+    }
+    in.lay = &r.lay; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.off = r.d_off;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr; in.E = r.ext.d_cis_sm;
+    in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    return MKT_OK;
+}
+
+extern "C" {
+
+int mkt_matrix_eigs(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* phasing, mkt_eigs_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    mkt_eigs_opts o;
+    EigsIn in;
+    double setup_ms = 0;
+    const int rc = mx_eigs_ready(m, res_index, opts, o, in, &setup_ms);
+    if (rc) return rc;
+    MxRes& r = m->res[res_index];
+    const hipError_t e = eigs_run(r.egs, in, r.off, o, phasing, m->stream);
+    if (e != hipSuccess) { r.egs = EigsState(); return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs: %s", hipGetErrorString(e)); }
+    r.egs.setup_ms += setup_ms;
+    if (info) *info = r.egs.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_eigs_apply(mkt_matrix* m, uint32_t res_index, const mkt_eigs_opts* opts, const double* x, uint32_t ncols, double* y) {
+    if (!m) return MKT_E_ARG;
+    mkt_eigs_opts o;
+    EigsIn in;
+    const int rc = mx_eigs_ready(m, res_index, opts, o, in, nullptr);
+    if (rc) return rc;
+    if (ncols < 1 || ncols > (uint32_t)kEgCols) return mfail(m, MKT_E_ARG, "eigs apply: ncols %u (1 .. 8)", ncols);
+    if (!x || !y) return mfail(m, MKT_E_ARG, "eigs apply: x and y are needed");
+    const hipError_t e = eigs_apply(in, m->res[res_index].off, o, x, ncols, y, m->stream);
+    if (e != hipSuccess) return mfail(m, e == hipErrorOutOfMemory ? MKT_E_NOMEM : MKT_E_HIP, "eigs apply: %s", hipGetErrorString(e));
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_eigvecs(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, double* out) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_EIGS);
+    const EigsState* s = &rp->egs;
+    const uint64_t nb = m->res[res_index].nbins;
+    if (k >= (uint32_t)s->n_eigs) return mfail(m, MKT_E_ARG, "eigenvector %u of %d", k, s->n_eigs);
+    if (first > nb || n > nb - first) return mfail(m, MKT_E_ARG, "eigenvector bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nb);
+    if (out && n) memcpy(out, s->vec.data() + (size_t)k * nb + first, (size_t)n * 8);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_eigvals(mkt_matrix* m, uint32_t res_index, uint32_t first_chrom, uint32_t n, double* lambda, double* resid, uint32_t* n_good,
+                             uint32_t* iterations, uint8_t* converged) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_EIGS);
+    const EigsState* s = &rp->egs;
+    const uint32_t nchr = (uint32_t)s->n_good.size();
+    if (first_chrom > nchr || n > nchr - first_chrom) return mfail(m, MKT_E_ARG, "eigenvalues of chromosomes [%u, +%u) of %u", first_chrom, n, nchr);
+    if (n == 0) return MKT_OK;
+    const size_t ne = (size_t)s->n_eigs;
+    if (lambda) memcpy(lambda, s->lambda.data() + first_chrom * ne, n * ne * 8);
+    if (resid) memcpy(resid, s->resid.data() + first_chrom * ne, n * ne * 8);
+    if (n_good) memcpy(n_good, s->n_good.data() + first_chrom, (size_t)n * 4);
+    if (iterations) memcpy(iterations, s->iterations.data() + first_chrom, (size_t)n * 4);
+    if (converged) memcpy(converged, s->converged.data() + first_chrom, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_eigs_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms, double* small_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const EigsState& s = m->res[res_index].egs;
+    const bool have = m->ran && s.built;
+    mx_ms(setup_ms, have, s.setup_ms); mx_ms(sweep_ms, have, s.sweep_ms); mx_ms(small_ms, have, s.small_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

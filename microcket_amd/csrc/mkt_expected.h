@@ -1,4 +1,4 @@
-// mkt_expected.h -- what mkt_matrix.hip needs of mkt_expected.hip: expected-contact tables (distance decay per chromosome and
+// mkt_expected.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_expected.hip: expected-contact tables (distance decay per chromosome and
 // genome-wide, trans block means) and per-cell observed / expected values over one resolution's resident cells.
 #pragma once
 #include <hip/hip_runtime.h>

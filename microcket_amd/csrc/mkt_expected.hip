@@ -1,5 +1,5 @@
 // mkt_expected.hip -- expected-contact tables and observed / expected values of one resolution's binned contact matrix on the GPU;
-// include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_expected, mkt_matrix_fetch_*).
+// include/mkt.h has the definition; the entry points (mkt_matrix_expected, mkt_matrix_fetch_*) are at the end (mkt_matrix_obj.h).
 //
 // A cell belongs to one SEGMENT: a cis cell of chromosome c on diagonal d to segment off_c + d (the row of the cis table), a trans
 // cell to segment nbins + its row of the trans table.  Once per resolution the cells are grouped by segment (KeyGroup, mkt_layout.h,
@@ -16,7 +16,7 @@
 #include <cmath>
 #include <limits>
 
-#include "mkt_expected.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 namespace mkt {
@@ -301,3 +301,114 @@ hipError_t exp_values(const ExpTables* t, const uint16_t* chr, const uint32_t* b
 }
 
 }  // namespace mkt
+
+// ---- the entry points -----------------------------------------------------------------------------------------------------------
+using namespace mkt;
+
+// the tables of res_index for a fetch of rows [first, first + n) of table `which` (0 cis, 1 trans, 2 genome), or the error
+static int mx_expected_tables(mkt_matrix* m, uint32_t res_index, const char* what, uint64_t first, uint64_t n, int which, const ExpTables** out) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_TABLES);
+    const MxRes& r = *rp;
+    const uint64_t rows = which == 0 ? r.nbins : which == 1 ? r.exs.trans_rows : r.exs.genome_rows;
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "%s rows [%llu, +%llu) of %llu", what, (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    *out = &r.ext;
+    return MKT_OK;
+}
+
+extern "C" {
+
+void mkt_expected_opts_default(mkt_expected_opts* o) {
+    if (!o) return;
+    o->use_weights = 1; o->reserved = 0;
+}
+
+int mkt_matrix_expected(mkt_matrix* m, uint32_t res_index, const mkt_expected_opts* opts, mkt_expected_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    const mkt_expected_opts o = mx_opts(opts, mkt_expected_opts_default);
+    if (o.use_weights != 0 && o.use_weights != 1) return mfail(m, MKT_E_ARG, "expected: use_weights %d (0 or 1)", o.use_weights);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "expected: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | (o.use_weights ? MX_WEIGHTS : 0), "expected")) return rc;
+    if (const int rc = mx_cells32(m, "expected", r.nnz)) return rc;
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    mx_invalidate(r, MX_NEW_TABLES);
+    r.exp_sums_ms = r.exp_setup_ms = 0;
+    if (!r.exs.built) {                                                 // with the chromosome of a bin when nothing has built it yet
+        const hipError_t e = mx_timed(m, &r.exp_setup_ms, [&]() -> hipError_t {
+            MKT_TRY(layout_chr(r.lay, mx_cells(r), st));
+            return exp_setup(r.exs, r.lay.chr, r.d_b1, r.d_b2, r.d_cnt, r.nnz, r.nbins, r.d_off, r.off, st);
+        });
+        if (e == hipErrorInvalidValue) return mfail(m, MKT_E_CAPACITY, "expected: segment ids and cell indices of resolution index %u do not fit 64 bits together", res_index);
+        MX_OR_RESET(m, "expected: ", r.ext, e);
+    }
+    MX_OR_RESET(m, "expected: ", r.ext, mx_timed(m, &r.exp_sums_ms, [&] { return exp_sums(r.exs, r.ext, r.lay.chr, r.nbins, r.d_off, o.use_weights ? r.d_w.get() : nullptr, st); }));
+    MX_OR_RESET(m, "expected: ", r.ext, exp_finish(r.exs, r.ext, r.nbins, r.off, st));
+    r.ext.use_weights = o.use_weights;
+    if (info) {
+        info->cis_rows = r.nbins; info->trans_rows = r.exs.trans_rows; info->genome_rows = r.exs.genome_rows;
+        info->n_chrom = (uint32_t)r.off.size(); info->smooth_groups = r.ext.smooth_groups;
+    }
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_expected_cis(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum) {
+    const ExpTables* t = nullptr;
+    const int rc = mx_expected_tables(m, res_index, "cis", first, n, 0, &t);
+    if (rc) return rc;
+    mx_copy_rows(n_valid, t->cis_n, first, n); mx_copy_rows(count_sum, t->cis_c, first, n); mx_copy_rows(balanced_sum, t->cis_s, first, n);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_expected_trans(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum, double* expected) {
+    const ExpTables* t = nullptr;
+    const int rc = mx_expected_tables(m, res_index, "trans", first, n, 1, &t);
+    if (rc) return rc;
+    mx_copy_rows(n_valid, t->tr_n, first, n); mx_copy_rows(count_sum, t->tr_c, first, n); mx_copy_rows(balanced_sum, t->tr_s, first, n); mx_copy_rows(expected, t->tr_e, first, n);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_expected_genome(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* count_sum, double* balanced_sum, double* expected,
+                                     double* expected_smooth) {
+    const ExpTables* t = nullptr;
+    const int rc = mx_expected_tables(m, res_index, "genome", first, n, 2, &t);
+    if (rc) return rc;
+    mx_copy_rows(n_valid, t->g_n, first, n); mx_copy_rows(count_sum, t->g_c, first, n); mx_copy_rows(balanced_sum, t->g_s, first, n);
+    mx_copy_rows(expected, t->g_e, first, n); mx_copy_rows(expected_smooth, t->g_sm, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_values(mkt_matrix* m, uint32_t res_index, int kind, uint64_t first, uint64_t n, double* out) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    if (const int rc = mx_kind(m, "values", kind)) return rc;
+    const MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | (kind != MKT_VALUE_BALANCED ? MX_TABLES : 0), "values")) return rc;
+    if (!r.ext.built) { if (const int rc = mx_need(m, res_index, r, MX_WEIGHTS)) return rc; }
+    if (first > r.nnz || n > r.nnz - first) return mfail(m, MKT_E_ARG, "values of cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)r.nnz);
+    if (!out || n == 0) return MKT_OK;
+    MCHK(m, hipSetDevice(m->device));
+    const double* w = r.ext.built && !r.ext.use_weights ? nullptr : r.d_w.get();       // the tables' own option; without tables, the weights
+    const uint64_t piece = n < (1ull << 24) ? n : (1ull << 24);
+    DevBuf<double> d_out;
+    { hipError_t e_ = d_out.alloc(piece); if (e_ != hipSuccess) return mfail(m, MKT_E_NOMEM, "values: hipMalloc of %llu doubles failed: %s", (unsigned long long)piece, hipGetErrorString(e_)); }
+    for (uint64_t at = 0; at < n; at += piece) {
+        const uint64_t k = n - at < piece ? n - at : piece;
+        hipError_t e = exp_values(r.ext.built ? &r.ext : nullptr, r.ext.built ? r.lay.chr.get() : nullptr, r.d_b1, r.d_b2, r.d_cnt, first + at, k, r.d_off, (uint32_t)r.off.size(), w, kind, d_out, m->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + at, d_out, (size_t)k * 8, hipMemcpyDeviceToHost, m->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+        if (e != hipSuccess) return mfail(m, MKT_E_HIP, "values: cells [%llu, +%llu) failed: %s", (unsigned long long)(first + at), (unsigned long long)k, hipGetErrorString(e));
+    }
+    return MKT_OK;
+}
+
+int mkt_matrix_expected_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sums_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const MxRes& r = m->res[res_index];
+    const bool have = m->ran && r.ext.built;
+    mx_ms(setup_ms, have, r.exp_setup_ms); mx_ms(sums_ms, have, r.exp_sums_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

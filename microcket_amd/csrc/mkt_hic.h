@@ -1,4 +1,4 @@
-// mkt_hic.h -- the .hic container from the resident cells of a matrix object: what mkt_matrix.hip hands to mkt_hic.hip and what it keeps.
+// mkt_hic.h -- the .hic container from the resident cells of a matrix object: what the matrix object (mkt_matrix_obj.h) hands to mkt_hic.hip and what it keeps.
 // include/mkt.h has the file definition, DESIGN.md 7l the design.
 #pragma once
 #include <hip/hip_runtime.h>

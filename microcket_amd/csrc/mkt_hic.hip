@@ -1,7 +1,7 @@
 // mkt_hic.hip -- the .hic container (include/mkt.h has the definition) from the resident cells of a matrix object: regroup the cells of
 // every resolution by chromosome pair and block, serialise the blocks, deflate them into zlib streams (mkt_deflate.h: the LZ77 + Huffman
 // stage of mkt_deflate.hip under its zlib framing) and place them in the file image; the host writes the header, the matrix records, the
-// footer and the normalisation vectors around them.  mkt_matrix.hip has the entry points (mkt_matrix_hic, mkt_matrix_fetch_hic).
+// footer and the normalisation vectors around them.  The entry points (mkt_matrix_hic, .._fetch_hic) are at the end (mkt_matrix_obj.h).
 //
 // Per resolution, from cells that are strictly ascending in (bin1, bin2), that is in (pair, x, y):
 //  * the order (pair, blockNumber, y, x) by STABLE radix passes (launch_radix64) over  composite << ib | cell index, composite =
@@ -25,7 +25,7 @@
 #include <cstring>
 #include <map>
 
-#include "mkt_hic.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_launch.h"
 #include "mkt_segred.h"
 #include "mkt_deflate.h"
@@ -486,3 +486,63 @@ int hic_build(HicState& s, const std::vector<HicResIn>& res, const std::vector<s
 }
 
 }  // namespace mkt
+
+// ---- the entry points -----------------------------------------------------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_hic_opts_default(mkt_hic_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->block_bins = 1000; o->level = 2; o->norm = 1;
+}
+
+int mkt_matrix_hic(mkt_matrix* m, const mkt_hic_opts* opts, mkt_hic_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    const mkt_hic_opts o = mx_opts(opts, mkt_hic_opts_default);
+    if (o.block_bins < 1 || o.block_bins > kHicBlockBinsMax) return mfail(m, MKT_E_ARG, "hic: block_bins %u (1 .. %u: block coordinates are int16)", o.block_bins, kHicBlockBinsMax);
+    if (o.level < 0 || o.level > 2) return mfail(m, MKT_E_ARG, "hic: level %d (0 stored, 1 fixed codes, 2 dynamic codes)", o.level);
+    if (o.norm != 0 && o.norm != 1) return mfail(m, MKT_E_ARG, "hic: norm %d (0 or 1)", o.norm);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "hic: the reserved field is not 0");
+    if (o.norm_label && !*o.norm_label) return mfail(m, MKT_E_ARG, "hic: an empty norm_label");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "hic before run");
+    MCHK(m, hipSetDevice(m->device));
+    std::vector<HicResIn> in(m->res.size());
+    for (size_t k = 0; k < m->res.size(); ++k) {
+        MxRes& r = m->res[k];
+        if (r.nnz) MX(m, "hic: ", layout_chr(r.lay, mx_cells(r), m->stream));
+        in[k].cells = mx_cells(r);
+        in[k].chr = r.nnz ? r.lay.chr.get() : nullptr;
+        in[k].off = &r.off;
+        in[k].bin_size = r.r;
+        in[k].d_w = r.balanced ? r.d_w.get() : nullptr;
+    }
+    HicState hs;                                                        // a refused or failed call leaves the previous file alone
+    std::string why;
+    const int rc = hic_build(hs, in, m->names, m->lens, o, m->stream, &why);
+    if (rc != MKT_OK) return mfail(m, rc, "%s", why.c_str());
+    m->hic = std::move(hs);
+    if (info) *info = m->hic.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_hic(mkt_matrix* m, uint64_t off, char* out, size_t n) {
+    if (!m || (n && !out)) return MKT_E_ARG;
+    if (!(m->ran && m->hic.built)) return mfail(m, MKT_E_STATE, "no .hic file: hic first");
+    const uint64_t fb = m->hic.info.file_bytes;
+    if (off > fb || n > fb - off) return mfail(m, MKT_E_ARG, "range past the end of the .hic file");
+    MCHK(m, hipSetDevice(m->device));
+    if (n) MCHK(m, hipMemcpy(out, m->hic.image.get() + off, n, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+
+int mkt_matrix_hic_timing(const mkt_matrix* m, uint32_t res_index, double* sort_ms, double* serialise_ms, double* deflate_ms, double* pack_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const bool have = m->ran && m->hic.built && res_index < m->hic.timing.size();
+    const HicTiming t = have ? m->hic.timing[res_index] : HicTiming();
+    mx_ms(sort_ms, have, t.sort_ms); mx_ms(serialise_ms, have, t.serialise_ms); mx_ms(deflate_ms, have, t.deflate_ms); mx_ms(pack_ms, have, t.pack_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// mkt_insulation.h -- what mkt_matrix.hip needs of mkt_insulation.hip: the diamond insulation score of every bin at up to four nested
+// mkt_insulation.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_insulation.hip: the diamond insulation score of every bin at up to four nested
 // windows over one resolution's resident cells, and the boundaries called from it.  include/mkt.h has the definition.
 #pragma once
 #include <hip/hip_runtime.h>

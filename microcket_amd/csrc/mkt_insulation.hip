@@ -1,6 +1,6 @@
 // mkt_insulation.hip -- the diamond insulation score of every bin over one resolution's binned contact matrix on the GPU, and the
-// boundaries called from it on the host; include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_insulation,
-// mkt_matrix_fetch_insulation).
+// boundaries called from it on the host; include/mkt.h has the definition; the entry points (mkt_matrix_insulation,
+// mkt_matrix_fetch_insulation) are at the end, on the object of mkt_matrix_obj.h.
 //
 // The sweep.  A GROUP of G lanes owns one bin i of chromosome [lo, hi).  The diamond of the largest window W_max is the rows
 // a = i - p (0 <= p < W_max, a >= lo) and in each row the columns max(i, a + ignore_diags) <= b < min(i + W_max, hi).  Lane l takes
@@ -19,8 +19,7 @@
 #include <cstring>
 #include <limits>
 
-#include "mkt_devbuf.h"
-#include "mkt_insulation.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 #pragma clang fp contract(off)
@@ -211,3 +210,68 @@ hipError_t insulation_run(InsState& s, const InsIn& in, const std::vector<uint32
 }
 
 }  // namespace mkt
+
+// ---- the entry points (comparisons and copies only: nothing here rounds) ------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_insulation_opts_default(mkt_insulation_opts* o) {
+    if (!o) return;
+    o->n_windows = 3; o->window[0] = 5; o->window[1] = 10; o->window[2] = 25; o->window[3] = 0;
+    o->ignore_diags = 2; o->use_weights = 1; o->reserved = 0; o->min_frac_valid = 0.66; o->min_strength = 0.2;
+}
+
+int mkt_matrix_insulation(mkt_matrix* m, uint32_t res_index, const mkt_insulation_opts* opts, mkt_insulation_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    const mkt_insulation_opts o = mx_opts(opts, mkt_insulation_opts_default);
+    if (o.n_windows < 1 || o.n_windows > kInsWindows) return mfail(m, MKT_E_ARG, "insulation: n_windows %d (1 .. 4)", o.n_windows);
+    for (int k = 0; k < o.n_windows; ++k) {
+        if (o.window[k] < 1 || o.window[k] > kInsWmax) return mfail(m, MKT_E_ARG, "insulation: window %d is outside 1 .. %d bins", o.window[k], kInsWmax);
+        if (k && o.window[k] <= o.window[k - 1]) return mfail(m, MKT_E_ARG, "insulation: windows %d, %d are not strictly ascending", o.window[k - 1], o.window[k]);
+    }
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "insulation: ignore_diags %d is negative", o.ignore_diags);
+    if (o.use_weights != 0 && o.use_weights != 1) return mfail(m, MKT_E_ARG, "insulation: use_weights %d (0 or 1)", o.use_weights);
+    if (!(o.min_frac_valid >= 0.0 && o.min_frac_valid <= 1.0)) return mfail(m, MKT_E_ARG, "insulation: min_frac_valid %g is not inside [0, 1]", o.min_frac_valid);
+    if (!(o.min_strength >= 0.0)) return mfail(m, MKT_E_ARG, "insulation: min_strength %g is negative or NaN", o.min_strength);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "insulation: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | (o.use_weights ? MX_WEIGHTS : 0), "insulation")) return rc;
+    if (const int rc = mx_cells32(m, "insulation", r.nnz)) return rc;
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    r.ins = InsState();
+    MX_OR_RESET(m, "insulation: ", r.ins, layout_rows(r.lay, mx_cells(r), st));   // the row pointers and the chromosome of a bin are all the sweep needs
+    InsIn in;
+    in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = r.lay.rowptr; in.off = r.d_off; in.chr = r.lay.chr;
+    in.w = o.use_weights ? r.d_w.get() : nullptr;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    MX_OR_RESET(m, "insulation: ", r.ins, insulation_run(r.ins, in, r.off, o, st));
+    if (info) *info = r.ins.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_insulation(mkt_matrix* m, uint32_t res_index, uint32_t k, uint64_t first, uint64_t n, uint64_t* n_valid, uint64_t* csum, double* bsum,
+                                double* score, double* log2_score, double* strength, uint8_t* boundary) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_INS);
+    const InsState* s = &rp->ins;
+    const uint64_t nb = rp->nbins;
+    if (k >= (uint32_t)s->n_windows) return mfail(m, MKT_E_ARG, "insulation window %u of %d", k, s->n_windows);
+    if (first > nb || n > nb - first) return mfail(m, MKT_E_ARG, "insulation bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nb);
+    const uint64_t at = (uint64_t)k * nb + first;
+    mx_copy_rows(n_valid, s->n_valid, at, n); mx_copy_rows(csum, s->csum, at, n); mx_copy_rows(bsum, s->bsum, at, n); mx_copy_rows(score, s->score, at, n);
+    mx_copy_rows(log2_score, s->log2_score, at, n); mx_copy_rows(strength, s->strength, at, n); mx_copy_rows(boundary, s->boundary, at, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_insulation_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const InsState& s = m->res[res_index].ins;
+    const bool have = m->ran && s.built;
+    mx_ms(setup_ms, have, s.setup_ms); mx_ms(sweep_ms, have, s.sweep_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// mkt_loops.h -- what mkt_matrix.hip needs of mkt_loops.hip: loop calling (donut enrichment, FDR thresholds, clustering) over one
+// mkt_loops.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_loops.hip: loop calling (donut enrichment, FDR thresholds, clustering) over one
 // resolution's resident cells, the weights and the smoothed genome-wide expected.  include/mkt.h has the definition.
 #pragma once
 #include <hip/hip_runtime.h>

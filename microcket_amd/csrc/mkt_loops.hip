@@ -1,6 +1,6 @@
 // mkt_loops.hip -- loop calling over one resolution's binned contact matrix on the GPU: donut enrichment of every candidate cell
 // against its neighbourhood, the (expected chunk x count) histogram, the flags against the FDR thresholds; include/mkt.h has the
-// definition, mkt_matrix.hip the entry points (mkt_matrix_loops, mkt_matrix_fetch_loop_*).
+// definition; the entry points (mkt_matrix_loops, mkt_matrix_fetch_loop_*) are at the end, on the object of mkt_matrix_obj.h.
 //
 // The neighbourhood pass.  A GROUP of lanes owns one candidate cell (i, j) and its window w.  The group stages what all its lanes
 // share: E[d] for the 4 w + 1 diagonals (j - i) - 2 w .. (j - i) + 2 w in LDS, the validity of the columns j - w .. j + w as a bit
@@ -24,7 +24,7 @@
 #include <cstring>
 #include <unordered_map>
 
-#include "mkt_loops.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 #pragma clang fp contract(off)
@@ -418,3 +418,92 @@ hipError_t loops_run(LoopsState& s, const LoopsIn& in, const std::vector<uint32_
 }
 
 }  // namespace mkt
+
+// ---- the entry points (comparisons and copies only: nothing here rounds) ------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_loops_opts_default(mkt_loops_opts* o) {
+    if (!o) return;
+    o->peak = 2; o->window = 5; o->window_max = 20; o->min_ll_count = 16; o->min_dist = 8; o->max_dist = 0; o->fdr = 0.1; o->cluster_radius = 2; o->reserved = 0;
+}
+
+int mkt_matrix_loops(mkt_matrix* m, uint32_t res_index, const mkt_loops_opts* opts, mkt_loops_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    const mkt_loops_opts o = mx_opts(opts, mkt_loops_opts_default);
+    if (o.peak < 0) return mfail(m, MKT_E_ARG, "loops: peak %d is negative", o.peak);
+    if (o.window <= o.peak) return mfail(m, MKT_E_ARG, "loops: window %d is not larger than peak %d", o.window, o.peak);
+    if (o.window_max < o.window || o.window_max > kLpWmax) return mfail(m, MKT_E_ARG, "loops: window_max %d (window %d .. %d)", o.window_max, o.window, kLpWmax);
+    if (o.min_ll_count < 0) return mfail(m, MKT_E_ARG, "loops: min_ll_count %d is negative", o.min_ll_count);
+    if (o.min_dist < 0 || o.max_dist < 0) return mfail(m, MKT_E_ARG, "loops: min_dist %d / max_dist %d is negative", o.min_dist, o.max_dist);
+    if (!(o.fdr > 0.0 && o.fdr < 1.0)) return mfail(m, MKT_E_ARG, "loops: fdr %g is not inside (0, 1)", o.fdr);
+    if (o.cluster_radius < 0) return mfail(m, MKT_E_ARG, "loops: cluster_radius %d is negative", o.cluster_radius);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "loops: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "loops")) return rc;
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    r.lps = LoopsState();
+    MX_OR_RESET(m, "loops: ", r.lps, layout_rows(r.lay, mx_cells(r), st));   // the row pointers are all the pass needs
+    LoopsIn in;
+    in.b1 = r.d_b1; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = r.lay.rowptr; in.off = r.d_off; in.chr = r.lay.chr;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr; in.E = r.ext.d_cis_sm;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.genome_rows = r.exs.genome_rows; in.nchr = (uint32_t)r.off.size();
+    MX_OR_RESET(m, "loops: ", r.lps, loops_run(r.lps, in, r.off, o, st));
+    if (info) *info = r.lps.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_loop_cells(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status, uint8_t* window, uint8_t* chunk, double* r,
+                                uint8_t* enriched, uint64_t* csum_ll, uint16_t* kept, double* bsum, double* esum, double* e) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    const LoopsState* s = &rp->lps;
+    const uint64_t nnz = m->res[res_index].nnz;
+    if (first > nnz || n > nnz - first) return mfail(m, MKT_E_ARG, "loop cells [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)nnz);
+    MCHK(m, hipSetDevice(m->device));
+    if (n == 0) return MKT_OK;
+    if (status) MCHK(m, hipMemcpy(status, s->status.get() + first, n, hipMemcpyDeviceToHost));
+    if (window) MCHK(m, hipMemcpy(window, s->window.get() + first, n, hipMemcpyDeviceToHost));
+    if (chunk) MCHK(m, hipMemcpy(chunk, s->chunk.get() + 4 * first, 4 * n, hipMemcpyDeviceToHost));
+    if (r) MCHK(m, hipMemcpy(r, s->r.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (enriched) MCHK(m, hipMemcpy(enriched, s->enriched.get() + first, n, hipMemcpyDeviceToHost));
+    if (csum_ll) MCHK(m, hipMemcpy(csum_ll, s->csum.get() + first, 8 * n, hipMemcpyDeviceToHost));
+    if (kept) MCHK(m, hipMemcpy(kept, s->kept.get() + 4 * first, 8 * n, hipMemcpyDeviceToHost));
+    if (bsum) MCHK(m, hipMemcpy(bsum, s->bsum.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (esum) MCHK(m, hipMemcpy(esum, s->esum.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    if (e) MCHK(m, hipMemcpy(e, s->e.get() + 4 * first, 32 * n, hipMemcpyDeviceToHost));
+    return MKT_OK;
+}
+int mkt_matrix_fetch_loop_hist(mkt_matrix* m, uint32_t res_index, uint64_t* hist) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    if (hist) memcpy(hist, rp->lps.hist.data(), rp->lps.hist.size() * 8);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_loop_thresholds(mkt_matrix* m, uint32_t res_index, uint32_t* thresholds) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    if (thresholds) memcpy(thresholds, rp->lps.thr.data(), rp->lps.thr.size() * 4);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_loops(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, mkt_loop* out) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_LOOPS);
+    const LoopsState* s = &rp->lps;
+    const uint64_t rows = s->loops.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "loops [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    if (out && n) memcpy(out, s->loops.data() + first, (size_t)n * sizeof(mkt_loop));
+    return MKT_OK;
+}
+int mkt_matrix_loops_timing(const mkt_matrix* m, uint32_t res_index, double* pass_ms, double* hist_ms, double* flag_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const LoopsState& s = m->res[res_index].lps;
+    const bool have = m->ran && s.built;
+    mx_ms(pass_ms, have, s.pass_ms); mx_ms(hist_ms, have, s.hist_ms); mx_ms(flag_ms, have, s.flag_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

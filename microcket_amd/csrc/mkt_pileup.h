@@ -1,4 +1,4 @@
-// mkt_pileup.h -- what mkt_matrix.hip needs of mkt_pileup.hip: the pileup (the average contact map in a window of 2 * flank + 1 bins
+// mkt_pileup.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_pileup.hip: the pileup (the average contact map in a window of 2 * flank + 1 bins
 // around a list of features) over one resolution's resident cells, and the scores formed from it.  include/mkt.h has the definition.
 #pragma once
 #include <hip/hip_runtime.h>

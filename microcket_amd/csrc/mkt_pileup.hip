@@ -1,5 +1,5 @@
 // mkt_pileup.hip -- the pileup of one resolution's binned contact matrix around a list of features on the GPU, and the scores formed
-// from it on the host; include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_pileup, mkt_matrix_fetch_pileup).
+// from it on the host; include/mkt.h has the definition; the entry points (mkt_matrix_pileup, .._fetch_pileup) are at the end (mkt_matrix_obj.h).
 //
 // The sweep.  One workgroup owns one CHUNK of 256 features, and inside it one thread owns a position (p, q) of the window (a thread
 // takes the positions t, t + threads, ..), so a position's values are added by one thread in ascending feature index and no sum is
@@ -22,8 +22,7 @@
 #include <cstring>
 #include <limits>
 
-#include "mkt_devbuf.h"
-#include "mkt_pileup.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 #pragma clang fp contract(off)
@@ -241,3 +240,76 @@ hipError_t pileup_run(PileState& s, const PileIn& in, const uint32_t* a, const u
 }
 
 }  // namespace mkt
+
+// ---- the entry points (comparisons and copies only: nothing here rounds) ------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_pileup_opts_default(mkt_pileup_opts* o) {
+    if (!o) return;
+    o->flank = 10; o->corner = 6; o->kind = MKT_VALUE_OE_SMOOTH; o->ignore_diags = 2; o->edges = 0; o->min_dist = 0; o->max_dist = 0; o->reserved = 0;
+}
+
+int mkt_matrix_pileup(mkt_matrix* m, uint32_t res_index, const uint32_t* bin1, const uint32_t* bin2, uint64_t n, const mkt_pileup_opts* opts, mkt_pileup_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    const mkt_pileup_opts o = mx_opts(opts, mkt_pileup_opts_default);
+    if (o.flank < 1 || o.flank > kPileFlankMax) return mfail(m, MKT_E_ARG, "pileup: flank %d is outside 1 .. %d", o.flank, kPileFlankMax);
+    if (o.corner < 1 || o.corner > o.flank) return mfail(m, MKT_E_ARG, "pileup: corner %d is outside 1 .. flank %d", o.corner, o.flank);
+    if (const int rc = mx_kind(m, "pileup", o.kind)) return rc;
+    if (o.ignore_diags < 0) return mfail(m, MKT_E_ARG, "pileup: ignore_diags %d is negative", o.ignore_diags);
+    if (o.edges != 0 && o.edges != 1) return mfail(m, MKT_E_ARG, "pileup: edges %d (0 or 1)", o.edges);
+    if (o.min_dist < 0 || o.max_dist < 0) return mfail(m, MKT_E_ARG, "pileup: min_dist %d / max_dist %d is negative", o.min_dist, o.max_dist);
+    if (o.max_dist && o.max_dist < o.min_dist) return mfail(m, MKT_E_ARG, "pileup: max_dist %d is below min_dist %d", o.max_dist, o.min_dist);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "pileup: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "pileup")) return rc;
+    if (n && (!bin1 || !bin2)) return mfail(m, MKT_E_ARG, "pileup: %llu features without their bins (bin1 or bin2 is NULL)", (unsigned long long)n);
+    if (n >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "pileup: %llu features: fewer than 2^32 are needed", (unsigned long long)n);
+    if (const int rc = mx_cells32(m, "pileup", r.nnz)) return rc;
+    PileState ps;                                                       // a refused or failed call leaves the previous results alone
+    std::string why;
+    if (!pileup_status(bin1, bin2, n, r.off, r.nbins, o, ps.status, why)) return mfail(m, MKT_E_ARG, "%s", why.c_str());
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    MX(m, "pileup: ", layout_rows(r.lay, mx_cells(r), st));             // the row pointers and the chromosome of a bin are all the sweep needs
+    PileIn in;
+    in.b2 = r.d_b2; in.cnt = r.d_cnt; in.rowptr = r.lay.rowptr; in.off = r.d_off; in.chr = r.lay.chr;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr;
+    in.E = o.kind == MKT_VALUE_OE ? r.ext.d_cis_e.get() : o.kind == MKT_VALUE_OE_SMOOTH ? r.ext.d_cis_sm.get() : nullptr;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    MX(m, "pileup: ", pileup_run(ps, in, bin1, bin2, n, o, st));
+    r.pile = std::move(ps);
+    if (info) *info = r.pile.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_pileup(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* csum, double* vsum, double* mean) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_PILE);
+    const PileState* s = &rp->pile;
+    const uint64_t rows = s->n.size();
+    mx_copy_rows(n, s->n, 0, rows); mx_copy_rows(csum, s->csum, 0, rows); mx_copy_rows(vsum, s->vsum, 0, rows); mx_copy_rows(mean, s->mean, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_pileup_status(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* status) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_PILE);
+    const PileState* s = &rp->pile;
+    const uint64_t rows = s->status.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "pileup features [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    mx_copy_rows(status, s->status, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_pileup_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const PileState& s = m->res[res_index].pile;
+    const bool have = m->ran && s.built;
+    mx_ms(setup_ms, have, s.setup_ms); mx_ms(sweep_ms, have, s.sweep_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// mkt_saddle.h -- what mkt_matrix.hip needs of mkt_saddle.hip: the saddle tables (the mean observed / expected of every pair of groups
+// mkt_saddle.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_saddle.hip: the saddle tables (the mean observed / expected of every pair of groups
 // of bins ranked by a track) over one resolution's resident cells, and the compartment strength formed from them.  include/mkt.h has
 // the definition.
 #pragma once

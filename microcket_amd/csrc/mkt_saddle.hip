@@ -1,6 +1,6 @@
 // mkt_saddle.hip -- the saddle tables of one resolution's binned contact matrix on the GPU (the sum of observed / expected over the
 // cells of every pair of groups of bins ranked by a track), and the groups, the positions and the compartment strength formed on the
-// host; include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_saddle, mkt_matrix_fetch_saddle*).
+// host; include/mkt.h has the definition; the entry points (mkt_matrix_saddle, mkt_matrix_fetch_saddle*) are at the end (mkt_matrix_obj.h).
 //
 // The sweep.  One workgroup owns one CHUNK of 4096 cells in stored order and keeps the chunk's table T_c in LDS, one double per unordered
 // pair of groups (a <= b; Q (Q + 1) / 2 of them).  The chunk is walked in pieces of 1024 cells.  Per piece every thread first works out,
@@ -22,8 +22,7 @@
 #include <limits>
 #include <numeric>
 
-#include "mkt_devbuf.h"
-#include "mkt_saddle.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 #pragma clang fp contract(off)
@@ -277,3 +276,93 @@ hipError_t saddle_run(SaddleState& s, const SaddleIn& in, const std::vector<uint
 }
 
 }  // namespace mkt
+
+// ---- the entry points (comparisons and copies only: nothing here rounds) ------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_saddle_opts_default(mkt_saddle_opts* o) {
+    if (!o) return;
+    o->n_groups = 50; o->trim_lo = 250; o->trim_hi = 250; o->contact = 0; o->kind = MKT_VALUE_OE; o->min_diag = 2; o->max_diag = 0; o->corner = 0; o->reserved = 0;
+}
+
+int mkt_matrix_saddle(mkt_matrix* m, uint32_t res_index, const mkt_saddle_opts* opts, const double* track, mkt_saddle_info* info) {
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp);
+    const mkt_saddle_opts o = mx_opts(opts, mkt_saddle_opts_default);
+    if (o.n_groups < 2 || o.n_groups > kSaddleGroupsMax) return mfail(m, MKT_E_ARG, "saddle: n_groups %d is outside 2 .. %d", o.n_groups, kSaddleGroupsMax);
+    if (o.trim_lo < 0 || o.trim_hi < 0) return mfail(m, MKT_E_ARG, "saddle: trim_lo %d / trim_hi %d is negative", o.trim_lo, o.trim_hi);
+    if ((int64_t)o.trim_lo + o.trim_hi >= 10000) return mfail(m, MKT_E_ARG, "saddle: trim_lo %d + trim_hi %d leaves nothing (basis points: below 10000 together)", o.trim_lo, o.trim_hi);
+    if (o.contact != 0 && o.contact != 1) return mfail(m, MKT_E_ARG, "saddle: contact %d (0 cis, 1 trans)", o.contact);
+    if (o.kind != MKT_VALUE_OE && o.kind != MKT_VALUE_OE_SMOOTH) return mfail(m, MKT_E_ARG, "saddle: kind %d (1 oe, 2 oe_smooth)", o.kind);
+    if (o.min_diag < 0 || o.max_diag < 0) return mfail(m, MKT_E_ARG, "saddle: min_diag %d / max_diag %d is negative", o.min_diag, o.max_diag);
+    if (o.max_diag && o.max_diag < o.min_diag) return mfail(m, MKT_E_ARG, "saddle: max_diag %d is below min_diag %d", o.max_diag, o.min_diag);
+    if (o.corner < 0 || o.corner > o.n_groups / 2) return mfail(m, MKT_E_ARG, "saddle: corner %d is outside 1 .. n_groups / 2 = %d (0: the default)", o.corner, o.n_groups / 2);
+    if (o.reserved != 0) return mfail(m, MKT_E_ARG, "saddle: the reserved field is not 0");
+    MxRes& r = *rp;
+    if (const int rc = mx_need(m, res_index, r, MX_RAN | MX_TABLES, "saddle")) return rc;
+    if (!track) return mfail(m, MKT_E_ARG, "saddle: no track (track is NULL)");
+    if (const int rc = mx_cells32(m, "saddle", r.nnz)) return rc;
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    MX(m, "saddle: ", layout_chr(r.lay, mx_cells(r), st));              // the chromosome of a bin is all the sweep needs of the layout
+    SaddleIn in;
+    in.b1 = r.d_b1; in.b2 = r.d_b2; in.cnt = r.d_cnt; in.chr = r.lay.chr;
+    in.w = r.ext.use_weights ? r.d_w.get() : nullptr;
+    in.cis_div = o.kind == MKT_VALUE_OE ? r.ext.d_cis_e.get() : r.ext.d_cis_sm.get(); in.tr_div = r.ext.d_tr_e;
+    in.nnz = r.nnz; in.nbins = r.nbins; in.nchr = (uint32_t)r.off.size();
+    SaddleState ss;                                                     // a refused or failed call leaves the previous results alone
+    MX(m, "saddle: ", saddle_run(ss, in, r.off, track, o, st));
+    r.sad = std::move(ss);
+    if (info) *info = r.sad.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle(mkt_matrix* m, uint32_t res_index, uint64_t* n, uint64_t* nnz, uint64_t* csum, double* vsum, double* mean) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->n.size();
+    mx_copy_rows(n, s->n, 0, rows); mx_copy_rows(nnz, s->nnz, 0, rows); mx_copy_rows(csum, s->csum, 0, rows); mx_copy_rows(vsum, s->vsum, 0, rows);
+    mx_copy_rows(mean, s->mean, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle_groups(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint8_t* group) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->group.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "saddle groups of bins [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    mx_copy_rows(group, s->group, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle_edges(mkt_matrix* m, uint32_t res_index, uint64_t* bins, double* lo, double* hi) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->g_bins.size();
+    mx_copy_rows(bins, s->g_bins, 0, rows); mx_copy_rows(lo, s->g_lo, 0, rows); mx_copy_rows(hi, s->g_hi, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_saddle_profile(mkt_matrix* m, uint32_t res_index, double* strength, double* aa_ab, double* bb_ab) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SADDLE);
+    const SaddleState* s = &rp->sad;
+    const uint64_t rows = s->strength.size();
+    mx_copy_rows(strength, s->strength, 0, rows); mx_copy_rows(aa_ab, s->aa_ab, 0, rows); mx_copy_rows(bb_ab, s->bb_ab, 0, rows);
+    return MKT_OK;
+}
+
+int mkt_matrix_saddle_timing(const mkt_matrix* m, uint32_t res_index, double* setup_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const SaddleState& s = m->res[res_index].sad;
+    const bool have = m->ran && s.built;
+    mx_ms(setup_ms, have, s.setup_ms); mx_ms(sweep_ms, have, s.sweep_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

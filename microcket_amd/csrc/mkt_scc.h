@@ -1,4 +1,4 @@
-// mkt_scc.h -- what mkt_matrix.hip needs of mkt_scc.hip: the stratum-adjusted correlation of two binned contact matrices of one
+// mkt_scc.h -- what the matrix object (mkt_matrix_obj.h) needs of mkt_scc.hip: the stratum-adjusted correlation of two binned contact matrices of one
 // resolution (both smoothed with a box filter, correlated diagonal by diagonal, the correlations combined with weights).
 // include/mkt.h has the definition.
 #pragma once

@@ -1,7 +1,7 @@
 // mkt_scc.hip -- the stratum-adjusted correlation of two binned contact matrices of one resolution on the GPU: both maps smoothed with
 // a (2h + 1)^2 box filter, then the five sums of every diagonal (stratum) of every chromosome; the correlations and their weighted
-// mean are formed on the host.  include/mkt.h has the definition, mkt_matrix.hip the entry points (mkt_matrix_scc,
-// mkt_matrix_fetch_scc_*).
+// mean are formed on the host.  include/mkt.h has the definition; the entry points (mkt_matrix_scc, mkt_matrix_fetch_scc_*) are at
+// the end, on the object of mkt_matrix_obj.h.
 //
 // Work goes chromosome by chromosome, in SLABS of whole chunks of 256 rows.
 //  * The fill.  A slab's part of both matrices is laid out densely in BAND coordinates (row i, e = j - i): the rows of the slab and h
@@ -29,8 +29,7 @@
 #include <cstring>
 #include <limits>
 
-#include "mkt_devbuf.h"
-#include "mkt_scc.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_segred.h"
 
 #pragma clang fp contract(off)
@@ -326,3 +325,95 @@ hipError_t scc_run(SccState& s, const SccSide& a, const SccSide& b, const std::v
 }
 
 }  // namespace mkt
+
+// ---- the entry points (comparisons and copies only: nothing here rounds) ------------------------------------------------------------
+using namespace mkt;
+extern "C" {
+
+void mkt_scc_opts_default(mkt_scc_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->h = 5; o->weighting = MKT_SCC_WEIGHT_N; o->min_n = 3;
+}
+
+int mkt_matrix_scc(mkt_matrix* a, uint32_t res_a, mkt_matrix* b, uint32_t res_b, const mkt_scc_opts* opts, mkt_scc_info* info) {
+    mkt_matrix* m = a;
+    if (m && info) memset(info, 0, sizeof *info);
+    MxRes* rp = nullptr;
+    MX_RES(m, res_a, &rp);
+    if (!b) return mfail(m, MKT_E_ARG, "scc: no second matrix (b is NULL)");
+    if (res_b >= b->res.size()) return mfail(m, MKT_E_ARG, "scc: resolution index %u of %zu in the second matrix", res_b, b->res.size());
+    MxRes& ra = *rp;
+    MxRes& rb = b->res[res_b];
+    if (ra.r != rb.r) return mfail(m, MKT_E_ARG, "scc: resolution %u against resolution %u", ra.r, rb.r);
+    if (a->names != b->names || a->lens != b->lens) return mfail(m, MKT_E_ARG, "scc: the chromosome tables of the two matrices differ");
+    if (a->device != b->device) return mfail(m, MKT_E_ARG, "scc: the matrices live on devices %d and %d", a->device, b->device);
+    mkt_scc_opts o = mx_opts(opts, mkt_scc_opts_default);
+    if (o.h < 0 || o.h > kSccHMax) return mfail(m, MKT_E_ARG, "scc: h %d is outside 0 .. %d", o.h, kSccHMax);
+    if (o.min_diag < 0 || o.max_diag < 0) return mfail(m, MKT_E_ARG, "scc: min_diag %d / max_diag %d is negative", o.min_diag, o.max_diag);
+    if (o.use_weights != 0 && o.use_weights != 1) return mfail(m, MKT_E_ARG, "scc: use_weights %d (0 or 1)", o.use_weights);
+    if (o.weighting != MKT_SCC_WEIGHT_N && o.weighting != MKT_SCC_WEIGHT_VAR) return mfail(m, MKT_E_ARG, "scc: weighting %d (0 n, 1 var)", o.weighting);
+    if (o.min_n < 2) return mfail(m, MKT_E_ARG, "scc: min_n %d is below 2", o.min_n);
+    if (o.slab_rows < 0 || o.slab_rows % (int32_t)kSccChunk != 0) return mfail(m, MKT_E_ARG, "scc: slab_rows %d is not 0 or a positive multiple of %u", o.slab_rows, kSccChunk);
+    if (o.reserved[0] != 0 || o.reserved[1] != 0 || o.reserved[2] != 0) return mfail(m, MKT_E_ARG, "scc: a reserved word is not 0");
+    if (o.max_diag == 0) {                                              // every diagonal of the longest chromosome
+        uint64_t longest = 1;
+        for (size_t c = 0; c < ra.off.size(); ++c) longest = std::max<uint64_t>(longest, (c + 1 < ra.off.size() ? ra.off[c + 1] : ra.nbins) - ra.off[c]);
+        o.max_diag = (int32_t)std::min<uint64_t>(longest - 1, 0x7FFFFF00u);
+    }
+    if (o.max_diag < o.min_diag) return mfail(m, MKT_E_ARG, "scc: max_diag %d is below min_diag %d", o.max_diag, o.min_diag);
+    if (!a->ran || !b->ran) return mfail(m, MKT_E_STATE, "scc before run%s", a->ran ? " of the second matrix" : "");
+    if (o.use_weights && !ra.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u: balance first", res_a);
+    if (o.use_weights && !rb.balanced) return mfail(m, MKT_E_STATE, "no weights for resolution index %u of the second matrix: balance first", res_b);
+    if (ra.nnz >= (1ull << 32) || rb.nnz >= (1ull << 32)) return mfail(m, MKT_E_CAPACITY, "scc: %llu and %llu cells: fewer than 2^32 are needed (cell indices are 32-bit)", (unsigned long long)ra.nnz, (unsigned long long)rb.nnz);
+    MCHK(m, hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    MX(m, "scc: ", layout_rows(ra.lay, mx_cells(ra), st));              // the row pointers find a slab's cells
+    if (b != a || res_b != res_a) {
+        MX(m, "scc: ", layout_rows(rb.lay, mx_cells(rb), b->stream));
+        MX(m, "scc: ", hipStreamSynchronize(b->stream));                // b's buffers are read on a's stream from here on
+    }
+    SccSide sa, sb;
+    sa.b1 = ra.d_b1; sa.b2 = ra.d_b2; sa.cnt = ra.d_cnt; sa.rowptr = ra.lay.rowptr; sa.w = o.use_weights ? ra.d_w.get() : nullptr; sa.nnz = ra.nnz;
+    sb.b1 = rb.d_b1; sb.b2 = rb.d_b2; sb.cnt = rb.d_cnt; sb.rowptr = rb.lay.rowptr; sb.w = o.use_weights ? rb.d_w.get() : nullptr; sb.nnz = rb.nnz;
+    SccState ss;                                                        // a refused or failed call leaves the previous results alone
+    std::string why;
+    const hipError_t e = scc_run(ss, sa, sb, ra.off, ra.nbins, o, st, &why);
+    if (e == hipErrorOutOfMemory && !why.empty()) return mfail(m, MKT_E_NOMEM, "scc: %s", why.c_str());
+    if (e != hipSuccess) return mx_hip(m, "scc: ", e, true);
+    ra.scc = std::move(ss);
+    if (info) *info = ra.scc.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_scc_strata(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, uint64_t* n_cand, uint64_t* n_used, double* sx, double* sy, double* sxx,
+                                double* syy, double* sxy, double* rho, double* w) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SCC);
+    const SccState* s = &rp->scc;
+    const uint64_t rows = s->n.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "scc strata [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    mx_copy_rows(n_cand, s->n_cand, first, n); mx_copy_rows(n_used, s->n, first, n); mx_copy_rows(sx, s->sx, first, n); mx_copy_rows(sy, s->sy, first, n);
+    mx_copy_rows(sxx, s->sxx, first, n); mx_copy_rows(syy, s->syy, first, n); mx_copy_rows(sxy, s->sxy, first, n); mx_copy_rows(rho, s->rho, first, n); mx_copy_rows(w, s->w, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_scc_chrom(mkt_matrix* m, uint32_t res_index, uint64_t first, uint64_t n, double* scc, double* num, double* den, uint64_t* n_scored) {
+    MxRes* rp = nullptr;
+    MX_RES(m, res_index, &rp, MX_SCC);
+    const SccState* s = &rp->scc;
+    const uint64_t rows = s->c_scc.size();
+    if (first > rows || n > rows - first) return mfail(m, MKT_E_ARG, "scc chromosomes [%llu, +%llu) of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)rows);
+    mx_copy_rows(scc, s->c_scc, first, n); mx_copy_rows(num, s->c_num, first, n); mx_copy_rows(den, s->c_den, first, n); mx_copy_rows(n_scored, s->c_scored, first, n);
+    return MKT_OK;
+}
+
+int mkt_matrix_scc_timing(const mkt_matrix* m, uint32_t res_index, double* fill_ms, double* sweep_ms) {
+    if (!m || res_index >= m->res.size()) return MKT_E_ARG;
+    const SccState& s = m->res[res_index].scc;
+    const bool have = m->ran && s.built;
+    mx_ms(fill_ms, have, s.fill_ms); mx_ms(sweep_ms, have, s.sweep_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

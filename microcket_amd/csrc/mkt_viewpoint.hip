@@ -1,7 +1,7 @@
 // mkt_viewpoint.hip -- viewpoint contact profiles (a virtual 4C) over the resident pair records of a matrix object: the contacts between
 // one chromosome (the viewpoint) and a set of partner chromosomes, the two sides binned at different sizes.  include/mkt.h has the
-// definition, mkt_matrix.hip the entry points (mkt_matrix_viewpoint, mkt_matrix_fetch_viewpoint_*), mkt_viewpoint.h the host half
-// (hotspot cut, string order, texts).
+// definition, mkt_viewpoint.h the host half (hotspot cut, string order, texts); the entry points (mkt_matrix_viewpoint,
+// mkt_matrix_fetch_viewpoint_*) are at the end, on the object of mkt_matrix_obj.h.
 //
 // The hot path is a streaming pass over the n 16-byte records, made twice: one 16-byte vector load per lane, the roles of the two
 // chromosomes from a byte table staged in LDS once per workgroup, the two bin indices by one integer division each.
@@ -22,11 +22,10 @@
 #include <cstdio>
 #include <cstring>
 
-#include "mkt_devbuf.h"
 #include "mkt_launch.h"
+#include "mkt_matrix_obj.h"
 #include "mkt_rle.h"
 #include "mkt_segred.h"
-#include "mkt_viewpoint.h"
 
 namespace mkt {
 
@@ -266,3 +265,87 @@ int vp_run(VpState& s, const uint4* rec, uint64_t n, const std::vector<std::stri
 }
 
 }  // namespace mkt
+
+// ---- the entry points -----------------------------------------------------------------------------------------------------------
+using namespace mkt;
+
+static int vp_have(mkt_matrix* m) {
+    if (!m) return MKT_E_ARG;
+    if (!(m->ran && m->vp.built)) return mfail(m, MKT_E_STATE, "no viewpoint profile: viewpoint first");
+    return MKT_OK;
+}
+
+extern "C" {
+
+void mkt_viewpoint_opts_default(mkt_viewpoint_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->vbin = 200; o->pbin = 1000000; o->min_count = 1; o->hotspot_ratio = 0.01;
+}
+
+int mkt_matrix_viewpoint(mkt_matrix* m, const mkt_viewpoint_opts* opts, mkt_viewpoint_info* info) {
+    if (!m) return MKT_E_ARG;
+    if (info) memset(info, 0, sizeof *info);
+    const mkt_viewpoint_opts o = mx_opts(opts, mkt_viewpoint_opts_default);
+    const uint32_t nc = (uint32_t)m->names.size();
+    if (o.viewpoint >= nc) return mfail(m, MKT_E_ARG, "viewpoint: chromosome index %u of %u", o.viewpoint, nc);
+    if (o.partner_mask && o.partner_mask[o.viewpoint]) return mfail(m, MKT_E_ARG, "viewpoint: %s is in its own partner mask", m->names[o.viewpoint].c_str());
+    if (o.vbin == 0 || o.pbin == 0) return mfail(m, MKT_E_ARG, "viewpoint: a bin size of 0 (vbin %u, pbin %u)", o.vbin, o.pbin);
+    if (o.origin != 0 && o.origin != 1) return mfail(m, MKT_E_ARG, "viewpoint: origin %d (0 or 1)", o.origin);
+    if (o.second_side_only != 0 && o.second_side_only != 1) return mfail(m, MKT_E_ARG, "viewpoint: second_side_only %d (0 or 1)", o.second_side_only);
+    if (o.min_count == 0) return mfail(m, MKT_E_ARG, "viewpoint: min_count 0 (at least 1 is needed)");
+    if (!(o.hotspot_ratio >= 0.0 && o.hotspot_ratio < 1.0)) return mfail(m, MKT_E_ARG, "viewpoint: hotspot_ratio %g is outside [0, 1)", o.hotspot_ratio);
+    if (o.reserved[0] != 0 || o.reserved[1] != 0) return mfail(m, MKT_E_ARG, "viewpoint: a reserved word is not 0");
+    if (!m->ran) return mfail(m, MKT_E_STATE, "viewpoint before run");
+    std::vector<uint8_t> role(nc, 0);
+    for (uint32_t c = 0; c < nc; ++c) role[c] = c == o.viewpoint ? 1 : (!o.partner_mask || o.partner_mask[c]) ? 2 : 0;
+    MCHK(m, hipSetDevice(m->device));
+    VpState vs;                                                         // a refused or failed call leaves the previous results alone
+    std::string why;
+    const int rc = vp_run(vs, reinterpret_cast<const uint4*>(m->d_rec.get()), m->n, m->names, m->lens, role, o, m->stream, &why);
+    if (rc != MKT_OK) return mfail(m, rc, "viewpoint: %s", why.c_str());
+    m->vp = std::move(vs);
+    if (info) *info = m->vp.info;
+    return MKT_OK;
+}
+
+int mkt_matrix_fetch_viewpoint_links(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* vbin, uint32_t* chrom, uint32_t* pbin, uint32_t* count) {
+    if (const int rc = vp_have(m)) return rc;
+    const std::vector<VpLink>& v = m->vp.links;
+    if (first > v.size() || n > v.size() - first) return mfail(m, MKT_E_ARG, "viewpoint links [%llu, +%llu) of %zu", (unsigned long long)first, (unsigned long long)n, v.size());
+    for (uint64_t k = 0; k < n; ++k) {
+        const VpLink& l = v[first + k];
+        if (vbin) vbin[k] = l.vbin;
+        if (chrom) chrom[k] = l.chrom;
+        if (pbin) pbin[k] = l.pbin;
+        if (count) count[k] = l.count;
+    }
+    return MKT_OK;
+}
+int mkt_matrix_fetch_viewpoint_track(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* count) {
+    if (const int rc = vp_have(m)) return rc;
+    const std::vector<uint32_t>& v = m->vp.track;
+    if (first > v.size() || n > v.size() - first) return mfail(m, MKT_E_ARG, "viewpoint track bins [%llu, +%llu) of %zu", (unsigned long long)first, (unsigned long long)n, v.size());
+    if (count && n) memcpy(count, v.data() + first, n * 4);
+    return MKT_OK;
+}
+int mkt_matrix_fetch_viewpoint_partners(mkt_matrix* m, uint64_t first, uint64_t n, uint32_t* chrom, uint32_t* pbin, uint32_t* count) {
+    if (const int rc = vp_have(m)) return rc;
+    const std::vector<VpCell>& v = m->vp.partners;
+    if (first > v.size() || n > v.size() - first) return mfail(m, MKT_E_ARG, "viewpoint partner cells [%llu, +%llu) of %zu", (unsigned long long)first, (unsigned long long)n, v.size());
+    for (uint64_t k = 0; k < n; ++k) {
+        const VpCell& c = v[first + k];
+        if (chrom) chrom[k] = c.chrom;
+        if (pbin) pbin[k] = c.pbin;
+        if (count) count[k] = c.count;
+    }
+    return MKT_OK;
+}
+int mkt_matrix_viewpoint_timing(const mkt_matrix* m, double* scan_ms, double* sort_ms) {
+    if (!m) return MKT_E_ARG;
+    const bool have = m->ran && m->vp.built;
+    mx_ms(scan_ms, have, m->vp.scan_ms); mx_ms(sort_ms, have, m->vp.sort_ms);
+    return MKT_OK;
+}
+
+}  // extern "C"

@@ -7,7 +7,7 @@ cells, and the property the case exists for.  A case therefore cannot pass becau
 it aims at moved.
 
 The constants and rules of the code under test are restated below, in the manner of test_gpu_dedup_keys.py; each names the line
-it restates."""
+it restates by the name of the constant or function (all under microcket_amd/csrc)."""
 import functools
 from collections import namedtuple
 
@@ -15,14 +15,14 @@ import numpy as np
 
 import matrixdef as md
 
-MXWG = 256                    # microcket_amd/csrc/mkt_matrix.hip:40    threads per workgroup, and the sub-tile of the head passes
-MX_TILE = 8 * MXWG            # microcket_amd/csrc/mkt_matrix.hip:175   sorted keys per workgroup in the two head passes (2048)
-MX_CPW = 4 * MXWG             # microcket_amd/csrc/mkt_matrix.hip:203   cells per workgroup in the two text passes (1024)
-DS_T = 8192                   # microcket_amd/csrc/mkt_kernels.hip:1224 records per tile of a radix pass
-DS_D = 7                      # microcket_amd/csrc/mkt_kernels.hip:1226 bits per radix digit
-K_CHR_SLOTS = 8192            # microcket_amd/csrc/mkt_core.h:689       names a table may hold
-K_MX_SLOTS = 2 * K_CHR_SLOTS  # microcket_amd/csrc/mkt_matrix.hip:47    slots of the name table (16384)
-NAME_MAX = 63                 # microcket_amd/csrc/mkt_matrix.hip:51    bytes of a name
+MXWG = 256                    # MXWG in mkt_matrix.hip          threads per workgroup, and the sub-tile of the head passes
+MX_TILE = 8 * MXWG            # MX_TILE in mkt_matrix.hip       sorted keys per workgroup in the two head passes (2048)
+MX_CPW = 4 * MXWG             # MX_CPW in mkt_matrix.hip        cells per workgroup in the two text passes (1024)
+DS_T = 8192                   # DS_T in mkt_kernels.hip         records per tile of a radix pass
+DS_D = 7                      # DS_D in mkt_kernels.hip         bits per radix digit
+K_CHR_SLOTS = 8192            # kChrSlots in mkt_core.h         names a table may hold
+K_MX_SLOTS = 2 * K_CHR_SLOTS  # kMxSlots in mkt_matrix_obj.h    slots of the name table (16384)
+NAME_MAX = 63                 # MxTab::name in mkt_matrix_obj.h bytes of a name ([63] holds the length)
 assert (MX_TILE, MX_CPW, K_MX_SLOTS) == (2048, 1024, 16384)
 M64 = (1 << 64) - 1
 
@@ -31,7 +31,7 @@ Case = namedtuple("Case", "table res text want pairs skipped nbins facts")   # w
 
 # ---- the rules restated ---------------------------------------------------------------------------------------------------------
 def key_bits(nbins):
-    """B of mkt_matrix_create (mkt_matrix.hip:524): the bits of nbins itself, at most 32"""
+    """MxRes::B as mkt_matrix_create sets it (mkt_matrix.hip): the bits of nbins itself, at most 32"""
     B = 0
     while B < 32 and (1 << B) <= nbins:
         B += 1
@@ -39,22 +39,22 @@ def key_bits(nbins):
 
 
 def radix_shifts(B):
-    """the shifts of launch_radix64(.., 0, 2 * B, ..) (mkt_kernels.hip:1436): one pass per started 7-bit digit"""
+    """the shifts of launch_radix64(.., 0, 2 * B, ..) (mkt_kernels.hip): one pass per started 7-bit digit"""
     return list(range(0, 2 * B, DS_D))
 
 
 def cell_key(b1, b2, nbins):
-    """k_mx_keys (mkt_matrix.hip:171)"""
+    """k_mx_keys (mkt_matrix.hip): the key of a binned pair"""
     return (min(b1, b2) << key_bits(nbins)) | max(b1, b2)
 
 
 def unbinned_key(nbins):
-    """k_mx_keys (mkt_matrix.hip:168): what is not binned sorts behind every cell"""
+    """k_mx_keys (mkt_matrix.hip): what is not binned sorts behind every cell"""
     return (nbins << key_bits(nbins)) | nbins
 
 
 def mx_fnv(name: bytes):
-    """mx_fnv (mkt_matrix.hip:57): FNV-1a, 0 is kept for "empty" """
+    """mx_fnv (mkt_matrix.hip): FNV-1a, 0 is kept for "empty" """
     h = 0xcbf29ce484222325
     for c in name:
         h = ((h ^ c) * 0x100000001b3) & M64
@@ -62,12 +62,12 @@ def mx_fnv(name: bytes):
 
 
 def home_slot(name: bytes):
-    """find / mkt_matrix_create (mkt_matrix.hip:122, :540)"""
+    """the first slot of a name: find in k_mx_parse and the fill loop of mkt_matrix_create (mkt_matrix.hip)"""
     return (mx_fnv(name) >> 17) & (K_MX_SLOTS - 1)
 
 
 def build_slots(names):
-    """the table as mkt_matrix_create fills it (mkt_matrix.hip:534-543): names in table order, linear probing with wrap-around"""
+    """the table as mkt_matrix_create fills it (hostTab in mkt_matrix.hip): names in table order, linear probing with wrap-around"""
     slots = [None] * K_MX_SLOTS
     for i, nm in enumerate(names):
         s = home_slot(nm)
@@ -78,7 +78,7 @@ def build_slots(names):
 
 
 def probe(slots, names, q: bytes):
-    """(table index or -1, the slots looked at) for a name of the text, as find walks them (mkt_matrix.hip:118-136)"""
+    """(table index or -1, the slots looked at) for a name of the text, as find walks them (the lambda in k_mx_parse, mkt_matrix.hip)"""
     seen = []
     if not 1 <= len(q) <= NAME_MAX:
         return -1, seen
