@@ -1172,6 +1172,76 @@ int mkt_paircmp_fetch_lines(mkt_paircmp* p, uint64_t off, char* out, size_t n);
 long mkt_paircmp_report(const mkt_paircmp_info* info, uint32_t max_dist, const char* name_a, const char* name_b, char* out, size_t cap);
 int mkt_paircmp_timing(const mkt_paircmp* p, double* parse_ms, double* sort_ms, double* join_ms, double* emit_ms);
 
+/* ---- final.pairs.gz and its pairix index final.pairs.gz.px2 (the driver's `bgzip -c final.pairs > final.pairs.gz; pairix final.pairs.gz`) ----
+ * The definition is what the reference's bin/bgzip (1.17) and bin/pairix (0.3.7) write; tests/px2def.py states it in Python and
+ * tests/golden/px2_golden.json records their output.  Independent of mkt_matrix.
+ *
+ * GZ      BGZF (SAMv1 4.1): the text in blocks of 0xff00 bytes, each a gzip member with its CRC-32 and ISIZE, then the 28-byte EOF
+ *         block.  The text is compressed as it is: no newline is added.  (bgzip itself puts the leading '#' lines into a block of
+ *         their own and ends every block at a line end; the index does not depend on where blocks are cut, see OFFSETS.)
+ * LINES   a line that starts with '#' is counted and not indexed, wherever it stands; it belongs to the chunk in front of it.  A last
+ *         line without a newline is a line.  Every other line is a record of tab-separated columns  id chr1 pos1 chr2 pos2 ...  : the 4DN
+ *         `pairs` preset, the only one offered.  Only chr1, pos1 and chr2 are read.
+ * NAMES   the pair "chr1|chr2" of a record, compared as bytes; the name table lists them in order of first appearance (no order of
+ *         the names is asked for: chr2|chr2 may stand in front of chr1|chr1).
+ * BINS    pairix indexes the single base [pos1 - 1, pos1) (pos1 0 counts as 1), which always fits the finest of its six levels
+ *         (windows of 2^15, 2^18, ... 2^30 positions; first bins 4681, 585, 73, 9, 1, 0): bin = 4681 + ((pos1 - 1) >> 15).  This is
+ *         not tabix's 14-bit scheme.  The formula goes on past 2^30: pos1 = 2^31 - 1 has bin 70216.  The linear window is the same
+ *         2^15 positions, so a name's linear index has ((largest pos1 - 1) >> 15) + 1 entries.
+ * CHUNKS  a chunk {beg, end} of a bin runs from the start of the first record of a run of records with one name and one bin to the
+ *         start of the first record of the next run, or to the end of the text.  pairix joins two chunks of one bin when the first ends
+ *         in the block in which the second begins (tabix's rule); in a file that is accepted this never happens, because a (name,
+ *         bin) is a single run.  So every bin holds exactly one chunk.
+ * LINEAR  entry w of a name is the begin of the chunk of window w; a window without a record repeats the entry before it; windows in
+ *         front of the name's first record hold 0.
+ * OFFSETS virtual offsets, coffset << 16 | offset in block, of the reader that has consumed the text up to there: a position at which
+ *         a block ends is offset 0 of the NEXT block, and the end of the text is offset 0 of the EOF block.
+ * PX2     itself BGZF.  Uncompressed, little-endian:  "PX2.004\1", int32 n_ref, uint64 lines (all of them, '#' lines too), int32 3 (the
+ *         preset), 2 3 3 (columns of chr1, begin, end), 4 5 5 (of chr2), bytes 09 '|' 00 00 (delimiter, region separator), int32 '#',
+ *         int32 0 (lines to skip), int32 l_nm, the names each with a NUL; then PER NAME  int32 n_bin, n_bin x { uint32 bin, int32
+ *         n_chunk, n_chunk x { uint64 beg, uint64 end } }, int32 n_intv, n_intv x uint64.  pairix writes the bins of a name in the
+ *         order of a hash walk; this project writes them ascending.  A text without a record has n_ref 0 and l_nm 0 and ends there.
+ * REFUSED with MKT_E_ARG and a message that begins "line N:" (1-based, all lines counted), the smallest such N, nothing being written:
+ *         a record with fewer than five columns (an empty line too; pairix fails there as well); a pos1 that is empty, holds another
+ *         byte than a digit, has more than ten digits or exceeds 2^31 - 1 (pairix reads it with strtol into an int32 and writes an
+ *         index that is wrong or refuses the file as unsorted); a pos1 smaller than that of the record before it in the same pair
+ *         (pairix: "the file out of order"); a pair that reappears after another (pairix: "the chromosome blocks not continuous").
+ * QUERIES are not part of this library.  pairix's reader answers a region of which the first range lies below 2^30 only: records behind
+ *         that are indexed and never returned.
+ * Both files depend on the text and the level only: not on how `add` was fed, and they are the same bytes on every call.  Integers only,
+ * no atomics.  The text, its compressed blocks (64 KiB each) and 28 bytes per line are resident; fewer than 2^32 - 1 lines
+ * (MKT_E_CAPACITY beyond, MKT_E_NOMEM with a message when device memory does not suffice).
+ *
+ *   mkt_pairsgz_add            repeatable; a piece need not end at a line end; the bytes are copied before the call returns
+ *   mkt_pairsgz_opts_default   level 1, preset MKT_PAIRSGZ_PRESET_PAIRS
+ *   mkt_pairsgz_run            opts NULL = the defaults; info may be NULL; repeatable.  level: 0 stored, 1 the fixed code, 2 a code per
+ *                              block (both files).  MKT_E_ARG for another level or preset, a non-zero reserved word, a refused text.
+ *   mkt_pairsgz_fetch_gz / _fetch_px2   bytes [off, off + n) of the two files of the last run (MKT_E_STATE unless it succeeded)
+ *   mkt_pairsgz_timing         of the last run, ms from HIP events: deflate and pack of the text; line index; the per-line kernel; names
+ *                              and chunks (scans, the name table, the host's check for a reappearing pair); the index and its deflate */
+#define MKT_PAIRSGZ_PRESET_PAIRS 0u
+typedef struct mkt_pairsgz mkt_pairsgz;
+typedef struct mkt_pairsgz_opts {
+    int32_t level;
+    uint32_t preset;
+    uint32_t reserved[6];                 /* 0 */
+} mkt_pairsgz_opts;
+typedef struct mkt_pairsgz_info {
+    uint64_t lines, records;              /* all lines; those that do not start with '#' */
+    uint64_t names, bins, chunks;         /* pairs; (name, bin) entries; their chunks (one each) */
+    uint64_t blocks;                      /* BGZF blocks of the text, without the EOF block */
+    uint64_t gz_bytes, px2_bytes;
+} mkt_pairsgz_info;
+int mkt_pairsgz_create(int device, mkt_pairsgz** out);
+void mkt_pairsgz_destroy(mkt_pairsgz* p);
+const char* mkt_pairsgz_error(const mkt_pairsgz* p);
+int mkt_pairsgz_add(mkt_pairsgz* p, const char* bytes, size_t n);
+void mkt_pairsgz_opts_default(mkt_pairsgz_opts* o);
+int mkt_pairsgz_run(mkt_pairsgz* p, const mkt_pairsgz_opts* opts, mkt_pairsgz_info* info);
+int mkt_pairsgz_fetch_gz(mkt_pairsgz* p, uint64_t off, char* out, size_t n);
+int mkt_pairsgz_fetch_px2(mkt_pairsgz* p, uint64_t off, char* out, size_t n);
+int mkt_pairsgz_timing(const mkt_pairsgz* p, double ms[5]);
+
 #ifdef __cplusplus
 }
 #endif

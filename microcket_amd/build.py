@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -193,6 +193,20 @@ def build_pairscmp(force=False):
     return PAIRSCMP
 
 
+PAIRSBGZ = os.path.join(HERE, "bin", "pairsbgz")
+
+
+def build_pairsbgz(force=False):
+    """bin/pairsbgz: the driver's `bgzip -c final.pairs > final.pairs.gz; pairix final.pairs.gz` on the GPU: writes
+    the BGZF file and its .px2 index."""
+    src = os.path.join(CSRC, "pairsbgz_main.cpp")
+    if force or _newer(PAIRSBGZ, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(PAIRSBGZ), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", PAIRSBGZ, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return PAIRSBGZ
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -267,6 +281,13 @@ def build_test_tools():
         pch = os.path.join(out, name)
         if os.path.exists(psrc) and _newer(pch, [psrc, os.path.join(CSRC, "mkt_paircmp.h"), os.path.join(ROOT, "include", "mkt.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", pch, psrc])
+    # host driver of the pairs.gz index's host half (mkt_px2.h: the header, the reappearing-pair check), plain and sanitized like the
+    # ones above; a tree that carries an older tests/ has no such source
+    xsrc = os.path.join(ROOT, "tests", "host", "px2_host.cpp")
+    for name, extra in (("px2_host", ()), ("px2_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        pxh = os.path.join(out, name)
+        if os.path.exists(xsrc) and _newer(pxh, [xsrc, os.path.join(CSRC, "mkt_px2.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", pxh, xsrc])
     build_emit_parts()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
@@ -285,6 +306,7 @@ def build_all(force=False, extras=True):
     build_sam2bam(force)
     build_pairs2matrix(force)
     build_pairscmp(force)
+    build_pairsbgz(force)
     build_makestat(force)
     if extras:
         build_oracle()

@@ -42,6 +42,8 @@ EXPORTS = [
     "mkt_hic_opts_default", "mkt_matrix_hic", "mkt_matrix_fetch_hic", "mkt_matrix_hic_timing",
     "mkt_paircmp_create", "mkt_paircmp_destroy", "mkt_paircmp_error", "mkt_paircmp_add", "mkt_paircmp_add_device", "mkt_paircmp_opts_default", "mkt_paircmp_run",
     "mkt_paircmp_fetch_classes", "mkt_paircmp_fetch_lines", "mkt_paircmp_report", "mkt_paircmp_timing",
+    "mkt_pairsgz_create", "mkt_pairsgz_destroy", "mkt_pairsgz_error", "mkt_pairsgz_add", "mkt_pairsgz_opts_default", "mkt_pairsgz_run", "mkt_pairsgz_fetch_gz",
+    "mkt_pairsgz_fetch_px2", "mkt_pairsgz_timing",
 ]
 
 
@@ -231,6 +233,18 @@ class _PairCompareInfoC(C.Structure):
                 ("a_only", C.c_uint64), ("b_only", C.c_uint64), ("dist", (C.c_uint64 * 4) * 2), ("host_runs", C.c_uint64), ("lines_bytes", C.c_uint64)]
 
 
+class PairsGzOpts(C.Structure):
+    """mkt_pairsgz_opts of include/mkt.h"""
+    _fields_ = [("level", C.c_int32), ("preset", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class _PairsGzInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("lines", "records", "names", "bins", "chunks", "blocks", "gz_bytes", "px2_bytes")]
+
+
+PairsGzInfo = collections.namedtuple("PairsGzInfo", "lines records names bins chunks blocks gz_bytes px2_bytes")
+
+
 class Timing(C.Structure):
     _fields_ = [("tile_kernel_ms", C.c_double), ("tile_launches", C.c_uint64), ("tile_bytes", C.c_uint64), ("other_ms", C.c_double),
                 ("tiles", C.c_uint64), ("deferred_tiles", C.c_uint64)]
@@ -340,6 +354,18 @@ def load_library():
     L.mkt_sorter_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.mkt_sorter_sort.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.mkt_sorter_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_pairsgz_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mkt_pairsgz_destroy.argtypes = [C.c_void_p]
+    L.mkt_pairsgz_destroy.restype = None
+    L.mkt_pairsgz_error.argtypes = [C.c_void_p]
+    L.mkt_pairsgz_error.restype = C.c_char_p
+    L.mkt_pairsgz_add.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.mkt_pairsgz_opts_default.argtypes = [C.POINTER(PairsGzOpts)]
+    L.mkt_pairsgz_opts_default.restype = None
+    L.mkt_pairsgz_run.argtypes = [C.c_void_p, C.POINTER(PairsGzOpts), C.POINTER(_PairsGzInfoC)]
+    L.mkt_pairsgz_fetch_gz.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_pairsgz_fetch_px2.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_pairsgz_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
     L.mkt_paircmp_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_paircmp_destroy.argtypes = [C.c_void_p]
     L.mkt_paircmp_destroy.restype = None
@@ -802,6 +828,79 @@ class PairsSorter:
     def close(self):
         if self.h:
             self.L.mkt_sorter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class PairsGz:
+    """final.pairs.gz (BGZF) and its pairix index .px2 from a sorted .pairs text on the GPU (the driver's bgzip | pairix tail): see
+    mkt_pairsgz_* in include/mkt.h, where the definition stands."""
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.h = C.c_void_p()
+        self.info = None
+        rc = self.L.mkt_pairsgz_create(device, C.byref(self.h))
+        if rc != 0:
+            raise MktError(f"mkt_pairsgz_create: {self.L.mkt_strerror(rc).decode()}")
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise MktError(f"{what}: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_pairsgz_error(self.h).decode()}")
+
+    def add(self, data: bytes):
+        """A piece of the text; it need not end at a line end."""
+        self._chk(self.L.mkt_pairsgz_add(self.h, data, len(data)), "mkt_pairsgz_add")
+        self.info = None
+
+    def run(self, level=1):
+        """Compresses and indexes what was added; returns the counters (also kept in .info).  A text that is refused (unsorted, a pair
+        that reappears, a malformed line) raises MktError with "line N:" in its message and leaves nothing to fetch."""
+        o = PairsGzOpts()
+        self.L.mkt_pairsgz_opts_default(C.byref(o))
+        o.level = level
+        info = _PairsGzInfoC()
+        self.info = None
+        self._chk(self.L.mkt_pairsgz_run(self.h, C.byref(o), C.byref(info)), "mkt_pairsgz_run")
+        self.info = PairsGzInfo(*(int(getattr(info, k)) for k in PairsGzInfo._fields))
+        return self.info
+
+    def _fetch(self, fn, what, n):
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(fn(self.h, 0, buf, n), what)
+        return buf.raw[:n]
+
+    def gz_bytes(self):
+        if self.info is None:
+            raise MktError("gz_bytes before a run that succeeded")
+        return self._fetch(self.L.mkt_pairsgz_fetch_gz, "mkt_pairsgz_fetch_gz", self.info.gz_bytes)
+
+    def px2_bytes(self):
+        if self.info is None:
+            raise MktError("px2_bytes before a run that succeeded")
+        return self._fetch(self.L.mkt_pairsgz_fetch_px2, "mkt_pairsgz_fetch_px2", self.info.px2_bytes)
+
+    def write(self, path):
+        """Writes `path` and `path + ".px2"`."""
+        gz, px2 = self.gz_bytes(), self.px2_bytes()
+        with open(path, "wb") as f:
+            f.write(gz)
+        with open(os.fspath(path) + ".px2", "wb") as f:
+            f.write(px2)
+
+    def timing_ms(self):
+        t = (C.c_double * 5)()
+        self._chk(self.L.mkt_pairsgz_timing(self.h, C.byref(t)), "mkt_pairsgz_timing")
+        return dict(zip(("deflate", "line_index", "lines", "names_chunks", "index"), (float(x) for x in t)))
+
+    def close(self):
+        if self.h:
+            self.L.mkt_pairsgz_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):
