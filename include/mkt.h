@@ -41,7 +41,8 @@ enum {
     MKT_E_CAPACITY = -5,     /* a QNAME group does not fit the block buffer */
     MKT_E_KERNEL = -6,       /* the kernel reported an internal error bit */
     MKT_E_STATE = -7,        /* call order violated (e.g. submit after finish) */
-    MKT_E_IO = -8            /* a temporary file could not be created, written or read (the error text names it) */
+    MKT_E_IO = -8,           /* a temporary file could not be created, written or read (the error text names it) */
+    MKT_E_FORMAT = -9        /* a BGZF file or a deflate stream is refused (mkt_bgzf_error names the reason and the block's offset) */
 };
 
 /* tile geometry selection (tests force the small-tile build to exercise every slow path) */
@@ -1241,6 +1242,63 @@ int mkt_pairsgz_run(mkt_pairsgz* p, const mkt_pairsgz_opts* opts, mkt_pairsgz_in
 int mkt_pairsgz_fetch_gz(mkt_pairsgz* p, uint64_t off, char* out, size_t n);
 int mkt_pairsgz_fetch_px2(mkt_pairsgz* p, uint64_t off, char* out, size_t n);
 int mkt_pairsgz_timing(const mkt_pairsgz* p, double ms[5]);
+
+/* ---- reading BGZF back: final.pairs.gz (and any other BGZF file, sam2bam's BAM included, as bytes) inflated on the GPU ----
+ * The definition of the format is SAMv1 4.1 and RFC 1951; tests/px2def.py (bgzf_blocks) and tests/inflatedef.py state in Python what is
+ * accepted and what is refused.  Independent of mkt_pairsgz and mkt_matrix.
+ *
+ * FILE     a sequence of gzip members, each  1f 8b 08 04 | mtime xfl os | XLEN = 6 | 'B' 'C' 02 00 BSIZE | deflate | CRC-32 ISIZE .  Anything
+ *          else is refused with the file offset of the member: other magic bytes, a plain gzip member (no extra field: "not BGZF"), another
+ *          extra field, a BSIZE that runs past the file (a truncated file), a BSIZE below 26, an ISIZE above 65536.  The empty EOF block
+ *          may stand anywhere and need not be there; info.has_eof says whether the file ends with one.
+ * TEXT     the inflated members one behind the other: member k begins at the sum of the ISIZE in front of it.
+ * DEFLATE  stored, fixed and dynamic blocks, any number per member.  REFUSED, each with a reason of its own: block type 3; a stored block
+ *          whose NLEN is not the complement of LEN or that has non-zero bits up to its byte boundary; more than 286 literal/length or 30
+ *          distance codes; an over-subscribed or incomplete code (code-length, literal/length, distance; one distance code of length 1 and
+ *          no distance code at all are accepted); no end-of-block code; a repeat at the first length or past the last; length symbols 286,
+ *          287 and distance symbols 30, 31; a match without a distance code; a bit pattern that is no code; a distance that reaches before
+ *          the member's own first byte; output longer or shorter than ISIZE; a stream that runs past its member; bytes or non-zero
+ *          bits behind the final block; a CRC-32 that differs from the footer.  zlib's tolerated oddities are not accepted.
+ * SAFETY   a malformed file ends in MKT_E_FORMAT, never in a fault: every read is bounded to the member, every write to the member's
+ *          ISIZE bytes of the text, every loop by the bits left in the member.
+ * LIMITS   resident only: the compressed bytes and the whole text are held in device memory at once (MKT_E_NOMEM with a message when
+ *          they do not fit; no streaming in batches).  BGZF only, no plain gzip.  No BAM decoding: a BAM inflates to its bytes.  Region
+ *          queries through the .px2 are not part of this library yet: mkt_bgzf_load_index checks an index and keeps its line count.
+ *          bin/pairscmp and bin/pairsbgz still refuse .gz names; `pairsgunzip a.pairs.gz | pairscmp - b.pairs` is the route.
+ * The text depends on the file only: integers, no atomics.
+ *
+ *   mkt_bgzf_add           compressed bytes, any chunking; copied before the call returns; forgets the text of an earlier run
+ *   mkt_bgzf_run           opts NULL = the defaults; info may be NULL; repeatable.  On refusal MKT_E_FORMAT: the first refused member's
+ *                          reason and file offset in mkt_bgzf_error ("... block at N: sentence [key]") and in info.reason / info.bad_offset
+ *   mkt_bgzf_fetch_text    bytes [off, off + n) of the text (MKT_E_STATE unless the last run succeeded)
+ *   mkt_bgzf_device_text   the text on the device, valid until the next add / run / destroy: what mkt_matrix_add_device,
+ *                          mkt_paircmp_add_device and mkt_sorter_add_device take.  64 zero bytes stand behind it.
+ *   mkt_bgzf_load_index    the bytes of a .px2 (BGZF itself: inflated by the same kernel, every field walked on the host)
+ *   mkt_bgzf_count         the line count of the loaded index: `pairix -n`
+ *   mkt_bgzf_timing        of the last run, ms from HIP events: table upload, inflate, CRC; [3] and [4] are 0 (kept for queries) */
+typedef struct mkt_bgzf mkt_bgzf;
+typedef struct mkt_bgzf_opts {
+    uint32_t reserved[8];                 /* 0 */
+} mkt_bgzf_opts;
+typedef struct mkt_bgzf_info {
+    uint64_t blocks;                      /* members, empty ones included */
+    uint64_t gz_bytes, text_bytes;
+    uint64_t stored, fixed, dynamic;      /* deflate blocks by type, over all members */
+    uint32_t has_eof;                     /* 1: the file ends with the 28-byte EOF block */
+    uint32_t reason;                      /* 0, or why the file is refused (the numbers of mkt_inflate.h; the key stands in the message) */
+    uint64_t bad_offset;                  /* file offset of the refused member */
+} mkt_bgzf_info;
+int mkt_bgzf_create(int device, mkt_bgzf** out);
+void mkt_bgzf_destroy(mkt_bgzf* r);
+const char* mkt_bgzf_error(const mkt_bgzf* r);
+int mkt_bgzf_add(mkt_bgzf* r, const char* bytes, size_t n);
+void mkt_bgzf_opts_default(mkt_bgzf_opts* o);
+int mkt_bgzf_run(mkt_bgzf* r, const mkt_bgzf_opts* opts, mkt_bgzf_info* info);
+int mkt_bgzf_fetch_text(mkt_bgzf* r, uint64_t off, char* out, size_t n);
+int mkt_bgzf_device_text(mkt_bgzf* r, const void** d_ptr, uint64_t* n);
+int mkt_bgzf_load_index(mkt_bgzf* r, const char* px2_bytes, size_t n);
+int mkt_bgzf_count(mkt_bgzf* r, uint64_t* n_lines);
+int mkt_bgzf_timing(const mkt_bgzf* r, double ms[5]);
 
 #ifdef __cplusplus
 }

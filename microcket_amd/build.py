@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -207,6 +207,19 @@ def build_pairsbgz(force=False):
     return PAIRSBGZ
 
 
+PAIRSGUNZIP = os.path.join(HERE, "bin", "pairsgunzip")
+
+
+def build_pairsgunzip(force=False):
+    """bin/pairsgunzip: the `bgzip -d -c` of this project (the BGZF inflate of DESIGN.md 6g): how a .pairs.gz reaches pairscmp."""
+    src = os.path.join(CSRC, "pairsgunzip_main.cpp")
+    if force or _newer(PAIRSGUNZIP, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(PAIRSGUNZIP), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", PAIRSGUNZIP, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return PAIRSGUNZIP
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -288,6 +301,13 @@ def build_test_tools():
         pxh = os.path.join(out, name)
         if os.path.exists(xsrc) and _newer(pxh, [xsrc, os.path.join(CSRC, "mkt_px2.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", pxh, xsrc])
+    # host driver of the BGZF reader's shared half (mkt_inflate.h: the block table, the header parse, the table build, the token
+    # decode), plain and sanitized like the ones above; a tree that carries an older tests/ has no such source
+    isrc = os.path.join(ROOT, "tests", "host", "inflate_host.cpp")
+    for name, extra in (("inflate_host", ()), ("inflate_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        ifh = os.path.join(out, name)
+        if os.path.exists(isrc) and _newer(ifh, [isrc, os.path.join(CSRC, "mkt_inflate.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", ifh, isrc])
     build_emit_parts()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
@@ -307,6 +327,7 @@ def build_all(force=False, extras=True):
     build_pairs2matrix(force)
     build_pairscmp(force)
     build_pairsbgz(force)
+    build_pairsgunzip(force)
     build_makestat(force)
     if extras:
         build_oracle()

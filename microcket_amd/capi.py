@@ -44,6 +44,8 @@ EXPORTS = [
     "mkt_paircmp_fetch_classes", "mkt_paircmp_fetch_lines", "mkt_paircmp_report", "mkt_paircmp_timing",
     "mkt_pairsgz_create", "mkt_pairsgz_destroy", "mkt_pairsgz_error", "mkt_pairsgz_add", "mkt_pairsgz_opts_default", "mkt_pairsgz_run", "mkt_pairsgz_fetch_gz",
     "mkt_pairsgz_fetch_px2", "mkt_pairsgz_timing",
+    "mkt_bgzf_create", "mkt_bgzf_destroy", "mkt_bgzf_error", "mkt_bgzf_add", "mkt_bgzf_opts_default", "mkt_bgzf_run", "mkt_bgzf_fetch_text", "mkt_bgzf_device_text",
+    "mkt_bgzf_load_index", "mkt_bgzf_count", "mkt_bgzf_timing",
 ]
 
 
@@ -245,6 +247,13 @@ class _PairsGzInfoC(C.Structure):
 PairsGzInfo = collections.namedtuple("PairsGzInfo", "lines records names bins chunks blocks gz_bytes px2_bytes")
 
 
+class _BgzfInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("blocks", "gz_bytes", "text_bytes", "stored", "fixed", "dynamic")] + [("has_eof", C.c_uint32), ("reason", C.c_uint32), ("bad_offset", C.c_uint64)]
+
+
+BgzfInfo = collections.namedtuple("BgzfInfo", "blocks gz_bytes text_bytes stored fixed dynamic has_eof")
+
+
 class Timing(C.Structure):
     _fields_ = [("tile_kernel_ms", C.c_double), ("tile_launches", C.c_uint64), ("tile_bytes", C.c_uint64), ("other_ms", C.c_double),
                 ("tiles", C.c_uint64), ("deferred_tiles", C.c_uint64)]
@@ -366,6 +375,18 @@ def load_library():
     L.mkt_pairsgz_fetch_gz.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
     L.mkt_pairsgz_fetch_px2.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
     L.mkt_pairsgz_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
+    L.mkt_bgzf_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mkt_bgzf_destroy.argtypes = [C.c_void_p]
+    L.mkt_bgzf_destroy.restype = None
+    L.mkt_bgzf_error.argtypes = [C.c_void_p]
+    L.mkt_bgzf_error.restype = C.c_char_p
+    L.mkt_bgzf_add.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.mkt_bgzf_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_BgzfInfoC)]
+    L.mkt_bgzf_fetch_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_bgzf_device_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.mkt_bgzf_load_index.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.mkt_bgzf_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mkt_bgzf_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
     L.mkt_paircmp_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_paircmp_destroy.argtypes = [C.c_void_p]
     L.mkt_paircmp_destroy.restype = None
@@ -901,6 +922,91 @@ class PairsGz:
     def close(self):
         if self.h:
             self.L.mkt_pairsgz_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class BgzfRefused(MktError):
+    """A BGZF file the reader refuses: .reason is the key of the reason (e.g. "crc", "ll_oversubscribed"; the list stands in
+    csrc/mkt_inflate.h), .offset the file offset of the refused block."""
+
+    def __init__(self, msg, reason, offset):
+        MktError.__init__(self, msg)
+        self.reason = reason
+        self.offset = offset
+
+
+class BgzfReader:
+    """A BGZF file (final.pairs.gz, its .px2, a BAM as bytes) inflated on the GPU: see mkt_bgzf_* in include/mkt.h, where the
+    definition and the limits stand (resident only, BGZF only, no region queries yet)."""
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.h = C.c_void_p()
+        self.info = None
+        rc = self.L.mkt_bgzf_create(device, C.byref(self.h))
+        if rc != 0:
+            raise MktError(f"mkt_bgzf_create: {self.L.mkt_strerror(rc).decode()}")
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise MktError(f"{what}: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_bgzf_error(self.h).decode()}")
+
+    def add(self, data: bytes):
+        """A piece of the compressed file, cut anywhere."""
+        self._chk(self.L.mkt_bgzf_add(self.h, data, len(data)), "mkt_bgzf_add")
+        self.info = None
+
+    def run(self):
+        """Inflates what was added and checks every CRC-32 and ISIZE; returns the counters (also kept in .info).  A refused file
+        raises BgzfRefused with the reason and the block's offset and leaves no text."""
+        info = _BgzfInfoC()
+        self.info = None
+        rc = self.L.mkt_bgzf_run(self.h, None, C.byref(info))
+        if rc == -9:
+            msg = self.L.mkt_bgzf_error(self.h).decode()
+            raise BgzfRefused(f"mkt_bgzf_run: {msg}", msg[msg.rfind("[") + 1:msg.rfind("]")], int(info.bad_offset))
+        self._chk(rc, "mkt_bgzf_run")
+        self.info = BgzfInfo(*(int(getattr(info, k)) for k in BgzfInfo._fields))
+        return self.info
+
+    def text(self):
+        if self.info is None:
+            raise MktError("text before a run that succeeded")
+        n = self.info.text_bytes
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_bgzf_fetch_text(self.h, 0, buf, n), "mkt_bgzf_fetch_text")
+        return buf.raw[:n]
+
+    def device_text(self):
+        """(device pointer, bytes) of the text: what PairCompare.add_device and Matrix.add_device take; valid until the next add, run or close."""
+        d, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mkt_bgzf_device_text(self.h, C.byref(d), C.byref(n)), "mkt_bgzf_device_text")
+        return d.value or 0, int(n.value)
+
+    def load_index(self, px2: bytes):
+        """The bytes of the file's .px2 (inflated by the same kernel and checked field by field)."""
+        self._chk(self.L.mkt_bgzf_load_index(self.h, px2, len(px2)), "mkt_bgzf_load_index")
+
+    def count(self):
+        """`pairix -n`: the line count the loaded index records."""
+        n = C.c_uint64()
+        self._chk(self.L.mkt_bgzf_count(self.h, C.byref(n)), "mkt_bgzf_count")
+        return int(n.value)
+
+    def timing_ms(self):
+        t = (C.c_double * 5)()
+        self._chk(self.L.mkt_bgzf_timing(self.h, C.byref(t)), "mkt_bgzf_timing")
+        return dict(zip(("table_upload", "inflate", "crc"), (float(x) for x in t)))
+
+    def close(self):
+        if self.h:
+            self.L.mkt_bgzf_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):

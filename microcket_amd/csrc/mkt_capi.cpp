@@ -18,6 +18,7 @@ const char* mkt_strerror(int code) {
     case MKT_E_KERNEL: return "kernel reported an internal error";
     case MKT_E_STATE: return "call order violated";
     case MKT_E_IO: return "temporary file error";
+    case MKT_E_FORMAT: return "file refused";
     default: return "unknown error";
     }
 }

@@ -10,46 +10,6 @@ namespace mkt {
 
 constexpr int BWG = 256;
 
-// ---- CRC-32 (RFC 1952) of a block: every thread takes a slice, the slices are combined as polynomials ------------------------
-__device__ inline uint32_t crc_mulmod(uint32_t a, uint32_t b) {       // a(x) * b(x) mod P(x), reflected representation (zlib's multmodp)
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) { p ^= b; if ((a & (m - 1u)) == 0u) break; }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
-}
-__device__ inline uint32_t crc_x8n(uint32_t nbytes, const uint32_t* x2n /* x^(2^k) mod P, k = 0..31 */) {        // x^(8 * nbytes) mod P
-    uint32_t p = 1u << 31;                                            // the polynomial 1
-    uint32_t n = nbytes;
-    int k = 3;                                                        // bits -> bytes
-    while (n) { if (n & 1u) p = crc_mulmod(x2n[k & 31], p); n >>= 1; ++k; }
-    return p;
-}
-__device__ inline uint32_t crc_bytes(const uint8_t* d, uint32_t n, const uint32_t* tabl) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < n; ++i) c = tabl[(c ^ d[i]) & 0xFFu] ^ (c >> 8);
-    return c ^ 0xFFFFFFFFu;
-}
-
-// block-wide CRC of n bytes at src (global or LDS): slices of ceil(n / NTH) bytes
-template <int NTH>
-__device__ inline uint32_t block_crc(const uint8_t* src, uint32_t n, const uint32_t* tabl, const uint32_t* x2n, uint32_t* sh /* [NTH / 64] */) {
-    const uint32_t per = (n + NTH - 1) / NTH;
-    const uint32_t a = threadIdx.x * per < n ? threadIdx.x * per : n, b = a + per < n ? a + per : n;
-    uint32_t c = 0;
-    if (b > a) { c = crc_bytes(src + a, b - a, tabl); if (n - b) c = crc_mulmod(crc_x8n(n - b, x2n), c); }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c ^= (uint32_t)__shfl_xor((int)c, d, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-    __syncthreads();
-    uint32_t r = 0;
-#pragma unroll
-    for (int w = 0; w < NTH / 64; ++w) r ^= sh[w];
-    __syncthreads();
-    return r;
-}
 // block-wide Adler-32 (RFC 1950) of n <= 65 280 bytes at src, from the state (1, 0): slices of ceil(n / NTH) bytes; a slice [s, e) gives
 // a = sum d_i and b = sum (e - i) d_i, and the whole is A = 1 + sum a, B = n + sum (b + (n - e) a), both mod 65521.  Integer sums in a
 // fixed tree: the value does not depend on the order anything ran in.

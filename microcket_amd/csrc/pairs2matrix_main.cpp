@@ -4,6 +4,7 @@
 // The work is mkt_matrix_* of libmkt_hip.so (include/mkt.h, where the binning is defined); this file only moves bytes.
 //
 //   pairs2matrix -g <chrom.sizes> -r r1[,r2,...] -o <prefix> [in.pairs ...]        (no input file: stdin; $MKT_DEVICE: GPU ordinal)
+//                an input (and --compare OTHER) that begins with the gzip magic bytes is read as BGZF and inflated on the device
 //                [--balance [--ignore-diags N] [--min-nnz N] [--min-count N] [--mad-max X] [--tol X] [--max-iters N]] [--expected]
 //                [--loops [--loop-peak N] [--loop-window N] [--loop-window-max N] [--loop-min-ll-count N] [--loop-min-dist N]
 //                         [--loop-max-dist N] [--loop-fdr X] [--loop-cluster-radius N]]
@@ -655,11 +656,47 @@ static int open_inputs(Run& R) {
 
 // ---- the device: every function returns 0 or the exit code, and calls the library in the order the parent of this file did ---------------
 // every byte of f into matrix mx; a file without a final newline does not run into the next one
+// A BGZF file (known by its magic bytes, not by its name) is inflated on the device (mkt_bgzf_* of include/mkt.h) and handed over
+// there: the text makes no host round trip, except the part of a last line that has no newline.
+struct Bgzf {                                        // owns a mkt_bgzf
+    mkt_bgzf* p = nullptr;
+    ~Bgzf() { if (p) mkt_bgzf_destroy(p); }
+};
+static int add_bgzf(Run& R, mkt_matrix* mx, File& f, bool compare, size_t k) {
+    const char* e = getenv("MKT_DEVICE");
+    Bgzf z;
+    if (!R.ok(mkt_bgzf_create(e ? atoi(e) : 0, &z.p))) { fprintf(stderr, "Error: GPU inflate: %s\n", mkt_strerror(R.rc)); return 20; }
+    auto fail = [&]() { fprintf(stderr, "Error: GPU inflate%s: %s: %s\n", compare ? " (--compare)" : "", mkt_strerror(R.rc), mkt_bgzf_error(z.p)); return R.rc == MKT_E_FORMAT ? 12 : 21; };
+    for (; k > 0; k = fread(R.buf.data(), 1, R.buf.size(), f.get()))
+        if (!R.ok(mkt_bgzf_add(z.p, R.buf.data(), k))) return fail();
+    if (ferror(f.get())) return R.fail_read();
+    f.reset();
+    const void* d = nullptr;
+    uint64_t n = 0;
+    if (!R.ok(mkt_bgzf_run(z.p, nullptr, nullptr)) || !R.ok(mkt_bgzf_device_text(z.p, &d, &n))) return fail();
+    if (!n) return 0;
+    // whole lines go over on the device; what stands behind the last newline (looked for in the last MiB) goes the way of plain text
+    const uint64_t w = n < ((uint64_t)1 << 20) ? n : ((uint64_t)1 << 20);
+    if (!R.ok(mkt_bgzf_fetch_text(z.p, n - w, R.buf.data(), (size_t)w))) return fail();
+    uint64_t t = w;
+    while (t > 0 && R.buf[t - 1] != '\n') --t;
+    const uint64_t whole = t ? n - w + t : 0;         // no newline in the window: everything goes through the host
+    std::string tail;
+    if (t) tail.assign(R.buf.data() + t, (size_t)(w - t));
+    else { tail.resize((size_t)n); if (!R.ok(mkt_bgzf_fetch_text(z.p, 0, &tail[0], (size_t)n))) return fail(); }
+    if (whole && !R.ok(mkt_matrix_add_device(mx, d, (size_t)whole))) return R.fail_lib("GPU matrix", compare);
+    if (!tail.empty()) {
+        if (!compare) tail.push_back('\n');
+        if (!R.ok(mkt_matrix_add(mx, tail.data(), tail.size()))) return R.fail_lib("GPU matrix", compare);
+    }
+    return 0;
+}
 static int add_file(Run& R, mkt_matrix* mx, File& f, bool compare) {
     char last = '\n';
-    for (;;) {
+    for (bool first = true;; first = false) {
         const size_t k = fread(R.buf.data(), 1, R.buf.size(), f.get());
         if (k == 0) break;
+        if (first && k >= 4 && (unsigned char)R.buf[0] == 0x1f && (unsigned char)R.buf[1] == 0x8b) return add_bgzf(R, mx, f, compare, k);
         last = R.buf[k - 1];
         if (!R.ok(mkt_matrix_add(mx, R.buf.data(), k))) return R.fail_lib("GPU matrix", compare);
     }
