@@ -1207,8 +1207,8 @@ int mkt_paircmp_timing(const mkt_paircmp* p, double* parse_ms, double* sort_ms, 
  *         byte than a digit, has more than ten digits or exceeds 2^31 - 1 (pairix reads it with strtol into an int32 and writes an
  *         index that is wrong or refuses the file as unsorted); a pos1 smaller than that of the record before it in the same pair
  *         (pairix: "the file out of order"); a pair that reappears after another (pairix: "the chromosome blocks not continuous").
- * QUERIES are not part of this library.  pairix's reader answers a region of which the first range lies below 2^30 only: records behind
- *         that are indexed and never returned.
+ * QUERIES are answered by the reader below (mkt_bgzf_query).  pairix's reader answers a region of which the first range lies below 2^30
+ *         only: records behind that are indexed and never returned.
  * Both files depend on the text and the level only: not on how `add` was fed, and they are the same bytes on every call.  Integers only,
  * no atomics.  The text, its compressed blocks (64 KiB each) and 28 bytes per line are resident; fewer than 2^32 - 1 lines
  * (MKT_E_CAPACITY beyond, MKT_E_NOMEM with a message when device memory does not suffice).
@@ -1262,20 +1262,58 @@ int mkt_pairsgz_timing(const mkt_pairsgz* p, double ms[5]);
  * SAFETY   a malformed file ends in MKT_E_FORMAT, never in a fault: every read is bounded to the member, every write to the member's
  *          ISIZE bytes of the text, every loop by the bits left in the member.
  * LIMITS   resident only: the compressed bytes and the whole text are held in device memory at once (MKT_E_NOMEM with a message when
- *          they do not fit; no streaming in batches).  BGZF only, no plain gzip.  No BAM decoding: a BAM inflates to its bytes.  Region
- *          queries through the .px2 are not part of this library yet: mkt_bgzf_load_index checks an index and keeps its line count.
+ *          they do not fit; no streaming in batches).  BGZF only, no plain gzip.  No BAM decoding: a BAM inflates to its bytes.
  *          bin/pairscmp and bin/pairsbgz still refuse .gz names; `pairsgunzip a.pairs.gz | pairscmp - b.pairs` is the route.
  * The text depends on the file only: integers, no atomics.
  *
- *   mkt_bgzf_add           compressed bytes, any chunking; copied before the call returns; forgets the text of an earlier run
+ * REGION QUERIES through the file's .px2: what `pairix file.pairs.gz REGION ...` prints (pairix 0.3.7, preset pairs; tests/pairsquerydef.py
+ * states it in Python on top of tests/px2def.py query, tests/golden/pairsquery_golden.json records pairix's answers).  A query needs add and
+ * load_index, not run: only the members the index points to are inflated.  After a run that succeeded the resident text is used and
+ * nothing is inflated; both routes give the same bytes, the same on every call (integers only, no atomics).
+ * REGION   A[:b-e]|B[:b-e], 1-based inclusive, commas allowed in a number.  [b1, e1) and [b2, e2) are 0-based half-open: b - 1 (b = 0
+ *          counts as b = 1, as pairix answers it) and e.  A side without a range is [0, 2^30).  e1 is clipped to 2^30 (pairix's reader; e2
+ *          is not); b1 >= e1 answers nothing.  The pair A|B is compared as bytes against the name table; an absent pair answers nothing.
+ *          `*` as one side (no range) is every name whose other side is the chromosome given, in the order of the name table.  With
+ *          autoflip (`pairix -a`) a pair A|B that is absent while B|A is present is answered as B:range2|A:range1.
+ *          REFUSED with MKT_E_ARG and a message "region R: why" (R the index in the batch, from 0): no '|' (a one-sided query on a 2D
+ *          file is not offered) or more than one, b > e, a bound that is not 1 to 18 digits, an empty chromosome, *|*, a range on *.
+ *          pairix itself answers some of these (it reads a bound with strtol) and ends a call at a pair that is absent while its flip
+ *          is present; neither is reproduced.
+ * LOOKUP   min_off = linear[min(b1 >> 15, n_intv - 1)] of the name; every bin of the name whose range overlaps [b1, e1) contributes
+ *          its chunks with end > min_off; sorted by begin; chunks that overlap (a foreign index) are merged, so that a line is never
+ *          reported twice within one region.  A chunk of the index whose coffset is neither the start of a member of the file nor the
+ *          file's length, or whose in-block offset exceeds that member's ISIZE: MKT_E_FORMAT "the index does not belong to this file".
+ * LINES    in every chunk each line that starts in [beg, end) is a candidate (it ends at its newline or at the chunk's end).  One that
+ *          starts with '#' is skipped.  A record with fewer than five columns (an empty line too), with a pos1 or pos2 that is empty,
+ *          holds another byte than a digit, has more than ten digits or exceeds 2^31 - 1, or of more than 2^24 - 2 bytes never matches
+ *          and is counted in info.unparsed (pairix reads such a field with strtol and may answer the line).  The others match when
+ *          columns 2 and 4 equal A and B, max(pos1 - 1, 0) < e1, b1 < max(pos1, 1), and the same for pos2 against [b2, e2).
+ * ANSWER   the matching lines, each with a '\n' behind it (the file's last line too where it has none), in the order of the regions,
+ *          then of the sub-queries a star expands to, then of the file.  A line that two regions match stands twice.
+ * SAFETY   the members of the plan are inflated into a compact buffer in which members adjacent in the file are adjacent, so that a
+ *          line that straddles a member edge is contiguous; a member that is refused ends the query in MKT_E_FORMAT with reason and
+ *          offset as run does.  Every read of the text lies inside a chunk, every write inside the counted size of the answer.
+ *
+ *   mkt_bgzf_add           compressed bytes, any chunking; copied before the call returns; forgets the text of an earlier run and the
+ *                          answer of an earlier query, keeps a loaded index
  *   mkt_bgzf_run           opts NULL = the defaults; info may be NULL; repeatable.  On refusal MKT_E_FORMAT: the first refused member's
  *                          reason and file offset in mkt_bgzf_error ("... block at N: sentence [key]") and in info.reason / info.bad_offset
  *   mkt_bgzf_fetch_text    bytes [off, off + n) of the text (MKT_E_STATE unless the last run succeeded)
  *   mkt_bgzf_device_text   the text on the device, valid until the next add / run / destroy: what mkt_matrix_add_device,
  *                          mkt_paircmp_add_device and mkt_sorter_add_device take.  64 zero bytes stand behind it.
- *   mkt_bgzf_load_index    the bytes of a .px2 (BGZF itself: inflated by the same kernel, every field walked on the host)
+ *   mkt_bgzf_load_index    the bytes of a .px2 (BGZF itself: inflated by the same kernel, every field walked on the host; names, bins,
+ *                          chunks and linear indexes are kept).  The file that was added stays.
  *   mkt_bgzf_count         the line count of the loaded index: `pairix -n`
- *   mkt_bgzf_timing        of the last run, ms from HIP events: table upload, inflate, CRC; [3] and [4] are 0 (kept for queries) */
+ *   mkt_bgzf_names         bytes [off, off + n) of the name table, every name with a NUL behind it, *total its length: `pairix -l`
+ *   mkt_bgzf_query         n regions (n = 0: an empty answer); opts NULL = no autoflip; info may be NULL.  MKT_E_STATE without a file or
+ *                          without an index, MKT_E_ARG for a refused region, MKT_E_FORMAT for a refused member (info.reason,
+ *                          info.bad_offset) or an index of another file
+ *   mkt_bgzf_fetch_query   bytes [off, off + n) of the concatenated answer of the last query (MKT_E_STATE unless it succeeded)
+ *   mkt_bgzf_fetch_query_offsets / _counts   n + 1 offsets at which the lines of each region begin in the answer (the last: its length);
+ *                          n line counts
+ *   mkt_bgzf_query_device  the answer on the device (64 zero bytes behind it), valid until the next add / run / query / destroy
+ *   mkt_bgzf_timing        ms from HIP events.  Of the last run: table upload, inflate, CRC.  Of the last query: [3] plan upload, inflate
+ *                          and CRC of the selected members; [4] line index, filter, scan and gather */
 typedef struct mkt_bgzf mkt_bgzf;
 typedef struct mkt_bgzf_opts {
     uint32_t reserved[8];                 /* 0 */
@@ -1299,6 +1337,24 @@ int mkt_bgzf_device_text(mkt_bgzf* r, const void** d_ptr, uint64_t* n);
 int mkt_bgzf_load_index(mkt_bgzf* r, const char* px2_bytes, size_t n);
 int mkt_bgzf_count(mkt_bgzf* r, uint64_t* n_lines);
 int mkt_bgzf_timing(const mkt_bgzf* r, double ms[5]);
+typedef struct mkt_bgzf_query_opts {
+    uint32_t autoflip;                    /* 1: `pairix -a` */
+    uint32_t reserved[7];                 /* 0 */
+} mkt_bgzf_query_opts;
+typedef struct mkt_bgzf_query_info {
+    uint64_t regions, subqueries, chunks;       /* sub-queries after the expansion of stars and flips; chunks scanned (merged ones count once) */
+    uint64_t blocks_inflated, bytes_inflated;   /* members of the plan and their ISIZE; 0 when the resident text was used */
+    uint64_t candidate_lines, lines, answer_bytes, unparsed;
+    uint32_t reason;                      /* 0, or why a member is refused (as in mkt_bgzf_info) */
+    uint32_t pad;
+    uint64_t bad_offset;                  /* file offset of the refused member */
+} mkt_bgzf_query_info;
+int mkt_bgzf_query(mkt_bgzf* r, const char* const* regions, uint32_t n, const mkt_bgzf_query_opts* opts, mkt_bgzf_query_info* info);
+int mkt_bgzf_fetch_query(mkt_bgzf* r, uint64_t off, char* out, size_t n);
+int mkt_bgzf_fetch_query_offsets(mkt_bgzf* r, uint64_t* out);
+int mkt_bgzf_fetch_query_counts(mkt_bgzf* r, uint64_t* out);
+int mkt_bgzf_query_device(mkt_bgzf* r, const void** d_ptr, uint64_t* n);
+int mkt_bgzf_names(mkt_bgzf* r, uint64_t off, char* out, size_t n, uint64_t* total);
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,20 @@ def build_pairsgunzip(force=False):
     return PAIRSGUNZIP
 
 
+PAIRSQUERY = os.path.join(HERE, "bin", "pairsquery")
+
+
+def build_pairsquery(force=False):
+    """bin/pairsquery: `pairix file.pairs.gz REGION ...` on the GPU (region queries through the .px2): only the blocks
+    the index points to are inflated."""
+    src = os.path.join(CSRC, "pairsquery_main.cpp")
+    if force or _newer(PAIRSQUERY, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(PAIRSQUERY), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", PAIRSQUERY, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return PAIRSQUERY
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -308,6 +322,13 @@ def build_test_tools():
         ifh = os.path.join(out, name)
         if os.path.exists(isrc) and _newer(ifh, [isrc, os.path.join(CSRC, "mkt_inflate.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", ifh, isrc])
+    # host driver of the region queries' host and shared half (mkt_px2query.h: the region grammar, the index kept, the block plan,
+    # the line filter of the kernel), plain and sanitized like the ones above; a tree that carries an older tests/ has no such source
+    qsrc = os.path.join(ROOT, "tests", "host", "pairsquery_host.cpp")
+    for name, extra in (("pairsquery_host", ()), ("pairsquery_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        pqh = os.path.join(out, name)
+        if os.path.exists(qsrc) and _newer(pqh, [qsrc, os.path.join(CSRC, "mkt_px2query.h"), os.path.join(CSRC, "mkt_inflate.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", pqh, qsrc])
     build_emit_parts()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
@@ -328,6 +349,7 @@ def build_all(force=False, extras=True):
     build_pairscmp(force)
     build_pairsbgz(force)
     build_pairsgunzip(force)
+    build_pairsquery(force)
     build_makestat(force)
     if extras:
         build_oracle()

@@ -45,7 +45,8 @@ EXPORTS = [
     "mkt_pairsgz_create", "mkt_pairsgz_destroy", "mkt_pairsgz_error", "mkt_pairsgz_add", "mkt_pairsgz_opts_default", "mkt_pairsgz_run", "mkt_pairsgz_fetch_gz",
     "mkt_pairsgz_fetch_px2", "mkt_pairsgz_timing",
     "mkt_bgzf_create", "mkt_bgzf_destroy", "mkt_bgzf_error", "mkt_bgzf_add", "mkt_bgzf_opts_default", "mkt_bgzf_run", "mkt_bgzf_fetch_text", "mkt_bgzf_device_text",
-    "mkt_bgzf_load_index", "mkt_bgzf_count", "mkt_bgzf_timing",
+    "mkt_bgzf_load_index", "mkt_bgzf_count", "mkt_bgzf_timing", "mkt_bgzf_query", "mkt_bgzf_fetch_query", "mkt_bgzf_fetch_query_offsets", "mkt_bgzf_fetch_query_counts",
+    "mkt_bgzf_query_device", "mkt_bgzf_names",
 ]
 
 
@@ -254,6 +255,18 @@ class _BgzfInfoC(C.Structure):
 BgzfInfo = collections.namedtuple("BgzfInfo", "blocks gz_bytes text_bytes stored fixed dynamic has_eof")
 
 
+class BgzfQueryOpts(C.Structure):
+    _fields_ = [("autoflip", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
+class _BgzfQueryInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("regions", "subqueries", "chunks", "blocks_inflated", "bytes_inflated", "candidate_lines", "lines", "answer_bytes", "unparsed")] + \
+               [("reason", C.c_uint32), ("pad", C.c_uint32), ("bad_offset", C.c_uint64)]
+
+
+BgzfQueryInfo = collections.namedtuple("BgzfQueryInfo", "regions subqueries chunks blocks_inflated bytes_inflated candidate_lines lines answer_bytes unparsed")
+
+
 class Timing(C.Structure):
     _fields_ = [("tile_kernel_ms", C.c_double), ("tile_launches", C.c_uint64), ("tile_bytes", C.c_uint64), ("other_ms", C.c_double),
                 ("tiles", C.c_uint64), ("deferred_tiles", C.c_uint64)]
@@ -387,6 +400,12 @@ def load_library():
     L.mkt_bgzf_load_index.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
     L.mkt_bgzf_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mkt_bgzf_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double * 5)]
+    L.mkt_bgzf_query.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(BgzfQueryOpts), C.POINTER(_BgzfQueryInfoC)]
+    L.mkt_bgzf_fetch_query.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_bgzf_fetch_query_offsets.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mkt_bgzf_fetch_query_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mkt_bgzf_query_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.mkt_bgzf_names.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
     L.mkt_paircmp_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_paircmp_destroy.argtypes = [C.c_void_p]
     L.mkt_paircmp_destroy.restype = None
@@ -943,12 +962,15 @@ class BgzfRefused(MktError):
 
 class BgzfReader:
     """A BGZF file (final.pairs.gz, its .px2, a BAM as bytes) inflated on the GPU: see mkt_bgzf_* in include/mkt.h, where the
-    definition and the limits stand (resident only, BGZF only, no region queries yet)."""
+    definition and the limits stand (resident only, BGZF only).  With the file's .px2 loaded, `query` answers regions the way
+    `pairix file.pairs.gz REGION ...` prints them: without a `run` only the blocks the index points to are inflated, after a `run` the
+    resident text is used; the bytes are the same."""
 
     def __init__(self, device=0):
         self.L = load_library()
         self.h = C.c_void_p()
         self.info = None
+        self.query_info = None
         rc = self.L.mkt_bgzf_create(device, C.byref(self.h))
         if rc != 0:
             raise MktError(f"mkt_bgzf_create: {self.L.mkt_strerror(rc).decode()}")
@@ -999,10 +1021,61 @@ class BgzfReader:
         self._chk(self.L.mkt_bgzf_count(self.h, C.byref(n)), "mkt_bgzf_count")
         return int(n.value)
 
+    def names(self):
+        """`pairix -l`: the pairs of the loaded index in the order of its name table, as bytes."""
+        total = C.c_uint64()
+        self._chk(self.L.mkt_bgzf_names(self.h, 0, None, 0, C.byref(total)), "mkt_bgzf_names")
+        buf = C.create_string_buffer(max(total.value, 1))
+        self._chk(self.L.mkt_bgzf_names(self.h, 0, buf, total.value, None), "mkt_bgzf_names")
+        return buf.raw[:total.value].split(b"\0")[:-1]
+
+    def query(self, regions, autoflip=False):
+        """One `bytes` per region ('chrA:b-e|chrB:b-e', a side may be '*' or lack its range; str or bytes): the lines pairix prints for
+        it.  Needs add and load_index; the counters are kept in .query_info.  A refused region raises MktError naming its index in
+        the batch, a refused block BgzfRefused, an index of another file MktError."""
+        regs = [r if isinstance(r, bytes) else r.encode("latin-1") for r in regions]
+        arr = (C.c_char_p * max(len(regs), 1))(*regs)
+        o = BgzfQueryOpts()
+        o.autoflip = 1 if autoflip else 0
+        info = _BgzfQueryInfoC()
+        self.query_info = None
+        rc = self.L.mkt_bgzf_query(self.h, arr, len(regs), C.byref(o), C.byref(info))
+        if rc == -9 and info.reason:
+            msg = self.L.mkt_bgzf_error(self.h).decode()
+            raise BgzfRefused(f"mkt_bgzf_query: {msg}", msg[msg.rfind("[") + 1:msg.rfind("]")], int(info.bad_offset))
+        self._chk(rc, "mkt_bgzf_query")
+        self.query_info = BgzfQueryInfo(*(int(getattr(info, k)) for k in BgzfQueryInfo._fields))
+        n = self.query_info.answer_bytes
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_bgzf_fetch_query(self.h, 0, buf, n), "mkt_bgzf_fetch_query")
+        off = (C.c_uint64 * (len(regs) + 1))()
+        self._chk(self.L.mkt_bgzf_fetch_query_offsets(self.h, off), "mkt_bgzf_fetch_query_offsets")
+        return [buf.raw[off[k]:off[k + 1]] for k in range(len(regs))]
+
+    def query_counts(self):
+        """Lines per region of the last query."""
+        n = self.query_info.regions if self.query_info else 0
+        out = (C.c_uint64 * max(n, 1))()
+        self._chk(self.L.mkt_bgzf_fetch_query_counts(self.h, out), "mkt_bgzf_fetch_query_counts")
+        return [int(out[k]) for k in range(n)]
+
+    def query_device(self):
+        """(device pointer, bytes) of the last query's concatenated answer: what Matrix.add_device takes; valid until the next add, run,
+        query or close."""
+        d, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mkt_bgzf_query_device(self.h, C.byref(d), C.byref(n)), "mkt_bgzf_query_device")
+        return d.value or 0, int(n.value)
+
     def timing_ms(self):
         t = (C.c_double * 5)()
         self._chk(self.L.mkt_bgzf_timing(self.h, C.byref(t)), "mkt_bgzf_timing")
         return dict(zip(("table_upload", "inflate", "crc"), (float(x) for x in t)))
+
+    def query_timing_ms(self):
+        """Of the last query: plan upload, inflate and CRC of the selected blocks; line index, filter, scan and gather."""
+        t = (C.c_double * 5)()
+        self._chk(self.L.mkt_bgzf_timing(self.h, C.byref(t)), "mkt_bgzf_timing")
+        return {"inflate_selected": float(t[3]), "filter_gather": float(t[4])}
 
     def close(self):
         if self.h:
