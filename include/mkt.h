@@ -1262,7 +1262,7 @@ int mkt_pairsgz_timing(const mkt_pairsgz* p, double ms[5]);
  * SAFETY   a malformed file ends in MKT_E_FORMAT, never in a fault: every read is bounded to the member, every write to the member's
  *          ISIZE bytes of the text, every loop by the bits left in the member.
  * LIMITS   resident only: the compressed bytes and the whole text are held in device memory at once (MKT_E_NOMEM with a message when
- *          they do not fit; no streaming in batches).  BGZF only, no plain gzip.  No BAM decoding: a BAM inflates to its bytes.
+ *          they do not fit; no streaming in batches).  BGZF only, no plain gzip.  A BAM inflates to its bytes: mkt_bamtext below decodes them.
  *          bin/pairscmp and bin/pairsbgz still refuse .gz names; `pairsgunzip a.pairs.gz | pairscmp - b.pairs` is the route.
  * The text depends on the file only: integers, no atomics.
  *
@@ -1355,6 +1355,82 @@ int mkt_bgzf_fetch_query_offsets(mkt_bgzf* r, uint64_t* out);
 int mkt_bgzf_fetch_query_counts(mkt_bgzf* r, uint64_t* out);
 int mkt_bgzf_query_device(mkt_bgzf* r, const void** d_ptr, uint64_t* n);
 int mkt_bgzf_names(mkt_bgzf* r, uint64_t off, char* out, size_t n, uint64_t* total);
+/* forgets the file, the text, a loaded index and the last answer: the reader is as it was created, so that one reader inflates a large
+ * file in batches of whole members (bin/bam2sam) */
+int mkt_bgzf_clear(mkt_bgzf* r);
+
+/* ---- reading BAM: the inflated stream of a BAM (SAMv1 4.2) decoded to SAM text on the GPU, the driver's `samtools view` ----
+ * The text is what samtools 1.17 `view` prints for the records and `view -H` for the header, byte for byte, for every stream inside the
+ * definition; tests/bamtextdef.py states it in Python, tests/golden/bamtext_golden.json records what samtools printed.  The input is
+ * the INFLATED stream: mkt_bgzf_device_text hands it out, or the caller uploads it.  Independent of mkt_bgzf and of sam2bam.
+ *
+ * HEADER   magic BAM\1, l_text, text, n_ref, then l_name, name (with its NUL), l_ref per reference: walked on the host.  The header text
+ *          as `view -H` prints it is the stored l_text bytes, NULs at their end included; where the text in front of those NULs is not
+ *          empty and lacks its last newline, a '\n' stands in place of the first of them (behind the text where there is none).
+ * LINE     per record, tab-separated, '\n' at the end: QNAME (the bytes before the first NUL), FLAG, RNAME (`*` for refID -1), pos + 1,
+ *          MAPQ, CIGAR (MIDNSHP=X; `*` without operations), RNEXT (`*` for next_refID -1, `=` where it equals refID, else the name),
+ *          next_pos + 1, TLEN, SEQ (=ACMGRSVTWYHKDBN; `*` for l_seq 0), QUAL (+ 33; `*` for l_seq 0 or a first byte 0xFF), then the tags
+ *          in stored order: c C s S i I print as i; A, Z, H as stored; B as B:t,v,v,...; f and B:f as "%g" of the float (formatted on
+ *          the host: the values are gathered in record order, their strings uploaded; no round trip for a stream without floats).
+ * REFUSED  never trusted, never a fault; MKT_E_FORMAT with info.reason (key in brackets in mkt_bamtext_error), info.bad_record (the
+ *          ordinal of the record in the whole stream, from 0) and info.bad_offset (its offset in the inflated stream):
+ *          1 bad_magic; 2 bad_header (a negative l_text, n_ref or l_name, a name without its NUL); 3 no_sq_lines (n_ref > 0 and a text
+ *          without an @SQ line: samtools makes lines up); 4 block_size_small (< 32); 5 block_size_large (> max_record); 6 past_end
+ *          (32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq exceeds block_size); 7 ref_id (refID or next_refID below -1 or not
+ *          below n_ref); 8 read_name (l_read_name 0, or a last byte that is not NUL); 9 cigar_op (a code above 8); 10 tag_overrun (the
+ *          tags do not end exactly at the record's end); 11 tag_type (outside AcCsSiIfZHB); 12 b_subtype (outside cCsSiIf);
+ *          13 z_unterminated; 14 cg_tag (a CG:B:I tag: the convention for more than 65535 operations, which samtools rewrites);
+ *          15 truncated (finish with a partial record held); 16 header_truncated (finish before the header was complete, an n_ref
+ *          that passes the data included); 17 cigar_seq_length (a mapped record whose CIGAR takes another number of bases than a
+ *          non-zero l_seq: samtools ends with an error there); 18 header_nul (a NUL inside the header text, in front of its last byte that is not NUL:
+ *          samtools cuts and mends such a text).  After a refusal the reader has forgotten the stream and takes a new one.
+ * PIECES   the stream is added in any chunking.  A run decodes every complete record held and keeps what is no complete record (at
+ *          most max_record + 4 bytes, or a header that is not complete yet) in front of the next piece; the texts of the runs, one
+ *          behind the other, are the text of the whole.  finish refuses a tail that is not empty.
+ * INDEX    records chain through block_size.  The record region of a run is cut into segments of segment_bytes; a workgroup per segment
+ *          takes the lowest offset at which the fixed fields of four chained records are plausible and walks the chain from there;
+ *          the segments are then put in order, and one whose guess is not where the segment before it ended is walked again from the
+ *          true start (info.repairs).  The text never depends on a guess, only the time does.
+ * SAFETY   every read lies inside a complete record (block_size is checked against the data held before anything else is read, every
+ *          variable part against block_size), every write inside the line whose length the same routines measured from the same bytes.
+ * LIMITS   max_record at most 16 MiB; the stream held, the record arrays and the text of one run are resident (feed pieces).
+ *
+ *   mkt_bamtext_add / _add_device   bytes of the inflated stream (host / device memory), copied before the call returns
+ *   mkt_bamtext_run        decodes what is held; opts NULL = the defaults; info may be NULL.  The text of the run replaces the last one's.
+ *   mkt_bamtext_finish     the end of the stream: MKT_E_FORMAT (truncated / header_truncated) unless nothing is held; a new stream may follow
+ *   mkt_bamtext_fetch_header   bytes [off, off + n) of the header text as `view -H` prints it, *total its length (MKT_E_STATE before a run
+ *                          reached the end of the header)
+ *   mkt_bamtext_fetch_ref  reference k: name (cap bytes of room, NUL included) and length; *n_ref their number (name and length may be NULL)
+ *   mkt_bamtext_fetch_text / _device_text   the text of the last run (64 zero bytes behind it on the device; valid until the next run)
+ *   mkt_bamtext_timing     ms of the last run from HIP events: header, index guess, resolve + scan + fill, length, scan, emit */
+typedef struct mkt_bamtext mkt_bamtext;
+typedef struct mkt_bamtext_opts {
+    uint32_t segment_bytes;               /* 0 = 256 KiB; a power of two >= 256 */
+    uint32_t max_record;                  /* 0 = 16 MiB (the most); the largest block_size accepted */
+    uint32_t reserved[6];                 /* 0 */
+} mkt_bamtext_opts;
+typedef struct mkt_bamtext_info {
+    uint64_t records, text_bytes;         /* of this run */
+    uint64_t segments, repairs;
+    uint64_t float_records;               /* records that hold at least one float (an f tag, an element of a B:f array) */
+    uint64_t carry_bytes;                 /* held for the next run */
+    uint32_t reason;                      /* 0, or why the stream is refused (the numbers above) */
+    uint32_t header_done;                 /* 1: the header is complete */
+    uint64_t bad_record, bad_offset;
+} mkt_bamtext_info;
+int mkt_bamtext_create(int device, mkt_bamtext** out);
+void mkt_bamtext_destroy(mkt_bamtext* r);
+const char* mkt_bamtext_error(const mkt_bamtext* r);
+int mkt_bamtext_add(mkt_bamtext* r, const char* bytes, size_t n);
+int mkt_bamtext_add_device(mkt_bamtext* r, const void* d_bytes, uint64_t n);
+void mkt_bamtext_opts_default(mkt_bamtext_opts* o);
+int mkt_bamtext_run(mkt_bamtext* r, const mkt_bamtext_opts* opts, mkt_bamtext_info* info);
+int mkt_bamtext_finish(mkt_bamtext* r, mkt_bamtext_info* info);
+int mkt_bamtext_fetch_header(mkt_bamtext* r, uint64_t off, char* out, size_t n, uint64_t* total);
+int mkt_bamtext_fetch_ref(mkt_bamtext* r, uint32_t k, char* name, size_t cap, int32_t* length, uint32_t* n_ref);
+int mkt_bamtext_fetch_text(mkt_bamtext* r, uint64_t off, char* out, size_t n);
+int mkt_bamtext_device_text(mkt_bamtext* r, const void** d_ptr, uint64_t* n);
+int mkt_bamtext_timing(const mkt_bamtext* r, double ms[6]);
 
 #ifdef __cplusplus
 }

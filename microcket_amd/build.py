@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip", "mkt_bamtext.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -234,6 +234,20 @@ def build_pairsquery(force=False):
     return PAIRSQUERY
 
 
+BAM2SAM = os.path.join(HERE, "bin", "bam2sam")
+
+
+def build_bam2sam(force=False):
+    """bin/bam2sam: the driver's `samtools view x.bam | sam2pairs /dev/stdin` front on the GPU (BGZF inflate, then BAM records to SAM
+    text: DESIGN.md 6i); same stdout as `samtools view [-h | -H]`."""
+    src = os.path.join(CSRC, "bam2sam_main.cpp")
+    if force or _newer(BAM2SAM, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(BAM2SAM), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", BAM2SAM, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return BAM2SAM
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -329,6 +343,14 @@ def build_test_tools():
         pqh = os.path.join(out, name)
         if os.path.exists(qsrc) and _newer(pqh, [qsrc, os.path.join(CSRC, "mkt_px2query.h"), os.path.join(CSRC, "mkt_inflate.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", pqh, qsrc])
+    # host driver of the BAM-to-SAM decoder's shared half (mkt_bamtext.h: the header walk, the record index with its resolve step, the
+    # validation, length and emit routines of a record), plain and sanitized like the ones above; a tree that carries an older tests/
+    # has no such source
+    bsrc2 = os.path.join(ROOT, "tests", "host", "bamtext_host.cpp")
+    for name, extra in (("bamtext_host", ()), ("bamtext_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        bth = os.path.join(out, name)
+        if os.path.exists(bsrc2) and _newer(bth, [bsrc2, os.path.join(CSRC, "mkt_bamtext.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", bth, bsrc2])
     build_emit_parts()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
@@ -350,6 +372,7 @@ def build_all(force=False, extras=True):
     build_pairsbgz(force)
     build_pairsgunzip(force)
     build_pairsquery(force)
+    build_bam2sam(force)
     build_makestat(force)
     if extras:
         build_oracle()

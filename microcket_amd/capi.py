@@ -46,7 +46,9 @@ EXPORTS = [
     "mkt_pairsgz_fetch_px2", "mkt_pairsgz_timing",
     "mkt_bgzf_create", "mkt_bgzf_destroy", "mkt_bgzf_error", "mkt_bgzf_add", "mkt_bgzf_opts_default", "mkt_bgzf_run", "mkt_bgzf_fetch_text", "mkt_bgzf_device_text",
     "mkt_bgzf_load_index", "mkt_bgzf_count", "mkt_bgzf_timing", "mkt_bgzf_query", "mkt_bgzf_fetch_query", "mkt_bgzf_fetch_query_offsets", "mkt_bgzf_fetch_query_counts",
-    "mkt_bgzf_query_device", "mkt_bgzf_names",
+    "mkt_bgzf_query_device", "mkt_bgzf_names", "mkt_bgzf_clear",
+    "mkt_bamtext_create", "mkt_bamtext_destroy", "mkt_bamtext_error", "mkt_bamtext_add", "mkt_bamtext_add_device", "mkt_bamtext_opts_default", "mkt_bamtext_run",
+    "mkt_bamtext_finish", "mkt_bamtext_fetch_header", "mkt_bamtext_fetch_ref", "mkt_bamtext_fetch_text", "mkt_bamtext_device_text", "mkt_bamtext_timing",
 ]
 
 
@@ -267,6 +269,19 @@ class _BgzfQueryInfoC(C.Structure):
 BgzfQueryInfo = collections.namedtuple("BgzfQueryInfo", "regions subqueries chunks blocks_inflated bytes_inflated candidate_lines lines answer_bytes unparsed")
 
 
+class BamTextOpts(C.Structure):
+    """mkt_bamtext_opts of include/mkt.h"""
+    _fields_ = [("segment_bytes", C.c_uint32), ("max_record", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
+class _BamTextInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records", "text_bytes", "segments", "repairs", "float_records", "carry_bytes")] + \
+               [("reason", C.c_uint32), ("header_done", C.c_uint32), ("bad_record", C.c_uint64), ("bad_offset", C.c_uint64)]
+
+
+BamTextInfo = collections.namedtuple("BamTextInfo", "records text_bytes segments repairs float_records carry_bytes header_done")
+
+
 class Timing(C.Structure):
     _fields_ = [("tile_kernel_ms", C.c_double), ("tile_launches", C.c_uint64), ("tile_bytes", C.c_uint64), ("other_ms", C.c_double),
                 ("tiles", C.c_uint64), ("deferred_tiles", C.c_uint64)]
@@ -406,6 +421,23 @@ def load_library():
     L.mkt_bgzf_fetch_query_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.mkt_bgzf_query_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.mkt_bgzf_names.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.mkt_bgzf_clear.argtypes = [C.c_void_p]
+    L.mkt_bamtext_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mkt_bamtext_destroy.argtypes = [C.c_void_p]
+    L.mkt_bamtext_destroy.restype = None
+    L.mkt_bamtext_error.argtypes = [C.c_void_p]
+    L.mkt_bamtext_error.restype = C.c_char_p
+    L.mkt_bamtext_add.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.mkt_bamtext_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.mkt_bamtext_opts_default.argtypes = [C.POINTER(BamTextOpts)]
+    L.mkt_bamtext_opts_default.restype = None
+    L.mkt_bamtext_run.argtypes = [C.c_void_p, C.POINTER(BamTextOpts), C.POINTER(_BamTextInfoC)]
+    L.mkt_bamtext_finish.argtypes = [C.c_void_p, C.POINTER(_BamTextInfoC)]
+    L.mkt_bamtext_fetch_header.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    L.mkt_bamtext_fetch_ref.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    L.mkt_bamtext_fetch_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_bamtext_device_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.mkt_bamtext_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.mkt_paircmp_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_paircmp_destroy.argtypes = [C.c_void_p]
     L.mkt_paircmp_destroy.restype = None
@@ -1077,6 +1109,11 @@ class BgzfReader:
         self._chk(self.L.mkt_bgzf_timing(self.h, C.byref(t)), "mkt_bgzf_timing")
         return {"inflate_selected": float(t[3]), "filter_gather": float(t[4])}
 
+    def clear(self):
+        """Forgets the file, the text, a loaded index and the last answer."""
+        self._chk(self.L.mkt_bgzf_clear(self.h), "mkt_bgzf_clear")
+        self.info = self.query_info = None
+
     def close(self):
         if self.h:
             self.L.mkt_bgzf_destroy(self.h)
@@ -1087,6 +1124,130 @@ class BgzfReader:
 
     def __exit__(self, *a):
         self.close()
+
+
+class BamRefused(MktError):
+    """A BAM stream the decoder refuses: .reason is the key of the reason (the list stands in include/mkt.h), .record the ordinal of the
+    record in the whole stream, .offset its offset in the inflated stream."""
+
+    def __init__(self, msg, reason, record, offset):
+        MktError.__init__(self, msg)
+        self.reason = reason
+        self.record = record
+        self.offset = offset
+
+
+class BamReader:
+    """The inflated stream of a BAM decoded to SAM text on the GPU, what `samtools view` prints: see mkt_bamtext_* in include/mkt.h,
+    where the definition stands.  add / add_device take the stream in any chunking, every run decodes the complete records held and
+    carries the rest, finish ends the stream."""
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.h = C.c_void_p()
+        self.info = None
+        rc = self.L.mkt_bamtext_create(device, C.byref(self.h))
+        if rc != 0:
+            raise MktError(f"mkt_bamtext_create: {self.L.mkt_strerror(rc).decode()}")
+
+    def _chk(self, rc, what, info=None):
+        if rc == -9 and info is not None:
+            msg = self.L.mkt_bamtext_error(self.h).decode()
+            raise BamRefused(f"{what}: {msg}", msg[msg.rfind("[") + 1:msg.rfind("]")], int(info.bad_record), int(info.bad_offset))
+        if rc != 0:
+            raise MktError(f"{what}: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_bamtext_error(self.h).decode()}")
+
+    def add(self, data: bytes):
+        self._chk(self.L.mkt_bamtext_add(self.h, data, len(data)), "mkt_bamtext_add")
+
+    def add_device(self, d_ptr, n):
+        self._chk(self.L.mkt_bamtext_add_device(self.h, C.c_void_p(d_ptr), n), "mkt_bamtext_add_device")
+
+    def run(self, segment_bytes=0, max_record=0):
+        """Decodes every complete record held; returns the counters (also kept in .info).  A refused stream raises BamRefused and
+        leaves no text; the reader then takes a new stream."""
+        o = BamTextOpts()
+        o.segment_bytes, o.max_record = segment_bytes, max_record
+        info = _BamTextInfoC()
+        self.info = None
+        self._chk(self.L.mkt_bamtext_run(self.h, C.byref(o), C.byref(info)), "mkt_bamtext_run", info)
+        self.info = BamTextInfo(*(int(getattr(info, k)) for k in BamTextInfo._fields))
+        return self.info
+
+    def finish(self):
+        """The end of the stream: BamRefused (truncated / header_truncated) where a partial record or header is held."""
+        info = _BamTextInfoC()
+        rc = self.L.mkt_bamtext_finish(self.h, C.byref(info))
+        if rc != 0:
+            self.info = None                             # a refused stream leaves no text
+        self._chk(rc, "mkt_bamtext_finish", info)
+
+    def header(self):
+        """The header text as `samtools view -H` prints it."""
+        total = C.c_uint64()
+        self._chk(self.L.mkt_bamtext_fetch_header(self.h, 0, None, 0, C.byref(total)), "mkt_bamtext_fetch_header")
+        buf = C.create_string_buffer(max(total.value, 1))
+        self._chk(self.L.mkt_bamtext_fetch_header(self.h, 0, buf, total.value, None), "mkt_bamtext_fetch_header")
+        return buf.raw[:total.value]
+
+    def refs(self):
+        """[(name, length)] of the references."""
+        n, ln = C.c_uint32(), C.c_int32()
+        self._chk(self.L.mkt_bamtext_fetch_ref(self.h, 0, None, 0, None, C.byref(n)), "mkt_bamtext_fetch_ref")
+        out = []
+        buf = C.create_string_buffer(1 << 16)
+        for k in range(n.value):
+            self._chk(self.L.mkt_bamtext_fetch_ref(self.h, k, buf, len(buf), C.byref(ln), None), "mkt_bamtext_fetch_ref")
+            out.append((buf.value, int(ln.value)))
+        return out
+
+    def text(self):
+        """The SAM lines of the last run."""
+        if self.info is None:
+            raise MktError("text before a run that succeeded")
+        n = self.info.text_bytes
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_bamtext_fetch_text(self.h, 0, buf, n), "mkt_bamtext_fetch_text")
+        return buf.raw[:n]
+
+    def device_text(self):
+        """(device pointer, bytes) of the last run's text; valid until the next run or close."""
+        d, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mkt_bamtext_device_text(self.h, C.byref(d), C.byref(n)), "mkt_bamtext_device_text")
+        return d.value or 0, int(n.value)
+
+    def timing_ms(self):
+        t = (C.c_double * 6)()
+        self._chk(self.L.mkt_bamtext_timing(self.h, t), "mkt_bamtext_timing")
+        return dict(zip(("header", "index_guess", "resolve", "length", "scan", "emit"), (float(x) for x in t)))
+
+    def close(self):
+        if self.h:
+            self.L.mkt_bamtext_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def bam_to_sam(bam: bytes, header=False, piece=None, device=0, **opts):
+    """The bytes of a BAM file -> what `samtools view` (header=True: `view -h`) prints: BgzfReader inflates the file, BamReader decodes
+    the inflated stream from device memory, `piece` inflated bytes per run (None: all at once)."""
+    with BgzfReader(device) as z, BamReader(device) as r:
+        z.add(bam)
+        z.run()
+        d, n = z.device_text()
+        out = []
+        step = piece or max(n, 1)
+        for k in range(0, max(n, 1), step):
+            r.add_device(d + k, min(step, n - k))
+            r.run(**opts)
+            out.append(r.text())
+        r.finish()
+        return (r.header() if header else b"") + b"".join(out)
 
 
 class PairCompare:

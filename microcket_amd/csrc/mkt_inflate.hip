@@ -669,6 +669,20 @@ int mkt_bgzf_query_device(mkt_bgzf* p, const void** d_ptr, uint64_t* n) {
     *n = p->qans_len;
     return MKT_OK;
 }
+int mkt_bgzf_clear(mkt_bgzf* p) {
+    if (!p) return MKT_E_ARG;
+    BCHK(p, hipSetDevice(p->device));
+    BCHK(p, hipStreamSynchronize(p->stream));
+    p->hgz.clear();                                     // (the device buffer of the compressed bytes keeps its room: nothing of it is read again)
+    p->text.reset(); p->text_len = 0;
+    p->ran = p->have_index = p->have_blocks = p->index_checked = p->have_query = false;
+    p->index_lines = 0;
+    p->ix = Px2Index();
+    p->dnames.reset(); p->dblocks.reset(); p->qans.reset(); p->qans_len = 0;
+    p->blocks.clear(); p->qoff.clear(); p->qcnt.clear();
+    for (double& m : p->ms) m = 0;
+    return MKT_OK;
+}
 int mkt_bgzf_names(mkt_bgzf* p, uint64_t off, char* out, size_t n, uint64_t* total) {
     if (!p || (n && !out)) return MKT_E_ARG;
     if (!p->have_index) return bfail(p, MKT_E_STATE, "names before an index was loaded");
