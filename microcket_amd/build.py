@@ -280,6 +280,22 @@ def build_emit_parts():
     return made
 
 
+def build_parse_chain():
+    """tests/host/parse_chain: host driver of what the lean kernel's heads phase leaves for its parser (fast_head_line) and of the
+    parser's QNAME compare (lean_eq in mkt_fast.h), plain and with the address and undefined-behaviour sanitizers (a stand-alone
+    program: nothing of it is loaded into python)."""
+    out = os.path.join(ROOT, "tests", "host", "_build")
+    os.makedirs(out, exist_ok=True)
+    src = os.path.join(ROOT, "tests", "host", "parse_chain.cpp")
+    made = []
+    for name, extra in (("parse_chain", ()), ("parse_chain_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        exe = os.path.join(out, name)
+        if os.path.exists(src) and _newer(exe, [src] + _headers()):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", exe, src])
+        made.append(exe)
+    return made
+
+
 def build_test_tools():
     out = os.path.join(ROOT, "tests", "host", "_build")
     os.makedirs(out, exist_ok=True)
@@ -352,6 +368,7 @@ def build_test_tools():
         if os.path.exists(bsrc2) and _newer(bth, [bsrc2, os.path.join(CSRC, "mkt_bamtext.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", bth, bsrc2])
     build_emit_parts()
+    build_parse_chain()
     tout = os.path.join(ROOT, "tools", "_build")
     os.makedirs(tout, exist_ok=True)
     synth = os.path.join(tout, "synth_sam")

@@ -94,14 +94,14 @@ struct FastState {
         struct { uint32_t pos[Cfg::LCAP], lclip[Cfg::LCAP], rclip[Cfg::LCAP], mappable[Cfg::LCAP], right0[Cfg::LCAP], left1[Cfg::LCAP], right1[Cfg::LCAP]; } f;
     } rc;
     uint16_t hv16[Cfg::LCAP];            // window vector that holds the newline in front of line i (line table); the head row starts there
-    uint16_t off16[Cfg::LCAP];           // line start in the head store: i * HSTRIDE + (1 + byte of that newline in its vector), set while parsing
+    uint16_t off16[Cfg::LCAP];           // line start in the head store: i * HSTRIDE + (1 + byte of that newline in its vector), set by the heads phase (fast_head_line)
     uint16_t goff[Cfg::LCAP];            // line start, window relative: 16 * hv16 + the same; may be >= the window length for the last entry
     uint16_t flag[Cfg::LCAP];
     uint8_t qn_off[Cfg::LCAP], qn_len[Cfg::LCAP], rn_off[Cfg::LCAP], rn_len[Cfg::LCAP], segCnt[Cfg::LCAP], bits[Cfg::LCAP];
     union alignas(16) Phase {
         struct {                                               // while parsing
             uint64_t hitmap[Cfg::HMW + 1];                     // bit v: window vector v (16 bytes) holds a newline (scan phase -> line table)
-            alignas(8) uint16_t hmask[Cfg::LCAP][Cfg::HCH];    // per line: whitespace bits of its head chunks
+            alignas(8) uint16_t hmask[Cfg::LCAP][Cfg::HCH];    // per line: whitespace bits of its head chunks; once the row is complete shifted to the line's first byte (fast_head_line)
         } m;
         struct {                                               // afterwards, indexed by the group's first line / by line
             uint32_t g_info[Cfg::LCAP], g_slen[Cfg::LCAP];
@@ -166,14 +166,13 @@ template <class Cfg> MKT_HD uint32_t fast_line_end(const FastState<Cfg>& st, con
     return i + 1 < st.NL ? G.w0 + st.goff[i + 1] - 1u : st.last_line_end;
 }
 
-// the two 64-bit SEPARATOR words of line i's head (bit k <-> byte k of the line is <= 0x20), from its head-mask row
+// the two 64-bit SEPARATOR words of line i's head (bit k <-> byte k of the line is <= 0x20): its head-mask row, which
+// fast_head_line has shifted to the line's first byte
 template <class Cfg> MKT_HD void fast_head_ws(const FastState<Cfg>& st, uint32_t i, uint64_t& ws0, uint64_t& ws1) {
     const uint64_t* row = reinterpret_cast<const uint64_t*>(st.u.m.hmask[i]);
-    const uint64_t A = row[0], B = row[1];
-    const uint32_t sh = (uint32_t)st.off16[i] - mul24(i, (uint32_t)Cfg::HSTRIDE);  // 0 (first line of a block) .. 16
-    ws0 = sh ? ((A >> sh) | (B << (64u - sh))) : A;
-    ws1 = B >> sh;
+    ws0 = row[0]; ws1 = row[1];
 }
+template <class Cfg> MKT_HD void fast_head_line(FastState<Cfg>& st, const TileGeom& G, uint32_t i);
 // one head chunk: the 16 text bytes at window offset r0 (multiple of 16); bytes at or past the block end read as 0 and are
 // no separators.  Separator bits: byte <= 0x20 (tab, newline, the other whitespace and control bytes)
 template <class Cfg> MKT_HD void fast_head_chunk_ref(FastState<Cfg>& st, const uint8_t* text, uint32_t n, const TileGeom& G, uint32_t i, uint32_t c) {
@@ -186,6 +185,7 @@ template <class Cfg> MKT_HD void fast_head_chunk_ref(FastState<Cfg>& st, const u
         if (g < n && ch <= 0x20u) m |= 1u << b;
     }
     st.u.m.hmask[i][c] = (uint16_t)m;
+    if (c + 1u == (uint32_t)Cfg::HCH) fast_head_line(st, G, i);                // the row is complete
 }
 
 // ---- where line i starts inside its head row ------------------------------------------------------------
@@ -206,6 +206,23 @@ template <class Cfg> MKT_HD uint32_t fast_row_start(const FastState<Cfg>& st, co
     *multi = (m & (m - 1u)) != 0u;
     const uint32_t p = f0 ? (ctz32(f0) >> 3) : (f1 ? 4u + (ctz32(f1) >> 3) : (f2 ? 8u + (ctz32(f2) >> 3) : 12u + (ctz32(f3 | 0x80000000u) >> 3)));
     return p + 1u;                                                             // first newline of the vector (none: cannot happen)
+}
+// What the parser needs to know about line i before it reads a byte of it, once per line at the end of the heads phase (the
+// kernel: by a lane of the wave that stored the row, behind its stores; fast_head_chunk_ref: behind the row's last chunk):
+// goff[i], off16[i], the head-mask row shifted to the line's first byte (fast_head_ws), and in bits[i], until the parser puts
+// the line's bits there, LB_HEAD_SHORT when the row's first vector holds a second newline (AB_SHORT_LINE is the parser's to
+// report, beside its other reasons).  The parser of line i + 1 wants off16[i] as well: it is there before any parser starts.
+constexpr uint8_t LB_HEAD_SHORT = 1;
+template <class Cfg> MKT_HD void fast_head_line(FastState<Cfg>& st, const TileGeom& G, uint32_t i) {
+    bool multi;
+    const uint32_t sh = fast_row_start(st, G, i, &multi);                      // 0 (first line of a block) .. 16
+    st.goff[i] = (uint16_t)(16u * (uint32_t)st.hv16[i] + sh);
+    st.off16[i] = (uint16_t)(mul24(i, (uint32_t)Cfg::HSTRIDE) + sh);
+    st.bits[i] = multi ? LB_HEAD_SHORT : 0;
+    uint64_t* row = reinterpret_cast<uint64_t*>(st.u.m.hmask[i]);
+    const uint64_t A = row[0], B = row[1];
+    row[0] = sh ? ((A >> sh) | (B << (64u - sh))) : A;
+    row[1] = B >> sh;
 }
 
 // ---- parse line i ------------------------------------------------------------------------------
@@ -254,29 +271,40 @@ MKT_HD uint32_t lean_uint12(const TextView& tv, uint32_t e, uint32_t len, bool& 
     if (v > 0xFFFFFFFFull) ok = false;
     return (uint32_t)v;
 }
-// len bytes at head-store offsets a and b equal?  (eight bytes per step; reads up to 11 bytes past the ranges)
+// bytes s .. s + 3 of the eight bytes lo | hi << 32 (s = 0 .. 3)
+MKT_HD uint32_t lean_align(uint32_t hi, uint32_t lo, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbyte(hi, lo, s);
+#else
+    return s ? ((lo >> (8u * s)) | (hi << (32u - 8u * s))) : lo;
+#endif
+}
+// len (>= 1) bytes at head-store offsets a and b equal?  Reads up to 11 bytes past the ranges and no further.
+// Sixteen bytes per step while more than sixteen are left: four new dwords per side, the fifth one of a step is the first one
+// of the next (carried in a register), and no step but the last masks anything.  The last 1 .. 16 bytes: the same loads, the
+// third and fourth dword of a side only when more than eight bytes are left (else the second one again: a lane never reads
+// behind what an eight-byte step would have read there), the bytes past the end shifted out of the two 64-bit differences.
 MKT_HD bool lean_eq(const TextView& tv, uint32_t a, uint32_t b, uint32_t len) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(tv.win);
-    const uint32_t ka = a >> 2, sa = a & 3u, kb = b >> 2, sb = b & 3u;
+    const uint32_t sa = a & 3u, sb = b & 3u;
+    uint32_t ka = a >> 2, kb = b >> 2, rem = len;
+    uint32_t a0 = w[ka], b0 = w[kb];
     uint32_t acc = 0;
-    for (uint32_t i = 0; i < len; i += 8u) {
-        const uint32_t j = i >> 2;
-        const uint32_t a0 = w[ka + j], a1 = w[ka + j + 1], a2 = w[ka + j + 2], b0 = w[kb + j], b1 = w[kb + j + 1], b2 = w[kb + j + 2];
-        uint32_t x0, x1, y0, y1;
-#if defined(__HIP_DEVICE_COMPILE__)
-        x0 = __builtin_amdgcn_alignbyte(a1, a0, sa); x1 = __builtin_amdgcn_alignbyte(a2, a1, sa);
-        y0 = __builtin_amdgcn_alignbyte(b1, b0, sb); y1 = __builtin_amdgcn_alignbyte(b2, b1, sb);
-#else
-        x0 = sa ? ((a0 >> (8u * sa)) | (a1 << (32u - 8u * sa))) : a0; x1 = sa ? ((a1 >> (8u * sa)) | (a2 << (32u - 8u * sa))) : a1;
-        y0 = sb ? ((b0 >> (8u * sb)) | (b1 << (32u - 8u * sb))) : b0; y1 = sb ? ((b1 >> (8u * sb)) | (b2 << (32u - 8u * sb))) : b1;
-#endif
-        uint32_t d0 = x0 ^ y0, d1 = x1 ^ y1;
-        const uint32_t rem = len - i;                                           // >= 1
-        if (rem < 4u) { d0 &= (1u << (8u * rem)) - 1u; d1 = 0; }
-        else if (rem < 8u) { d1 &= (1u << (8u * (rem - 4u))) - 1u; }
-        acc |= d0 | d1;
+    for (; rem > 16u; rem -= 16u) {
+        const uint32_t a1 = w[ka + 1], a2 = w[ka + 2], a3 = w[ka + 3], a4 = w[ka + 4];
+        const uint32_t b1 = w[kb + 1], b2 = w[kb + 2], b3 = w[kb + 3], b4 = w[kb + 4];
+        acc |= (lean_align(a1, a0, sa) ^ lean_align(b1, b0, sb)) | (lean_align(a2, a1, sa) ^ lean_align(b2, b1, sb));
+        acc |= (lean_align(a3, a2, sa) ^ lean_align(b3, b2, sb)) | (lean_align(a4, a3, sa) ^ lean_align(b4, b3, sb));
+        a0 = a4; b0 = b4; ka += 4u; kb += 4u;
     }
-    return acc == 0u;
+    const uint32_t far = rem > 8u ? 1u : 0u;
+    const uint32_t a1 = w[ka + 1], a2 = w[ka + 2], a3 = w[ka + 2 + far], a4 = w[ka + 2 + 2u * far];
+    const uint32_t b1 = w[kb + 1], b2 = w[kb + 2], b3 = w[kb + 2 + far], b4 = w[kb + 2 + 2u * far];
+    const uint64_t d0 = (uint64_t)(lean_align(a1, a0, sa) ^ lean_align(b1, b0, sb)) | ((uint64_t)(lean_align(a2, a1, sa) ^ lean_align(b2, b1, sb)) << 32);
+    const uint64_t d1 = (uint64_t)(lean_align(a3, a2, sa) ^ lean_align(b3, b2, sb)) | ((uint64_t)(lean_align(a4, a3, sa) ^ lean_align(b4, b3, sb)) << 32);
+    const uint32_t n0 = far ? 8u : rem;                                         // bytes of d0 / d1 inside the range: 1 .. 8 / 0 .. 8
+    const uint64_t t0 = d0 << (64u - 8u * n0), t1 = far ? d1 << (128u - 8u * rem) : 0ull;
+    return (t0 | t1 | (uint64_t)acc) == 0ull;
 }
 
 // One CIGAR operation on the walk state, as CigarWalk::op but as selects instead of branches (the lanes of a wave meet
@@ -399,14 +427,10 @@ MKT_HD int parse_record_lean(const TextView& tv, uint32_t off, const Params& P, 
 }
 
 template <class Cfg> MKT_HD void fast_parse(FastState<Cfg>& st, const TextView& tv, const Params& P, const TileGeom& G, uint32_t i) {
-    bool multi;
-    const uint32_t soff = fast_row_start(st, G, i, &multi);
-    if (multi) st.abn = AB_SHORT_LINE;
-    const uint32_t goff = 16u * (uint32_t)st.hv16[i] + soff;
-    const uint32_t off = mul24(i, (uint32_t)Cfg::HSTRIDE) + soff;  // line start in the head store
-    st.goff[i] = (uint16_t)goff;
-    st.off16[i] = (uint16_t)off;
-    const uint32_t gl = G.w0 + goff;                               // ... and in the block
+    // where the line starts, in the head store and in the window: left by the heads phase (fast_head_line)
+    const uint32_t off = st.off16[i];
+    if (st.bits[i]) st.abn = AB_SHORT_LINE;                        // (LB_HEAD_SHORT; every way out of here sets bits[i])
+    const uint32_t gl = G.w0 + (uint32_t)st.goff[i];               // ... and in the block
     if (gl >= G.w1) {                                              // the newline is the window's last byte: no line of this window
         st.bits[i] = LB_CUT;                                       // (always the table's last entry; the line before it ends right here)
         if (i + 1u != st.NL) st.abn = AB_SHORT_LINE;
@@ -429,12 +453,11 @@ template <class Cfg> MKT_HD void fast_parse(FastState<Cfg>& st, const TextView& 
     st.segCnt[i] = (uint8_t)(r.segCnt > 4 ? 4 : r.segCnt);
     uint8_t b = r.survive ? LB_SURVIVE : 0;
     if (i > 0 && pf == LP_OK) {
-        // same QNAME token as the line before: its first r.qn_len bytes and the tab behind them (its own lane sets off16[i - 1]
-        // in this same phase: recompute).  A line before that is no lean record only ever costs the direct comparison in
-        // fast_is_start (or defers the tile by itself).
-        bool pm;
-        const uint32_t psoff = fast_row_start(st, G, i - 1u, &pm);
-        const uint32_t poff = mul24(i - 1u, (uint32_t)Cfg::HSTRIDE) + psoff;
+        // same QNAME token as the line before: its first r.qn_len bytes and the tab behind them (off16[i - 1] is from the heads
+        // phase).  A line before that is no lean record only ever costs the direct comparison in fast_is_start (or defers the
+        // tile by itself).
+        const uint32_t poff = st.off16[i - 1u];
+        const uint32_t psoff = poff - mul24(i - 1u, (uint32_t)Cfg::HSTRIDE);
         const uint32_t ql = r.qn_len;
         if (ql + 1u > (uint32_t)Cfg::HEADB - psoff || ql > 100u) st.abn = AB_PREV_HEAD;      // beyond the previous line's head (lean_eq reads 11 bytes past the names)
         else if (lean_eq(tv, off, poff, ql + 1u)) b |= LB_EQPREV;

@@ -725,6 +725,19 @@ __global__ __launch_bounds__(NTW, WPS) void k_fast(KArgs a) {
                     if (EDGE && keep < 16u) m &= (1u << keep) - 1u;            // cleared bytes are no separators
                     st.u.m.hmask[i][c] = (uint16_t)m;
                 }
+                // ... and per line its start and its separator words (fast_head_line), off the parser's chain.  The HCH chunks of
+                // a line are neighbouring lanes, so step k of this wave filled the rows of LPW whole lines, 8 wave + (NTW / HCH) k
+                // onwards: one lane per such line reads them back behind the wave's own stores -- no barrier
+                constexpr uint32_t LPW = 64u / (uint32_t)Cfg::HCH;
+                static_assert(64 % Cfg::HCH == 0 && NTW % Cfg::HCH == 0 && HPT * (64 / Cfg::HCH) <= 64, "the lines of a wave's chunks, a lane each");
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                {
+                    const uint32_t l = (uint32_t)tid & 63u;
+                    const uint32_t i = (((uint32_t)tid >> 6) * LPW) + (l / LPW) * (uint32_t)(NTW / Cfg::HCH) + (l % LPW);
+                    if (l < (uint32_t)HPT * LPW && i < NL) fast_head_line(st, G, i);
+                }
             };
             if ((uint64_t)G.w1 + 16u * ((uint32_t)Cfg::HCH + 2u) > (uint64_t)n) heads(std::true_type{});
             else heads(std::false_type{});
