@@ -326,6 +326,71 @@ int mkt_stitch_fetch(mkt_stitch* s, int which /* MKT_STITCH_* */, uint64_t off, 
 int mkt_stitch_stats(const mkt_stitch* s, uint64_t* total, uint64_t* combined, uint64_t* uncombined, uint64_t* pass);
 int mkt_stitch_timing(const mkt_stitch* s, double* index_ms, double* score_ms, double* scan_ms, double* write_ms);
 
+/* ---- adapter and quality trimming: the driver's `ktrim -k KIT -t T -o PREFIX -1 R1 -2 R2 -c` (microcket:371, 405, 413, 430, 444) ------
+ * Paired FASTQ in (two streams, or one interleaved stream), out in input order
+ *   MKT_TRIM_INTERLEAVED   what the program writes to stdout with -c: read 1's record, then read 2's, of every pair kept
+ *   MKT_TRIM_READ1 / MKT_TRIM_READ2   PREFIX.read1.fq / PREFIX.read2.fq, what it writes without -c
+ * and the six counters of PREFIX.trim.log.  The definition (restated in tests/ktrimdef.py, pinned to Ktrim 1.6.0's paired-end route by
+ * tests/golden/ktrim_golden.json).  Bytes are compared as they stand: lower case never equals upper case, N equals only N.
+ *   common length  n = min(len1, len2); all four strings of the pair are cut to n
+ *   quality        a cycle passes when its byte is >= phred + min_qual in both reads.  k = the largest i + 1, i >= min_size - 1, for
+ *                  which the `window` cycles i - window + 1 .. i all pass (a window that would begin before cycle 0 does not pass).
+ *                  No such i: the pair is dropped.  The four strings are cut to k.
+ *   seeds          every position at which the first 3 letters of adapter 1 stand in read 1, or the first 3 of adapter 2 in read 2,
+ *                  wholly inside the k cycles; ascending, each position once
+ *   verification   at a seed p: L = min(k - p, adapter length), limit = ceil(float32(L) * float32(mismatch)) (float32 throughout).
+ *                  Read 1's [p, p + L) differs from adapter 1's first L letters in at most `limit` places AND read 2's from adapter
+ *                  2's.  Nothing else is compared (the reads are not compared with each other).  The first seed that verifies wins
+ *                  and counts as "Aadaptor": p >= min_size keeps p cycles, otherwise the pair is dropped, and is a dimer when p <= 1.
+ *   tail           only when no seed verifies.  With i = k - 2, of the six conditions  r1[i] == a1[0], r1[i+1] == a1[1], r2[i] == a2[0],
+ *                  r2[i+1] == a2[1], revcomp(r1[5], r2[i-6]), revcomp(r2[5], r1[i-6])  at most one fails: a tail hit, i cycles are kept
+ *                  (dropped when i < min_size).  Otherwise with i = k - 1, of  r1[i] == a1[0], r2[i] == a2[0], revcomp(r1[5], r2[i-6]),
+ *                  revcomp(r2[5], r1[i-6]), revcomp(r1[6], r2[i-7]), revcomp(r2[6], r1[i-7])  at most one fails: a tail hit, i cycles.
+ *                  revcomp(x, y) holds for (A,T), (C,G), (G,C), (T,A) only.
+ *   adapters       kit: illumina | nextera | transposase | bgi in the program's spellings; it wins over adapter1 / adapter2.  Without
+ *                  a kit: adapter1 (and adapter2, default adapter1), cut to their common length, 8 .. 64 letters; neither: illumina.
+ *   output         header lines whole, the third line is "+"
+ * The float32 limit is tabulated on the host for L = 0 .. 64; the kernels work in integers.
+ * Deliberately different from the program, which damages such records and exits 0: here each is MKT_E_ARG with a message that names
+ * the pair (counted from 0), never a truncation: sequence and quality of different lengths; a header line longer than
+ * MKT_TRIM_MAX_HEADER or a read longer than MKT_TRIM_MAX_READ (the program's line buffers); a record without '@' or '+'; a quality byte
+ * outside phred .. 126; at the end of the input a line count that is no multiple of 4, or streams of different pair counts.
+ * Not accepted although the program accepts them (unpinned or meaningless): phred, min_qual and window of 0 are refused by the program
+ * too (exit 12), min_size below 10 too (exit 11); mismatch outside 0 .. 1; the CLIP kit.  A pair with more than 128 seeds overruns the
+ * program's seed list; here the rule above holds for any number.
+ * The input is worked off in segments of whole pairs (mkt_trim_segment_pairs, default 2^20; MKT_TRIM_SEGMENT_PAIRS); the bytes do not
+ * depend on the segment size or on where the pushes are cut.
+ *   mkt_trim_check     the argument check of mkt_trim_begin without a device: MKT_OK, or MKT_E_ARG with the message in msg
+ *   mkt_trim_push      the next bytes of both streams (either may be none), cut anywhere; with opts.interleaved_input one interleaved
+ *                      stream in bytes1 and n2 = 0.  final != 0 ends the input.  out_bytes = what this push left in the three streams
+ *   mkt_trim_fetch     a range of one of them (valid until the next push)
+ *   mkt_trim_timing    ms (HIP events) of the segments so far: line indexes, decisions, sizes and their scans, writing */
+#define MKT_TRIM_MAX_READ 510
+#define MKT_TRIM_MAX_HEADER 126
+#define MKT_TRIM_MIN_ADAPTER 8
+#define MKT_TRIM_MAX_ADAPTER 64
+enum { MKT_TRIM_INTERLEAVED = 0, MKT_TRIM_READ1 = 1, MKT_TRIM_READ2 = 2 };
+typedef struct mkt_trim_opts {
+    const char* adapter1;      /* NULL: by kit */
+    const char* adapter2;      /* NULL: adapter1 */
+    const char* kit;           /* NULL: by adapter1 / adapter2, or illumina */
+    uint32_t min_size, phred, min_qual, window;
+    double mismatch;
+    int interleaved_input;
+} mkt_trim_opts;
+typedef struct mkt_trim mkt_trim;
+void mkt_trim_default_opts(mkt_trim_opts* o);      /* illumina, 36, 33, 20, 5, 0.125, two streams */
+int mkt_trim_create(int device, mkt_trim** out);
+void mkt_trim_destroy(mkt_trim* t);
+const char* mkt_trim_error(const mkt_trim* t);
+int mkt_trim_check(const mkt_trim_opts* o, char* msg, size_t msg_cap);
+int mkt_trim_segment_pairs(mkt_trim* t, uint64_t pairs);        /* before begin; at least 1 */
+int mkt_trim_begin(mkt_trim* t, const mkt_trim_opts* o);
+int mkt_trim_push(mkt_trim* t, const char* bytes1, size_t n1, const char* bytes2, size_t n2, int final, uint64_t out_bytes[3]);
+int mkt_trim_fetch(mkt_trim* t, int which /* MKT_TRIM_* */, uint64_t off, char* out, size_t n);
+int mkt_trim_stats(const mkt_trim* t, uint64_t* total, uint64_t* dropped, uint64_t* adapter, uint64_t* tailhit, uint64_t* dimer, uint64_t* pass);
+int mkt_trim_timing(const mkt_trim* t, double* index_ms, double* decide_ms, double* scan_ms, double* write_ms);
+
 /* ---- the .sam -> BAM tail of the pipeline -----------------------------------------------------------
  * Replaces microcket:533-540: `cat header flash.sam unc.sam | samtools view -b | samtools sort -o valid.bam; samtools index`.
  * SAM text in (leading '@' lines = the header, then alignment lines), out a BGZF-compressed BAM -- records in input order

@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip", "mkt_bamtext.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_trim.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip", "mkt_bamtext.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -150,6 +150,20 @@ def build_stitch(force=False):
         _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", STITCH, "-L" + HERE, "-lmkt_hip",
               "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
     return STITCH
+
+
+KTRIM = os.path.join(HERE, "bin", "ktrim")
+
+
+def build_ktrim(force=False):
+    """bin/ktrim: the driver's `ktrim -k KIT -o PREFIX -1 R1 -2 R2 -c` step on the GPU (adapter and quality trimming, DESIGN.md 6j);
+    the reference's argv for the paired-end route, the same stdout and PREFIX.trim.log."""
+    src = os.path.join(CSRC, "ktrim_main.cpp")
+    if force or _newer(KTRIM, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(KTRIM), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", src, "-o", KTRIM, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return KTRIM
 
 
 SAM2BAM = os.path.join(HERE, "bin", "sam2bam")
@@ -367,6 +381,13 @@ def build_test_tools():
         bth = os.path.join(out, name)
         if os.path.exists(bsrc2) and _newer(bth, [bsrc2, os.path.join(CSRC, "mkt_bamtext.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", bth, bsrc2])
+    # host driver of trimming's host half (mkt_trim.h: the argument check, the adapter table, the limit table, the record check, the
+    # tail rule), plain and sanitized like the ones above; a tree that carries an older tests/ has no such source
+    trsrc = os.path.join(ROOT, "tests", "host", "trim_host.cpp")
+    for name, extra in (("trim_host", ()), ("trim_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        trh = os.path.join(out, name)
+        if os.path.exists(trsrc) and _newer(trh, [trsrc, os.path.join(CSRC, "mkt_trim.h"), os.path.join(ROOT, "include", "mkt.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", trh, trsrc])
     build_emit_parts()
     build_parse_chain()
     tout = os.path.join(ROOT, "tools", "_build")
@@ -383,6 +404,7 @@ def build_all(force=False, extras=True):
     build_pairsort(force)
     build_krmdup(force)
     build_stitch(force)
+    build_ktrim(force)
     build_sam2bam(force)
     build_pairs2matrix(force)
     build_pairscmp(force)

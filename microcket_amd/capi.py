@@ -22,6 +22,8 @@ EXPORTS = [
     "mkt_rmdup_begin", "mkt_rmdup_push", "mkt_rmdup_stats",
     "mkt_stitch_create", "mkt_stitch_destroy", "mkt_stitch_error", "mkt_stitch_check", "mkt_stitch_segment_pairs", "mkt_stitch_begin", "mkt_stitch_push",
     "mkt_stitch_fetch", "mkt_stitch_stats", "mkt_stitch_timing",
+    "mkt_trim_default_opts", "mkt_trim_create", "mkt_trim_destroy", "mkt_trim_error", "mkt_trim_check", "mkt_trim_segment_pairs", "mkt_trim_begin", "mkt_trim_push",
+    "mkt_trim_fetch", "mkt_trim_stats", "mkt_trim_timing",
     "mkt_bam_create", "mkt_bam_destroy", "mkt_bam_error", "mkt_bam_note", "mkt_bam_add", "mkt_bam_add_device", "mkt_bam_run", "mkt_bam_fetch",
     "mkt_bam_reserve", "mkt_bam_window", "mkt_bam_commit", "mkt_bam_read", "mkt_bam_spill", "mkt_bam_pull", "mkt_bam_stats",
     "mkt_matrix_create", "mkt_matrix_destroy", "mkt_matrix_error", "mkt_matrix_add", "mkt_matrix_add_device", "mkt_matrix_add_keys", "mkt_matrix_run",
@@ -476,6 +478,20 @@ def load_library():
     L.mkt_stitch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
     L.mkt_stitch_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.mkt_stitch_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_trim_default_opts.argtypes = [C.POINTER(TrimOpts)]
+    L.mkt_trim_default_opts.restype = None
+    L.mkt_trim_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.mkt_trim_destroy.argtypes = [C.c_void_p]
+    L.mkt_trim_destroy.restype = None
+    L.mkt_trim_error.argtypes = [C.c_void_p]
+    L.mkt_trim_error.restype = C.c_char_p
+    L.mkt_trim_check.argtypes = [C.POINTER(TrimOpts), C.c_char_p, C.c_size_t]
+    L.mkt_trim_segment_pairs.argtypes = [C.c_void_p, C.c_uint64]
+    L.mkt_trim_begin.argtypes = [C.c_void_p, C.POINTER(TrimOpts)]
+    L.mkt_trim_push.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
+    L.mkt_trim_fetch.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
+    L.mkt_trim_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 6
+    L.mkt_trim_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mkt_bam_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_bam_destroy.argtypes = [C.c_void_p]
     L.mkt_bam_destroy.restype = None
@@ -2013,6 +2029,127 @@ class Stitcher:
 
     def __exit__(self, *a):
         self.close()
+
+
+TRIM_MAX_READ, TRIM_MAX_HEADER = 510, 126
+TRIM_INTERLEAVED, TRIM_READ1, TRIM_READ2 = 0, 1, 2
+TrimStats = collections.namedtuple("TrimStats", "total dropped adapter tailhit dimer passed")
+
+
+class TrimOpts(C.Structure):
+    """mkt_trim_opts (include/mkt.h)"""
+    _fields_ = [("adapter1", C.c_char_p), ("adapter2", C.c_char_p), ("kit", C.c_char_p), ("min_size", C.c_uint32), ("phred", C.c_uint32),
+                ("min_qual", C.c_uint32), ("window", C.c_uint32), ("mismatch", C.c_double), ("interleaved_input", C.c_int)]
+
+
+def _trim_opts(L, adapter1=None, adapter2=None, kit=None, min_size=36, phred=33, min_qual=20, window=5, mismatch=0.125, interleaved_input=False):
+    o = TrimOpts()
+    L.mkt_trim_default_opts(C.byref(o))
+    enc = lambda v: v.encode() if isinstance(v, str) else v
+    o.adapter1, o.adapter2, o.kit = enc(adapter1), enc(adapter2), enc(kit)
+    for name, v in (("min_size", min_size), ("phred", phred), ("min_qual", min_qual), ("window", window)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise MktError(f"{name} {v}: need a number of 0 .. 2^32 - 1")
+        setattr(o, name, int(v))
+    o.mismatch = float(mismatch)
+    o.interleaved_input = 1 if interleaved_input else 0
+    return o
+
+
+def trim_check(**opts):
+    """mkt_trim_check: the argument check of Trimmer.begin, which needs no device.  Returns None or the refusal's text."""
+    L = load_library()
+    try:
+        o = _trim_opts(L, **opts)
+    except MktError as e:
+        return str(e)
+    msg = C.create_string_buffer(256)
+    rc = L.mkt_trim_check(C.byref(o), msg, 256)
+    return None if rc == 0 else msg.value.decode()
+
+
+class Trimmer:
+    """Adapter and quality trimming on the GPU (mkt_trim_*, include/mkt.h): the driver's `ktrim` step.  begin(**opts), push(r1, r2) the
+    two FASTQ streams in any pieces (or the interleaved stream as r1 with interleaved_input=True), the last one with final=True;
+    interleaved() / read1() / read2() collect the three streams (input order), stats() the counters, log_text() PREFIX.trim.log.
+    One object serves any number of runs.  segment_pairs: pairs per segment (default 2^20)."""
+
+    def __init__(self, device=0, segment_pairs=None):
+        self._L = L = load_library()
+        self._h = C.c_void_p()
+        rc = L.mkt_trim_create(device, C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise MktError(f"mkt_trim_create: {L.mkt_strerror(rc).decode()} (no GPU, no CPU path)")
+        self._parts = ([], [], [])
+        if segment_pairs is not None:
+            try:
+                self._check(L.mkt_trim_segment_pairs(self._h, segment_pairs), "mkt_trim_segment_pairs")
+            except MktError:
+                self.close()
+                raise
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise MktError(f"{what}: {self._L.mkt_strerror(rc).decode()}: {self._L.mkt_trim_error(self._h).decode()}")
+
+    def begin(self, **opts):
+        self._opts = _trim_opts(self._L, **opts)      # (kept: the strings it points to live as long as it does)
+        self._check(self._L.mkt_trim_begin(self._h, C.byref(self._opts)), "mkt_trim_begin")
+        self._parts = ([], [], [])
+        return self
+
+    def push(self, r1: bytes = b"", r2: bytes = b"", final=False):
+        ob = (C.c_uint64 * 3)()
+        self._check(self._L.mkt_trim_push(self._h, r1, len(r1), r2, len(r2), 1 if final else 0, ob), "mkt_trim_push")
+        for which in range(3):
+            if ob[which]:
+                buf = C.create_string_buffer(ob[which])
+                self._check(self._L.mkt_trim_fetch(self._h, which, 0, buf, ob[which]), "mkt_trim_fetch")
+                self._parts[which].append(buf.raw[:ob[which]])
+        return self
+
+    def interleaved(self):
+        return b"".join(self._parts[TRIM_INTERLEAVED])
+
+    def read1(self):
+        return b"".join(self._parts[TRIM_READ1])
+
+    def read2(self):
+        return b"".join(self._parts[TRIM_READ2])
+
+    def stats(self):
+        v = [C.c_uint64() for _ in range(6)]
+        self._check(self._L.mkt_trim_stats(self._h, *[C.byref(x) for x in v]), "mkt_trim_stats")
+        return TrimStats(*[int(x.value) for x in v])
+
+    def log_text(self):
+        """PREFIX.trim.log"""
+        return "".join(f"{n}\t{v}\n" for n, v in zip(("Total", "Dropped", "Aadaptor", "TailHit", "Dimer", "Pass"), self.stats()))
+
+    def timing_ms(self):
+        """ms so far: (line indexes, decisions, sizes and scans, writing)"""
+        v = [C.c_double() for _ in range(4)]
+        self._check(self._L.mkt_trim_timing(self._h, *[C.byref(x) for x in v]), "mkt_trim_timing")
+        return tuple(x.value for x in v)
+
+    def close(self):
+        if self._h:
+            self._L.mkt_trim_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def trim(r1: bytes, r2: bytes, device=0, **opts):
+    """One-shot trimming of two FASTQ streams -> (interleaved, read1, read2, TrimStats)."""
+    with Trimmer(device=device) as t:
+        t.begin(**opts).push(r1, r2, final=True)
+        return t.interleaved(), t.read1(), t.read2(), t.stats()
 
 
 def run_sam2pairs(in_sam, mode, prefix, threads=4, ratio=0.5, mapq=10, sam="yes", env=None, exe=None):
