@@ -42,7 +42,8 @@ enum {
     MKT_E_KERNEL = -6,       /* the kernel reported an internal error bit */
     MKT_E_STATE = -7,        /* call order violated (e.g. submit after finish) */
     MKT_E_IO = -8,           /* a temporary file could not be created, written or read (the error text names it) */
-    MKT_E_FORMAT = -9        /* a BGZF file or a deflate stream is refused (mkt_bgzf_error names the reason and the block's offset) */
+    MKT_E_FORMAT = -9,       /* a BGZF file or a deflate stream is refused (mkt_bgzf_error names the reason and the block's offset) */
+    MKT_E_RANGE = -10        /* more than an object is built for (the pair statistics' table of more than 2048 names) */
 };
 
 /* tile geometry selection (tests force the small-tile build to exercise every slow path) */
@@ -1496,6 +1497,90 @@ int mkt_bamtext_fetch_ref(mkt_bamtext* r, uint32_t k, char* name, size_t cap, in
 int mkt_bamtext_fetch_text(mkt_bamtext* r, uint64_t off, char* out, size_t n);
 int mkt_bamtext_device_text(mkt_bamtext* r, const void** d_ptr, uint64_t* n);
 int mkt_bamtext_timing(const mkt_bamtext* r, double ms[6]);
+
+/* ---- pair statistics: distance by orientation, P(s), chromosome pairs of a .pairs text (what `pairtools stats` / `scaling` give) ----
+ * One streaming pass; integers only on the device, so every number is the same on every call.  tests/pairstatdef.py states the
+ * definition in Python; the host half (csrc/mkt_pairstat.h) needs no GPU.
+ *
+ * INPUT    .pairs text: readID chr1 pos1 chr2 pos2 strand1 strand2 [...], tab-separated, one pair per line.  A line that starts with
+ *          '#' is skipped and counted in header_lines.  A chrom.sizes table is required: the grammar and the name lookup of
+ *          mkt_matrix_create (name<TAB>length lines, names of 1 .. 63 bytes, lengths below 2^32, no name twice).
+ * REFUSED  a data line with fewer than five columns (an empty line included) or a position that is empty or no plain decimal:
+ *          mkt_pairstat_run fails with MKT_E_FORMAT and a message that names the smallest such line (1-based, all lines counted).
+ * CLASSES  every data line counts in `total`; a position above 2^40 counts as 2^40.  A side whose name is not in the table, or whose position is 0 or past the chromosome's
+ *          length, makes the pair `skipped` and it counts nowhere else.  counted = total - skipped; a counted pair is `cis` when both
+ *          sides name one chromosome, else `trans`.  For a cis pair d = |pos2 - pos1|: cis_ge[k] counts d >= 1000, 2000, 4000, 10000,
+ *          20000, 40000 (cis_1kb+ ... cis_40kb+).  A counted pair with fewer than seven columns, or whose strand fields are not
+ *          exactly one byte '+' or '-', counts in everything but dist_freq, and in no_strand.
+ * REFERENCE  cis0 (d < 1000), cis1K (1000 .. 9999), cis10K (>= 10000) and ref_trans are the reference's log counters cis0, cis1K, cis10K
+ *          and trans: like the reference they take EVERY data line, skipped or not, and know no table: a line is cis when its two name
+ *          fields are the same bytes.  (Names of more than 63 bytes, which no table can hold, occur in the reference's own test inputs.)
+ *          Without skipped pairs they equal cis - cis_1kb+, cis_1kb+ - cis_10kb+, cis_10kb+ and trans.
+ * CHROM    chrom_freq[i][j]: counted pairs per ordered (chr1 index, chr2 index) as written on the line, no flipping; dense n x n.
+ * DIST     dist_freq[74][4]: cis pairs with strands by distance bin and orientation in the order ++ +- -+ --.  The 74 edges are 0 and
+ *          round(10^(k/8)) for k = 0 .. 72 (0 1 1 2 2 3 4 6 7 10 ... 749894209 1000000000; kPsEdges in csrc/mkt_pairstat.h); the bin of
+ *          d is (number of edges <= d) - 1, so [1,1) and [2,2) stay empty and bin 73 is 1000000000+.  The repeated edges are kept so
+ *          that the keys line up with `pairtools stats`.
+ * P(s)     area[k] = sum over chromosomes of sum_{d = lo}^{min(hi, L) - 1} (L - d) for bin [lo, hi) (hi = 2^32 for bin 73), exact in
+ *          128 bits, converted to double once (round to nearest even); P[k] = double(sum_o dist_freq[k][o]) / area[k], 0.0 where the
+ *          area is 0.  No logarithm and no slope.
+ * CONVERGENCE  T_k = sum_o c[k][o]; bin k is thick when T_k >= min_count; a thick bin is balanced when for every o
+ *          |4 c[k][o] - T_k| * 1000 <= 4 T_k tol_permille.  K is the smallest k such that bin k is thick and balanced and every thick
+ *          bin behind it is balanced; convergence_dist = edge[K], or -1 when there is none.
+ * TEXT     which 0, PREFIX.pairs.stat: key<TAB>value lines: total, skipped, counted, cis, trans, no_strand, header_lines, cis_1kb+ ...
+ *          cis_40kb+, reference/trans, reference/cis10K, reference/cis1K, reference/cis0; summary/frac_cis, summary/frac_cis_1kb+ ... summary/frac_cis_40kb+, summary/frac_trans
+ *          (double(x) / double(counted), 0 for counted 0, printed "%.17g" as PREFIX.<r>.expected.tsv prints a double),
+ *          summary/convergence_dist; chrom_freq/A/B for the non-zero cells in table order; dist_freq/lo-hi/oo for all 74 x 4 (the last
+ *          bin is written 1000000000+).  which 1, PREFIX.scaling.tsv: the header line lo hi area ++ +- -+ -- total P, then one row per
+ *          bin (area as the exact integer, P as "%.17g").
+ * STREAM   add / add_device take pieces cut anywhere, any number of times; the whole lines of a piece are counted and dropped, the
+ *          partial last line is carried, run closes the carry.  Nothing is resident but one piece and the counters.  More may be added
+ *          after a run; the next run reports everything seen so far.
+ * LIMITS   at most 2048 names in the table (the dense chrom_freq is 32 MB there): mkt_pairstat_create refuses more with MKT_E_RANGE
+ *          and a message that says so.  Compressed input is BGZF only (mkt_bgzf_*).  No slope, no pair types, no per-chromosome P(s).
+ *
+ *   mkt_pairstat_create        the table as bytes; mkt_pairstat_error(NULL) has the message of a failed create
+ *   mkt_pairstat_add / _add_device   host / device bytes, copied (counted) before the call returns
+ *   mkt_pairstat_add_keys      the reported pairs of a context created with MKT_EXT_KEYS, as mkt_matrix_add_keys takes them: drop_last,
+ *                              and skip_flags (one byte per reported pair, non-zero = leave out; NULL = none) with n_flags >= the pairs
+ *   mkt_pairstat_opts_default  tol_permille 50, min_count 1000
+ *   mkt_pairstat_run           opts NULL = the defaults; info may be NULL.  MKT_E_FORMAT for a refused line, MKT_E_ARG for a non-zero
+ *                              reserved word
+ *   mkt_pairstat_fetch_dist    the 74 x 4 counts (MKT_E_STATE before a run that succeeded, as every fetch)
+ *   mkt_pairstat_fetch_chrom   rows [first_row, first_row + n_rows) of chrom_freq, n_chrom values each
+ *   mkt_pairstat_fetch_scaling edges (75 values: the 74 edges and 2^32), area and P (74 each); any pointer may be NULL
+ *   mkt_pairstat_text          the text `which` into out (cap bytes, no NUL is added); returns its length, which may exceed cap (then
+ *                              nothing is written), or a negative MKT_E_* code
+ *   mkt_pairstat_timing        ms from HIP events, summed over every piece since create: line index, kernels, and both with the copies */
+#define MKT_PAIRSTAT_BINS 74
+#define MKT_PAIRSTAT_MAX_CHROM 2048
+typedef struct mkt_pairstat mkt_pairstat;
+typedef struct mkt_pairstat_opts {
+    uint32_t tol_permille;                /* 50 */
+    uint32_t reserved0;                   /* 0 */
+    uint64_t min_count;                   /* 1000 */
+    uint32_t reserved[4];                 /* 0 */
+} mkt_pairstat_opts;
+typedef struct mkt_pairstat_info {
+    uint64_t total, skipped, counted, cis, trans, no_strand, header_lines;
+    uint64_t cis_ge[6];                   /* d >= 1000, 2000, 4000, 10000, 20000, 40000 */
+    uint64_t cis0, cis1K, cis10K, ref_trans;      /* the reference's classes: every data line, by name bytes and distance alone */
+    int64_t convergence_dist;             /* -1: none */
+    uint32_t n_chrom, reserved;
+} mkt_pairstat_info;
+int mkt_pairstat_create(int device, const char* chromsizes, size_t len, mkt_pairstat** out);
+void mkt_pairstat_destroy(mkt_pairstat* ps);
+const char* mkt_pairstat_error(const mkt_pairstat* ps);
+int mkt_pairstat_add(mkt_pairstat* ps, const char* bytes, size_t n);
+int mkt_pairstat_add_device(mkt_pairstat* ps, const void* d_bytes, size_t n);
+int mkt_pairstat_add_keys(mkt_pairstat* ps, mkt_ctx* ctx, int drop_last, const uint8_t* skip_flags, size_t n_flags);
+void mkt_pairstat_opts_default(mkt_pairstat_opts* o);
+int mkt_pairstat_run(mkt_pairstat* ps, const mkt_pairstat_opts* opts, mkt_pairstat_info* info);
+int mkt_pairstat_fetch_dist(mkt_pairstat* ps, uint64_t* out);
+int mkt_pairstat_fetch_chrom(mkt_pairstat* ps, uint32_t first_row, uint32_t n_rows, uint64_t* out);
+int mkt_pairstat_fetch_scaling(mkt_pairstat* ps, uint64_t* edges, double* area, double* p);
+long mkt_pairstat_text(mkt_pairstat* ps, int which, char* out, size_t cap);
+int mkt_pairstat_timing(const mkt_pairstat* ps, double* index_ms, double* kernel_ms, double* total_ms);
 
 #ifdef __cplusplus
 }

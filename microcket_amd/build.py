@@ -45,7 +45,7 @@ def hipcc():
 
 
 def _lib_sources():
-    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_trim.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip", "mkt_bamtext.hip")]
+    return [os.path.join(CSRC, f) for f in ("mkt_kernels.hip", "mkt_sort.hip", "mkt_rmdup.hip", "mkt_stitch.hip", "mkt_trim.hip", "mkt_bam.hip", "mkt_capi.cpp", "mkt_capi_ext.cpp", "mkt_capi_util.cpp", "mkt_matrix.hip", "mkt_layout.hip", "mkt_balance.hip", "mkt_expected.hip", "mkt_loops.hip", "mkt_eigs.hip", "mkt_insulation.hip", "mkt_pileup.hip", "mkt_saddle.hip", "mkt_scc.hip", "mkt_viewpoint.hip", "mkt_hic.hip", "mkt_deflate.hip", "mkt_paircmp.hip", "mkt_px2.hip", "mkt_inflate.hip", "mkt_bamtext.hip", "mkt_pairstat.hip")]
 
 
 OBJ = os.path.join(HERE, "_build", "obj")
@@ -262,6 +262,20 @@ def build_bam2sam(force=False):
     return BAM2SAM
 
 
+PAIRSSTAT = os.path.join(HERE, "bin", "pairsstat")
+
+
+def build_pairsstat(force=False):
+    """bin/pairsstat: pair-level QC of final.pairs on the GPU (distance by orientation, P(s), chromosome pairs: DESIGN.md 6k); writes
+    PREFIX.pairs.stat and PREFIX.scaling.tsv."""
+    src = os.path.join(CSRC, "pairsstat_main.cpp")
+    if force or _newer(PAIRSSTAT, [src, LIB] + _headers()):
+        os.makedirs(os.path.dirname(PAIRSSTAT), exist_ok=True)
+        _run(["g++", "-O2", "-std=c++17", "-Wall", src, "-o", PAIRSSTAT, "-L" + HERE, "-lmkt_hip",
+              "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib"])
+    return PAIRSSTAT
+
+
 MAKESTAT = os.path.join(HERE, "bin", "makestat")
 
 
@@ -388,6 +402,13 @@ def build_test_tools():
         trh = os.path.join(out, name)
         if os.path.exists(trsrc) and _newer(trh, [trsrc, os.path.join(CSRC, "mkt_trim.h"), os.path.join(ROOT, "include", "mkt.h")]):
             _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", trh, trsrc])
+    # host driver of the pair statistics' host and shared half (mkt_pairstat.h: the parse and the classes of a line, the areas, the
+    # convergence rule, the two texts), plain and sanitized like the ones above; a tree that carries an older tests/ has no such source
+    sssrc = os.path.join(ROOT, "tests", "host", "pairstat_host.cpp")
+    for name, extra in (("pairstat_host", ()), ("pairstat_host_san", ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"))):
+        psh = os.path.join(out, name)
+        if os.path.exists(sssrc) and _newer(psh, [sssrc, os.path.join(CSRC, "mkt_pairstat.h"), os.path.join(CSRC, "mkt_chromtab.h"), os.path.join(CSRC, "mkt_core.h"), os.path.join(ROOT, "include", "mkt.h")]):
+            _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", *extra, "-o", psh, sssrc])
     build_emit_parts()
     build_parse_chain()
     tout = os.path.join(ROOT, "tools", "_build")
@@ -412,6 +433,7 @@ def build_all(force=False, extras=True):
     build_pairsgunzip(force)
     build_pairsquery(force)
     build_bam2sam(force)
+    build_pairsstat(force)
     build_makestat(force)
     if extras:
         build_oracle()

@@ -51,6 +51,8 @@ EXPORTS = [
     "mkt_bgzf_query_device", "mkt_bgzf_names", "mkt_bgzf_clear",
     "mkt_bamtext_create", "mkt_bamtext_destroy", "mkt_bamtext_error", "mkt_bamtext_add", "mkt_bamtext_add_device", "mkt_bamtext_opts_default", "mkt_bamtext_run",
     "mkt_bamtext_finish", "mkt_bamtext_fetch_header", "mkt_bamtext_fetch_ref", "mkt_bamtext_fetch_text", "mkt_bamtext_device_text", "mkt_bamtext_timing",
+    "mkt_pairstat_create", "mkt_pairstat_destroy", "mkt_pairstat_error", "mkt_pairstat_add", "mkt_pairstat_add_device", "mkt_pairstat_add_keys", "mkt_pairstat_opts_default",
+    "mkt_pairstat_run", "mkt_pairstat_fetch_dist", "mkt_pairstat_fetch_chrom", "mkt_pairstat_fetch_scaling", "mkt_pairstat_text", "mkt_pairstat_timing",
 ]
 
 
@@ -229,6 +231,20 @@ class _ViewpointInfoC(C.Structure):
 ViewpointInfo = collections.namedtuple("ViewpointInfo", "total links links_kept partner_cells partner_cells_kept min_loop viewpoint_bins")
 Viewpoint = collections.namedtuple("Viewpoint", "link_vbin link_chrom link_pbin link_count track partner_chrom partner_pbin partner_count info")
 VIEWPOINT_OPTS = ("vbin", "pbin", "origin", "second_side_only", "min_count", "hotspot_ratio", "reserved")
+
+
+class PairStatsOpts(C.Structure):
+    """mkt_pairstat_opts of include/mkt.h"""
+    _fields_ = [("tol_permille", C.c_uint32), ("reserved0", C.c_uint32), ("min_count", C.c_uint64), ("reserved", C.c_uint32 * 4)]
+
+
+class _PairStatsInfoC(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("total", "skipped", "counted", "cis", "trans", "no_strand", "header_lines")] + \
+               [("cis_ge", C.c_uint64 * 6), ("cis0", C.c_uint64), ("cis1K", C.c_uint64), ("cis10K", C.c_uint64), ("ref_trans", C.c_uint64), ("convergence_dist", C.c_int64),
+                ("n_chrom", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PairStatsScaling = collections.namedtuple("PairStatsScaling", "edges area P")
 
 
 class PairCompareOpts(C.Structure):
@@ -455,6 +471,23 @@ def load_library():
     L.mkt_paircmp_report.argtypes = [C.POINTER(_PairCompareInfoC), C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
     L.mkt_paircmp_report.restype = C.c_long
     L.mkt_paircmp_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mkt_pairstat_create.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.mkt_pairstat_destroy.argtypes = [C.c_void_p]
+    L.mkt_pairstat_destroy.restype = None
+    L.mkt_pairstat_error.argtypes = [C.c_void_p]
+    L.mkt_pairstat_error.restype = C.c_char_p
+    L.mkt_pairstat_add.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    L.mkt_pairstat_add_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.mkt_pairstat_add_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.mkt_pairstat_opts_default.argtypes = [C.POINTER(PairStatsOpts)]
+    L.mkt_pairstat_opts_default.restype = None
+    L.mkt_pairstat_run.argtypes = [C.c_void_p, C.POINTER(PairStatsOpts), C.POINTER(_PairStatsInfoC)]
+    L.mkt_pairstat_fetch_dist.argtypes = [C.c_void_p, C.c_void_p]
+    L.mkt_pairstat_fetch_chrom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.mkt_pairstat_fetch_scaling.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mkt_pairstat_text.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    L.mkt_pairstat_text.restype = C.c_long
+    L.mkt_pairstat_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mkt_rmdup_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.mkt_rmdup_destroy.argtypes = [C.c_void_p]
     L.mkt_rmdup_destroy.restype = None
@@ -1347,6 +1380,120 @@ class PairCompare:
     def close(self):
         if self.h:
             self.L.mkt_paircmp_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class PairStats:
+    """Pair-level QC of .pairs text on the GPU in one streaming pass: totals, distance thresholds, the reference's cis0 / cis1K / cis10K /
+    trans, chromosome-pair counts, distance by strand orientation and P(s): see mkt_pairstat_* in include/mkt.h, where the definition
+    and the limits stand (at most 2048 names in the table).  chromsizes: bytes of name<TAB>length lines."""
+    GE_KEYS = ("cis_1kb+", "cis_2kb+", "cis_4kb+", "cis_10kb+", "cis_20kb+", "cis_40kb+")
+    ORIENTATIONS = ("++", "+-", "-+", "--")
+    BINS = 74
+
+    def __init__(self, chromsizes: bytes, device=0):
+        self.L = load_library()
+        self.names = [ln.split(b"\t")[0].decode("latin-1") for ln in (x.rstrip(b"\r") for x in bytes(chromsizes).split(b"\n")) if ln and not ln.startswith(b"#")]
+        self.h = C.c_void_p()
+        self.info = None
+        rc = self.L.mkt_pairstat_create(device, bytes(chromsizes), len(chromsizes), C.byref(self.h))
+        if rc != 0:
+            raise MktError(f"mkt_pairstat_create: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_pairstat_error(None).decode()}")
+
+    def _chk(self, rc, what):
+        if rc < 0:
+            raise MktError(f"{what}: {self.L.mkt_strerror(rc).decode()}: {self.L.mkt_pairstat_error(self.h).decode()}")
+        return rc
+
+    def add(self, data: bytes):
+        """A piece of the text, cut anywhere."""
+        self._chk(self.L.mkt_pairstat_add(self.h, data, len(data)), "mkt_pairstat_add")
+        self.info = None
+
+    def add_device(self, d_ptr, n):
+        """n bytes of device memory at d_ptr (e.g. BgzfReader.device_text())."""
+        self._chk(self.L.mkt_pairstat_add_device(self.h, C.c_void_p(d_ptr), n), "mkt_pairstat_add_device")
+        self.info = None
+
+    def add_keys(self, ctx, drop_last=True, flags=None):
+        """The reported pairs of a Context created with EXT_KEYS; flags (bytes, one per reported pair, e.g. from ext_dedup): leave those out."""
+        self._chk(self.L.mkt_pairstat_add_keys(self.h, ctx.h, 1 if drop_last else 0, flags, len(flags) if flags is not None else 0), "mkt_pairstat_add_keys")
+        self.info = None
+
+    def run(self, tol_permille=50, min_count=1000):
+        """Closes the carried line and computes everything; returns the counters as a dict (also kept in .info)."""
+        o = PairStatsOpts()
+        self.L.mkt_pairstat_opts_default(C.byref(o))
+        o.tol_permille, o.min_count = tol_permille, min_count
+        info = _PairStatsInfoC()
+        self.info = None
+        self._chk(self.L.mkt_pairstat_run(self.h, C.byref(o), C.byref(info)), "mkt_pairstat_run")
+        d = {k: int(getattr(info, k)) for k in ("total", "skipped", "counted", "cis", "trans", "no_strand", "header_lines", "cis0", "cis1K", "cis10K", "ref_trans", "convergence_dist")}
+        d.update(zip(self.GE_KEYS, (int(x) for x in info.cis_ge)))
+        self.info = d
+        return d
+
+    def _ran(self, what):
+        if self.info is None:
+            raise MktError(f"{what} before a run that succeeded")
+
+    @property
+    def dist_freq(self):
+        """numpy uint64 [74, 4]: cis pairs by distance bin and orientation (++ +- -+ --)"""
+        import numpy as np
+        self._ran("dist_freq")
+        out = np.zeros((self.BINS, 4), dtype=np.uint64)
+        self._chk(self.L.mkt_pairstat_fetch_dist(self.h, C.c_void_p(out.ctypes.data)), "mkt_pairstat_fetch_dist")
+        return out
+
+    @property
+    def chrom_freq(self):
+        """numpy uint64 [n, n]: counted pairs per ordered (chr1, chr2) in table order"""
+        import numpy as np
+        self._ran("chrom_freq")
+        n = len(self.names)
+        out = np.zeros((n, n), dtype=np.uint64)
+        self._chk(self.L.mkt_pairstat_fetch_chrom(self.h, 0, n, C.c_void_p(out.ctypes.data)), "mkt_pairstat_fetch_chrom")
+        return out
+
+    @property
+    def scaling(self):
+        """(edges uint64 [75], area float64 [74], P float64 [74])"""
+        import numpy as np
+        self._ran("scaling")
+        e, a, p = np.zeros(self.BINS + 1, dtype=np.uint64), np.zeros(self.BINS, dtype=np.float64), np.zeros(self.BINS, dtype=np.float64)
+        self._chk(self.L.mkt_pairstat_fetch_scaling(self.h, C.c_void_p(e.ctypes.data), C.c_void_p(a.ctypes.data), C.c_void_p(p.ctypes.data)), "mkt_pairstat_fetch_scaling")
+        return PairStatsScaling(e, a, p)
+
+    def _text(self, which):
+        self._ran("text")
+        n = self._chk(self.L.mkt_pairstat_text(self.h, which, None, 0), "mkt_pairstat_text")
+        buf = C.create_string_buffer(max(n, 1))
+        self._chk(self.L.mkt_pairstat_text(self.h, which, buf, n), "mkt_pairstat_text")
+        return buf.raw[:n]
+
+    def stat_text(self):
+        """The bytes of PREFIX.pairs.stat"""
+        return self._text(0)
+
+    def scaling_text(self):
+        """The bytes of PREFIX.scaling.tsv"""
+        return self._text(1)
+
+    def timing_ms(self):
+        t = [C.c_double() for _ in range(3)]
+        self._chk(self.L.mkt_pairstat_timing(self.h, *[C.byref(x) for x in t]), "mkt_pairstat_timing")
+        return dict(zip(("index", "kernel", "total"), (x.value for x in t)))
+
+    def close(self):
+        if self.h:
+            self.L.mkt_pairstat_destroy(self.h)
             self.h = C.c_void_p()
 
     def __enter__(self):

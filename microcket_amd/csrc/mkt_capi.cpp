@@ -19,6 +19,7 @@ const char* mkt_strerror(int code) {
     case MKT_E_STATE: return "call order violated";
     case MKT_E_IO: return "temporary file error";
     case MKT_E_FORMAT: return "file refused";
+    case MKT_E_RANGE: return "out of range";
     default: return "unknown error";
     }
 }

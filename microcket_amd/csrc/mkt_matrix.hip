@@ -30,11 +30,6 @@ namespace mkt {
 constexpr int MXWG = 256;
 enum { ME_FIELDS = 1 };                             // MxCounters::err
 
-__host__ __device__ inline uint64_t mx_fnv(const uint8_t* p, uint64_t n) {
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (uint64_t i = 0; i < n; ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
-    return h ? h : 1ull;
-}
 __device__ inline uint32_t mx_exscan(uint32_t v, uint32_t* total, uint32_t* sh /* [MXWG / 64] */) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t inc = v;
@@ -91,26 +86,7 @@ __global__ __launch_bounds__(MXWG) void k_mx_parse(const uint8_t* text, const ui
                     }
                     return v;
                 };
-                auto find = [&](uint64_t a, uint64_t b) -> uint32_t {
-                    const uint64_t L = b - a;
-                    if (L == 0 || L > 63) return MX_SKIP;
-                    const uint64_t h = mx_fnv(text + a, L);
-                    uint32_t s = (uint32_t)(h >> 17) & (kMxSlots - 1u);
-                    for (uint32_t probe = 0; probe < kMxSlots; ++probe) {
-                        const unsigned long long cur = tab->hash[s];
-                        if (cur == 0ull) return MX_SKIP;
-                        if (cur == h) {
-                            const uint32_t i = tab->idx[s];
-                            const uint8_t* nm = tab->name[i];
-                            bool same = nm[63] == (uint8_t)L;
-                            for (uint64_t k = 0; same && k < L; ++k) same = nm[k] == text[a + k];
-                            if (same) return i;
-                        }
-                        s = (s + 1u) & (kMxSlots - 1u);
-                    }
-                    return MX_SKIP;
-                };
-                const uint32_t ia = find(tabs[0] + 1, tabs[1]), ib = find(tabs[2] + 1, tabs[3]);
+                const uint32_t ia = mx_tab_find(tab, text, tabs[0] + 1, tabs[1]), ib = mx_tab_find(tab, text, tabs[2] + 1, tabs[3]);
                 r = mx_make(ia, num(tabs[1] + 1, tabs[2]), ib, num(tabs[3] + 1, p5), tab, &skipped);
             }
         }
@@ -246,33 +222,7 @@ __global__ __launch_bounds__(MXWG) void k_mx_text(const uint32_t* bin1, const ui
 // ---------------------------------------------------------------------------------------------------------------
 thread_local std::string mkt::g_mx_create_err;     // the one the header declares
 
-// lines name \t length [\t ...]; empty lines and '#' lines are ignored.  Returns an empty string or what is wrong.
-static std::string mx_parse_table(const char* txt, size_t len, std::vector<std::string>& names, std::vector<uint32_t>& lens) {
-    size_t p = 0, line = 0;
-    char msg[160];
-    while (p < len) {
-        const char* nlp = (const char*)memchr(txt + p, '\n', len - p);
-        size_t q = nlp ? (size_t)(nlp - txt) : len, e = q;
-        ++line;
-        if (e > p && txt[e - 1] == '\r') --e;
-        if (e > p && txt[p] != '#') {
-            size_t t = p;
-            while (t < e && txt[t] != '\t') ++t;
-            if (t == p || t - p > 63) { snprintf(msg, sizeof msg, "chromosome table line %zu: a name of 1 .. 63 bytes is needed", line); return msg; }
-            size_t d = t + 1;
-            uint64_t v = 0;
-            size_t nd = 0;
-            while (d < e && txt[d] >= '0' && txt[d] <= '9' && nd < 11) { v = v * 10 + (uint64_t)(txt[d] - '0'); ++d; ++nd; }
-            if (t >= e || nd == 0 || (d < e && txt[d] != '\t') || v > 0xFFFFFFFFull) { snprintf(msg, sizeof msg, "chromosome table line %zu: no length (name<TAB>length, length < 2^32)", line); return msg; }
-            names.emplace_back(txt + p, t - p);
-            lens.push_back((uint32_t)v);
-        }
-        p = q + 1;
-    }
-    if (names.empty()) return "chromosome table: no chromosome";
-    if (names.size() > kChrSlots) return "chromosome table: more than 8192 chromosomes";
-    return "";
-}
+// the table's grammar (mx_parse_table), its lookup and how it is filled: mkt_chromtab.h
 
 static void mx_free_results(mkt_matrix* m) {
     for (MxRes& r : m->res) mx_invalidate(r, MX_NEW_CELLS);
@@ -415,16 +365,7 @@ int mkt_matrix_create(int device, const char* chromsizes, size_t len, const uint
     if ((e = hipEventCreate(&m->ev0)) != hipSuccess || (e = hipEventCreate(&m->ev1)) != hipSuccess) return dfail("hipEventCreate", e);
     std::vector<uint8_t> hostTab(sizeof(MxTab), 0);
     MxTab* ht = reinterpret_cast<MxTab*>(hostTab.data());
-    for (uint32_t i = 0; i < nc; ++i) {
-        const std::string& nm = m->names[i];
-        memcpy(ht->name[i], nm.data(), nm.size());
-        ht->name[i][63] = (uint8_t)nm.size();
-        ht->len[i] = m->lens[i];
-        const uint64_t h = mx_fnv((const uint8_t*)nm.data(), nm.size());
-        uint32_t s = (uint32_t)(h >> 17) & (kMxSlots - 1u);
-        while (ht->hash[s]) s = (s + 1u) & (kMxSlots - 1u);            // at most 8192 names in 16384 slots
-        ht->hash[s] = h; ht->idx[s] = (uint16_t)i;
-    }
+    mx_tab_fill(ht, m->names, m->lens);
     if ((e = m->d_tab.alloc(1)) != hipSuccess) return dfail("hipMalloc", e);
     if ((e = hipMemcpy(m->d_tab, ht, sizeof(MxTab), hipMemcpyHostToDevice)) != hipSuccess) return dfail("hipMemcpy", e);
     if ((e = m->d_counters.alloc(1)) != hipSuccess) return dfail("hipMalloc", e);

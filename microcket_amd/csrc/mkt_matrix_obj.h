@@ -12,6 +12,7 @@
 
 #include "../../include/mkt.h"
 #include "mkt_core.h"
+#include "mkt_chromtab.h"
 #include "mkt_layout.h"
 #include "mkt_balance.h"
 #include "mkt_expected.h"
@@ -26,19 +27,11 @@
 
 namespace mkt {
 
-constexpr uint32_t MX_SKIP = 0xFFFFFFFFu;          // MxRec::ia of a skipped pair
-constexpr uint32_t MX_NONE = 0xFFFFFFFEu;          // ... of something that is not a pair (a '#' line, a pair left out by its flag)
+// MX_SKIP (MxRec::ia of a skipped pair), the given table MxTab and its lookup: mkt_chromtab.h
+constexpr uint32_t MX_NONE = 0xFFFFFFFEu;          // MxRec::ia of something that is not a pair (a '#' line, a pair left out by its flag)
 struct MxRec { uint32_t ia, pa, ib, pb; };         // table index and 1-based position of the two sides
 static_assert(sizeof(MxRec) == 16, "one 16-byte vector per pair");
 
-// the given table, read-only on the device: open addressing over FNV-1a of the name (nothing is ever inserted by a kernel)
-constexpr uint32_t kMxSlots = 2 * kChrSlots;
-struct MxTab {
-    unsigned long long hash[kMxSlots];             // 0 = empty
-    uint16_t idx[kMxSlots];                        // table index of the slot's name
-    uint8_t name[kChrSlots][64];                   // by table index; [63] = length (<= 63)
-    uint32_t len[kChrSlots];                       // L_i
-};
 struct MxCounters { unsigned long long skipped, none; uint32_t err, pad; };
 
 // One resolution.  A member's lifetime is the group it stands in, and mx_invalidate below is the only code that ends one: a new member
